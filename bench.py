@@ -5,7 +5,11 @@
 One "step" = one pass of the hot path (X int8 resident in HBM -> B -> proba f32 + labels) over the
 batch.  Haplotypes shard across ranks with no data-path collective (weak scaling: per-GPU batch fixed).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, the per-kernel
+figures of the same timed steps).  --full adds every other leg described below and writes the whole object to
+bench_last.json.  --dump-outputs DIR writes the last step's outputs (a fixed sample of rows) as .npy files.
 
 N > 1 without a torch.distributed environment: bench.py launches its own N ranks (re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`), one process per GPU,
@@ -14,12 +18,12 @@ WORLD_SIZE it finds differs from --gpus.  GNX_BENCH_FORCE_DIST=1 runs the N=1 ca
 process-group / RCCL code (what a 1-GPU box can exercise of it).
 
 Prints ONE JSON line on rank 0 (contract in the task statement) carrying `roofline` (dominant kernel, measured
-with hipEvents on the launch stream inside libgnomix_hip), `e2e` (host pointers in, labels out, PCIe included —
-never `value`) and, at N=1, `cpu_baseline` (the oracle's C restatement timed on ALL of this box's host cores on a
-bounded sample, base and smoother timed separately) and `configs` (BASELINE.json's configs 3, 4, 5 at their one-GPU
+with hipEvents on the launch stream inside libgnomix_hip) and, with --full, `e2e` (host pointers in, labels out, PCIe
+included — never `value`) and, at N=1, `cpu_baseline` (the oracle's C restatement timed on ALL of this box's host cores
+on a bounded sample, base and smoother timed separately) and `configs` (BASELINE.json's configs 3, 4, 5 at their one-GPU
 shard sizes: scripts/bench_configs.py bench_legs(); never `value`).  The line is kept compact (the driver's record
 holds its last ~8 KB: `configs`, `roofline` and `cpu_baseline` are printed last); what every field means is DESIGN.md 5;
-the same object, indented, is also written to gpurun_out/bench_last.json.
+with --full the same object, indented, is also written to bench_last.json.
 """
 import argparse
 import json
@@ -132,9 +136,17 @@ def main():
     ap.add_argument("--phase-leg", type=int, default=1, help="file-to-file with phase=True on admixed individuals through a device-trained model (N=1; needs --vcf-reps > 0)")
     ap.add_argument("--vcf-dir", default="", help="where the synthetic VCF and the outputs go (default: /dev/shm when it has room, else a temp dir)")
     ap.add_argument("--seed", type=int, default=94305)
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline figure (resident_2bit, e2e, "
+                    "trained_ensemble, e2e_vcf, cpu_baseline, configs; each still switchable by its own option above) and write "
+                    "the whole result object to bench_last.json; a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write what the last step computed as "
+                    "DIR/<name>.npy (float32 / float64, < 64 MB): probabilities and labels of a fixed, seeded sample of the batch's "
+                    "haplotypes and the sample's row indices (rank 0's shard)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     in_dist_env = "WORLD_SIZE" in os.environ and "RANK" in os.environ
     if not in_dist_env and args.gpus > 1:
@@ -223,6 +235,8 @@ def main():
             lab_sum = int(lab_all.to(torch.int64).sum().item())
     else:
         lab_sum = int(out[1].to(torch.int64).sum().item())
+    if rank == 0 and args.dump_outputs:
+        _dump_outputs(args.dump_outputs, out)
 
     W, A, C = model.W, model.A, model.C
     ms_base, n_base = ctx.profile_get(_lib.K_BASE_LOGISTIC)
@@ -303,7 +317,7 @@ def main():
 
     # ---- the same batch resident in HBM as 2-bit rows (gnx_pack_x layout): the logistic pass reads a quarter of the X bytes
     # (k_base_logistic_p2); never `value` (SURVEY.md 8d quotes the metric on int8-resident X), printed beside it -------------
-    if rank == 0 and world == 1 and args.resident_2bit:
+    if rank == 0 and world == 1 and args.full and args.resident_2bit:
         try:
             Pk = model.pack_device(X)
             for _ in range(max(1, args.warmup)):
@@ -336,13 +350,13 @@ def main():
             res["resident_2bit"] = {"error": repr(e)}
 
     # ---- PCIe-inclusive rate: host pointers in, labels + probabilities out (never `value`) ----------------------------
-    if rank == 0 and world == 1 and args.e2e_steps > 0:
+    if rank == 0 and world == 1 and args.full and args.e2e_steps > 0:
         try:
             res["e2e"] = _e2e(model, X, args.e2e_steps, out)
         except Exception as e:  # the headline line must still print
             res["e2e"] = {"error": repr(e)}
 
-    if rank == 0 and world == 1 and args.trained:
+    if rank == 0 and world == 1 and args.full and args.trained:
         try:
             te = _trained_ensemble(ctx, data, avg_sm * 1e3)
             res["trained_ensemble"] = te
@@ -364,7 +378,7 @@ def main():
     # ---- file to file: synthetic phased VCF -> .msp / .fb through the command line's own run_inference (never `value`) ----
     # at N > 1 it is ONE process (rank 0) driving all N devices (gnomix_amd/multi.py: one parse, one context and host thread per
     # GPU, outputs written once) while the other ranks wait — the file path has no collective either
-    if rank == 0 and args.vcf_reps > 0:
+    if rank == 0 and args.full and args.vcf_reps > 0:
         try:
             # GNX_BENCH_VCF_DEVICES="0,0": the one-process multi-context file path on a box with fewer GPUs (tests)
             vdev = [int(t) for t in os.environ["GNX_BENCH_VCF_DEVICES"].split(",")] if os.environ.get("GNX_BENCH_VCF_DEVICES") else None
@@ -385,12 +399,12 @@ def main():
             pass
         dist.barrier()
 
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if rank == 0 and world == 1 and args.full and args.cpu_seconds > 0:
         res["cpu_baseline"] = _cpu_baseline(args, data, X, out)
     res["kernels"] = kernels
     res["roofline"] = roofline
     # ---- BASELINE.json's configs 3, 4, 5 at their one-GPU shard sizes (scripts/bench_configs.py; never `value`) -------------
-    if rank == 0 and world == 1 and args.configs:
+    if rank == 0 and world == 1 and args.full and args.configs:
         try:
             del X, out
             torch.cuda.empty_cache()
@@ -404,12 +418,13 @@ def main():
     if dist is not None:
         dist.destroy_process_group()
     sys.stdout.flush()
-    if rank == 0:
+    if rank == 0 and args.full:
         try:   # the whole object, indented, where gpurun merges it back (the driver's record keeps the tail of stdout only)
             os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
             json.dump(res, open(os.path.join(ROOT, "gpurun_out", "bench_last.json"), "w"), indent=1)
         except Exception:
             pass
+    if rank == 0:
         print(json.dumps(_compact(res)), flush=True)
     # RCCL prints a version banner to STDOUT from a library destructor at process exit (after anything Python can
     # print): point fd 1 at stderr from here on, on every rank, so the JSON line stays the last line of stdout
@@ -426,6 +441,25 @@ def _compact(x, nd=5, notes=False):
     if isinstance(x, (list, tuple)):
         return [_compact(v, nd, notes) for v in x]
     return x
+
+
+DUMP_BYTES = 48 << 20   # --dump-outputs stays well under 64 MB
+
+
+def _dump_outputs(dirname, out):
+    """--dump-outputs: what the timed path returns (probabilities f32 (N, W, A), labels (N, W)) for a fixed, seeded sample of the
+    batch's rows: proba.npy float32, labels.npy float32, rows.npy float64 (the sampled row indices, ascending)"""
+    import numpy as np
+    import torch
+    proba, labels = out[0], out[1]
+    N, W, A = proba.shape
+    k = min(N, max(1, DUMP_BYTES // (W * (A + 1) * 4 + 8)))
+    rows = np.sort(np.random.RandomState(0).choice(N, size=k, replace=False))
+    idx = torch.from_numpy(rows).to(proba.device)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "proba.npy"), proba.index_select(0, idx).float().cpu().numpy())
+    np.save(os.path.join(dirname, "labels.npy"), labels.index_select(0, idx).float().cpu().numpy())
+    np.save(os.path.join(dirname, "rows.npy"), rows.astype(np.float64))
 
 
 def _e2e(model, X, steps, out_dev):

@@ -22,8 +22,8 @@ SQ="SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_BUSY_CY
 TC="TCC_HIT_sum TCC_MISS_sum TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_PENDING_STALL_CYCLES_sum TCP_TCC_READ_REQ_LATENCY_sum"
 for cfg in $WHICH; do
   if [ "$cfg" = "bench" ]; then
-    CMD="python bench.py --steps 3 --warmup 1 --passes 1 --cpu-seconds 0 --e2e-steps 0 --vcf-reps 0 --trained 0 --configs 0"
-    STATS="python bench.py --steps 20 --warmup 3 --cpu-seconds 0 --e2e-steps 0 --vcf-reps 0 --trained 0 --configs 0"
+    CMD="python bench.py --full --steps 3 --warmup 1 --passes 1 --cpu-seconds 0 --e2e-steps 0 --vcf-reps 0 --trained 0 --configs 0"
+    STATS="python bench.py --full --steps 20 --warmup 3 --cpu-seconds 0 --e2e-steps 0 --vcf-reps 0 --trained 0 --configs 0"
   elif [ "$cfg" = "smbs" ]; then   # the tree smoother alone: rank walk (pointer nodes) against the bit-sliced kernel (k_smooth_xgb_bs)
     CMD="python scripts/dev/bs_check.py bench"
     STATS="$CMD"

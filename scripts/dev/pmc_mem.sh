@@ -1,7 +1,7 @@
 # memory-path counters of the bench kernels (TLB, L1 stalls, request latency): development aid
 export TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:-.}"
-CMD="python bench.py --steps 3 --warmup 1 --cpu-seconds 0 --e2e-steps 0"
+CMD="python bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 --e2e-steps 0"
 i=0
 for set in "TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_TRANSLATION_HIT_sum TCP_UTCL1_REQUEST_sum TCP_UTCL1_STALL_INFLIGHT_MAX_sum" \
            "TCP_PENDING_STALL_CYCLES_sum TCP_TCR_TCP_STALL_CYCLES_sum TCP_TCP_TA_DATA_STALL_CYCLES_sum TCP_GATE_EN1_sum" \

@@ -24,6 +24,8 @@ input/output pair produced by executing its own functions:
   G15_lr_binary.npz  A = 2 logistic base (sklearn's one-row binary form)
   G16_lr_train.npz   LogisticRegressionBase.train (base.py:104-127): training data + the reference's fitted coefficients
   G17_cnn_train.npz  CNN.fit (Smooth/cnn.py:104-118): data, initial and trained Conv1d parameters, the DataLoader's row order
+  G20_convert_ref/   LogisticRegressionBase / RFBase objects trained by Base.train, pickled as Gnomix.save pickles a base, with
+                     query haplotypes and the reference's own Base.predict_proba (tests/test_convert_reference.py)
 
 Third-party modules the reference imports at module import time but that are absent here
 (xgboost, allel, seaborn, calibration, sklearn_crfsuite) are replaced by empty stubs; no code path
@@ -855,7 +857,7 @@ def make_G16(out):
 
 
 def main():
-    which = sys.argv[1:] or ["G1", "G2", "G3", "G4", "G5", "G6", "G7", "G8", "G9", "G10", "G11", "G12", "G13", "G14", "G15", "G16", "G17", "G18", "G19"]
+    which = sys.argv[1:] or ["G1", "G2", "G3", "G4", "G5", "G6", "G7", "G8", "G9", "G10", "G11", "G12", "G13", "G14", "G15", "G16", "G17", "G18", "G19", "G20"]
     have_ref = import_reference()
     if not have_ref:
         _stub_modules()
@@ -880,6 +882,7 @@ def main():
     if "G17" in which: make_G17(os.path.join(HERE, "G17_cnn_train.npz"))
     if "G18" in which: make_G18(os.path.join(HERE, "G18_lgbm_base.npz"))
     if "G19" in which: make_G19(os.path.join(HERE, "G19_catboost_base.npz"))
+    if "G20" in which: make_G20(os.path.join(HERE, "G20_convert_ref"))
     return 0
 
 
@@ -939,6 +942,42 @@ def make_G17(out):
         proba = model.predict_proba(B[:16])
     np.savez_compressed(out, A=A, S=S, W=W, epochs=EP, B=B, y=y.astype(np.int32), order=order, w0=w0, b0=b0, w1=w1, b1=b1, proba16=proba)
     print("G17", "moved", float(np.abs(w1 - w0).max()), "train acc", float((np.argmax(model.predict_proba(B), -1) == y).mean()))
+
+
+def make_G20(outdir):
+    """Real reference base objects for gnomix_amd.convert / gnomix_amd.refpickle (tests/test_convert_reference.py): each base is
+    trained by the reference's own Base.train, pickled as {"base": base} (what Gnomix.save pickles of it, model.py:100-102; gzip), and stored
+    with query haplotypes and the reference's own Base.predict_proba of them.  export_lr: A = 4, C = 1237; LogisticRegressionBase /
+    RFBase: A = 3, C = 937."""
+    import gzip
+    import pickle
+    import warnings
+    from src.Base.models import LogisticRegressionBase, RFBase
+    os.makedirs(outdir, exist_ok=True)
+
+    def train(cls, C, M, A, ctx, rng, n_train, n_query):
+        W = C // M
+        Xt, yt = synth_admixed(rng, n_train, C, A, W, M)
+        for w in range(W):
+            yt[:A, w] = np.arange(A)
+        Xq, _ = synth_admixed(rng, n_query, C, A, W, M, miss=0.05)
+        base = cls(chm_len=C, window_size=M, num_ancestry=A, missing_encoding=2, context=ctx, n_jobs=1, seed=1, verbose=False)
+        base.base_multithread = False
+        np.random.seed(1)  # RandomForestClassifier(random_state=None) draws from numpy's global state
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            base.train(Xt, yt)
+        return base, Xq, base.predict_proba(Xq)
+
+    jobs = [("export_lr", LogisticRegressionBase, 1237, 50, 4, 25, 1, 200, 9),
+            ("LogisticRegressionBase", LogisticRegressionBase, 937, 50, 3, 25, 2, 150, 7),
+            ("RFBase", RFBase, 937, 50, 3, 25, 2, 150, 7)]
+    for name, cls, C, M, A, ctx, seed, n_train, n_query in jobs:
+        base, Xq, B = train(cls, C, M, A, ctx, np.random.RandomState(seed), n_train, n_query)
+        with gzip.open(os.path.join(outdir, name + ".pkl.gz"), "wb") as f:
+            pickle.dump({"base": base}, f, protocol=4)
+        np.savez_compressed(os.path.join(outdir, name + ".npz"), C=C, M=M, A=A, ctx=ctx, Xq=Xq, B_ref=B)
+        print("G20", name, B.shape, B.dtype, "pickle", os.path.getsize(os.path.join(outdir, name + ".pkl.gz")), "B")
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Pickle REAL reference models under an OLDER scikit-learn than the one that will read them.
 
-  /opt/conda/bin/python3.9 tests/golden/make_refpickle_py39.py <outdir>
+  python3.9 tests/golden/make_refpickle_py39.py [outdir]      (an environment with scikit-learn 0.24.2 / numpy 1.26.4)
 
 The published Gnomix bundles (reference gnomix.py:26-35, download_pretrained_models.sh:2-10) were pickled by scikit-learn 1.0.1 /
 numpy 1.20.3 (requirements.txt:2,6); the image's test interpreter has scikit-learn 1.7.2 / numpy 2.2.  This script runs in the
@@ -10,14 +10,17 @@ read-only from /root/reference, trains three small `src.model.Gnomix` objects wi
 
     LogisticRegressionBase   CovRSKBase   RFBase          (src/Base/models.py:12-21, 195-215, 54-66)
 
-and writes, per model, <outdir>/<name>.pkl (pickle.dump of the Gnomix object, exactly what Gnomix.save does: model.py:100-102)
+and writes, per model, <outdir>/<name>.pkl.gz (pickle.dump of the Gnomix object, exactly what Gnomix.save does: model.py:100-102,
+gzip-compressed as a published model.pkl.gz is)
 and <outdir>/<name>.npz with the query haplotypes and the reference's OWN base.predict_proba(Xq) computed in that environment.
 tests/test_refpickle_crossversion.py reads them under Python 3.10 with gnomix_amd.refpickle (both modes), converts, and compares.
 
 The smoother is a CRF_Smoother carrying hand-set weights in the attributes gnomix_amd.convert reads (xgboost / sklearn_crfsuite
 are absent from both environments: the booster bytes of a real bundle stay unpinned, VERDICT r5 "missing" 2).
-NOTHING written here is committed or travels: the test writes into pytest's tmp_path.
+The default <outdir> is tests/golden/refpickle_py39/, whose files are committed: the test reads them and needs neither this
+environment nor the reference.
 """
+import gzip
 import os
 import pickle
 import sys
@@ -113,9 +116,9 @@ def main(outdir):
         sm.model.CRF.state_features_ = {(str(a), str(y)): float(st[a, y]) for a in range(A) for y in range(A)}
         sm.model.CRF.transition_features_ = {(str(a), str(y)): float(tr[a, y]) for a in range(A) for y in range(A)}
         g.smooth = sm
-        with open(os.path.join(outdir, name + ".pkl"), "wb") as f:
+        with gzip.open(os.path.join(outdir, name + ".pkl.gz"), "wb") as f:
             pickle.dump(g, f)
-        np.savez(os.path.join(outdir, name + ".npz"), Xq=Xq, B_ref=np.asarray(B_ref, dtype=np.float64), crf_state=st, crf_trans=tr,
+        np.savez_compressed(os.path.join(outdir, name + ".npz"), Xq=Xq, B_ref=np.asarray(B_ref, dtype=np.float64), crf_state=st, crf_trans=tr,
                  C=C, M=M, A=A, S=S, context=ctx, sklearn_version=np.array(sklearn.__version__), numpy_version=np.array(np.__version__),
                  python_version=np.array("%d.%d" % sys.version_info[:2]))
         print("%s: pickled under python %d.%d / scikit-learn %s / numpy %s, B_ref %s" %
@@ -124,4 +127,4 @@ def main(outdir):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1] if len(sys.argv) > 1 else os.path.join(HERE, "_refpickle_py39")))
+    sys.exit(main(sys.argv[1] if len(sys.argv) > 1 else os.path.join(HERE, "refpickle_py39")))

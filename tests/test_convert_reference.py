@@ -1,23 +1,21 @@
-"""CPU: gnomix_amd.convert against REAL reference objects (needs /root/reference and sklearn; skipped elsewhere).
-A model trained by the reference's own LogisticRegressionBase / CovRSKBase is exported to flat arrays and run through
-the oracle: the export must reproduce the reference's predict_proba."""
+"""CPU: gnomix_amd.convert against REAL reference objects.  Bases trained by the reference's own LogisticRegressionBase / RFBase
+(Base.train) are stored pickled, with query haplotypes and the reference's own predict_proba of them, in tests/golden/G20_convert_ref/
+(tests/golden/make_golden.py G20).  A base is read back with gnomix_amd.refpickle (which never imports `src`), exported to flat arrays
+and run through the oracle: the export must reproduce the reference's predict_proba."""
 import os
-import sys
 import types
 
 import numpy as np
 import pytest
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
+G20 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "G20_convert_ref")
 
 
-@pytest.fixture(scope="module")
-def ref():
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
-    import make_golden as mg
-    assert mg.import_reference()
-    return mg
+def _stored_base(name, use_sklearn=True):
+    """(base read back from its pickle, the fixture's arrays)"""
+    from gnomix_amd import refpickle
+    base = refpickle.load_reference_pickle(os.path.join(G20, name + ".pkl.gz"), use_sklearn=use_sklearn)["base"]
+    return base, np.load(os.path.join(G20, name + ".npz"))
 
 
 class CRF_Smoother:  # name-compatible stand-ins: from_reference_model dispatches on the class name like the pickle would
@@ -40,24 +38,16 @@ def _fake_crf_smoother(A, S, rng):
     return sm, st, tr
 
 
-def test_export_logistic_model_reproduces_reference(ref, oracle):
-    import warnings
-    from src.Base.models import LogisticRegressionBase
+def test_export_logistic_model_reproduces_reference(oracle):
+    """a LogisticRegressionBase with its scikit-learn estimators rebuilt for real (refpickle's use_sklearn=True: cli.load_model's first
+    choice)"""
     from gnomix_amd import convert, GnxModelData
+    base, z = _stored_base("export_lr")
+    assert type(base).__name__ == "LogisticRegressionBase" and type(base.models[0]).__name__ == "LogisticRegression"
+    C, M, A, ctx = int(z["C"]), int(z["M"]), int(z["A"]), int(z["ctx"])
+    W = C // M
+    Xq, B_ref = z["Xq"], z["B_ref"]
     rng = np.random.RandomState(1)
-    C, M, A = 1237, 50, 4
-    W, ctx = C // M, 25
-    Xt, yt = ref.synth_admixed(rng, 200, C, A, W, M)
-    for w in range(W):
-        yt[:A, w] = np.arange(A)
-    base = LogisticRegressionBase(chm_len=C, window_size=M, num_ancestry=A, missing_encoding=2, context=ctx, n_jobs=1,
-                                  seed=1, verbose=False)
-    base.base_multithread = False
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        base.train(Xt, yt)
-    Xq, _ = ref.synth_admixed(rng, 9, C, A, W, M, miss=0.05)
-    B_ref = base.predict_proba(Xq)
     sm, st, tr = _fake_crf_smoother(A, 75, rng)
     model = types.SimpleNamespace(C=C, M=M, A=A, context=ctx, base=base, smooth=sm, snp_pos=np.arange(C), snp_ref=None,
                                   snp_alt=None, population_order=["a", "b", "c", "d"], gen_map_df={})
@@ -71,7 +61,7 @@ def test_export_logistic_model_reproduces_reference(ref, oracle):
     assert desc.lr_ldc == d.lr_coef.shape[2] and desc.C == C
 
 
-def test_export_calibrator_and_string_kernel_lengths(ref):
+def test_export_calibrator_and_string_kernel_lengths():
     from sklearn.isotonic import IsotonicRegression
     from gnomix_amd import convert
     rng = np.random.RandomState(2)
@@ -84,38 +74,22 @@ def test_export_calibrator_and_string_kernel_lengths(ref):
         convert.string_kernel_lengths(5, "poly_kernel")
 
 
-def test_restricted_unpickle_of_real_reference_objects(ref, oracle, tmp_path):
-    """pickle REAL reference objects (src.Base.models.LogisticRegressionBase / RFBase trained by Base.train), read the
-    pickle back with gnomix_amd.refpickle (which never imports `src`), convert, and reproduce the reference's output"""
-    import pickle
-    import warnings
-    from src.Base.models import LogisticRegressionBase, RFBase
+def test_restricted_unpickle_of_real_reference_objects(oracle):
+    """REAL reference objects (src.Base.models.LogisticRegressionBase / RFBase trained by Base.train) read back from their pickle
+    with gnomix_amd.refpickle (which never imports `src`), converted, reproduce the reference's output"""
     from gnomix_amd import convert, refpickle
     rng = np.random.RandomState(2)
-    C, M, A = 937, 50, 3
-    W, ctx = C // M, 25
-    Xt, yt = ref.synth_admixed(rng, 150, C, A, W, M)
-    for w in range(W):
-        yt[:A, w] = np.arange(A)
-    Xq, _ = ref.synth_admixed(rng, 7, C, A, W, M, miss=0.05)
-    for cls in (LogisticRegressionBase, RFBase):
-        base = cls(chm_len=C, window_size=M, num_ancestry=A, missing_encoding=2, context=ctx, n_jobs=1, seed=1, verbose=False)
-        base.base_multithread = False
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            base.train(Xt, yt)
-        B_ref = base.predict_proba(Xq)
+    for name in ("LogisticRegressionBase", "RFBase"):
+        got, z = _stored_base(name)
+        C, M, A, ctx = int(z["C"]), int(z["M"]), int(z["A"]), int(z["ctx"])
+        Xq, B_ref = z["Xq"], z["B_ref"]
         sm, st, tr = _fake_crf_smoother(A, 75, rng)
-        model = types.SimpleNamespace(C=C, M=M, A=A, context=ctx, base=base, smooth=sm, snp_pos=np.arange(C), snp_ref=None,
+        model = types.SimpleNamespace(C=C, M=M, A=A, context=ctx, base=None, smooth=sm, snp_pos=np.arange(C), snp_ref=None,
                                       snp_alt=None, population_order=["a", "b", "c"], gen_map_df=None)
-        p = tmp_path / (cls.__name__ + ".pkl")
-        with open(p, "wb") as f:
-            pickle.dump({"base": base}, f)
-        got = refpickle.load_reference_pickle(str(p))["base"]
-        assert isinstance(got, refpickle.Stub) and type(got).__name__ == cls.__name__ and type(got).__module__ == "src.Base.models"
+        assert isinstance(got, refpickle.Stub) and type(got).__name__ == name and type(got).__module__ == "src.Base.models"
         model.base = got
         d = convert.from_reference_model(model)
-        if cls is LogisticRegressionBase:
+        if name == "LogisticRegressionBase":
             B = oracle.base_lr(Xq, M, ctx, d.lr_coef, d.lr_intercept)
             assert np.max(np.abs(B - B_ref)) < 1e-13
         else:

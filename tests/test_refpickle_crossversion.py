@@ -1,41 +1,28 @@
 """A reference `model.pkl` pickled by an OLDER scikit-learn / numpy than the one reading it (the closable half of SURVEY 8(f).1:
 the published bundles were written by scikit-learn 1.0.1 / numpy 1.20.3, requirements.txt:2,6; the test interpreter has 1.7.2 / 2.2).
 
-tests/golden/make_refpickle_py39.py runs in the image's second environment (/opt/conda/bin/python3.9: scikit-learn 0.24.2,
-numpy 1.26.4), imports the reference from /root/reference, trains small `src.model.Gnomix` objects with the reference's own
-LogisticRegressionBase / CovRSKBase / RFBase, pickles them as Gnomix.save does and stores the reference's OWN predict_proba next to
-them — all into pytest's tmp_path (nothing pickled is committed or travels).  Here, under Python 3.10:
+tests/golden/make_refpickle_py39.py, run under Python 3.9 with scikit-learn 0.24.2 / numpy 1.26.4 and the reference importable, trains
+small `src.model.Gnomix` objects with the reference's own LogisticRegressionBase / CovRSKBase / RFBase, pickles them as Gnomix.save does
+and stores the reference's OWN predict_proba next to them, in tests/golden/refpickle_py39/.  Here, under Python 3.10:
 
     load_reference_pickle (use_sklearn = False AND True; cli.load_model's fallback order) -> from_reference_model -> oracle
-    == the old environment's reference output (<= 1e-12, arg-max labels identical); under -m gpu the HIP path as well.
-
-Skipped when the reference tree or the conda interpreter is absent (the GPU box has neither: the -m gpu leg documents the intent and
-runs wherever both a GPU and the reference exist)."""
+    == the old environment's reference output (<= 1e-12, arg-max labels identical); under -m gpu the HIP path as well."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-PY39 = os.environ.get("GNX_OLD_PYTHON", "/opt/conda/bin/python3.9")
-pytestmark = pytest.mark.skipif(not (os.path.isdir(REF) and os.path.exists(PY39)), reason="needs /root/reference and the image's older Python environment")
 
 
 @pytest.fixture(scope="module")
-def old_pickles(tmp_path_factory):
-    out = tmp_path_factory.mktemp("refpickle_py39")
-    r = subprocess.run([PY39, os.path.join(ROOT, "tests", "golden", "make_refpickle_py39.py"), str(out)], capture_output=True, text=True,
-                       env={k: v for k, v in os.environ.items() if k not in ("PYTHONPATH", "PYTHONHOME")})
-    if r.returncode != 0:
-        pytest.skip("the older environment could not run the reference: " + (r.stderr or r.stdout)[-400:])
+def old_pickles():
+    out = os.path.join(ROOT, "tests", "golden", "refpickle_py39")
     meta = np.load(os.path.join(out, "lr.npz"))
     import sklearn
     # the point of the test: a scikit-learn MAJOR version gap between writer and reader
     assert str(meta["sklearn_version"]).split(".")[0] != sklearn.__version__.split(".")[0], (str(meta["sklearn_version"]), sklearn.__version__)
-    return str(out)
+    return out
 
 
 def _load_both_modes(path):
@@ -68,7 +55,7 @@ def test_pickle_from_older_sklearn_converts_and_reproduces_the_reference(old_pic
     from gnomix_amd import convert, refpickle
     z = np.load(os.path.join(old_pickles, name + ".npz"))
     Xq, B_ref = z["Xq"], z["B_ref"]
-    path = os.path.join(old_pickles, name + ".pkl")
+    path = os.path.join(old_pickles, name + ".pkl.gz")
     modes = _load_both_modes(path)
     assert not isinstance(modes[0][1], Exception), "attribute-bag mode (use_sklearn=False) must always read the pickle: %r" % (modes[0][1],)
     worked = 0
@@ -88,18 +75,18 @@ def test_pickle_from_older_sklearn_converts_and_reproduces_the_reference(old_pic
     assert worked >= 1
 
 
-def test_command_line_loader_reads_the_old_pickle(old_pickles, monkeypatch):
+def test_command_line_loader_reads_the_old_pickle(old_pickles, tmp_path):
     """gnomix_amd.cli.load_model's own order (rebuild scikit-learn objects, fall back to attribute bags) up to the point where a device
     is needed: the converted model of the old LogisticRegression pickle round-trips through .gnx"""
     from gnomix_amd import convert, refpickle
     from gnomix_amd.model import GnxModelData
-    path = os.path.join(old_pickles, "lr.pkl")
+    path = os.path.join(old_pickles, "lr.pkl.gz")
     try:
         ref_model = refpickle.load_reference_pickle(path)
     except Exception:
         ref_model = refpickle.load_reference_pickle(path, use_sklearn=False)
     d = convert.from_reference_model(ref_model)
-    out = os.path.join(old_pickles, "lr.gnx")
+    out = str(tmp_path / "lr.gnx")
     d.save(out)
     d2 = GnxModelData.load(out)
     assert np.array_equal(d2.lr_coef, d.lr_coef) and d2.smooth_kind == "crf" and list(d2.population_order) == ["p0", "p1", "p2"]
@@ -111,7 +98,7 @@ def test_hip_path_on_the_old_pickle(old_pickles, name):
     import gnomix_amd
     from gnomix_amd import convert, refpickle
     z = np.load(os.path.join(old_pickles, name + ".npz"))
-    d = convert.from_reference_model(refpickle.load_reference_pickle(os.path.join(old_pickles, name + ".pkl"), use_sklearn=False))
+    d = convert.from_reference_model(refpickle.load_reference_pickle(os.path.join(old_pickles, name + ".pkl.gz"), use_sklearn=False))
     dev = gnomix_amd.DeviceModel(d)
-    B = dev.base_predict(z["Xq"])
+    _, B = dev.base_predict(z["Xq"])   # (f32, f64): the f64 probabilities are what the reference returns
     assert np.max(np.abs(B - z["B_ref"])) <= 1e-12 and np.array_equal(B.argmax(-1), z["B_ref"].argmax(-1))
