@@ -5,7 +5,15 @@
 `path_to_model` is a flat `.gnx` model (gnomix_amd.GnxModelData.save) or a reference `model.pkl[.gz]`, which is read
 with a restricted unpickler (gnomix_amd.refpickle: neither the reference's `src` package nor xgboost is needed; CRF
 models still need sklearn_crfsuite's attributes in the pickle) and converted by gnomix_amd.convert.from_reference_model.
-Training mode (7-8 arguments) is out of scope.
+Training mode (7-8 arguments, gnomix.py:158-306, 374-403):
+
+    python -m gnomix_amd <query_file|None> <output_basename> <chr_nr> <phase> <genetic_map_file> <reference_file> <sample_map_file> [config.yaml]
+
+simulates admixed haplotypes from the reference panel (gnomix_amd.simulate: draws on the host, matrix on the GPU), trains base and
+smoother on the device (HipGnomix.train) and writes <output_basename>/models/<name>_chm_<chr>/<name>_chm_<chr>.gnx (a flat .gnx,
+not the reference's pickled .pkl; it loads through the 5-argument form), analysis/confusion_matrix_{train,val}.txt and config.txt.
+Mode "best" (CovRSK base, an SVC fit) is not built.  The extra config key model.smoother_kwargs (a dict) is passed to the smoother's
+training (e.g. {max_ep: 20} for "large", {n_rounds: 50} for the default tree smoother).
 Outputs: <output_basename>/query_results.msp, .fb (+ .lai, query_results_bed/, query_file_phased.vcf as configured).
 """
 from __future__ import annotations
@@ -15,9 +23,10 @@ import sys
 
 import numpy as np
 
-USAGE = ("Usage when using a pre-trained model:\n"
-         "   $ python3 gnomix.py <query_file> <output_basename> <chr_nr> <phase> <path_to_model>\n"
-         "(training a model from scratch is not part of the MI355X inference path; train with the reference and export)")
+USAGE = ("Usage when training a model from scratch:\n"
+         "   $ python3 gnomix.py <query_file> <output_basename> <chr_nr> <phase> <genetic_map_file> <reference_file> <sample_map_file> [config.yaml]\n"
+         "Usage when using a pre-trained model:\n"
+         "   $ python3 gnomix.py <query_file> <output_basename> <chr_nr> <phase> <path_to_model>")
 
 
 PLANES_SUFFIX = ".planes"   # <model>.gnx.planes: the logistic base's prepared planes (DeviceModel.export_prepared), a cache
@@ -226,8 +235,7 @@ def main(argv=None):
     if "torch" not in sys.modules:
         os.environ.setdefault("GNX_NO_TORCH", "1")   # the command line needs no torch: do not pay for its import
     if len(argv) in (8, 9):
-        print("Training mode is not part of this build.\n" + USAGE)
-        return 2
+        return train_main(argv)
     if len(argv) != 6:
         if len(argv) > 1:
             print("Error: Incorrect number of arguments.")
@@ -274,6 +282,155 @@ def main(argv=None):
         if os.environ.get("GNX_CLI_TIMING"):
             T["since_process_start"] = _since_process_start()
             sys.stderr.write("gnomix_amd timings (s): " + ", ".join("%s %.3f" % kv for kv in T.items()) + "\n")
+    return 0
+
+
+def training_setup(argv):
+    """the host half of training mode up to the first device call: arguments, config (the reference's defaults under the file's
+    values), the checks the reference makes (gnomix.py:335-389) -> (base_args, config, error message or None)"""
+    base_args = {"mode": "train", "query_file": argv[1] if argv[1].strip() != "None" else None, "output_basename": argv[2],
+                 "chm": argv[3], "phase": argv[4].lower() == "true", "genetic_map_file": argv[5], "reference_file": argv[6],
+                 "sample_map_file": argv[7], "config_file": argv[8] if len(argv) == 9 else "./config.yaml"}
+    from .simulate import merge_config
+    user = {}
+    if len(argv) == 9 or os.path.exists(base_args["config_file"]):
+        if not os.path.exists(base_args["config_file"]):
+            return base_args, None, "config file %s not found" % base_args["config_file"]
+        import yaml
+        with open(base_args["config_file"]) as f:
+            user = yaml.safe_load(f) or {}
+    config = merge_config(user)
+    sim = config["simulation"]
+    mode = config["model"].get("inference") or "default"
+    if mode == "best":
+        return base_args, config, ('model mode "best" (CovRSK base, an SVC fit per window) cannot be trained by this build: '
+                                   'use "default", "fast" or "large"')
+    if mode not in ("default", "fast", "large"):
+        return base_args, config, "unknown model mode %r" % mode
+    from_path = sim.get("run") is False and sim.get("path") is not None
+    need = ["genetic_map_file"] + ([] if from_path else ["reference_file", "sample_map_file"])
+    for k in need:
+        if not os.path.isfile(base_args[k]):
+            return base_args, config, "%s %s not found" % (k.replace("_", " "), base_args[k])
+    if from_path and not os.path.isfile(os.path.join(sim["path"], "metadata.pkl")):
+        return base_args, config, "no simulated data at %s (metadata.pkl missing)" % sim["path"]
+    if base_args["query_file"] and not os.path.isfile(base_args["query_file"]):
+        return base_args, config, "query file %s not found" % base_args["query_file"]
+    return base_args, config, None
+
+
+def _initial_model(C, M, A, S, context, mode, seed, meta):
+    """an untrained model of the mode's kinds: gnomix_amd trains in place of a description that can be loaded (zero logistic
+    weights; the smoother's starting point: one placeholder tree, zero CRF weights, Conv1d's default initialisation)"""
+    from .model import GnxModelData
+    from . import synth
+    W = C // M
+    d = GnxModelData(C=C, M=M, A=A, S=S, context=context, snp_pos=np.asarray(meta["snp_pos"]), snp_ref=np.asarray(meta["snp_ref"]),
+                     snp_alt=np.asarray(meta["snp_alt"]), population_order=list(meta["pop_order"]))
+    d.base_kind, d.lr_coef, d.lr_intercept = "logistic", np.zeros((W, A, M + 2 * context + C - M * W)), np.zeros((W, A))
+    if mode == "fast":
+        d.smooth_kind, d.crf_state, d.crf_trans = "crf", np.zeros((A, A)), np.zeros((A, A))
+    elif mode == "large":
+        from .train import cnn_init
+        d.smooth_kind = "cnn"
+        d.cnn_weight, d.cnn_bias = cnn_init(A, S if S % 2 else S - 1, seed=seed)
+    else:
+        d.smooth_kind = "xgb"
+        for k, v in synth.synthetic_trees(1, A, (S if S % 2 else S - 1) * A, seed=seed).items():
+            setattr(d, k, v)
+    return d
+
+
+def write_model_config(model, path):
+    """what Gnomix.write_config (src/model.py) means to write: every public int / float / str / bool attribute, one per line"""
+    with open(path, "w") as f:
+        for attr in sorted(vars(model)):
+            val = getattr(model, attr)
+            if not attr.startswith("_") and isinstance(val, (int, float, str, bool, np.integer, np.floating)):
+                f.write("{}\t{}\n".format(attr, val))
+
+
+def train_main(argv):
+    """gnomix.py:372-403 (simulate_splits, train_model) and, with a query, run_inference on the model just trained"""
+    base_args, config, err = training_setup(argv)
+    if err:
+        print("Error: " + err)
+        return 2
+    from time import perf_counter as clock
+    from . import simulate as sim_mod
+    from . import _lib
+    from .gnomix import HipGnomix
+    print("Launching in training mode...")
+    verbose = bool(config.get("verbose"))
+    sim, mcfg, chm = config["simulation"], config["model"], base_args["chm"]
+    out = base_args["output_basename"]
+    os.makedirs(out, exist_ok=True)
+    gmap = sim_mod.read_genetic_map(base_args["genetic_map_file"], chm)
+    T = {}
+    t0 = clock()
+    if sim.get("run") is False and sim.get("path") is not None:
+        print("Using pre-simulated data from: ", sim["path"])
+        ratios = {k: v for k, v in sim["splits"]["ratios"].items() if not (k == "val" and v == 0)}
+        gens = {k: v for k, v in sim_mod.split_generations(sim).items() if k in ratios}
+        data, meta = sim_mod.read_generated_data(sim["path"], gens, mcfg["window_size_cM"])
+        C, M, A = meta["C"], meta["M"], meta["A"]
+        ctx = _lib.default_context(0)
+        T["read_data"] = clock() - t0
+    else:
+        try:
+            plan = sim_mod.plan_splits(base_args["reference_file"], gmap, base_args["sample_map_file"], config, chm=chm, verbose=False)
+        except ValueError as e:
+            print("Error: %s" % e)
+            return 2
+        T["plan"] = clock() - t0
+        C, A = plan.C, plan.A
+        M = plan.window_size(mcfg["window_size_cM"])
+        meta = {"snp_pos": plan.meta["pos_snps"], "snp_ref": plan.meta["ref_snps"], "snp_alt": plan.meta["alt_snps"], "pop_order": plan.pop_order}
+        if verbose:
+            print("Running Simulation...")
+        t0 = clock()
+        ctx = _lib.default_context(0)
+        keep = not sim.get("rm_data")
+        (data, anc) = plan.materialise(ctx, M=M, want_anc=True) if keep else (plan.materialise(ctx, M=M), None)
+        T["simulate"] = clock() - t0
+        if keep:
+            t0 = clock()
+            X_all = np.concatenate([d[0] for d in data if d[0] is not None])
+            sim_mod.write_generated_data(plan, os.path.join(out, "generated_data"), X_all, anc, gen_map=gmap)
+            del X_all, anc
+            T["write_data"] = clock() - t0
+    mode = mcfg.get("inference") or "default"
+    context = int(M * mcfg["context_ratio"])
+    d = _initial_model(C, M, A, int(mcfg["smooth_size"]), context, mode, config["seed"], meta)
+    d.gen_map_pos, d.gen_map_cm = gmap["pos"].to_numpy(np.int64), gmap["pos_cm"].to_numpy(np.float64)
+    model = HipGnomix(d, ctx=ctx, calibrate=bool(mcfg.get("calibrate")))
+    kw = dict(mcfg.get("smoother_kwargs") or {})
+    if mode == "large":
+        kw.setdefault("seed", config["seed"])
+    if verbose:
+        print("Building model...")
+    t0 = clock()
+    model.train(data=data, retrain_base=bool(mcfg.get("retrain_base")), evaluate=True, verbose=verbose, **kw)
+    T["train"] = clock() - t0
+    validate = data[2][0] is not None
+    name = mcfg.get("name") or "model"
+    repo = os.path.join(out, "models", "%s_chm_%s" % (name, chm))
+    os.makedirs(os.path.join(repo, "analysis"), exist_ok=True)
+    model.save(os.path.join(repo, "%s_chm_%s.gnx" % (name, chm)))
+    for split in (["train", "val"] if validate else ["train"]):
+        cm, _ = model.Confusion_Matrices[split]
+        n_digits = int(np.ceil(np.log10(np.max(cm))))
+        np.savetxt(os.path.join(repo, "analysis", "confusion_matrix_%s.txt" % split), cm, fmt="%-" + str(n_digits) + ".0f")
+        print("Estimated " + split + " accuracy: {}%".format(model.accuracies["smooth_" + split + "_acc"]))
+    write_model_config(model, os.path.join(repo, "config.txt"))
+    print("Model, info and analysis saved at {}".format(repo))
+    if os.environ.get("GNX_CLI_TIMING"):
+        sys.stderr.write("gnomix_amd training timings (s): " + ", ".join("%s %.3f" % kv for kv in T.items()) + "\n")
+    if base_args["query_file"]:
+        print("Launching inference...")
+        inf = config.get("inference") or {}
+        run_inference(base_args, model, snp_level=bool(inf.get("snp_level_inference")), bed_file_output=bool(inf.get("bed_file_output")),
+                      verbose=True)
     return 0
 
 

@@ -16,6 +16,8 @@
  *   gnx_train_gbt         <- Smoother.train(B, y) of XGB_Smoother         src/Smooth/smooth.py:28-38, src/model.py:137
  *   gnx_train_crf         <- Smoother.train(B, y) of CRF_Smoother         src/Smooth/crf.py:51-58, src/Smooth/models.py:27-32
  *   gnx_train_cnn         <- Smoother.train(B, y) of CNN_Smoother         src/Smooth/cnn.py:104-118, src/Smooth/models.py:35-42
+ *   gnx_simulate_admix    <- LAIDataset.simulate + write_output + data_process   src/laidataset.py:119-201, 362-428,
+ *                                                                          src/preprocess.py:37-82, gnomix.py:102-156
  *
  * Conventions
  *   - return 0 (GNX_OK) or a negative GNX_E* code; the message is kept per context (gnx_last_error).
@@ -410,6 +412,30 @@ int gnx_train_crf(gnx_ctx* ctx, const void* B, int32_t b_is_f64, const int32_t* 
  * Host arithmetic (no context, no device): x, y (n,) float32 in any order -> thresholds x_thr / y_thr (caller-allocated, n each),
  * *n_thr of them; they go into gnx_model_desc.calib_x / calib_y (as float64) with calib_is_f32 = 1. */
 int gnx_fit_isotonic_f32(const float* x, const float* y, int64_t n, float* x_thr, float* y_thr, int64_t* n_thr);
+
+/* ---- the admixture simulator's training data: LAIDataset.simulate (src/laidataset.py:362-428) + admix (:119-176) write each
+ *      simulated haplotype as founder slices; write_output (:180-201) stacks them; window_reshape / data_process
+ *      (src/preprocess.py:37-82, called from gnomix.py:139-146) reduce the per-SNP ancestry to window labels.
+ * The random draws are the host's (gnomix_amd/simulate.py); they arrive as segment tables.  Haplotype n (0 <= n < N) is the
+ * segments seg_off[n] .. seg_off[n+1]-1: segment s covers SNPs seg_begin[s] .. (the next begin, or C) - 1 and copies them from
+ * founder row seg_src[s] of F (n_founder_haps rows of C int8 values, ldf bytes apart; founder haplotype = 2 * sample + {0 maternal,
+ * 1 paternal}).  anc_of_src[r] is row r's ancestry code; a code >= A marks a row that is not a founder (never referenced, not
+ * checked).  Outputs: X (N, C) rows ldx bytes apart = mat_vcf_2d; Y (N, W) int32 window labels, W = C / M, windows 0 .. W-2 of M
+ * SNPs and the last of M + C % M, label = the most frequent ancestry with ties to the smallest code (scipy.stats.mode); anc
+ * (N, C) = mat_map, written only when non-NULL.
+ * GNX_EINVAL, nothing written: bad sizes, 1 <= A <= GNX_SIM_MAX_A violated, seg_off[0] != 0 or a haplotype without segments, a
+ * first begin != 0, begins not increasing or >= C, a source outside [0, n_founder_haps) or not a founder, a founder row holding a
+ * value other than 0 / 1 (the message names the row and the SNP).  N == 0: GNX_OK, nothing launched.
+ * The _dev form validates on the device and reads the verdict back (it synchronises the context stream once); the host form
+ * stages everything through device memory of its own, freed before it returns. */
+#define GNX_SIM_MAX_A 255
+int gnx_simulate_admix_dev(gnx_ctx* ctx, const int8_t* dF, int64_t n_founder_haps, int64_t ldf, int64_t C, int64_t M,
+                           const int64_t* d_seg_off, const int32_t* d_seg_begin, const int32_t* d_seg_src,
+                           const uint8_t* d_anc_of_src, int32_t A, int64_t N, int8_t* dX, int64_t ldx, int32_t* dY,
+                           uint8_t* d_anc);
+int gnx_simulate_admix(gnx_ctx* ctx, const int8_t* F, int64_t n_founder_haps, int64_t ldf, int64_t C, int64_t M,
+                       const int64_t* seg_off, const int32_t* seg_begin, const int32_t* seg_src, const uint8_t* anc_of_src,
+                       int32_t A, int64_t N, int8_t* X, int64_t ldx, int32_t* Y, uint8_t* anc);
 
 /* per-kernel device time, measured with hipEvents on the context stream around every launch */
 int gnx_profile_enable(gnx_ctx* ctx, int on);
