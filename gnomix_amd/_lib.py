@@ -68,6 +68,11 @@ class TrainInfo(C.Structure):
                 ("worst_rel_gradient", C.c_double), ("objective_sum", C.c_double)]
 
 
+class SvcTrainInfo(C.Structure):
+    _fields_ = [("smo_iterations", C.c_int64), ("n_solves", C.c_int32), ("n_guarded", C.c_int32), ("gram_ms", C.c_double),
+                ("smo_ms", C.c_double), ("platt_ms", C.c_double)]
+
+
 class GbtParams(C.Structure):
     _fields_ = [("n_rounds", C.c_int32), ("max_depth", C.c_int32), ("max_bin", C.c_int32), ("tree_method", C.c_int32),
                 ("eta", C.c_double), ("lam", C.c_double), ("gamma", C.c_double), ("min_child_weight", C.c_double),
@@ -143,6 +148,9 @@ SYMBOLS = {
                                      C.POINTER(TrainInfo)]),
     "gnx_train_logistic_dev": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, C.c_double, C.c_double, C.c_int32, _VP, _I64,
                                          _VP, C.POINTER(TrainInfo)]),
+    "gnx_train_svc": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, C.c_int32] + [_VP] * 8 + [C.POINTER(SvcTrainInfo)]),
+    "gnx_train_svc_dev": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, C.c_int32] + [_VP] * 8 + [C.POINTER(SvcTrainInfo)]),
+    "gnx_svc_fold_permutation": (C.c_int, [C.c_uint32, C.c_int32, _VP]),
     "gnx_fit_isotonic_f32": (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP]),
     "gnx_train_gbt": (C.c_int, [_VP, _VP, C.c_int32, _VP, _I64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(GbtParams)] + [_VP] * 8),
     "gnx_train_crf": (C.c_int, [_VP, _VP, C.c_int32, _VP, _I64, C.c_int32, C.c_int32, C.POINTER(CrfParams), _VP, _VP, C.POINTER(CrfInfo)]),

@@ -27,15 +27,25 @@ class HipBase:
         self.time = {}
 
     def train(self, X, y, verbose=False):
-        """Base.train (base.py:104-127) for the logistic base: fits every window's LogisticRegression on the device and swaps
-        the device model for the freshly trained one.  X (N, C) int8, y (N, W) window labels."""
-        from .train import train_logistic_base
+        """Base.train (base.py:104-127) on the device, X (N, C) int8, y (N, W) window labels; swaps the device model for the freshly
+        trained one.  Logistic base: every window's LogisticRegression.  CovRSK base: every window's SVC(kernel=CovRSK,
+        probability=True), seeded as the reference's sequential fits are (window 0 from numpy's global generator, like
+        BaseLibSVM.fit; later windows from the state each CovRSK kernel call leaves), and the global generator is left where the
+        reference leaves it."""
+        from .train import train_logistic_base, train_svc_base, svc_seed_chain, svc_rng_after_kernel, SVC_SEED_HIGH
         from .model import DeviceModel
-        if self.dev.data.base_kind not in (None, "logistic"):
-            raise NotImplementedError("on-device training is built for the logistic base (LogisticRegressionBase)")
+        d = self.dev.data
+        if d.base_kind not in (None, "logistic", "covrsk"):
+            raise NotImplementedError("on-device training is built for the logistic and the CovRSK (SVC) bases")
         t = time()
-        self.train_info = train_logistic_base(self.dev.data, X, y, ctx=self.dev.ctx)
-        self.dev = DeviceModel(self.dev.data, ctx=self.dev.ctx)   # (a HipGnomix re-binds its smoother: HipGnomix.train_base)
+        if d.base_kind == "covrsk":
+            widths = [d.window_width(w) for w in range(d.W)]
+            seeds = svc_seed_chain(widths, np.random.randint(SVC_SEED_HIGH))
+            self.train_info = train_svc_base(d, X, y, ctx=self.dev.ctx, seeds=seeds)
+            svc_rng_after_kernel(widths[-1])
+        else:
+            self.train_info = train_logistic_base(d, X, y, ctx=self.dev.ctx)
+        self.dev = DeviceModel(d, ctx=self.dev.ctx)   # (a HipGnomix re-binds its smoother: HipGnomix.train_base)
         self.time["train"] = time() - t
         return self
 

@@ -320,25 +320,9 @@ def training_setup(argv):
 
 
 def _initial_model(C, M, A, S, context, mode, seed, meta):
-    """an untrained model of the mode's kinds: gnomix_amd trains in place of a description that can be loaded (zero logistic
-    weights; the smoother's starting point: one placeholder tree, zero CRF weights, Conv1d's default initialisation)"""
-    from .model import GnxModelData
-    from . import synth
-    W = C // M
-    d = GnxModelData(C=C, M=M, A=A, S=S, context=context, snp_pos=np.asarray(meta["snp_pos"]), snp_ref=np.asarray(meta["snp_ref"]),
-                     snp_alt=np.asarray(meta["snp_alt"]), population_order=list(meta["pop_order"]))
-    d.base_kind, d.lr_coef, d.lr_intercept = "logistic", np.zeros((W, A, M + 2 * context + C - M * W)), np.zeros((W, A))
-    if mode == "fast":
-        d.smooth_kind, d.crf_state, d.crf_trans = "crf", np.zeros((A, A)), np.zeros((A, A))
-    elif mode == "large":
-        from .train import cnn_init
-        d.smooth_kind = "cnn"
-        d.cnn_weight, d.cnn_bias = cnn_init(A, S if S % 2 else S - 1, seed=seed)
-    else:
-        d.smooth_kind = "xgb"
-        for k, v in synth.synthetic_trees(1, A, (S if S % 2 else S - 1) * A, seed=seed).items():
-            setattr(d, k, v)
-    return d
+    """an untrained model of the mode's kinds (gnomix_amd.train.untrained_model)"""
+    from .train import untrained_model
+    return untrained_model(C, M, A, S, context, mode, seed=seed, meta=meta)
 
 
 def write_model_config(model, path):

@@ -46,7 +46,7 @@ class HipGnomix:
         return path
 
     def train_base(self, X, y):
-        """the base half of Gnomix.train (src/model.py:113, 155): fit the logistic base on the device, then re-bind base,
+        """the base half of Gnomix.train (src/model.py:113, 155): fit the base (logistic or CovRSK SVC) on the device, then re-bind base,
         smoother and the fused path to the freshly loaded model"""
         self.base.train(X, y)
         self.dev = self.base.dev
@@ -103,6 +103,11 @@ class HipGnomix:
             self.accuracies, self.Confusion_Matrices = self._score_splits(
                 {"train": ((X_t1, y_t1), (B_t2, y_t2)), "val": None if X_v is None else ((X_v, y_v), None)})
         if retrain_base:
+            if self.dev.data.base_kind == "covrsk":
+                # the reference's kernel calls between the two fits (its base predictions of train2 / val) leave numpy's global
+                # generator where a CovRSK kernel call on the last window leaves it; this build's predictions do not touch it
+                from .train import svc_rng_after_kernel
+                svc_rng_after_kernel(self.data.window_width(self.W - 1))
             parts = [(X_t1, y_t1), (X_t2, y_t2)] + ([(X_v, y_v)] if X_v is not None else [])
             self.train_base(np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]))
         self.time["training"] = round(time() - t0, 2)

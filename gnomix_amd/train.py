@@ -198,3 +198,140 @@ def train_crf_smoother(data: GnxModelData, B, y, **kw) -> dict:
     st, tr, info = train_crf_arrays(B, y, **kw)
     data.smooth_kind, data.crf_state, data.crf_trans = "crf", st, tr
     return info
+
+
+# ---- the CovRSK SVC base (mode "best") ---------------------------------------------------------------------------------------
+SVC_SEED_HIGH = int(np.iinfo("i").max)          # BaseLibSVM.fit: seed = rnd.randint(np.iinfo("i").max)
+SVC_KERNEL_KINDS = {"CovRSK": 0, "string_kernel": 2}   # GNX_SVC_KERNEL_SUBSTRINGS (CovSample lengths), GNX_SVC_KERNEL_ALL_LENGTHS
+
+
+def svc_rng_after_kernel(width):
+    """numpy's global generator where one CovRSK kernel call on a window of `width` SNPs leaves it: CovSample
+    (string_kernel.py:80-89) runs np.random.seed(37), then width - 1 draws"""
+    np.random.seed(37)
+    if int(width) > 1:
+        np.random.rand(int(width) - 1)
+
+
+def svc_seed_chain(widths, first_seed):
+    """libsvm seeds of the reference's sequential window fits (CovRSKBase.train): window 0 uses `first_seed`, drawn from the global
+    generator before any kernel call (BaseLibSVM.fit draws it before _compute_kernel); window w >= 1 draws from the state that window
+    w-1's kernel call left, RandomState(37) after width_{w-1} - 1 draws -> uint32 (W,)"""
+    seeds, memo = [int(first_seed)], {}
+    for w in range(1, len(widths)):
+        pw = int(widths[w - 1])
+        if pw not in memo:
+            rs = np.random.RandomState(37)
+            if pw > 1:
+                rs.random_sample(pw - 1)
+            memo[pw] = int(rs.randint(SVC_SEED_HIGH))
+        seeds.append(memo[pw])
+    return np.asarray(seeds, dtype=np.uint32)
+
+
+def svc_fold_permutation(seed, l):
+    """the Platt fold permutation libsvm draws for an l-row class pair fitted with `seed` (gnx_svc_fold_permutation)"""
+    perm = np.empty(max(int(l), 1), np.int32)
+    rc = _lib.load().gnx_svc_fold_permutation(int(seed), int(l), perm.ctypes.data)
+    if rc != _lib.GNX_OK:
+        raise _lib.GnxError(rc, "gnx_svc_fold_permutation: bad length")
+    return perm[:int(l)]
+
+
+def window_columns(C, M, context, w):
+    """columns of X that window w reads, in order: base.py's reflect padding (base.py:41-44) and window slicing (:146-164)"""
+    W, rem = C // M, C - M * (C // M)
+    width = M + 2 * context + (rem if w == W - 1 else 0)
+    p = w * M + np.arange(width)
+    return np.where(p < context, context - 1 - p, np.where(p < context + C, p - context, C - 1 - (p - context - C)))
+
+
+def train_svc_arrays(X, y, M, context, A, seeds, kernel="CovRSK", ctx=None, device=0):
+    """SVC(kernel=<kernel>, probability=True).fit of every window on the device (gnx_train_svc).  X (N, C) int8 {0,1,2}, y (N, W)
+    labels, seeds (W,) libsvm seeds -> dict of (W, ...) arrays in sklearn's layout (support / dual_coef padded to N columns, n_sv
+    valid) and an info dict"""
+    if kernel not in SVC_KERNEL_KINDS:
+        raise ValueError(f"kernel must be one of {sorted(SVC_KERNEL_KINDS)}")
+    ctx = ctx or _lib.default_context(device)
+    X = np.ascontiguousarray(X, dtype=np.int8)
+    N, Cn = X.shape
+    W = Cn // int(M)
+    y = np.ascontiguousarray(y, dtype=np.int32)
+    if y.shape != (N, W):
+        raise ValueError(f"y must be (N, W) = ({N}, {W}), got {y.shape}")
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
+    if seeds.shape != (W,):
+        raise ValueError(f"seeds must be (W,) = ({W},), got {seeds.shape}")
+    A, P = int(A), int(A) * (int(A) - 1) // 2
+    out = dict(n_sv=np.zeros(W, np.int32), n_support=np.zeros((W, A), np.int32), support=np.zeros((W, N), np.int32),
+               dual_coef=np.zeros((W, A - 1, N), np.float64), intercept=np.zeros((W, P), np.float64),
+               prob_a=np.zeros((W, P), np.float64), prob_b=np.zeros((W, P), np.float64))
+    info = _lib.SvcTrainInfo()
+    ctx.check(ctx.lib.gnx_train_svc(ctx.h, X.ctypes.data, N, Cn, y.ctypes.data, Cn, int(M), int(context), A, SVC_KERNEL_KINDS[kernel],
+                                    seeds.ctypes.data, *(out[k].ctypes.data for k in ("n_sv", "n_support", "support", "dual_coef",
+                                                                                      "intercept", "prob_a", "prob_b")), C.byref(info)))
+    return out, dict(smo_iterations=info.smo_iterations, n_solves=info.n_solves, n_guarded=info.n_guarded, gram_ms=info.gram_ms,
+                     smo_ms=info.smo_ms, platt_ms=info.platt_ms)
+
+
+def train_svc_base(data: GnxModelData, X, y, ctx=None, seeds=None, kernel="CovRSK", **kw) -> dict:
+    """fit the CovRSK SVC base of `data` in place (data.svc, base_kind "covrsk") -> info.  Each window keeps only its support
+    rows as `xfit` (support = arange(n_sv)): the full training window would put N x width bytes per window into the .gnx.  The
+    sklearn-order support_ indices (rows of X) are info["support"]."""
+    from .convert import string_kernel_lengths
+    W = data.W
+    if seeds is None:
+        seeds = svc_seed_chain([data.window_width(w) for w in range(W)], np.random.randint(SVC_SEED_HIGH))
+    X = np.ascontiguousarray(X, dtype=np.int8)
+    res, info = train_svc_arrays(X, y, data.M, data.context, data.A, seeds, kernel=kernel, ctx=ctx, **kw)
+    svc, sup_raw = [], []
+    for w in range(W):
+        n = int(res["n_sv"][w])
+        sup = res["support"][w, :n].copy()
+        cols = window_columns(data.C, data.M, data.context, w)
+        svc.append(dict(xfit=np.ascontiguousarray(X[sup][:, cols]), support=np.arange(n, dtype=np.int32),
+                        dual_coef=np.ascontiguousarray(res["dual_coef"][w, :, :n]), intercept=res["intercept"][w].copy(),
+                        prob_a=res["prob_a"][w].copy(), prob_b=res["prob_b"][w].copy(), n_support=res["n_support"][w].copy(),
+                        ms=string_kernel_lengths(len(cols), kernel)))
+        sup_raw.append(sup)
+    data.base_kind, data.svc = "covrsk", svc
+    info["support"] = sup_raw
+    info["seeds"] = np.asarray(seeds, dtype=np.uint32)
+    return info
+
+
+def untrained_model(C, M, A, S, context, mode, seed=None, meta=None):
+    """an untrained model of a mode's kinds (the reference's config model.inference: "default", "fast", "large", "best"), ready to
+    be loaded and then trained in place: zero logistic weights or, for "best", one placeholder SVC per window (A zero rows, zero
+    coefficients); the smoother's starting point: one placeholder tree, zero CRF weights, Conv1d's default initialisation.
+    meta: optional dict with snp_pos, snp_ref, snp_alt, pop_order (the simulation's metadata)"""
+    from . import synth
+    from .convert import cov_sample
+    if mode not in ("default", "fast", "large", "best"):
+        raise ValueError("unknown model mode %r" % (mode,))
+    W = C // M
+    kw = {}
+    if meta is not None:
+        kw = dict(snp_pos=np.asarray(meta["snp_pos"]), snp_ref=np.asarray(meta["snp_ref"]), snp_alt=np.asarray(meta["snp_alt"]),
+                  population_order=list(meta["pop_order"]))
+    d = GnxModelData(C=C, M=M, A=A, S=S, context=context, **kw)
+    if mode == "best":
+        P = A * (A - 1) // 2
+        d.base_kind, d.svc = "covrsk", []
+        for w in range(W):
+            width = d.window_width(w)
+            d.svc.append(dict(xfit=np.zeros((A, width), np.int8), support=np.arange(A, dtype=np.int32),
+                              dual_coef=np.zeros((A - 1, A)), intercept=np.zeros(P), prob_a=np.zeros(P), prob_b=np.zeros(P),
+                              n_support=np.ones(A, np.int32), ms=cov_sample(width)))
+    else:
+        d.base_kind, d.lr_coef, d.lr_intercept = "logistic", np.zeros((W, A, M + 2 * context + C - M * W)), np.zeros((W, A))
+    if mode == "fast":
+        d.smooth_kind, d.crf_state, d.crf_trans = "crf", np.zeros((A, A)), np.zeros((A, A))
+    elif mode == "large":
+        d.smooth_kind = "cnn"
+        d.cnn_weight, d.cnn_bias = cnn_init(A, S if S % 2 else S - 1, seed=seed)
+    else:
+        d.smooth_kind = "xgb"
+        for k, v in synth.synthetic_trees(1, A, (S if S % 2 else S - 1) * A, seed=seed).items():
+            setattr(d, k, v)
+    return d

@@ -13,6 +13,7 @@
  *   gnx_smooth_rows       <- smoother.model.predict_proba(rows)         src/Gnofix/gnofix.py:157
  *   gnx_gnofix            <- Gnomix.phase(X, B) -> gnofix() per indiv.  src/model.py:188-214, src/Gnofix/gnofix.py:58-208
  *   gnx_train_logistic    <- Base.train(X, y) of LogisticRegressionBase   src/Base/base.py:104-127, src/model.py:113,155
+ *   gnx_train_svc         <- Base.train(X, y) of CovRSKBase (mode "best") src/Base/base.py:104-127, src/Base/models.py:195-215
  *   gnx_train_gbt         <- Smoother.train(B, y) of XGB_Smoother         src/Smooth/smooth.py:28-38, src/model.py:137
  *   gnx_train_crf         <- Smoother.train(B, y) of CRF_Smoother         src/Smooth/crf.py:51-58, src/Smooth/models.py:27-32
  *   gnx_train_cnn         <- Smoother.train(B, y) of CNN_Smoother         src/Smooth/cnn.py:104-118, src/Smooth/models.py:35-42
@@ -64,7 +65,7 @@ enum {
                             loaded; load again without it (and write a new one) */
 };
 
-enum { GNX_SVC_KERNEL_SUBSTRINGS = 0, GNX_SVC_KERNEL_POLY = 1 };
+enum { GNX_SVC_KERNEL_SUBSTRINGS = 0, GNX_SVC_KERNEL_POLY = 1, GNX_SVC_KERNEL_ALL_LENGTHS = 2 /* gnx_train_svc only */ };
 enum { GNX_BASE_NONE = 0, GNX_BASE_LOGISTIC = 1, GNX_BASE_COVRSK_SVC = 2, GNX_BASE_FOREST = 3, GNX_BASE_RFOREST = 4 };
 enum { GNX_SMOOTH_NONE = 0, GNX_SMOOTH_XGB = 1, GNX_SMOOTH_CRF = 2, GNX_SMOOTH_CNN = 3 };
 
@@ -334,6 +335,40 @@ int gnx_train_logistic(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t ldx, co
 int gnx_train_logistic_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const int32_t* dy, int64_t C, int64_t M,
                            int64_t ctx_snps, int32_t A, double C_reg, double tol, int32_t max_iter, double* coef, int64_t ldc,
                            double* intercept, gnx_train_info* info);
+
+/* ---- training the CovRSK SVC base (mode "best"): CovRSKBase.train (src/Base/base.py:104-127, src/Base/models.py:195-215: per
+ *      window sklearn.svm.SVC(kernel=CovRSK, probability=True).fit(X_w, y_w)).  Restates sklearn's libsvm (C-SVC, C = 1, eps = 1e-3,
+ *      shrinking, one model per class pair, each with Platt's 5-fold cross-validated sigmoid) on the window's exact integer Gram matrix,
+ *      so the fit equals sklearn's on the same Gram and seed.
+ *   X (N, ldx) int8 {0,1,2}, y (N, W) int32 labels in [0, A), W = C / M; windows of the reflect-padded rows as base.py slices them
+ *     (M + 2 ctx_snps SNPs, the last one C % M more)
+ *   kernel_kind: GNX_SVC_KERNEL_SUBSTRINGS = CovRSK (the CovSample(width) lengths, string_kernel.py:80-110) or
+ *     GNX_SVC_KERNEL_ALL_LENGTHS = the plain string kernel (every length, string_kernel.py:5-24)
+ *   seeds (W,): libsvm's random_seed of each window's fit (what sklearn drew: gnomix_amd.train.svc_seed_chain)
+ *   outputs (HOST, caller-allocated), P = A (A - 1) / 2: n_sv (W); n_support (W, A); support (W, N): the first n_sv[w] entries are
+ *     sklearn's support_ (rows of X, class-major); dual_coef (W, A - 1, N): the first n_sv[w] columns of each row are _dual_coef_;
+ *     intercept / prob_a / prob_b (W, P) = _intercept_ / _probA / _probB
+ * Refused before anything is written: a window without a row of some class (GNX_EINVAL: the reference's fit fails there), a label
+ * outside [0, A) (GNX_EINVAL), GNX_SVC_KERNEL_POLY (GNX_EUNSUPPORTED), a window whose largest kernel value g(width) is not below 2^24
+ * (not exact in float) or wider than 16 384 SNPs (GNX_EINVAL), N whose Gram (N^2 floats) exceeds GNX_SVC_GRAM_BUDGET (GNX_EINVAL).
+ * Windows are batched so that a batch's Gram matrices stay within GNX_SVC_GRAM_BUDGET.  The _dev form takes device X / y; it reads
+ * y back to the host (the problems are laid out there).  Both are synchronous. */
+#define GNX_SVC_GRAM_BUDGET (8ull << 30)
+typedef struct gnx_svc_train_info {
+  int64_t smo_iterations;  /* over every solve: the full problems and the Platt fold problems */
+  int32_t n_solves;
+  int32_t n_guarded;       /* solves stopped by the hang guard (50 M iterations) or with a non-finite rho: 0 on a sound fit */
+  double gram_ms, smo_ms, platt_ms;  /* device time of the passes, summed over batches */
+} gnx_svc_train_info;
+int gnx_train_svc(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t ldx, const int32_t* y, int64_t C, int64_t M, int64_t ctx_snps,
+                  int32_t A, int32_t kernel_kind, const uint32_t* seeds, int32_t* n_sv, int32_t* n_support, int32_t* support,
+                  double* dual_coef, double* intercept, double* prob_a, double* prob_b, gnx_svc_train_info* info);
+int gnx_train_svc_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const int32_t* dy, int64_t C, int64_t M, int64_t ctx_snps,
+                      int32_t A, int32_t kernel_kind, const uint32_t* seeds, int32_t* n_sv, int32_t* n_support, int32_t* support,
+                      double* dual_coef, double* intercept, double* prob_a, double* prob_b, gnx_svc_train_info* info);
+/* the Platt fold permutation of an l-row class-pair problem fitted with libsvm seed `seed` (svm_binary_svc_probability: sklearn's
+ * mt19937 + bounded_rand_int); host only, no context */
+int gnx_svc_fold_permutation(uint32_t seed, int32_t l, int32_t* perm);
 
 /* ---- training the tree smoother: Smoother.train of XGB_Smoother (src/Smooth/smooth.py:28-38, src/Smooth/models.py:14-20:
  *      XGBClassifier(n_estimators=100, max_depth=4, learning_rate=0.1, reg_lambda=1, objective='multi:softprob').fit(slide_window(B), y))
