@@ -79,6 +79,12 @@ __device__ __forceinline__ double gnx_exp_sc(double x) {
 //   gnx_rcp_nr(y)   v_rcp_f64 + two Newton steps: within 1 ulp of 1 / y (five instructions)
 //   gnx_sigmoid     1 / (1 + e^-t) with -t capped at 708 (e^708 = 3e307 stays finite: beyond it the reference's own value is below
 //                   1e-307 — or, past 709.78, exactly 0 — and its row normaliser 0 / 0)
+//                   and floored at -746 (e^-746 is 0 in float64 and 1 + e^-t is 1 from -t = -37 down, so no finite result changes;
+//                   but the argument reduction of gnx_exp_scN is only good to |x| ~ 1e15, and beyond ~1e40 its polynomial overflows:
+//                   an intercept or logit of 1e300 gave e^-t = +-inf and a NaN out of the Newton steps, where the reference gives 1).
+//                   A row whose every class is beyond the cap comes out FINITE (1 / A each when all are), where the reference has
+//                   0 / 0 = NaN; and a class beyond the cap is lifted to 3.3e-308, which shows in B only when the row's largest
+//                   sigmoid is itself below ~1e-290 (every class at -t > 667).  Deliberate; DESIGN.md 4.1, tests/test_gpu_lr_numerics.py.
 //   normaliser      p * gnx_rcp_nr(sum): one reciprocal per row, one multiplication per class
 // against the reference's float64 division each result differs by at most ~2 ulp; the tests' bar on B is 1e-12.
 __device__ __forceinline__ double gnx_rcp_nr(double y) {
@@ -91,7 +97,7 @@ __device__ __forceinline__ double gnx_rcp_nr(double y) {
 template <int N>
 __device__ __forceinline__ void gnx_sigmoidN(double (&v)[N]) {  // in: t (logit + intercept); out: 1 / (1 + e^-t); N independent chains
 #pragma unroll
-  for (int i = 0; i < N; ++i) v[i] = __builtin_fmin(-v[i], 708.0);
+  for (int i = 0; i < N; ++i) v[i] = __builtin_fmax(__builtin_fmin(-v[i], 708.0), -746.0);
   gnx_exp_scN<N>(v);
   double r[N], e[N];
 #pragma unroll

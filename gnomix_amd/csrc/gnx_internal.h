@@ -134,6 +134,7 @@ struct BaseLRDev {
 };
 constexpr int GNX_LR_FLAT_COLS = 24;     // class columns per SNP the flat layout is built for
 constexpr int GNX_LR_FLAT_TILES = 11;    // ceil(24 * 7 / 16)
+constexpr int GNX_LR_FLAT_MAX_SPAN = 84; // runs of 256 SNPs a window may span in the flat kernel: 257 * 128 * 3 * 256 * span < 2^31 (int32 limb pairs, fields up to 3)
 
 struct BaseLRLaunch {
   const int8_t* X;

@@ -84,6 +84,26 @@ static uint64_t lr_key(const gnx_model_desc* d, int64_t W, int64_t M_, int64_t r
   return h;
 }
 
+// every coefficient a model uses (row i, class a: the first width_i float64 of its lr_ldc) and every intercept is a finite number.
+// A NaN is invisible to a running maximum (std::max(a, NaN) is a) and has no fixed-point image (llrint of it is unspecified: seven
+// garbage digits), an infinity none either: such a model is refused before anything is prepared, whichever kernels it would run on.
+static bool lr_all_finite(const gnx_model_desc* d, int64_t W, int64_t M_, int64_t rem) {
+  for (int64_t k = 0; k < W * d->A; ++k)
+    if (!std::isfinite(d->lr_intercept[k])) return false;
+  std::vector<uint8_t> bad(parallel_max_threads(), 0);
+  parallel_ranges((size_t)W, 16, [&](size_t lo, size_t hi, unsigned tid) {
+    for (size_t i = lo; i < hi; ++i) {
+      const int64_t width = M_ + ((int64_t)i == W - 1 ? rem : 0);
+      for (int a = 0; a < d->A; ++a) {
+        const double* row = d->lr_coef + ((size_t)i * d->A + a) * (size_t)d->lr_ldc;
+        for (int64_t k = 0; k < width; ++k)
+          if (!std::isfinite(row[k])) bad[tid] = 1;
+      }
+    }
+  });
+  return std::find(bad.begin(), bad.end(), (uint8_t)1) == bad.end();
+}
+
 template <typename T>
 static int dev_upload_raw(gnx_model* m, const void* src, size_t bytes, const T** out, size_t pad_bytes) {
   void* p = nullptr;
@@ -107,6 +127,7 @@ int gnx_build_lr(gnx_model* m, const gnx_model_desc* d) {
   const int64_t W = C / M, rem = C - M * W, M_ = M + 2 * cx, Cp = C + 2 * cx;
   if (!d->lr_coef || !d->lr_intercept) return fail(ctx, GNX_EINVAL, "logistic base: lr_coef / lr_intercept is NULL");
   if (d->lr_ldc < M_ + rem) return fail(ctx, GNX_EINVAL, "logistic base: lr_ldc < M + 2*ctx + rem");
+  if (!lr_all_finite(d, W, M_, rem)) return fail(ctx, GNX_EINVAL, "logistic base: non-finite coefficient or intercept (NaN / Inf)");
   const int64_t R = (M_ + M - 1) / M;
   const int64_t NC = R * A;
   const int NT = (int)((NC + 15) / 16);
@@ -222,7 +243,8 @@ int gnx_build_lr(gnx_model* m, const gnx_model_desc* d) {
             V[vi] = wsum;
             if (m->lr_i8) {
               Vwin[vi] = (int32_t)i;
-              maxabs[(size_t)i] = std::max(maxabs[(size_t)i], std::fabs(wsum));
+              // (a folded sum of finite weights can still overflow to Inf, or be Inf - Inf: NaN counts as the largest value here)
+              maxabs[(size_t)i] = std::isfinite(wsum) ? std::max(maxabs[(size_t)i], std::fabs(wsum)) : std::numeric_limits<double>::infinity();
             }
           }
         }
@@ -242,7 +264,7 @@ int gnx_build_lr(gnx_model* m, const gnx_model_desc* d) {
     const uint8_t* blob_v2 = ph ? blob_v8 + ((ph->v8_bytes + 15) & ~(int64_t)15) : nullptr;
     if (ph) std::memcpy(wscale.data(), blob + sizeof(GnxPreparedHdr), (size_t)W * 8);
     else for (int64_t i = 0; i < W; ++i) {
-      if (!(maxabs[(size_t)i] < 1e300)) return fail(ctx, GNX_EINVAL, "logistic base: non-finite coefficient");
+      if (!(maxabs[(size_t)i] < 1e300)) return fail(ctx, GNX_EINVAL, "logistic base: coefficient beyond 1e300 (or a folded sum that overflows)");
       if (maxabs[(size_t)i] > 0.0) fexp[(size_t)i] = 53 - std::ilogb(maxabs[(size_t)i]);
       wscale[(size_t)i] = std::ldexp(1.0, -fexp[(size_t)i]);
     }

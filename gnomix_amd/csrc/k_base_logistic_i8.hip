@@ -6,9 +6,12 @@
 //    v_mfma_i32_16x16x64_i8 (row = haplotype lane&15, k = the 16 SNPs of k-block lane>>4) — no conversion;
 //  * each float64 weight is fixed-point: q = round(c * 2^f_w) (f_w per window so |q| < 2^54), split into
 //    LIMBS = 7 balanced base-256 digits d_l in [-128,127]; digit plane l of the 14 (= R*A) class columns is
-//    one B operand.  Products <= 2*128 and K <= a few thousand keep every int32 accumulator exact, so the
+//    one B operand.  An X byte enters as the signed int8 it is (the reference's codes are 0, 1, 2; 3 is the
+//    largest a packed row can hold): |acc_l| <= 128 * max|x| * K for a window of K SNPs, an exact int32 while
+//    128 * max|x| * K < 2^31 (x <= 3: K < 5.59e6 SNPs; any int8: K < 131 072), so the
 //    logit  sum_k x_k q_k  is computed EXACTLY and order-independently;
-//  * recombination: hi = sum_{l>=3} acc_l 2^{8(l-3)}, lo = sum_{l<3} acc_l 2^{8l} in int64 (both < 2^53), then
+//  * recombination: hi = sum_{l>=3} acc_l 2^{8(l-3)}, lo = sum_{l<3} acc_l 2^{8l} in int64 (both < 2^53 while
+//    2^24 * 1.01 * 128 * max|x| * K < 2^53: K < 1.39e6 SNPs for x <= 3, the binding limit on a window's width), then
 //    Z = (double(hi) * 2^24 + double(lo)) * 2^-f_w : ONE float64 rounding.  Versus the reference's float64
 //    dot product the only difference is the 2^-56 relative weight quantisation — below BLAS reordering noise;
 //  * per 64-SNP chunk: 7 MFMAs (~16 cycles each) instead of 16 f64 MFMAs (64 cycles each): the matrix pipe

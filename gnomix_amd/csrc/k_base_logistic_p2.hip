@@ -76,8 +76,9 @@ __device__ __forceinline__ v4i unpack16(int w) {  // 16 two-bit fields -> 16 int
 }
 
 // Z = (hi 2^24 + lo) 2^-f_w with hi = sum_{l>=3} acc_l 2^{8(l-3)}, lo = sum_{l<3} acc_l 2^{8l}: the same exact integers
-// k_base_logistic_i8's combine() forms in int64 (|acc_l| < 2^20 for K <= 2500 SNPs, so |lo| < 2^37, |hi| < 2^45: every fma below is
-// exact), here on the float64 pipe: 7 conversions + 5 fmas instead of ~60 instructions of 64-bit integer arithmetic and two
+// k_base_logistic_i8's combine() forms in int64 (|acc_l| <= 128 * 3 * K for a window of K SNPs of 2-bit fields: an int32 while
+// K < 5.59e6, and |lo| < 2^17 * 1.01 |acc|, |hi| < 2^24 * 1.01 |acc| stay below 2^53, so that every fma below is exact, while
+// K < 1.39e6 — three orders of magnitude past any window of the reference), here on the float64 pipe: 7 conversions + 5 fmas instead of ~60 instructions of 64-bit integer arithmetic and two
 // int64 -> double conversions per accumulator register.  One rounding (the last addition), as there: bit-identical Z.
 __device__ __forceinline__ double combine(const v4i (&acc)[LIMBS], int reg, double scale) {
   const double lo = __builtin_fma(__builtin_fma((double)acc[2][reg], 256.0, (double)acc[1][reg]), 256.0, (double)acc[0][reg]);
@@ -979,8 +980,8 @@ __global__ __launch_bounds__((CW + EW + 2) * 64) void k_base_logistic_p2f(BaseLR
         for (int mt = 0; mt < MT; ++mt) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {  // int32 16x16 C/D layout: column = lane & 15, row = 4 (lane >> 4) + reg
-            // limbs in pairs, p_k = a_2k + 256 a_2k+1 in int32 (|a| <= 256 K for a window of K SNPs: the launcher declines models with
-            // wider windows), V = p_0 + 2^16 p_1 + 2^32 p_2 + 2^48 a_6 as P + 2^32 Q with P, Q exact in float64: ONE rounding, that of combine()
+            // limbs in pairs, p_k = a_2k + 256 a_2k+1 in int32 (|a| <= 384 K for a window of K SNPs: the launcher declines models whose
+            // windows span more than 84 runs = 21 504 SNPs), V = p_0 + 2^16 p_1 + 2^32 p_2 + 2^48 a_6 as P + 2^32 Q with P, Q exact in float64: ONE rounding, that of combine()
             int pk[3];
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
@@ -1099,12 +1100,14 @@ hipError_t launch_flat(const BaseLRLaunch& L, int n_cu, const gnx_tune& tune, hi
   constexpr bool NODBG = false;
   BaseLRLaunch P = L;
   P.flags = tune.lr_flags;
-  {  // limb pairs in int32 at a window's end: |a_2k + 256 a_2k+1| <= 257 * 256 K for a window of K SNPs — K < 32 640.  A model with
-     // wider windows (none of the reference's configurations) is declined: the caller widens the rows and runs the int8 kernels.
-     // GNX_LR_FLAGS bit 25: decline always (tests)
+  {  // limb pairs in int32 at a window's end: a digit is at most 128 and a 2-bit field at most 3 (gnx_pack_x packs the code 3 too), so
+     // |a_l| <= 384 K for a window of K SNPs and |a_2k + 256 a_2k+1| <= 257 * 384 K, below 2^31 for K < 21 760 = 85 runs of 256 SNPs.
+     // A window that spans more than 84 runs (none of the reference's configurations: chr22 windows span ten) is declined: the caller
+     // widens the rows and runs the int8 kernels.  (The limit was 120 runs, derived for fields <= 2: between 85 and 120 runs rows of
+     // 3s could wrap a pair.)  GNX_LR_FLAGS bit 25: decline always (tests)
     int span = 0;
     for (int64_t w = 0; w < L.W; ++w) span = std::max(span, L.h_win_chunk1[(size_t)w] - L.h_win_chunk0[(size_t)w]);
-    if (span > 120 || (tune.lr_flags & (1 << 25))) return hipErrorNotSupported;
+    if (span > GNX_LR_FLAT_MAX_SPAN || (tune.lr_flags & (1 << 25))) return hipErrorNotSupported;
   }
   const int haps_per_block = CW * MT * 16;
   const int64_t gx = (L.N + haps_per_block - 1) / haps_per_block;

@@ -37,7 +37,11 @@
  *     threads or processes (one process per GPU under torch.distributed).
  *   - haplotype rows 2i, 2i+1 of X are the two haplotypes of individual i (src/utils.py:121-123);
  *     X values are {0,1,2=missing} int8, the value 2 enters the logistic model as the number 2
- *     (sklearn sees it as a feature value) and string kernels as a third symbol.
+ *     (sklearn sees it as a feature value) and string kernels as a third symbol.  The logistic base takes
+ *     ANY int8 value as the signed number it is (exact in the integer kernels while 128 * max|x| * K < 2^31
+ *     for windows of K SNPs); 2-bit rows hold 0..3 and gnx_pack_x refuses anything else (GNX_EINVAL).
+ *   - a NaN or an infinity in lr_coef (the columns a window uses) or lr_intercept fails gnx_model_load with
+ *     GNX_EINVAL; so does a coefficient beyond 1e300.
  */
 #ifndef GNOMIX_HIP_H
 #define GNOMIX_HIP_H
