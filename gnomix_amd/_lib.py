@@ -14,9 +14,10 @@ import weakref
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("GNX_LIBRARY") or os.path.join(_HERE, "libgnomix_hip.so")   # GNX_LIBRARY: another build of the same ABI (kernel A/B timing, scripts/dev)
 
-GNX_ABI_VERSION = 14
+GNX_ABI_VERSION = 15
 GNX_OK, GNX_EINVAL, GNX_ENOMEM, GNX_EHIP, GNX_EUNSUPPORTED, GNX_ESTATE, GNX_ESTALE = 0, -1, -2, -3, -4, -5, -6
 BASE_NONE, BASE_LOGISTIC, BASE_COVRSK_SVC, BASE_FOREST, BASE_RFOREST = 0, 1, 2, 3, 4
+SVC_KERNEL_SUBSTRINGS, SVC_KERNEL_POLY, SVC_KERNEL_ALL_LENGTHS, SVC_KERNEL_RBF = 0, 1, 2, 3
 SMOOTH_NONE, SMOOTH_XGB, SMOOTH_CRF, SMOOTH_CNN = 0, 1, 2, 3
 K_BASE_LOGISTIC, K_SMOOTH_XGB, K_BASE_COVRSK, K_SMOOTH_CRF, K_GNOFIX, K_SMOOTH_ROWS, K_CALIBRATE, K_BASE_FOREST, K_SMOOTH_CNN = range(9)
 KERNEL_NAMES = {K_BASE_LOGISTIC: "k_base_logistic", K_SMOOTH_XGB: "k_smooth_xgb", K_BASE_COVRSK: "k_base_covrsk",
@@ -39,7 +40,7 @@ class SvcWindow(C.Structure):
     _fields_ = [("xfit", C.c_void_p), ("n_fit", C.c_int32), ("width", C.c_int32), ("support", C.c_void_p),
                 ("n_sv", C.c_int32), ("dual_coef", C.c_void_p), ("intercept", C.c_void_p), ("prob_a", C.c_void_p),
                 ("prob_b", C.c_void_p), ("n_support", C.c_void_p), ("ms", C.c_void_p), ("n_ms", C.c_int32),
-                ("kernel_kind", C.c_int32), ("poly_p", C.c_double), ("run_value", C.c_void_p)]
+                ("kernel_kind", C.c_int32), ("poly_p", C.c_double), ("run_value", C.c_void_p), ("gamma", C.c_double)]
 
 
 class ModelDesc(C.Structure):
@@ -71,6 +72,10 @@ class TrainInfo(C.Structure):
 class SvcTrainInfo(C.Structure):
     _fields_ = [("smo_iterations", C.c_int64), ("n_solves", C.c_int32), ("n_guarded", C.c_int32), ("gram_ms", C.c_double),
                 ("smo_ms", C.c_double), ("platt_ms", C.c_double)]
+
+
+class SvcParams(C.Structure):
+    _fields_ = [("kernel_kind", C.c_int32), ("reserved", C.c_int32), ("C", C.c_double), ("gamma", C.c_double)]
 
 
 class GbtParams(C.Structure):
@@ -150,6 +155,8 @@ SYMBOLS = {
                                          _VP, C.POINTER(TrainInfo)]),
     "gnx_train_svc": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, C.c_int32] + [_VP] * 8 + [C.POINTER(SvcTrainInfo)]),
     "gnx_train_svc_dev": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, C.c_int32] + [_VP] * 8 + [C.POINTER(SvcTrainInfo)]),
+    "gnx_train_svc2": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, C.POINTER(SvcParams)] + [_VP] * 8 + [C.POINTER(SvcTrainInfo)]),
+    "gnx_train_svc2_dev": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, C.POINTER(SvcParams)] + [_VP] * 8 + [C.POINTER(SvcTrainInfo)]),
     "gnx_svc_fold_permutation": (C.c_int, [C.c_uint32, C.c_int32, _VP]),
     "gnx_fit_isotonic_f32": (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP]),
     "gnx_train_gbt": (C.c_int, [_VP, _VP, C.c_int32, _VP, _I64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(GbtParams)] + [_VP] * 8),

@@ -31,14 +31,18 @@ class HipBase:
         trained one.  Logistic base: every window's LogisticRegression.  CovRSK base: every window's SVC(kernel=CovRSK,
         probability=True), seeded as the reference's sequential fits are (window 0 from numpy's global generator, like
         BaseLibSVM.fit; later windows from the state each CovRSK kernel call leaves), and the global generator is left where the
-        reference leaves it."""
+        reference leaves it.  RBF windows (SVMBase): every window's SVC(C=100, gamma, probability=True), one seed per window drawn
+        from numpy's global generator in window order."""
         from .train import train_logistic_base, train_svc_base, svc_seed_chain, svc_rng_after_kernel, SVC_SEED_HIGH
-        from .model import DeviceModel
+        from .model import DeviceModel, svc_window_is_rbf
         d = self.dev.data
         if d.base_kind not in (None, "logistic", "covrsk"):
-            raise NotImplementedError("on-device training is built for the logistic and the CovRSK (SVC) bases")
+            raise NotImplementedError("on-device training is built for the logistic and the SVC (CovRSK, RBF) bases")
         t = time()
-        if d.base_kind == "covrsk":
+        if d.base_kind == "covrsk" and d.svc and svc_window_is_rbf(d.svc[0]):
+            # SVMBase: the reference's workers fit with unseeded generators; one seed per window from the global generator, in order
+            self.train_info = train_svc_base(d, X, y, ctx=self.dev.ctx, kernel="rbf", gamma=float(d.svc[0]["gamma"]))
+        elif d.base_kind == "covrsk":
             widths = [d.window_width(w) for w in range(d.W)]
             seeds = svc_seed_chain(widths, np.random.randint(SVC_SEED_HIGH))
             self.train_info = train_svc_base(d, X, y, ctx=self.dev.ctx, seeds=seeds)

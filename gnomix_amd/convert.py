@@ -36,7 +36,12 @@ def string_kernel_lengths(width, kernel_name="CovRSK"):
 
 
 def svc_window_from_sklearn(svc, width, kernel_name="CovRSK"):
-    """One fitted sklearn.svm.SVC(kernel=callable, probability=True) -> the dict GnxModelData.svc holds."""
+    """One fitted sklearn.svm.SVC(probability=True) -> the dict GnxModelData.svc holds: kernel=callable (the string-kernel bases)
+    or kernel="rbf" (SVMBase, src/Base/models.py:148-159)."""
+    if isinstance(getattr(svc, "kernel", None), str):
+        if svc.kernel != "rbf":
+            raise NotImplementedError(f"SVC kernel {svc.kernel!r}: only 'rbf' (SVMBase) and the string kernels are built")
+        return svc_rbf_window_from_sklearn(svc, width)
     xfit = getattr(svc, "_BaseLibSVM__Xfit")
     d = dict(xfit=np.ascontiguousarray(xfit, dtype=np.int8), support=svc.support_.astype(np.int32),
              dual_coef=np.ascontiguousarray(svc._dual_coef_, dtype=np.float64),
@@ -49,6 +54,30 @@ def svc_window_from_sklearn(svc, width, kernel_name="CovRSK"):
     else:
         d["ms"] = string_kernel_lengths(width, kernel_name)
     return d
+
+
+def svc_rbf_window_from_sklearn(svc, width):
+    """One fitted SVC(kernel="rbf", probability=True) -> an RBF window dict.  Only the support rows are kept (support_vectors_,
+    float64 in sklearn: they must be whole numbers in 0..2, the SNP codes), gamma is the fitted _gamma."""
+    sv = np.asarray(svc.support_vectors_)
+    if hasattr(sv, "toarray"):
+        sv = sv.toarray()
+    sv = np.asarray(sv, dtype=np.float64)
+    if sv.ndim != 2 or sv.shape[1] != int(width):
+        raise ValueError(f"support_vectors_ must be (n_sv, {int(width)}), got {sv.shape}")
+    if not np.all(np.isfinite(sv)) or np.any(sv != np.rint(sv)) or sv.min() < 0 or sv.max() > 2:
+        raise ValueError("support_vectors_ must hold the SNP codes 0, 1, 2 (whole numbers): the RBF base computes |x - y|^2 "
+                         "in integers")
+    gamma = float(svc._gamma)
+    if not (np.isfinite(gamma) and gamma > 0):
+        raise ValueError(f"_gamma must be finite and > 0, got {gamma}")
+    n = sv.shape[0]
+    return dict(xfit=np.ascontiguousarray(sv, dtype=np.int8), support=np.arange(n, dtype=np.int32),
+                dual_coef=np.ascontiguousarray(svc._dual_coef_, dtype=np.float64),
+                intercept=np.ascontiguousarray(svc._intercept_, dtype=np.float64),
+                prob_a=np.ascontiguousarray(svc._probA, dtype=np.float64),
+                prob_b=np.ascontiguousarray(svc._probB, dtype=np.float64),
+                n_support=np.asarray(svc._n_support).astype(np.int32), kernel=np.array("rbf"), gamma=np.float64(gamma))
 
 
 def poly_run_values(width, p=1.2):

@@ -364,7 +364,9 @@ int gnx_model_load(gnx_ctx* ctx, const gnx_model_desc* d, gnx_model** out) {
   switch (d->base_kind) {
     case GNX_BASE_NONE: break;
     case GNX_BASE_LOGISTIC: rc = gnx_build_lr(m, d); break;
-    case GNX_BASE_COVRSK_SVC: rc = gnx_build_covrsk(m, d); break;
+    case GNX_BASE_COVRSK_SVC:  // the same libsvm model; the RBF kernel has its own preparation and pass 2a
+      rc = (d->svc && d->svc[0].kernel_kind == GNX_SVC_KERNEL_RBF) ? gnx_build_svc_rbf(m, d) : gnx_build_covrsk(m, d);
+      break;
     case GNX_BASE_FOREST: rc = gnx_build_forest(m, d); break;
     case GNX_BASE_RFOREST: rc = gnx_build_rforest(m, d); break;
     default: rc = fail(ctx, GNX_EINVAL, "unknown base_kind");
@@ -445,6 +447,10 @@ int gnx_base_predict_dev(gnx_model* m, const int8_t* dX, int64_t N, int64_t ldx,
   if (N < 0 || ldx < m->info.C || (N > 0 && !dX)) return fail(ctx, GNX_EINVAL, "base_predict: bad X / N / ldx");
   if (N == 0 || (!d_b32 && !d_b64)) return GNX_OK;
   GNX_BIND_DEVICE(ctx);
+  if (m->info.base_kind == GNX_BASE_COVRSK_SVC && m->rbf) {
+    ProfScope ps(ctx, GNX_K_BASE_COVRSK);
+    return gnx_base_predict_rbf(m, dX, N, ldx, d_b32, d_b64);
+  }
   if (m->info.base_kind == GNX_BASE_COVRSK_SVC) {
     const int64_t Cp = m->info.C + 2 * m->info.ctx, nwp = (Cp + 31) / 32 + 2;
     int rc = ws_reserve(ctx, ctx->ws_bits, (size_t)N * 2 * nwp * 4);

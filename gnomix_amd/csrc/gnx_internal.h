@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -415,6 +416,8 @@ struct ForestLaunch {
   double* b64;
 };
 
+struct SvcRbfModel;  // svm/k_base_rbf.hip
+
 struct gnx_model {
   gnx_ctx* ctx = nullptr;
   gnx_model_info info{};
@@ -428,6 +431,7 @@ struct gnx_model {
   int64_t lr_v8_bytes = 0, lr_v2_bytes = 0;   // V8 / V2 (or V2F) as uploaded, without padding
   SmoothXGBDev xgb;
   CovRSKDev svc;
+  std::shared_ptr<SvcRbfModel> rbf;  // set instead of `svc` when the windows are GNX_SVC_KERNEL_RBF (svm/k_base_rbf.hip)
   ForestDev forest;
   // class-major xgboost-schema copy for the rows kernel
   const int32_t* class_tree0 = nullptr;  // device [A+1]
@@ -483,6 +487,9 @@ void gnx_pin_free(void* p);
 // model preparation (gnx_model_build.hip), called by gnx_model_load
 int gnx_build_lr(gnx_model* m, const gnx_model_desc* d);
 int gnx_build_covrsk(gnx_model* m, const gnx_model_desc* d);
+// the RBF SVC base (svm/k_base_rbf.hip): model preparation and pass 2a (distances on the int8 matrix cores -> r_ij) + pass 2b
+int gnx_build_svc_rbf(gnx_model* m, const gnx_model_desc* d);
+int gnx_base_predict_rbf(gnx_model* m, const int8_t* dX, int64_t N, int64_t ldx, float* d_b32, double* d_b64);
 int gnx_build_forest(gnx_model* m, const gnx_model_desc* d);
 int gnx_build_rforest(gnx_model* m, const gnx_model_desc* d);
 int gnx_build_xgb(gnx_model* m, const gnx_model_desc* d);
@@ -545,6 +552,8 @@ hipError_t gnx_launch_smooth_rows(const SmoothXGBDev& d, const float* rows, int6
 hipError_t gnx_launch_pack_bits(const int8_t* X, int64_t N, int64_t ldx, int64_t C, int64_t ctx, int64_t nwp,
                                 uint32_t* planes, hipStream_t s);
 hipError_t gnx_launch_covrsk(const CovRSKLaunch& L, hipStream_t s);
+// pass 2b alone (multiclass_probability on L.rpair of the chunk n_first / n_count -> b32 / b64): shared with the RBF base
+hipError_t gnx_launch_svc_couple(const CovRSKLaunch& L, hipStream_t s);
 size_t gnx_covrsk_lds_bytes(int A, int max_nw, int max_width);
 hipError_t gnx_launch_gnofix_prep(const GnofixLaunch& L, int64_t n_ind, hipStream_t s);
 hipError_t gnx_launch_gnofix(const GnofixLaunch& L, int64_t n_ind, int threads, hipStream_t s);

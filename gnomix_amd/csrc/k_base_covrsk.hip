@@ -617,10 +617,8 @@ hipError_t gnx_launch_covrsk(const CovRSKLaunch& L0, hipStream_t s0) {
   const int A = L0.A, P = A * (A - 1) / 2;
   auto r16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
   const size_t lds_dec = r16((size_t)2 * L0.max_nw * 64 * 4) + r16((size_t)(L0.max_width + 2) * 8) + r16((size_t)P * 64 * 8);
-  const size_t lds_cpl = (size_t)(P + A * A + 2 * A) * 64 * 8;
   GNX_LDS_OPTIN(lds_dec, k_covrsk_dec<false>);
   GNX_LDS_OPTIN(lds_dec, k_covrsk_dec<true>);
-  GNX_LDS_OPTIN(lds_cpl, k_svc_couple);
   // the pairwise probabilities travel through a bounded global buffer: haplotypes in chunks of rpair_haps
   for (int64_t n0 = 0; n0 < L0.N; n0 += L0.rpair_haps) {
     CovRSKLaunch L = L0;
@@ -659,12 +657,22 @@ hipError_t gnx_launch_covrsk(const CovRSKLaunch& L0, hipStream_t s0) {
       }
       w0 = w1;
     }
-    const int64_t total = L.n_count * L.W;
-    hipStream_t s = s0;
     if (forked) { (void)hipEventRecord(L0.ev_join, L0.aux); (void)hipStreamWaitEvent(s0, L0.ev_join, 0); }
-    if (A == 7) hipLaunchKernelGGL(k_svc_couple_reg<7>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, s, L);
-    else if (A == 3) hipLaunchKernelGGL(k_svc_couple_reg<3>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, s, L);
-    else hipLaunchKernelGGL(k_svc_couple, dim3((unsigned)((total + 63) / 64)), dim3(64), lds_cpl, s, L);
+    (void)gnx_launch_svc_couple(L, s0);
+  }
+  return hipGetLastError();
+}
+
+hipError_t gnx_launch_svc_couple(const CovRSKLaunch& L, hipStream_t s) {
+  const int A = L.A, P = A * (A - 1) / 2;
+  const int64_t total = L.n_count * L.W;
+  if (total <= 0) return hipSuccess;
+  const size_t lds_cpl = (size_t)(P + A * A + 2 * A) * 64 * 8;
+  if (A == 7) hipLaunchKernelGGL(k_svc_couple_reg<7>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, s, L);
+  else if (A == 3) hipLaunchKernelGGL(k_svc_couple_reg<3>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, s, L);
+  else {
+    GNX_LDS_OPTIN(lds_cpl, k_svc_couple);
+    hipLaunchKernelGGL(k_svc_couple, dim3((unsigned)((total + 63) / 64)), dim3(64), lds_cpl, s, L);
   }
   return hipGetLastError();
 }

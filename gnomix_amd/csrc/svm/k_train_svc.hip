@@ -20,6 +20,10 @@
 //    reconstruct_gradient with every element summed in libsvm's order.  G, G_bar, alpha, status, y and the map live in
 //    global memory (L2-resident at these sizes); Q columns are read straight from the window's Gram.
 //  * k_svc_heldout: decision values of the held-out rows under their fold model, in svm_predict_values' order.
+//  * GNX_SVC_KERNEL_RBF (SVMBase, src/Base/models.py:148-159: SVC(C=100., gamma=0.001, probability=True)): the Gram pass is
+//    k_base_rbf.hip's (|x - y|^2 on the int8 matrix cores, Q = (float) T[d2] with T = the host's exp(-gamma k): libsvm's Qfloat of
+//    the double kernel value, QD = 1); the solver is the same with C a parameter; the held-out decision values take the DOUBLE
+//    kernel value T[d2] (svm_predict_values calls k_function, not Q).
 //  * k_svc_sigmoid: sigmoid_train (Newton with backtracking, 100 iterations), one thread per (window, pair).
 // The fold permutations (mt19937 + sklearn's Lemire bounded_rand_int) and the model assembly in sklearn's layout are host work.
 //
@@ -39,6 +43,7 @@
 //   LIABILITY, OR TORT (INCLUDING NEGLIGENCE OR OTHERWISE) ARISING IN ANY WAY OUT OF THE USE OF THIS SOFTWARE, EVEN IF ADVISED
 //   OF THE POSSIBILITY OF SUCH DAMAGE.
 #include "../gnx_internal.h"
+#include "gnx_svc_rbf.h"
 
 #include <cmath>
 #include <random>
@@ -159,6 +164,7 @@ struct SmoArgs {
   double* rho;           // per solve
   int32_t* iters;        // per solve
   int32_t* guard;        // per solve: 1 = stopped by the hang guard or a non-finite rho
+  double C;              // libsvm's cost Cp = Cn (1 for CovRSKBase, 100 for SVMBase; the fold models get the same through `weight`)
 };
 
 // (value, index) reductions over one wave: ties go to the larger index, as libsvm's sequential `>=` / `<=` scans
@@ -337,7 +343,7 @@ __global__ __launch_bounds__(64) void k_svc_smo(SmoArgs a) {
     ++iter;
 
     // ---- update alpha[i], alpha[j] (every lane computes the same values) ----
-    const double C_i = 1.0, C_j = 1.0;
+    const double C_i = a.C, C_j = a.C;
     const double Qij = (double)v.Q(i, j);
     const double QDi = v.QD(i), QDj = v.QD(j);
     const double Gi = v.G[i], Gj = v.G[j];
@@ -438,15 +444,24 @@ __global__ __launch_bounds__(64) void k_svc_smo(SmoArgs a) {
 // regrouped order (svm_predict_values: class 0 then class 1), minus rho, times submodel->label[0] = -1
 __global__ __launch_bounds__(256) void k_svc_heldout(const SvcSolve* solves, const float* gram, int64_t N, const int32_t* rows,
                                                       const double* alpha_out, const double* rho, int64_t n_tasks,
-                                                      const int32_t* t_solve, const int32_t* t_row, const int64_t* t_dst, double* decv) {
+                                                      const int32_t* t_solve, const int32_t* t_row, const int64_t* t_dst, double* decv,
+                                                      const int32_t* d2, const double* tab) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n_tasks) return;
   const SvcSolve s = solves[t_solve[t]];
   const float* Kx = gram + s.gram + (int64_t)t_row[t] * N;
   double sum = 0;
-  for (int e = 0; e < s.l; ++e) {
-    const double c = alpha_out[s.off + e];
-    if (fabs(c) > 0) sum += c * (double)Kx[rows[s.off + e]];
+  if (d2) {  // RBF: k_function's double kernel value, not the float Q
+    const int32_t* Dx = d2 + s.gram + (int64_t)t_row[t] * N;
+    for (int e = 0; e < s.l; ++e) {
+      const double c = alpha_out[s.off + e];
+      if (fabs(c) > 0) sum += c * tab[Dx[rows[s.off + e]]];
+    }
+  } else {
+    for (int e = 0; e < s.l; ++e) {
+      const double c = alpha_out[s.off + e];
+      if (fabs(c) > 0) sum += c * (double)Kx[rows[s.off + e]];
+    }
   }
   sum -= rho[t_solve[t]];
   decv[t_dst[t]] = sum * -1;
@@ -591,12 +606,14 @@ struct PairTask {  // one (window, class pair) of a batch
 };
 
 int train_svc_impl(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const int32_t* y, int64_t C, int64_t M, int64_t cx,
-                   int32_t A, int32_t kernel_kind, const uint32_t* seeds, int32_t* n_sv, int32_t* n_support, int32_t* support,
+                   int32_t A, const gnx_svc_params& prm, const uint32_t* seeds, int32_t* n_sv, int32_t* n_support, int32_t* support,
                    double* dual_coef, double* intercept, double* prob_a, double* prob_b, gnx_svc_train_info* info) {
+  const int32_t kernel_kind = prm.kernel_kind;
+  const bool rbf = kernel_kind == GNX_SVC_KERNEL_RBF;
   const int W = (int)(C / M), rem = (int)(C % M), P = A * (A - 1) / 2;
   const int width_main = (int)(M + 2 * cx), width_last = width_main + rem;
   // g(L) over the kernel's lengths (prefix-stable in the width: one table serves both widths)
-  const std::vector<int32_t> ms = kernel_lengths(kernel_kind, width_last);
+  const std::vector<int32_t> ms = rbf ? std::vector<int32_t>() : kernel_lengths(kernel_kind, width_last);
   std::vector<uint32_t> g(width_last + 1, 0);
   for (int L = 1; L <= width_last; ++L) {
     uint64_t s = 0;
@@ -605,22 +622,29 @@ int train_svc_impl(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const
     g[L] = (uint32_t)s;  // < 2^24: train_svc_check bounds g(width_last)
   }
   const int nwm = (width_last + 31) / 32;
+  // RBF: staged int8 rows (Np x kp per window) instead of bit-planes, the int32 distances beside the float Gram, one exp table
+  const int64_t Np = (N + 63) / 64 * 64;
+  const int kp = (width_last + 63) / 64 * 64;
+  std::vector<double> tab;
+  if (rbf) gnx_rbf_table(prm.gamma, gnx_rbf_table_len(width_last), tab);
   const size_t gram_w = (size_t)N * N * 4;
   // per window: every pair's full problem plus its folds' training parts: at most 5 l elements per pair, sum of l = (A - 1) N
   const size_t elems_w = (size_t)5 * (A - 1) * N;
   const size_t elem_bytes = 4 * 8 + 2 * 4 + 3;
-  size_t wbs = std::min<size_t>((size_t)W, GNX_SVC_GRAM_BUDGET / gram_w);
+  size_t wbs = std::min<size_t>((size_t)W, GNX_SVC_GRAM_BUDGET / (gram_w * (rbf ? 2 : 1)));
   wbs = std::min<size_t>(wbs, ((size_t)2 << 30) / (elems_w * elem_bytes));
   const int wb = (int)std::max<size_t>(1, std::min<size_t>(wbs, SVC_MAX_BATCH));
 
   // ---- device buffers, sized for a full batch ----
   const size_t max_solves = (size_t)wb * P * (1 + SVC_FOLDS), max_elems = (size_t)wb * elems_w;
   const size_t max_rows = (size_t)wb * (A - 1) * N, max_pairs = (size_t)wb * P;  // held-out tasks / decision values
-  const size_t bPl = up256((size_t)wb * N * 2 * nwm * 4), bGram = up256((size_t)wb * gram_w), bG = up256((size_t)(width_last + 1) * 4);
+  const size_t bXw = rbf ? up256((size_t)wb * Np * kp) : 0, bNrm = rbf ? up256((size_t)wb * Np * 4) : 0;
+  const size_t bD2 = rbf ? up256((size_t)wb * gram_w) : 0, bTab = rbf ? up256(tab.size() * 8) : 0;
+  const size_t bPl = rbf ? 0 : up256((size_t)wb * N * 2 * nwm * 4), bGram = up256((size_t)wb * gram_w), bG = up256((size_t)(width_last + 1) * 4);
   const size_t bSol = up256(max_solves * sizeof(SvcSolve)), bE8 = up256(max_elems * 8), bE4 = up256(max_elems * 4), bE1 = up256(max_elems);
   const size_t bS8 = up256(max_solves * 8), bS4 = up256(max_solves * 4);
   const size_t bT4 = up256(max_rows * 4), bT8 = up256(max_rows * 8), bP8 = up256(max_pairs * 8), bP4 = up256(max_pairs * 4);
-  const size_t total = bPl + bGram + bG + bSol + 4 * bE8 + 2 * bE4 + 3 * bE1 + bS8 + 2 * bS4 + 2 * bT4 + 2 * bT8 + 3 * bP8 + 2 * bP4;
+  const size_t total = bPl + bGram + bG + bSol + 4 * bE8 + 2 * bE4 + 3 * bE1 + bS8 + 2 * bS4 + 2 * bT4 + 2 * bT8 + 3 * bP8 + 2 * bP4 + bXw + bNrm + bD2 + bTab;
   DevBlock blk;
   hipError_t e = hipMalloc(&blk.p, total);
   if (e != hipSuccess) {
@@ -654,13 +678,18 @@ int train_svc_impl(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const
   double* dPb = (double*)take(bP8);
   int32_t* dPlen = (int32_t*)take(bP4);
   int32_t* dPci = (int32_t*)take(bP4);
+  int8_t* dXw = (int8_t*)take(bXw);
+  int32_t* dNrm = (int32_t*)take(bNrm);
+  int32_t* dD2 = rbf ? (int32_t*)take(bD2) : nullptr;
+  double* dTab = rbf ? (double*)take(bTab) : nullptr;
 
   hipStream_t s = ctx->stream;
   DevEvents ev;
   for (auto& x : ev.e) HIPCHK(ctx, hipEventCreate(&x));
   HIPCHK(ctx, hipMemcpyAsync(dg, g.data(), (size_t)(width_last + 1) * 4, hipMemcpyHostToDevice, s));
+  if (rbf) HIPCHK(ctx, hipMemcpyAsync(dTab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
   const size_t lds_g = (size_t)(width_last + 1) * 4;
-  if (lds_g > 64 * 1024) HIPCHK(ctx, hipFuncSetAttribute((const void*)k_svc_gram, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g));
+  if (!rbf && lds_g > 64 * 1024) HIPCHK(ctx, hipFuncSetAttribute((const void*)k_svc_gram, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g));
 
   gnx_svc_train_info inf{};
   std::vector<std::vector<int32_t>> cls_rows(A);
@@ -736,22 +765,27 @@ int train_svc_impl(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const
 
     // ---- Gram ----
     HIPCHK(ctx, hipEventRecord(ev.e[0], s));
-    const int64_t n_words = (int64_t)nb * N * nwm;
-    hipLaunchKernelGGL(k_svc_pack, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, s, dX, N, ldx, C, M, cx, w0, nb, W, rem, nwm, dPl);
-    HIPCHK(ctx, hipGetLastError());
-    const unsigned tiles = (unsigned)((N + 15) / 16);
-    hipLaunchKernelGGL(k_svc_gram, dim3(tiles, tiles, (unsigned)nb), dim3(256), lds_g, s, dPl, N, nwm, w0, W, width_main, width_last, dg, dGram);
-    HIPCHK(ctx, hipGetLastError());
+    if (rbf) {
+      HIPCHK(ctx, gnx_launch_rbf_stage(dX, N, ldx, C, M, cx, w0, nb, W, rem, Np, kp, dXw, dNrm, s));
+      HIPCHK(ctx, gnx_launch_rbf_gram(dXw, dNrm, N, Np, kp, nb, dTab, (int32_t)tab.size() - 1, dGram, dD2, s));
+    } else {
+      const int64_t n_words = (int64_t)nb * N * nwm;
+      hipLaunchKernelGGL(k_svc_pack, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, s, dX, N, ldx, C, M, cx, w0, nb, W, rem, nwm, dPl);
+      HIPCHK(ctx, hipGetLastError());
+      const unsigned tiles = (unsigned)((N + 15) / 16);
+      hipLaunchKernelGGL(k_svc_gram, dim3(tiles, tiles, (unsigned)nb), dim3(256), lds_g, s, dPl, N, nwm, w0, W, width_main, width_last, dg, dGram);
+      HIPCHK(ctx, hipGetLastError());
+    }
     HIPCHK(ctx, hipEventRecord(ev.e[1], s));
     // ---- SMO ----
-    SmoArgs sa{dSol, dGram, N, dRows, dYs, dGv, dGb, dAl, dAs, dYv, dSt, dAo, dRho, dIt, dGd};
+    SmoArgs sa{dSol, dGram, N, dRows, dYs, dGv, dGb, dAl, dAs, dYv, dSt, dAo, dRho, dIt, dGd, prm.C};
     hipLaunchKernelGGL(k_svc_smo, dim3((unsigned)n_sol), dim3(64), 0, s, sa);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(ev.e[2], s));
     // ---- Platt ----
     if (n_tasks) {
       hipLaunchKernelGGL(k_svc_heldout, dim3((unsigned)((n_tasks + 255) / 256)), dim3(256), 0, s, dSol, dGram, N, dRows, dAo, dRho, n_tasks,
-                         dTs, dTr, dTd, dDec);
+                         dTs, dTr, dTd, dDec, dD2, dTab);
       HIPCHK(ctx, hipGetLastError());
     }
     hipLaunchKernelGGL(k_svc_sigmoid, dim3((unsigned)((n_pairs + 63) / 64)), dim3(64), 0, s, n_pairs, dPoff, dPlen, dPci, dDec, dPa, dPb);
@@ -828,19 +862,29 @@ int train_svc_impl(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const
   return GNX_OK;
 }
 
-int train_svc_check(gnx_ctx* ctx, int64_t N, int64_t ldx, int64_t C, int64_t M, int64_t cx, int32_t A, int32_t kernel_kind,
+int train_svc_check(gnx_ctx* ctx, int64_t N, int64_t ldx, int64_t C, int64_t M, int64_t cx, int32_t A, const gnx_svc_params* prm,
                     const void* X, const void* y, const uint32_t* seeds, const void* o1, const void* o2, const void* o3, const void* o4,
                     const void* o5, const void* o6, const void* o7) {
   if (!ctx->usable) return gnx_fail(ctx, GNX_ESTATE, "context has no device (gnx_init failed)");
+  if (!prm) return gnx_fail(ctx, GNX_EINVAL, "train_svc: params is NULL");
+  const int32_t kernel_kind = prm->kernel_kind;
   if (!X || !y || !seeds || !o1 || !o2 || !o3 || !o4 || !o5 || !o6 || !o7) return gnx_fail(ctx, GNX_EINVAL, "train_svc: NULL array");
   if (A < 2 || A > 32) return gnx_fail(ctx, GNX_EINVAL, "A (ancestries) must be in [2, 32]");
   if (N < 2 || N > INT32_MAX || M <= 0 || C < M || cx < 0 || cx > C || ldx < C || C > INT32_MAX)
     return gnx_fail(ctx, GNX_EINVAL, "train_svc: bad N / C / M / ctx / ldx");
   if (kernel_kind == GNX_SVC_KERNEL_POLY)
     return gnx_fail(ctx, GNX_EUNSUPPORTED, "train_svc: the polynomial string kernel (GNX_SVC_KERNEL_POLY) has no trainer");
-  if (kernel_kind != GNX_SVC_KERNEL_SUBSTRINGS && kernel_kind != GNX_SVC_KERNEL_ALL_LENGTHS)
-    return gnx_fail(ctx, GNX_EINVAL, "train_svc: kernel_kind must be GNX_SVC_KERNEL_SUBSTRINGS or GNX_SVC_KERNEL_ALL_LENGTHS");
+  if (kernel_kind != GNX_SVC_KERNEL_SUBSTRINGS && kernel_kind != GNX_SVC_KERNEL_ALL_LENGTHS && kernel_kind != GNX_SVC_KERNEL_RBF)
+    return gnx_fail(ctx, GNX_EINVAL, "train_svc: kernel_kind must be GNX_SVC_KERNEL_SUBSTRINGS, GNX_SVC_KERNEL_ALL_LENGTHS or GNX_SVC_KERNEL_RBF");
+  if (!(prm->C > 0.0) || !std::isfinite(prm->C)) return gnx_fail(ctx, GNX_EINVAL, "train_svc: C must be finite and > 0");
   const int64_t width = M + 2 * cx + C % M;
+  if (kernel_kind == GNX_SVC_KERNEL_RBF) {
+    if (!(prm->gamma > 0.0) || !std::isfinite(prm->gamma)) return gnx_fail(ctx, GNX_EINVAL, "train_svc: gamma must be finite and > 0");
+    if (width > GNX_RBF_MAX_WIDTH) return gnx_fail(ctx, GNX_EINVAL, "train_svc: window wider than GNX_RBF_MAX_WIDTH SNPs");
+    if ((uint64_t)N * N * 8 > GNX_SVC_GRAM_BUDGET)
+      return gnx_fail(ctx, GNX_EINVAL, "train_svc: one window's Gram and distances (2 N^2 words) exceed GNX_SVC_GRAM_BUDGET");
+    return GNX_OK;
+  }
   if (width > SVC_MAX_WIDTH) return gnx_fail(ctx, GNX_EINVAL, "train_svc: window wider than " + std::to_string(SVC_MAX_WIDTH) + " SNPs");
   // the largest kernel value is K(x, x) = g(width): it must be an exact float
   uint64_t gw = 0;
@@ -876,12 +920,12 @@ extern "C" int gnx_svc_fold_permutation(uint32_t seed, int32_t l, int32_t* perm)
   return GNX_OK;
 }
 
-extern "C" int gnx_train_svc_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const int32_t* dy, int64_t C, int64_t M,
-                                 int64_t ctx_snps, int32_t A, int32_t kernel_kind, const uint32_t* seeds, int32_t* n_sv,
-                                 int32_t* n_support, int32_t* support, double* dual_coef, double* intercept, double* prob_a,
-                                 double* prob_b, gnx_svc_train_info* info) {
+extern "C" int gnx_train_svc2_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const int32_t* dy, int64_t C, int64_t M,
+                                  int64_t ctx_snps, int32_t A, const gnx_svc_params* params, const uint32_t* seeds, int32_t* n_sv,
+                                  int32_t* n_support, int32_t* support, double* dual_coef, double* intercept, double* prob_a,
+                                  double* prob_b, gnx_svc_train_info* info) {
   if (!ctx) return GNX_EINVAL;
-  int rc = train_svc_check(ctx, N, ldx, C, M, ctx_snps, A, kernel_kind, dX, dy, seeds, n_sv, n_support, support, dual_coef, intercept,
+  int rc = train_svc_check(ctx, N, ldx, C, M, ctx_snps, A, params, dX, dy, seeds, n_sv, n_support, support, dual_coef, intercept,
                            prob_a, prob_b);
   if (rc != GNX_OK) return rc;
   GNX_BIND_DEVICE(ctx);
@@ -890,16 +934,16 @@ extern "C" int gnx_train_svc_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int6
   HIPCHK(ctx, hipMemcpyAsync(y.data(), dy, y.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   if ((rc = train_svc_labels(ctx, y.data(), N, W, A)) != GNX_OK) return rc;
-  return train_svc_impl(ctx, dX, N, ldx, y.data(), C, M, ctx_snps, A, kernel_kind, seeds, n_sv, n_support, support, dual_coef, intercept,
+  return train_svc_impl(ctx, dX, N, ldx, y.data(), C, M, ctx_snps, A, *params, seeds, n_sv, n_support, support, dual_coef, intercept,
                         prob_a, prob_b, info);
 }
 
-extern "C" int gnx_train_svc(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t ldx, const int32_t* y, int64_t C, int64_t M,
-                             int64_t ctx_snps, int32_t A, int32_t kernel_kind, const uint32_t* seeds, int32_t* n_sv, int32_t* n_support,
-                             int32_t* support, double* dual_coef, double* intercept, double* prob_a, double* prob_b,
-                             gnx_svc_train_info* info) {
+extern "C" int gnx_train_svc2(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t ldx, const int32_t* y, int64_t C, int64_t M,
+                              int64_t ctx_snps, int32_t A, const gnx_svc_params* params, const uint32_t* seeds, int32_t* n_sv,
+                              int32_t* n_support, int32_t* support, double* dual_coef, double* intercept, double* prob_a, double* prob_b,
+                              gnx_svc_train_info* info) {
   if (!ctx) return GNX_EINVAL;
-  int rc = train_svc_check(ctx, N, ldx, C, M, ctx_snps, A, kernel_kind, X, y, seeds, n_sv, n_support, support, dual_coef, intercept,
+  int rc = train_svc_check(ctx, N, ldx, C, M, ctx_snps, A, params, X, y, seeds, n_sv, n_support, support, dual_coef, intercept,
                            prob_a, prob_b);
   if (rc != GNX_OK) return rc;
   if ((rc = train_svc_labels(ctx, y, N, (int)(C / M), A)) != GNX_OK) return rc;
@@ -911,6 +955,27 @@ extern "C" int gnx_train_svc(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t l
     return gnx_fail(ctx, GNX_ENOMEM, std::string("train_svc: hipMalloc: ") + hipGetErrorString(e));
   }
   HIPCHK(ctx, hipMemcpy2DAsync(xb.p, (size_t)C, X, (size_t)ldx, (size_t)C, (size_t)N, hipMemcpyHostToDevice, ctx->stream));
-  return train_svc_impl(ctx, (const int8_t*)xb.p, N, C, y, C, M, ctx_snps, A, kernel_kind, seeds, n_sv, n_support, support, dual_coef,
+  return train_svc_impl(ctx, (const int8_t*)xb.p, N, C, y, C, M, ctx_snps, A, *params, seeds, n_sv, n_support, support, dual_coef,
                         intercept, prob_a, prob_b, info);
+}
+
+// the CovRSK entries: C = 1 (sklearn's default)
+extern "C" int gnx_train_svc_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const int32_t* dy, int64_t C, int64_t M,
+                                 int64_t ctx_snps, int32_t A, int32_t kernel_kind, const uint32_t* seeds, int32_t* n_sv,
+                                 int32_t* n_support, int32_t* support, double* dual_coef, double* intercept, double* prob_a,
+                                 double* prob_b, gnx_svc_train_info* info) {
+  if (ctx && kernel_kind == GNX_SVC_KERNEL_RBF) return gnx_fail(ctx, GNX_EINVAL, "train_svc: GNX_SVC_KERNEL_RBF needs gamma: use gnx_train_svc2");
+  const gnx_svc_params prm{kernel_kind, 0, 1.0, 0.0};
+  return gnx_train_svc2_dev(ctx, dX, N, ldx, dy, C, M, ctx_snps, A, &prm, seeds, n_sv, n_support, support, dual_coef, intercept, prob_a,
+                            prob_b, info);
+}
+
+extern "C" int gnx_train_svc(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t ldx, const int32_t* y, int64_t C, int64_t M,
+                             int64_t ctx_snps, int32_t A, int32_t kernel_kind, const uint32_t* seeds, int32_t* n_sv, int32_t* n_support,
+                             int32_t* support, double* dual_coef, double* intercept, double* prob_a, double* prob_b,
+                             gnx_svc_train_info* info) {
+  if (ctx && kernel_kind == GNX_SVC_KERNEL_RBF) return gnx_fail(ctx, GNX_EINVAL, "train_svc: GNX_SVC_KERNEL_RBF needs gamma: use gnx_train_svc2");
+  const gnx_svc_params prm{kernel_kind, 0, 1.0, 0.0};
+  return gnx_train_svc2(ctx, X, N, ldx, y, C, M, ctx_snps, A, &prm, seeds, n_sv, n_support, support, dual_coef, intercept, prob_a, prob_b,
+                        info);
 }

@@ -21,6 +21,11 @@ def _c(a, dt):
     return np.ascontiguousarray(a, dtype=dt)
 
 
+def svc_window_is_rbf(w) -> bool:
+    """the kernel tag of a per-window SVC dict: "rbf" = SVMBase's libsvm RBF kernel; no tag (every older .gnx) = a string kernel"""
+    return "kernel" in w and str(np.asarray(w["kernel"])) == "rbf"
+
+
 @dataclass
 class GnxModelData:
     C: int
@@ -35,6 +40,7 @@ class GnxModelData:
     lr_intercept: np.ndarray | None = None  # (W, A)
     # CovRSK base: per-window fitted SVC (src/Base/models.py:195-215)
     svc: list | None = None               # list of dicts: xfit, support, dual_coef, intercept, prob_a, prob_b, n_support, ms
+                                          # (SVMBase windows: kernel = "rbf" and gamma instead of ms)
     # forest base: per-window XGBClassifier (src/Base/models.py:24-35), xgboost model schema, all windows concatenated
     fb_win_tree0: np.ndarray | None = None   # (W+1,) first tree of each window
     fb_tree_off: np.ndarray | None = None
@@ -189,7 +195,10 @@ class GnxModelData:
                 s.prob_a = ptr(w["prob_a"], np.float64)
                 s.prob_b = ptr(w["prob_b"], np.float64)
                 s.n_support = ptr(w["n_support"], np.int32)
-                if "poly_p" in w and float(w["poly_p"]) > 0:   # polynomial string kernel (string_kernel.py:40-61)
+                if svc_window_is_rbf(w):   # SVMBase (models.py:148-159): libsvm's RBF kernel on the SNP codes; xfit = the support rows
+                    s.kernel_kind, s.gamma = _lib.SVC_KERNEL_RBF, float(w["gamma"])
+                    s.ms, s.n_ms = None, 0
+                elif "poly_p" in w and float(w["poly_p"]) > 0:   # polynomial string kernel (string_kernel.py:40-61)
                     rv = _c(w["run_value"], np.float64)
                     if len(rv) < xf.shape[1] + 1:
                         raise ValueError("run_value must hold width+1 values")

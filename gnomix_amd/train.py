@@ -203,6 +203,7 @@ def train_crf_smoother(data: GnxModelData, B, y, **kw) -> dict:
 # ---- the CovRSK SVC base (mode "best") ---------------------------------------------------------------------------------------
 SVC_SEED_HIGH = int(np.iinfo("i").max)          # BaseLibSVM.fit: seed = rnd.randint(np.iinfo("i").max)
 SVC_KERNEL_KINDS = {"CovRSK": 0, "string_kernel": 2}   # GNX_SVC_KERNEL_SUBSTRINGS (CovSample lengths), GNX_SVC_KERNEL_ALL_LENGTHS
+SVC_TRAIN_KINDS = dict(SVC_KERNEL_KINDS, rbf=3)        # + GNX_SVC_KERNEL_RBF (SVMBase): what train_svc_arrays accepts
 
 
 def svc_rng_after_kernel(width):
@@ -246,12 +247,21 @@ def window_columns(C, M, context, w):
     return np.where(p < context, context - 1 - p, np.where(p < context + C, p - context, C - 1 - (p - context - C)))
 
 
-def train_svc_arrays(X, y, M, context, A, seeds, kernel="CovRSK", ctx=None, device=0):
-    """SVC(kernel=<kernel>, probability=True).fit of every window on the device (gnx_train_svc).  X (N, C) int8 {0,1,2}, y (N, W)
+def svc_seeds_unchained(W):
+    """libsvm seeds for SVMBase's window fits: the reference fits them in spawned workers with unseeded generators
+    (base_multithread = True), so there is nothing to reproduce; one seed per window from numpy's global generator, in window
+    order, as BaseLibSVM.fit draws it -> uint32 (W,)"""
+    return np.asarray([np.random.randint(SVC_SEED_HIGH) for _ in range(int(W))], dtype=np.uint32)
+
+
+def train_svc_arrays(X, y, M, context, A, seeds, kernel="CovRSK", ctx=None, device=0, gamma=0.001, C=None):
+    """SVC(kernel=<kernel>, probability=True).fit of every window on the device (gnx_train_svc2).  kernel "rbf" is SVMBase's
+    SVC(C=100., gamma=0.001) (C defaults to 100 for "rbf" and to sklearn's 1 for the string kernels).  X (N, C) int8 {0,1,2}, y (N, W)
     labels, seeds (W,) libsvm seeds -> dict of (W, ...) arrays in sklearn's layout (support / dual_coef padded to N columns, n_sv
     valid) and an info dict"""
-    if kernel not in SVC_KERNEL_KINDS:
-        raise ValueError(f"kernel must be one of {sorted(SVC_KERNEL_KINDS)}")
+    import ctypes as ct   # (the libsvm cost parameter of this function is named C, as sklearn's)
+    if kernel not in SVC_TRAIN_KINDS:
+        raise ValueError(f"kernel must be one of {sorted(SVC_TRAIN_KINDS)}")
     ctx = ctx or _lib.default_context(device)
     X = np.ascontiguousarray(X, dtype=np.int8)
     N, Cn = X.shape
@@ -267,23 +277,27 @@ def train_svc_arrays(X, y, M, context, A, seeds, kernel="CovRSK", ctx=None, devi
                dual_coef=np.zeros((W, A - 1, N), np.float64), intercept=np.zeros((W, P), np.float64),
                prob_a=np.zeros((W, P), np.float64), prob_b=np.zeros((W, P), np.float64))
     info = _lib.SvcTrainInfo()
-    ctx.check(ctx.lib.gnx_train_svc(ctx.h, X.ctypes.data, N, Cn, y.ctypes.data, Cn, int(M), int(context), A, SVC_KERNEL_KINDS[kernel],
+    prm = _lib.SvcParams(SVC_TRAIN_KINDS[kernel], 0, float((100.0 if kernel == "rbf" else 1.0) if C is None else C), float(gamma))
+    ctx.check(ctx.lib.gnx_train_svc2(ctx.h, X.ctypes.data, N, Cn, y.ctypes.data, Cn, int(M), int(context), A, ct.byref(prm),
                                     seeds.ctypes.data, *(out[k].ctypes.data for k in ("n_sv", "n_support", "support", "dual_coef",
-                                                                                      "intercept", "prob_a", "prob_b")), C.byref(info)))
+                                                                                      "intercept", "prob_a", "prob_b")), ct.byref(info)))
     return out, dict(smo_iterations=info.smo_iterations, n_solves=info.n_solves, n_guarded=info.n_guarded, gram_ms=info.gram_ms,
                      smo_ms=info.smo_ms, platt_ms=info.platt_ms)
 
 
 def train_svc_base(data: GnxModelData, X, y, ctx=None, seeds=None, kernel="CovRSK", **kw) -> dict:
-    """fit the CovRSK SVC base of `data` in place (data.svc, base_kind "covrsk") -> info.  Each window keeps only its support
+    """fit the SVC base of `data` in place (data.svc, base_kind "covrsk") -> info: the CovRSK string kernel, or kernel="rbf"
+    (SVMBase; gamma=0.001, C=100.0 unless given).  Each window keeps only its support
     rows as `xfit` (support = arange(n_sv)): the full training window would put N x width bytes per window into the .gnx.  The
     sklearn-order support_ indices (rows of X) are info["support"]."""
     from .convert import string_kernel_lengths
     W = data.W
+    rbf = kernel == "rbf"
     if seeds is None:
-        seeds = svc_seed_chain([data.window_width(w) for w in range(W)], np.random.randint(SVC_SEED_HIGH))
+        seeds = svc_seeds_unchained(W) if rbf else svc_seed_chain([data.window_width(w) for w in range(W)], np.random.randint(SVC_SEED_HIGH))
     X = np.ascontiguousarray(X, dtype=np.int8)
     res, info = train_svc_arrays(X, y, data.M, data.context, data.A, seeds, kernel=kernel, ctx=ctx, **kw)
+    tag = dict(kernel=np.array("rbf"), gamma=np.float64(kw.get("gamma", 0.001))) if rbf else None
     svc, sup_raw = [], []
     for w in range(W):
         n = int(res["n_sv"][w])
@@ -292,7 +306,7 @@ def train_svc_base(data: GnxModelData, X, y, ctx=None, seeds=None, kernel="CovRS
         svc.append(dict(xfit=np.ascontiguousarray(X[sup][:, cols]), support=np.arange(n, dtype=np.int32),
                         dual_coef=np.ascontiguousarray(res["dual_coef"][w, :, :n]), intercept=res["intercept"][w].copy(),
                         prob_a=res["prob_a"][w].copy(), prob_b=res["prob_b"][w].copy(), n_support=res["n_support"][w].copy(),
-                        ms=string_kernel_lengths(len(cols), kernel)))
+                        **(tag if rbf else dict(ms=string_kernel_lengths(len(cols), kernel)))))
         sup_raw.append(sup)
     data.base_kind, data.svc = "covrsk", svc
     info["support"] = sup_raw
@@ -300,7 +314,7 @@ def train_svc_base(data: GnxModelData, X, y, ctx=None, seeds=None, kernel="CovRS
     return info
 
 
-def untrained_model(C, M, A, S, context, mode, seed=None, meta=None):
+def untrained_model(C, M, A, S, context, mode, seed=None, meta=None, base=None):
     """an untrained model of a mode's kinds (the reference's config model.inference: "default", "fast", "large", "best"), ready to
     be loaded and then trained in place: zero logistic weights or, for "best", one placeholder SVC per window (A zero rows, zero
     coefficients); the smoother's starting point: one placeholder tree, zero CRF weights, Conv1d's default initialisation.
@@ -315,7 +329,16 @@ def untrained_model(C, M, A, S, context, mode, seed=None, meta=None):
         kw = dict(snp_pos=np.asarray(meta["snp_pos"]), snp_ref=np.asarray(meta["snp_ref"]), snp_alt=np.asarray(meta["snp_alt"]),
                   population_order=list(meta["pop_order"]))
     d = GnxModelData(C=C, M=M, A=A, S=S, context=context, **kw)
-    if mode == "best":
+    if base not in (None, "svm"):
+        raise ValueError("base must be None (the mode's own base) or \"svm\" (SVMBase: the RBF SVC), got %r" % (base,))
+    if base == "svm":   # SVMBase (src/Base/models.py:148-159) in place of the mode's base; the smoother stays the mode's
+        P = A * (A - 1) // 2
+        d.base_kind, d.svc = "covrsk", []
+        for w in range(W):
+            d.svc.append(dict(xfit=np.zeros((A, d.window_width(w)), np.int8), support=np.arange(A, dtype=np.int32),
+                              dual_coef=np.zeros((A - 1, A)), intercept=np.zeros(P), prob_a=np.zeros(P), prob_b=np.zeros(P),
+                              n_support=np.ones(A, np.int32), kernel=np.array("rbf"), gamma=np.float64(0.001)))
+    elif mode == "best":
         P = A * (A - 1) // 2
         d.base_kind, d.svc = "covrsk", []
         for w in range(W):

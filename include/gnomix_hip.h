@@ -14,6 +14,7 @@
  *   gnx_gnofix            <- Gnomix.phase(X, B) -> gnofix() per indiv.  src/model.py:188-214, src/Gnofix/gnofix.py:58-208
  *   gnx_train_logistic    <- Base.train(X, y) of LogisticRegressionBase   src/Base/base.py:104-127, src/model.py:113,155
  *   gnx_train_svc         <- Base.train(X, y) of CovRSKBase (mode "best") src/Base/base.py:104-127, src/Base/models.py:195-215
+ *   gnx_train_svc2        <- the same, and Base.train(X, y) of SVMBase (RBF)  src/Base/models.py:148-159
  *   gnx_train_gbt         <- Smoother.train(B, y) of XGB_Smoother         src/Smooth/smooth.py:28-38, src/model.py:137
  *   gnx_train_crf         <- Smoother.train(B, y) of CRF_Smoother         src/Smooth/crf.py:51-58, src/Smooth/models.py:27-32
  *   gnx_train_cnn         <- Smoother.train(B, y) of CNN_Smoother         src/Smooth/cnn.py:104-118, src/Smooth/models.py:35-42
@@ -53,7 +54,7 @@
 extern "C" {
 #endif
 
-#define GNX_ABI_VERSION 14
+#define GNX_ABI_VERSION 15
 
 typedef struct gnx_ctx gnx_ctx;
 typedef struct gnx_model gnx_model;
@@ -69,7 +70,8 @@ enum {
                             loaded; load again without it (and write a new one) */
 };
 
-enum { GNX_SVC_KERNEL_SUBSTRINGS = 0, GNX_SVC_KERNEL_POLY = 1, GNX_SVC_KERNEL_ALL_LENGTHS = 2 /* gnx_train_svc only */ };
+enum { GNX_SVC_KERNEL_SUBSTRINGS = 0, GNX_SVC_KERNEL_POLY = 1, GNX_SVC_KERNEL_ALL_LENGTHS = 2 /* gnx_train_svc only */,
+       GNX_SVC_KERNEL_RBF = 3 /* SVMBase: exp(-gamma |x - y|^2) on the SNP codes as numbers */ };
 enum { GNX_BASE_NONE = 0, GNX_BASE_LOGISTIC = 1, GNX_BASE_COVRSK_SVC = 2, GNX_BASE_FOREST = 3, GNX_BASE_RFOREST = 4 };
 enum { GNX_SMOOTH_NONE = 0, GNX_SMOOTH_XGB = 1, GNX_SMOOTH_CRF = 2, GNX_SMOOTH_CNN = 3 };
 
@@ -88,7 +90,20 @@ enum {
 };
 
 /* Per-window SVC of CovRSKBase (src/Base/models.py:195-215 -> sklearn.svm.SVC(kernel=callable,
- * probability=True)); field names follow the fitted sklearn attributes. */
+ * probability=True)) or of SVMBase (src/Base/models.py:148-159 -> SVC(C=100., gamma=0.001, probability=True), libsvm's RBF
+ * kernel); field names follow the fitted sklearn attributes.
+ * GNX_SVC_KERNEL_RBF: K(x, y) = exp(-gamma |x - y|^2) with the SNP codes taken as numbers (2 = missing is the number 2, as
+ * everywhere in the reference).  xfit rows must hold 0..2 (GNX_EINVAL otherwise), gamma must be finite and > 0, the width at
+ * most GNX_RBF_MAX_WIDTH; every window of a model has the same kernel_kind; ms / run_value / poly_p are unused.  |x - y|^2 is
+ * an exact integer (int8 matrix cores) and K is read from a table T[k] = exp(-gamma k) that gnx_model_load fills with the
+ * host C library's exp, k = 0 .. 9 * width: a QUERY code 3 (the largest a 2-bit packed row can hold) is HANDLED, as the
+ * number 3, identically by the int8 and the 2-bit entry points; other int8 query values are outside the contract (the
+ * distance is clamped to the table's last entry, nothing is read out of bounds).
+ * A model holds at most GNX_RBF_MAX_A ancestries (GNX_EUNSUPPORTED beyond): the limit of the CovRSK base, whose pairwise-coupling
+ * pass (multiclass_probability with A(A-1)/2 + A*A + 2A float64 values per haplotype in LDS) the RBF base shares.  gnx_train_svc2
+ * itself fits up to 32; what it fits beyond GNX_RBF_MAX_A cannot be loaded for inference by this build. */
+#define GNX_RBF_MAX_WIDTH 8192
+#define GNX_RBF_MAX_A 13
 typedef struct gnx_svc_window {
   const int8_t* xfit;       /* (n_fit, width) training rows, row-major (sklearn __Xfit) */
   int32_t n_fit;
@@ -106,6 +121,7 @@ typedef struct gnx_svc_window {
                                string kernel), 1 = polynomial string kernel (string_kernel.py:40-61) */
   double poly_p;            /* POLY: K = int(np.sum(run_value[run lengths]) / poly_p), p = 1.2 in the reference */
   const double* run_value;  /* POLY: (width+1,) value of a run of L equal SNPs = L ** p as numpy computed it */
+  double gamma;             /* RBF: sklearn's _gamma */
 } gnx_svc_window;
 
 /* Everything a pickled src.model.Gnomix carries for inference (src/model.py:28-88), as flat host
@@ -370,6 +386,23 @@ int gnx_train_svc(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t ldx, const i
 int gnx_train_svc_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const int32_t* dy, int64_t C, int64_t M, int64_t ctx_snps,
                       int32_t A, int32_t kernel_kind, const uint32_t* seeds, int32_t* n_sv, int32_t* n_support, int32_t* support,
                       double* dual_coef, double* intercept, double* prob_a, double* prob_b, gnx_svc_train_info* info);
+/* The same with the kernel's parameters in a struct: kernel_kind as above or GNX_SVC_KERNEL_RBF (SVMBase: gamma = 0.001,
+ * C = 100; the Gram is |x - y|^2 on the int8 matrix cores, Q = (float) exp(-gamma d2) from the host-built table as libsvm's
+ * Qfloat, the Platt folds' held-out decision values from the double table as svm_predict_values' k_function).  C is libsvm's
+ * cost (> 0, finite; the fold models get the same C, as through libsvm's weight); gamma is read for RBF only (> 0, finite,
+ * GNX_EINVAL otherwise).  gnx_train_svc(..., kind, ...) == gnx_train_svc2 with {kind, 0, 1.0, 0.0}. */
+typedef struct gnx_svc_params {
+  int32_t kernel_kind;  /* GNX_SVC_KERNEL_* */
+  int32_t reserved;
+  double C;             /* 1.0 for CovRSKBase (sklearn's default), 100.0 for SVMBase */
+  double gamma;         /* RBF only */
+} gnx_svc_params;
+int gnx_train_svc2(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t ldx, const int32_t* y, int64_t C, int64_t M, int64_t ctx_snps,
+                   int32_t A, const gnx_svc_params* params, const uint32_t* seeds, int32_t* n_sv, int32_t* n_support, int32_t* support,
+                   double* dual_coef, double* intercept, double* prob_a, double* prob_b, gnx_svc_train_info* info);
+int gnx_train_svc2_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const int32_t* dy, int64_t C, int64_t M, int64_t ctx_snps,
+                       int32_t A, const gnx_svc_params* params, const uint32_t* seeds, int32_t* n_sv, int32_t* n_support,
+                       int32_t* support, double* dual_coef, double* intercept, double* prob_a, double* prob_b, gnx_svc_train_info* info);
 /* the Platt fold permutation of an l-row class-pair problem fitted with libsvm seed `seed` (svm_binary_svc_probability: sklearn's
  * mt19937 + bounded_rand_int); host only, no context */
 int gnx_svc_fold_permutation(uint32_t seed, int32_t l, int32_t* perm);
