@@ -1,0 +1,555 @@
+// forest/k_train_gbt_base.hip — training the boosted-tree BASE (XGBBase) on gfx950, all windows at once.
+//
+// Replaces Base.train of XGBBase (reference src/Base/base.py:104-127 -> src/Base/models.py:24-35: per window
+// XGBClassifier(n_estimators=20, max_depth=4, learning_rate=0.1, reg_lambda=1, reg_alpha=0, missing=2).fit(Xw, yw)).  xgboost is a
+// third-party fitter that is not part of the reference tree, so what is rebuilt is the ALGORITHM that call asks for, not xgboost's own
+// floating-point trajectory (parity with xgboost itself is unpinned, as for k_train_gbt.hip).  Correctness is exact agreement with an
+// independent CPU restatement (tests/gbt_base_exact.py).
+//
+// THE ALGORITHM (for every window w independently)
+//   rows      n < N; features j < width_w = M + 2 ctx (+ C % M for the last window): feature j is column pad_src(w M + j) of X, the
+//             window's reflect-padded slice (train.window_columns); label y[n, w].
+//   codes     X holds 0, 1 and 2 = missing.  The trainer only ever COMPARES a code with 1 and with 2: any other value trains as 0
+//             (it is never an index).  The host entry refuses such values; the _dev entry does not read X back.
+//   objective A >= 3: multi:softprob, K = A trees per round, tree k of a round adds to class k; margins start at base_score.
+//             A == 2: binary:logistic, K = 1 tree per round on the label y == 1; the margin starts at float(log(bs / (1 - bs))) (= 0).
+//             Margins are float32 and take each round's leaf with one float32 addition.
+//   gradients multi:  m = max_c F_c (float32), e_c = det_exp(double(F_c - m)), s = sum e_c in class order, p_c = e_c / s,
+//                     g = p_c - [y == c], h = max(2 p_c (1 - p_c), 1e-16)              (k_train_gbt.hip's pair)
+//             binary: z = double(F), e = det_exp(-|z|), p = z >= 0 ? 1 / (1 + e) : e / (1 + e), g = p - [y == 1],
+//                     h = max(p (1 - p), 1e-16)
+//             both rounded to multiples of 2^-30: gi = llrint(g 2^30), hi = llrint(h 2^30).  EVERY sum below is an int64 of those, so
+//             no result depends on scheduling, atomics order or tile order.
+//   loss[r]   mean over the N W problems of -log(max(p_y, 1e-300)) before round r (r = n_rounds: after the last), float64
+//             (binary: p_y = y == 1 ? p : 1 - p; a label outside [0, A) has p_y = 0 in the multi-class form).
+//   node      (G, H) = its rows' sums.  For a feature, (G1, H1) and (Gm, Hm) are the sums over its rows with code 1 and code 2, the
+//             code-0 sums are the node's minus both.  Candidates, in this order, left | right:
+//               1: cond 0.5, missing right  {0} | {1, missing}       2: cond 0.5, missing left  {0, missing} | {1}
+//               3: cond 1.5, missing right  {0, 1} | {missing}
+//             gain = (GL^2 / (HL + lambda) + GR^2 / (HR + lambda)) - G^2 / (H + lambda) in float64 on the sums / 2^30, operations in
+//             that order.  A candidate is valid if HL >= min_child_weight, HR >= min_child_weight and gain > max(gamma, 1e-6) (the
+//             smoother trainer's floor).  The largest gain wins; ties go to the lowest feature, then the lowest candidate: a node
+//             without missing rows learns "default right".  No valid candidate, or depth max_depth reached: a leaf,
+//             value float32(eta * (-(G / 2^30) / (H / 2^30 + lambda))).
+//
+// THE STRUCTURE.  The hot loop is the per-level table of (G1, H1, Gm, Hm) for every (window, tree of the round, node, feature).  A row
+// sits in exactly ONE node of a tree, so the dense form of that table — indicator planes times node-masked gradient columns on the
+// int8 matrix cores — multiplies the visits by the node count (up to 16) and by the ~9 int8 limbs a 31-bit (g, h) pair splits into.
+// Built instead: a block takes one (window, tree, node), a chunk of FBT_CHUNK features (one per thread) and a slice of FBT_SLICE
+// rows; it first compacts the slice's rows OF THAT NODE, with their (g, h), into LDS (one pass over the position bytes), then every
+// thread walks that list: the row index and (g, h) are wave-uniform LDS broadcasts, the code is one coalesced byte load, and the
+// sums are four predicated int64 additions in REGISTERS — no atomics per matrix entry, no runtime-indexed arrays, no scratch.  One
+// int64 global atomic per (feature, sum) and block folds the row slices together (exact: integers).  The overlap of the windows
+// (a SNP belongs to up to ceil((M + 2 ctx) / M) windows) is left to the L2: X is read in place, never expanded per window.
+// All W windows train together: one launch sequence per round (gradients; per level: table, split search, row partition; leaves;
+// margins), W never appears as a host loop.
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../gnx_internal.h"
+
+namespace {
+
+constexpr double FIX = 1073741824.0;  // 2^30
+constexpr int MAXN = 63;               // heap positions of a tree of depth <= 5
+constexpr int FBT_CHUNK = 256;         // features of one histogram block (one per thread)
+constexpr int FBT_SLICE = 2048;        // rows of one histogram block: (index, g, h) = 20 bytes each, 40 KB of LDS
+
+struct FGeom {
+  int64_t N, ldx, C, M, ctx;
+  int32_t W, rem, A, K, maxw, R;  // K trees per round, R rounds
+};
+
+// column of X behind padded position p (base.py's reflect padding)
+__device__ __forceinline__ int64_t fbt_src(int64_t p, int64_t C, int64_t ctx) {
+  if (p < ctx) return ctx - 1 - p;
+  if (p < ctx + C) return p - ctx;
+  return C - 1 - (p - ctx - C);
+}
+__device__ __forceinline__ int fbt_width(int w, const FGeom& G) { return (int)(G.M + 2 * G.ctx) + (w == G.W - 1 ? G.rem : 0); }
+
+__device__ __forceinline__ double det_exp(double x) {  // x <= 0; the same operations, in the same order, as k_train_gbt.hip's
+  if (!(x > -745.0)) return 0.0;
+  const double LOG2E = 1.4426950408889634, LN2_HI = 6.93147180369123816490e-01, LN2_LO = 1.90821492927058770002e-10;
+  const double kf = rint(x * LOG2E);
+  const double r = (x - kf * LN2_HI) - kf * LN2_LO;
+  double p = 1.0 / 6227020800.0;
+  p = p * r + 1.0 / 479001600.0;
+  p = p * r + 1.0 / 39916800.0;
+  p = p * r + 1.0 / 3628800.0;
+  p = p * r + 1.0 / 362880.0;
+  p = p * r + 1.0 / 40320.0;
+  p = p * r + 1.0 / 5040.0;
+  p = p * r + 1.0 / 720.0;
+  p = p * r + 1.0 / 120.0;
+  p = p * r + 1.0 / 24.0;
+  p = p * r + 1.0 / 6.0;
+  p = p * r + 0.5;
+  p = p * r + 1.0;
+  p = p * r + 1.0;
+  return ldexp(p, (int)kf);
+}
+
+__global__ __launch_bounds__(256) void k_fbt_fill(float* p, float v, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) p[i] = v;
+}
+
+// node tables of tree (w, round r, k): [((w R + r) K + k)][MAXN]
+__device__ __forceinline__ size_t fbt_tab(int w, int r, int k, const FGeom& G) { return (((size_t)w * G.R + r) * G.K + k) * MAXN; }
+
+// gradients of one round: block = 256 rows of one window.  Root sums per tree (int64, exact), the block's loss in a fixed order.
+// fit == 0: only the loss (the pass after the last round).
+template <int AMAX>
+__global__ __launch_bounds__(256) void k_fbt_grad(const float* Fm, const int32_t* y, long long* gq, long long* hq, uint8_t* pos, long long* tG,
+                                                   long long* tH, int32_t* tS, double* loss_part, int r, int fit, int nb, FGeom G) {
+  __shared__ long long sg[AMAX], sh[AMAX];
+  __shared__ double sl[256];
+  const int w = blockIdx.x / nb, b = blockIdx.x - w * nb;
+  const int A = G.A, K = G.K;
+  if (threadIdx.x < AMAX) { sg[threadIdx.x] = 0; sh[threadIdx.x] = 0; }
+  __syncthreads();
+  const int64_t n = (int64_t)b * 256 + threadIdx.x;
+  double l = 0.0;
+  if (n < G.N) {
+    const float* f = Fm + ((size_t)w * G.N + n) * K;
+    const int yi = y[n * G.W + w];
+    double py = 0.0;
+    if (K == 1) {
+      const double z = (double)f[0];
+      const double e = det_exp(z >= 0.0 ? -z : z);
+      const double p = z >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
+      const double g = p - (yi == 1 ? 1.0 : 0.0);
+      double h = p * (1.0 - p);
+      if (h < 1e-16) h = 1e-16;
+      py = yi == 1 ? p : 1.0 - p;
+      if (fit) {
+        const long long gi = llrint(g * FIX), hi = llrint(h * FIX);
+        const size_t o = (size_t)w * G.N + n;
+        gq[o] = gi; hq[o] = hi; pos[o] = 0;
+        atomicAdd(reinterpret_cast<unsigned long long*>(&sg[0]), (unsigned long long)gi);
+        atomicAdd(reinterpret_cast<unsigned long long*>(&sh[0]), (unsigned long long)hi);
+      }
+    } else {
+      float m = f[0];
+      for (int c = 1; c < A; ++c) m = f[c] > m ? f[c] : m;
+      double e[AMAX], sum = 0.0;
+#pragma unroll
+      for (int c = 0; c < AMAX; ++c)
+        if (c < A) { e[c] = det_exp((double)(f[c] - m)); sum += e[c]; }
+#pragma unroll
+      for (int c = 0; c < AMAX; ++c)
+        if (c < A) {
+          const double p = e[c] / sum;
+          if (yi == c) py = p;
+          if (fit) {
+            const double g = p - (yi == c ? 1.0 : 0.0);
+            double h = 2.0 * p * (1.0 - p);
+            if (h < 1e-16) h = 1e-16;
+            const long long gi = llrint(g * FIX), hi = llrint(h * FIX);
+            const size_t o = ((size_t)w * K + c) * G.N + n;
+            gq[o] = gi; hq[o] = hi; pos[o] = 0;
+            atomicAdd(reinterpret_cast<unsigned long long*>(&sg[c]), (unsigned long long)gi);
+            atomicAdd(reinterpret_cast<unsigned long long*>(&sh[c]), (unsigned long long)hi);
+          }
+        }
+    }
+    l = -log(py > 1e-300 ? py : 1e-300);
+  }
+  sl[threadIdx.x] = l;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {  // a fixed tree: the same bits whatever the schedule
+    if ((int)threadIdx.x < o) sl[threadIdx.x] += sl[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss_part[blockIdx.x] = sl[0];
+  if (fit && (int)threadIdx.x < K) {
+    const size_t o = fbt_tab(w, r, threadIdx.x, G);
+    atomicAdd(reinterpret_cast<unsigned long long*>(&tG[o]), (unsigned long long)sg[threadIdx.x]);
+    atomicAdd(reinterpret_cast<unsigned long long*>(&tH[o]), (unsigned long long)sh[threadIdx.x]);
+    tS[o] = 1;  // (every block writes the same value)
+  }
+}
+
+// the blocks' losses, summed by one block in a fixed order -> mean over the N W problems
+__global__ __launch_bounds__(256) void k_fbt_loss(const double* part, int64_t n_part, double* loss, double inv_count) {
+  __shared__ double sl[256];
+  double a = 0.0;
+  for (int64_t i = threadIdx.x; i < n_part; i += 256) a += part[i];
+  sl[threadIdx.x] = a;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) sl[threadIdx.x] += sl[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *loss = sl[0] * inv_count;
+}
+
+// the level's table: hist[((w K + k) nl + node of level) maxw + j][4] = (G1, H1, Gm, Hm).
+// grid (w K + k, feature chunk x row slice, node of level); see the header for the structure.
+__global__ __launch_bounds__(FBT_CHUNK) void k_fbt_hist(const int8_t* __restrict__ X, const long long* __restrict__ gq, const long long* __restrict__ hq,
+                                                         const uint8_t* __restrict__ pos, const int32_t* __restrict__ tS, long long* hist, int r,
+                                                         int d, int n_chunks, int n_slices, FGeom G) {
+  __shared__ int32_t ln[FBT_SLICE];
+  __shared__ long long lg[FBT_SLICE], lh[FBT_SLICE];
+  __shared__ int cnt;
+  const int nl = 1 << d, node = nl - 1 + (int)blockIdx.z;
+  const int wk = blockIdx.x, w = wk / G.K, k = wk - w * G.K;
+  if (tS[fbt_tab(w, r, k, G) + node] != 1) return;  // not an open node (uniform over the block)
+  const int chunk = blockIdx.y % n_chunks, slice = blockIdx.y / n_chunks;
+  const int width = fbt_width(w, G);
+  if (chunk * FBT_CHUNK >= width) return;
+  if (threadIdx.x == 0) cnt = 0;
+  __syncthreads();
+  const int64_t r0 = (int64_t)slice * FBT_SLICE, r1 = min(G.N, r0 + FBT_SLICE);
+  const size_t row0 = (size_t)wk * G.N;
+  for (int64_t n = r0 + threadIdx.x; n < r1; n += FBT_CHUNK)
+    if (pos[row0 + n] == node) {
+      const int slot = atomicAdd(&cnt, 1);  // slot < r1 - r0 <= FBT_SLICE; any order: the sums are integers
+      ln[slot] = (int32_t)n; lg[slot] = gq[row0 + n]; lh[slot] = hq[row0 + n];
+    }
+  __syncthreads();
+  const int rows = cnt;
+  const int j = chunk * FBT_CHUNK + threadIdx.x;
+  if (j >= width || (rows == 0 && n_slices > 1)) return;  // (a single slice stores: an empty node stores zeros)
+  const int8_t* xc = X + fbt_src((int64_t)w * G.M + j, G.C, G.ctx);
+  long long G1 = 0, H1 = 0, Gm = 0, Hm = 0;
+#pragma unroll 4
+  for (int i = 0; i < rows; ++i) {
+    const int x = xc[(int64_t)ln[i] * G.ldx];
+    const long long g = lg[i], h = lh[i];
+    G1 += x == 1 ? g : 0; H1 += x == 1 ? h : 0;
+    Gm += x == 2 ? g : 0; Hm += x == 2 ? h : 0;
+  }
+  unsigned long long* dst = reinterpret_cast<unsigned long long*>(hist + (((size_t)wk * nl + blockIdx.z) * G.maxw + j) * 4);
+  if (n_slices == 1) {
+    dst[0] = (unsigned long long)G1; dst[1] = (unsigned long long)H1; dst[2] = (unsigned long long)Gm; dst[3] = (unsigned long long)Hm;
+  } else {  // (the table is zeroed before the launch)
+    atomicAdd(dst + 0, (unsigned long long)G1); atomicAdd(dst + 1, (unsigned long long)H1);
+    atomicAdd(dst + 2, (unsigned long long)Gm); atomicAdd(dst + 3, (unsigned long long)Hm);
+  }
+}
+
+// best split of every open node of the level: grid (w K + k, node of level); a thread per feature, three candidates each
+__global__ __launch_bounds__(256) void k_fbt_split(const long long* __restrict__ hist, long long* tG, long long* tH, int32_t* tF, int32_t* tC,
+                                                    int32_t* tS, int r, int d, double lambda, double gamma, double mcw, FGeom G) {
+  const int nl = 1 << d, kk = blockIdx.y, node = nl - 1 + kk;
+  const int wk = blockIdx.x, w = wk / G.K, k = wk - w * G.K;
+  const size_t o = fbt_tab(w, r, k, G);
+  if (tS[o + node] != 1) return;
+  const int width = fbt_width(w, G);
+  const long long Gn = tG[o + node], Hn = tH[o + node];
+  const double Gd = (double)Gn / FIX, Hd = (double)Hn / FIX;
+  const double root_term = Gd * Gd / (Hd + lambda);
+  const double floor_ = gamma > 1e-6 ? gamma : 1e-6;
+  // the running best as scalars; a candidate exists iff bf >= 0.  key = 4 f + candidate: lower key wins a tie
+  double bg = 0.0;
+  int bf = -1, bc = 0;
+  long long bGL = 0, bHL = 0;
+  const long long* hrow = hist + ((size_t)wk * nl + kk) * G.maxw * 4;
+  for (int j = threadIdx.x; j < width; j += 256) {
+    const long long G1 = hrow[(size_t)j * 4], H1 = hrow[(size_t)j * 4 + 1], Gm = hrow[(size_t)j * 4 + 2], Hm = hrow[(size_t)j * 4 + 3];
+#pragma unroll
+    for (int c = 1; c <= 3; ++c) {
+      const long long GL = c == 1 ? Gn - G1 - Gm : (c == 2 ? Gn - G1 : Gn - Gm);
+      const long long HL = c == 1 ? Hn - H1 - Hm : (c == 2 ? Hn - H1 : Hn - Hm);
+      const double gl = (double)GL / FIX, hl = (double)HL / FIX;
+      const double gr = (double)(Gn - GL) / FIX, hr = (double)(Hn - HL) / FIX;
+      if (hl < mcw || hr < mcw) continue;
+      const double gain = (gl * gl / (hl + lambda) + gr * gr / (hr + lambda)) - root_term;
+      if (!(gain > floor_)) continue;
+      if (bf < 0 || gain > bg) { bg = gain; bf = j; bc = c; bGL = GL; bHL = HL; }  // (j and c ascend: the first of equals stays)
+    }
+  }
+  auto beats = [](double g1, int f1, int c1, double g2, int f2, int c2) {
+    return g1 > g2 || (g1 == g2 && (f1 < f2 || (f1 == f2 && c1 < c2)));
+  };
+  for (int s = 32; s > 0; s >>= 1) {
+    const double tg = __shfl_down(bg, s);
+    const int tf = __shfl_down(bf, s), tc = __shfl_down(bc, s);
+    const long long tGL = __shfl_down(bGL, s), tHL = __shfl_down(bHL, s);
+    if (tf >= 0 && (bf < 0 || beats(tg, tf, tc, bg, bf, bc))) { bg = tg; bf = tf; bc = tc; bGL = tGL; bHL = tHL; }
+  }
+  __shared__ double wg[4];
+  __shared__ int wf[4], wc[4];
+  __shared__ long long wGL[4], wHL[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) { wg[wave] = bg; wf[wave] = bf; wc[wave] = bc; wGL[wave] = bGL; wHL[wave] = bHL; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int bw = -1;
+    for (int q = 0; q < 4; ++q)
+      if (wf[q] >= 0 && (bw < 0 || beats(wg[q], wf[q], wc[q], wg[bw], wf[bw], wc[bw]))) bw = q;
+    if (bw >= 0) {
+      const long long GL = wGL[bw], HL = wHL[bw];
+      tS[o + node] = 2; tF[o + node] = wf[bw]; tC[o + node] = wc[bw];
+      const int l = 2 * node + 1, rr = 2 * node + 2;
+      tS[o + l] = 1; tS[o + rr] = 1;
+      tG[o + l] = GL; tH[o + l] = HL; tG[o + rr] = Gn - GL; tH[o + rr] = Hn - HL;
+    } else {
+      tS[o + node] = 3;
+    }
+  }
+}
+
+// rows of the nodes split at level d move to their children: grid (blocks of rows, w K + k)
+__global__ __launch_bounds__(256) void k_fbt_partition(const int8_t* __restrict__ X, uint8_t* pos, const int32_t* __restrict__ tS,
+                                                        const int32_t* __restrict__ tF, const int32_t* __restrict__ tC, int r, int d, int nb, FGeom G) {
+  const int wk = blockIdx.x / nb, b = blockIdx.x - wk * nb;
+  const int w = wk / G.K, k = wk - w * G.K;
+  const int64_t n = (int64_t)b * 256 + threadIdx.x;
+  if (n >= G.N) return;
+  const size_t o = fbt_tab(w, r, k, G), i = (size_t)wk * G.N + n;
+  const int node = pos[i];
+  if (node < (1 << d) - 1 || tS[o + node] != 2) return;
+  const int x = X[n * G.ldx + fbt_src((int64_t)w * G.M + tF[o + node], G.C, G.ctx)];
+  const int c = tC[o + node];
+  // candidate 1: {0} | {1, m};  2: {0, m} | {1};  3: {0, 1} | {m}   (a code that is neither 1 nor 2 is a 0)
+  const bool left = c == 1 ? (x != 1 && x != 2) : (c == 2 ? x != 1 : x != 2);
+  pos[i] = (uint8_t)(left ? 2 * node + 1 : 2 * node + 2);
+}
+
+// leaves of the round: every node still open becomes one
+__global__ __launch_bounds__(256) void k_fbt_close(const long long* tG, const long long* tH, int32_t* tS, float* tV, int r, int64_t total, double eta,
+                                                    double lambda, FGeom G) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  const int64_t wk = e / MAXN;
+  const int node = (int)(e - wk * MAXN), w = (int)(wk / G.K), k = (int)(wk - (int64_t)w * G.K);
+  const size_t i = fbt_tab(w, r, k, G) + node;
+  if (tS[i] == 1) tS[i] = 3;
+  if (tS[i] == 3) {
+    const double Gd = (double)tG[i] / FIX, Hd = (double)tH[i] / FIX;
+    tV[i] = (float)(eta * (-Gd / (Hd + lambda)));
+  }
+}
+
+__global__ __launch_bounds__(256) void k_fbt_margin(float* Fm, const uint8_t* pos, const float* tV, int r, int64_t total, FGeom G) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;  // e = (w N + n) K + k
+  if (e >= total) return;
+  const int k = (int)(e % G.K);
+  const int64_t wn = e / G.K, w = wn / G.N, n = wn - w * G.N;
+  Fm[e] += tV[fbt_tab((int)w, r, k, G) + pos[((size_t)w * G.K + k) * G.N + n]];
+}
+
+struct DevBuf {
+  void* p = nullptr;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
+  template <typename T> T* as() { return reinterpret_cast<T*>(p); }
+};
+
+// per-phase wall times of the last run (gnx_train_gbt_base_phases): gradients + loss, table, split search, partition, leaves + margins
+bool g_phases_on = false;
+double g_phase_ms[5] = {0, 0, 0, 0, 0};
+
+}  // namespace
+
+#define FBT_HIP(x)                      \
+  do {                                  \
+    const hipError_t e_ = (x);          \
+    if (e_ != hipSuccess) return e_;    \
+  } while (0)
+
+// dX (N, ldx) int8 and dy (N, W) int32 on the device.  Host outputs as in gnx_train_gbt_base (include/gnomix_hip.h).
+static hipError_t gnx_train_gbt_base_run(const int8_t* dX, int64_t N, int64_t ldx, const int32_t* dy, int64_t C, int64_t M, int64_t ctx, int32_t A,
+                                  const gnx_gbt_params& P, int32_t* win_tree0, int32_t* tree_off, int32_t* left, int32_t* right, int32_t* feat,
+                                  float* cond, uint8_t* default_left, int32_t* tree_class, int64_t* n_nodes_out, double* loss_out, hipStream_t s) {
+  FGeom G;
+  G.N = N; G.ldx = ldx; G.C = C; G.M = M; G.ctx = ctx;
+  G.W = (int32_t)(C / M); G.rem = (int32_t)(C - M * (C / M)); G.A = A; G.K = A == 2 ? 1 : A; G.maxw = (int32_t)(M + 2 * ctx) + G.rem;
+  G.R = P.n_rounds;
+  const int D = P.max_depth, W = G.W, K = G.K, R = G.R;
+  const int64_t WK = (int64_t)W * K, rows = WK * N;
+  const size_t tab_n = (size_t)WK * R * MAXN;
+  const int nb = (int)((N + 255) / 256);
+  const int n_chunks = (G.maxw + FBT_CHUNK - 1) / FBT_CHUNK, n_slices = (int)((N + FBT_SLICE - 1) / FBT_SLICE);
+  const size_t hist_n = (size_t)WK * ((size_t)1 << (D - 1)) * G.maxw * 4;
+  DevBuf bFm, bG, bH, bPos, bTab, bHist, bPart, bLoss;
+  FBT_HIP(bFm.alloc((size_t)rows * 4));
+  FBT_HIP(bG.alloc((size_t)rows * 8));
+  FBT_HIP(bH.alloc((size_t)rows * 8));
+  FBT_HIP(bPos.alloc((size_t)rows));
+  FBT_HIP(bTab.alloc(tab_n * 32));
+  FBT_HIP(bHist.alloc(hist_n * 8));
+  FBT_HIP(bPart.alloc((size_t)W * nb * 8));
+  FBT_HIP(bLoss.alloc((size_t)(R + 1) * 8));
+  long long* tG = bTab.as<long long>();
+  long long* tH = tG + tab_n;
+  int32_t* tF = reinterpret_cast<int32_t*>(tH + tab_n);
+  int32_t* tC = tF + tab_n;
+  int32_t* tS = tC + tab_n;
+  float* tV = reinterpret_cast<float*>(tS + tab_n);
+  FBT_HIP(hipMemsetAsync(bTab.p, 0, tab_n * 32, s));
+  const float m0 = K == 1 ? (float)std::log(P.base_score / (1.0 - P.base_score)) : (float)P.base_score;
+  hipLaunchKernelGGL(k_fbt_fill, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, bFm.as<float>(), m0, rows);
+  FBT_HIP(hipGetLastError());
+
+  const bool prof = g_phases_on;
+  double ms[5] = {0, 0, 0, 0, 0};
+  auto t_prev = std::chrono::steady_clock::now();
+  hipError_t perr = hipSuccess;
+  auto phase = [&](int which) {  // (profiling only: a synchronisation per phase)
+    if (!prof) return;
+    const hipError_t e = hipStreamSynchronize(s);
+    if (e != hipSuccess && perr == hipSuccess) perr = e;
+    const auto t = std::chrono::steady_clock::now();
+    if (which >= 0) ms[which] += std::chrono::duration<double, std::milli>(t - t_prev).count();
+    t_prev = t;
+  };
+  auto grad = [&](int r, int fit) {
+    const int rr = r < R ? r : R - 1;
+#define FBT_GRAD(AM) hipLaunchKernelGGL(k_fbt_grad<AM>, dim3((unsigned)((int64_t)W * nb)), dim3(256), 0, s, bFm.as<float>(), dy, bG.as<long long>(), \
+                                        bH.as<long long>(), bPos.as<uint8_t>(), tG, tH, tS, bPart.as<double>(), rr, fit, nb, G)
+    if (A <= 8) FBT_GRAD(8);
+    else if (A <= 16) FBT_GRAD(16);
+    else FBT_GRAD(32);
+#undef FBT_GRAD
+    hipLaunchKernelGGL(k_fbt_loss, dim3(1), dim3(256), 0, s, bPart.as<double>(), (int64_t)W * nb, bLoss.as<double>() + r, 1.0 / ((double)N * (double)W));
+  };
+  phase(-1);
+  for (int r = 0; r < R; ++r) {
+    grad(r, 1);
+    FBT_HIP(hipGetLastError());
+    phase(0);
+    for (int d = 0; d < D; ++d) {
+      const int nl = 1 << d;
+      if (n_slices > 1) FBT_HIP(hipMemsetAsync(bHist.p, 0, (size_t)WK * nl * G.maxw * 32, s));
+      hipLaunchKernelGGL(k_fbt_hist, dim3((unsigned)WK, (unsigned)(n_chunks * n_slices), (unsigned)nl), dim3(FBT_CHUNK), 0, s, dX, bG.as<long long>(),
+                         bH.as<long long>(), bPos.as<uint8_t>(), tS, bHist.as<long long>(), r, d, n_chunks, n_slices, G);
+      phase(1);
+      hipLaunchKernelGGL(k_fbt_split, dim3((unsigned)WK, (unsigned)nl), dim3(256), 0, s, bHist.as<long long>(), tG, tH, tF, tC, tS, r, d, P.lambda,
+                         P.gamma, P.min_child_weight, G);
+      phase(2);
+      hipLaunchKernelGGL(k_fbt_partition, dim3((unsigned)(WK * nb)), dim3(256), 0, s, dX, bPos.as<uint8_t>(), tS, tF, tC, r, d, nb, G);
+      phase(3);
+    }
+    hipLaunchKernelGGL(k_fbt_close, dim3((unsigned)((WK * MAXN + 255) / 256)), dim3(256), 0, s, tG, tH, tS, tV, r, WK * MAXN, P.eta, P.lambda, G);
+    hipLaunchKernelGGL(k_fbt_margin, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, bFm.as<float>(), bPos.as<uint8_t>(), tV, r, rows, G);
+    FBT_HIP(hipGetLastError());
+    phase(4);
+  }
+  grad(R, 0);
+  FBT_HIP(hipGetLastError());
+  phase(0);
+  FBT_HIP(perr);
+
+  // ---- trees back to the host: window-major, round-major, nodes in heap order ----
+  std::vector<int32_t> hF(tab_n), hC(tab_n), hS(tab_n);
+  std::vector<float> hV(tab_n);
+  std::vector<double> hL((size_t)R + 1);
+  FBT_HIP(hipMemcpyAsync(hF.data(), tF, tab_n * 4, hipMemcpyDeviceToHost, s));
+  FBT_HIP(hipMemcpyAsync(hC.data(), tC, tab_n * 4, hipMemcpyDeviceToHost, s));
+  FBT_HIP(hipMemcpyAsync(hS.data(), tS, tab_n * 4, hipMemcpyDeviceToHost, s));
+  FBT_HIP(hipMemcpyAsync(hV.data(), tV, tab_n * 4, hipMemcpyDeviceToHost, s));
+  FBT_HIP(hipMemcpyAsync(hL.data(), bLoss.p, hL.size() * 8, hipMemcpyDeviceToHost, s));
+  FBT_HIP(hipStreamSynchronize(s));
+  int64_t nn = 0;
+  const int64_t T = WK * R;
+  tree_off[0] = 0;
+  for (int64_t t = 0; t < T; ++t) {
+    const size_t o = (size_t)t * MAXN;
+    int32_t idx[MAXN];
+    int32_t cntn = 0;
+    for (int node = 0; node < MAXN; ++node) idx[node] = (hS[o + node] >= 2) ? cntn++ : -1;
+    for (int node = 0; node < MAXN; ++node) {
+      if (hS[o + node] < 2) continue;
+      const int64_t q = nn + idx[node];
+      if (hS[o + node] == 2) {
+        left[q] = idx[2 * node + 1]; right[q] = idx[2 * node + 2]; feat[q] = hF[o + node];
+        cond[q] = hC[o + node] == 3 ? 1.5f : 0.5f;
+        default_left[q] = hC[o + node] == 2 ? 1 : 0;
+      } else {
+        left[q] = -1; right[q] = -1; feat[q] = 0; cond[q] = hV[o + node]; default_left[q] = 0;
+      }
+    }
+    nn += cntn;
+    tree_off[t + 1] = (int32_t)nn;
+    tree_class[t] = (int32_t)(t % K);
+  }
+  for (int w = 0; w <= W; ++w) win_tree0[w] = w * R * K;
+  *n_nodes_out = nn;
+  if (loss_out)
+    for (int r = 0; r <= R; ++r) loss_out[r] = hL[(size_t)r];
+  if (prof) std::memcpy(g_phase_ms, ms, sizeof(ms));
+  return hipSuccess;
+}
+
+#define HIPCHK(ctx, expr)                                                                          \
+  do {                                                                                             \
+    const hipError_t e__ = (expr);                                                                 \
+    if (e__ != hipSuccess)                                                                         \
+      return gnx_fail((ctx), GNX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));        \
+  } while (0)
+
+// ---- training the boosted-tree base (XGBBase) --------------------------------------------------------------------
+namespace {
+int gbt_base_check(gnx_ctx* ctx, const void* X, const int32_t* y, int64_t N, int64_t ldx, int64_t C, int64_t M, int64_t cx, int32_t A,
+                          const gnx_gbt_params* P, const void* o1, const void* o2, const void* o3, const void* o4, const void* o5, const void* o6,
+                          const void* o7, const void* o8, const void* o9) {
+  if (!ctx->usable) return gnx_fail(ctx, GNX_ESTATE, "context has no device (gnx_init failed)");
+  if (N <= 0 || !X || !y || !P || !o1 || !o2 || !o3 || !o4 || !o5 || !o6 || !o7 || !o8 || !o9)
+    return gnx_fail(ctx, GNX_EINVAL, "train_gbt_base: bad X / y / params / outputs (N must be positive)");
+  if (A < 2 || A > 32) return gnx_fail(ctx, GNX_EINVAL, "A (ancestries) must be in [2, 32]");
+  if (M <= 0 || C < M || cx < 0 || cx > C || ldx < C) return gnx_fail(ctx, GNX_EINVAL, "bad C / M / ctx / ldx");
+  if (C % M == 0) return gnx_fail(ctx, GNX_EINVAL, "C % M == 0: the reference's window slicing (base.py:158) requires a remainder");
+  if (P->n_rounds < 1 || P->n_rounds > 100000 || P->max_depth < 1 || P->max_depth > 5)
+    return gnx_fail(ctx, GNX_EINVAL, "train_gbt_base: n_rounds >= 1, 1 <= max_depth <= 5");
+  if (!(P->eta > 0.0) || !(P->lambda >= 0.0) || !(P->gamma >= 0.0) || !(P->min_child_weight >= 0.0))
+    return gnx_fail(ctx, GNX_EINVAL, "train_gbt_base: eta > 0, lambda / gamma / min_child_weight >= 0");
+  if (A == 2 && !(P->base_score > 0.0 && P->base_score < 1.0)) return gnx_fail(ctx, GNX_EINVAL, "train_gbt_base: binary:logistic needs 0 < base_score < 1");
+  // grid and index limits: rows in int32, (window, tree, row block) and every tree's 63 node slots in one grid dimension
+  const int64_t W = C / M, K = A == 2 ? 1 : A, width = M + 2 * cx + C % M;
+  if (N >= ((int64_t)1 << 31) || width >= ((int64_t)1 << 24) || W * K * ((N + 255) / 256) >= ((int64_t)1 << 31) ||
+      W * K * P->n_rounds * 63 >= ((int64_t)1 << 31) || ((width + 255) / 256) * ((N + 2047) / 2048) > 65535)
+    return gnx_fail(ctx, GNX_EINVAL, "train_gbt_base: problem too large for one launch sequence");
+  return GNX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int gnx_train_gbt_base_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const int32_t* dy, int64_t C, int64_t M, int64_t cx, int32_t A,
+                           const gnx_gbt_params* P, int32_t* win_tree0, int32_t* tree_off, int32_t* left, int32_t* right, int32_t* feat,
+                           float* cond, uint8_t* default_left, int32_t* tree_class, int64_t* n_nodes, double* loss) {
+  if (!ctx) return GNX_EINVAL;
+  int rc = gbt_base_check(ctx, dX, dy, N, ldx, C, M, cx, A, P, win_tree0, tree_off, left, right, feat, cond, default_left, tree_class, n_nodes);
+  if (rc != GNX_OK) return rc;
+  GNX_BIND_DEVICE(ctx);
+  HIPCHK(ctx, gnx_train_gbt_base_run(dX, N, ldx, dy, C, M, cx, A, *P, win_tree0, tree_off, left, right, feat, cond, default_left, tree_class,
+                                     n_nodes, loss, ctx->stream));
+  return GNX_OK;
+}
+
+int gnx_train_gbt_base(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t ldx, const int32_t* y, int64_t C, int64_t M, int64_t cx, int32_t A,
+                       const gnx_gbt_params* P, int32_t* win_tree0, int32_t* tree_off, int32_t* left, int32_t* right, int32_t* feat, float* cond,
+                       uint8_t* default_left, int32_t* tree_class, int64_t* n_nodes, double* loss) {
+  if (!ctx) return GNX_EINVAL;
+  int rc = gbt_base_check(ctx, X, y, N, ldx, C, M, cx, A, P, win_tree0, tree_off, left, right, feat, cond, default_left, tree_class, n_nodes);
+  if (rc != GNX_OK) return rc;
+  const int64_t W = C / M;
+  for (int64_t i = 0; i < N * W; ++i)
+    if (y[i] < 0 || y[i] >= A) return gnx_fail(ctx, GNX_EINVAL, "train_gbt_base: label outside [0, A)");
+  for (int64_t n = 0; n < N; ++n)
+    for (int64_t j = 0; j < C; ++j)
+      if ((uint8_t)X[n * ldx + j] > 2) return gnx_fail(ctx, GNX_EINVAL, "train_gbt_base: X holds a code outside {0, 1, 2}");
+  GNX_BIND_DEVICE(ctx);
+  if ((rc = gnx_ws_reserve(ctx, ctx->ws_x, (size_t)N * ldx + 64)) != GNX_OK) return rc;
+  if ((rc = gnx_ws_reserve(ctx, ctx->ws_lab, (size_t)N * W * 4)) != GNX_OK) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->ws_x.p, X, (size_t)(N - 1) * ldx + C, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->ws_lab.p, y, (size_t)N * W * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, gnx_train_gbt_base_run((const int8_t*)ctx->ws_x.p, N, ldx, (const int32_t*)ctx->ws_lab.p, C, M, cx, A, *P, win_tree0, tree_off, left,
+                                     right, feat, cond, default_left, tree_class, n_nodes, loss, ctx->stream));
+  return GNX_OK;
+}
+
+int gnx_train_gbt_base_phases(int32_t enable, double* ms) {
+  if (enable >= 0) g_phases_on = enable != 0;
+  if (ms) std::memcpy(ms, g_phase_ms, sizeof(g_phase_ms));
+  return GNX_OK;
+}
+
+}  // extern "C"

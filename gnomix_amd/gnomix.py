@@ -46,7 +46,7 @@ class HipGnomix:
         return path
 
     def train_base(self, X, y):
-        """the base half of Gnomix.train (src/model.py:113, 155): fit the base (logistic or CovRSK SVC) on the device, then re-bind base,
+        """the base half of Gnomix.train (src/model.py:113, 155): fit the base (logistic, SVC or boosted trees) on the device, then re-bind base,
         smoother and the fused path to the freshly loaded model"""
         self.base.train(X, y)
         self.dev = self.base.dev

@@ -120,6 +120,71 @@ def train_gbt_smoother(data: GnxModelData, B, y, **kw) -> np.ndarray:
     return loss
 
 
+def train_forest_arrays(X, y, M, context, A, n_rounds=20, max_depth=4, learning_rate=0.1, reg_lambda=1.0, gamma=0.0, min_child_weight=1.0,
+                        base_score=0.5, ctx=None, device=0):
+    """XGBBase's per-window XGBClassifier(n_estimators=20, max_depth=4, learning_rate=0.1, reg_lambda=1, missing=2).fit on the device,
+    all windows at once (gnx_train_gbt_base; the algorithm is stated in forest/k_train_gbt_base.hip, NOT pinned to xgboost's own trees).
+    X (N, C) int8 codes {0, 1, 2 = missing} — a numpy array, or a CUDA int8 tensor that stays on the device — y (N, W) labels ->
+    (dict of fb_* arrays as GnxModelData takes them, losses (n_rounds + 1,))."""
+    ctx = ctx or _lib.default_context(device)
+    on_dev = hasattr(X, "is_cuda") and X.is_cuda
+    if on_dev:
+        import torch
+        assert X.dtype == torch.int8 and X.dim() == 2 and X.stride(1) == 1
+        N, Cn = X.shape
+        ldx = X.stride(0) if N > 1 else Cn
+        W = Cn // int(M)
+        y = y if (hasattr(y, "is_cuda") and y.is_cuda) else torch.as_tensor(np.ascontiguousarray(y, dtype=np.int32), device=X.device)
+        assert y.dtype == torch.int32 and y.is_contiguous() and tuple(y.shape) == (N, W)
+        x_ptr, y_ptr, fn = X.data_ptr(), y.data_ptr(), ctx.lib.gnx_train_gbt_base_dev
+        ctx.set_stream(torch.cuda.current_stream(ctx.device).cuda_stream)
+    else:
+        X = np.ascontiguousarray(X, dtype=np.int8)
+        N, Cn = X.shape
+        ldx = Cn
+        W = Cn // int(M)
+        y = np.ascontiguousarray(y, dtype=np.int32)
+        if y.shape != (N, W):
+            raise ValueError(f"y must be (N, W) = ({N}, {W}), got {y.shape}")
+        x_ptr, y_ptr, fn = X.ctypes.data, y.ctypes.data, ctx.lib.gnx_train_gbt_base
+    T = W * int(n_rounds) * (1 if int(A) == 2 else int(A))
+    # a complete tree of that depth (the library rejects depths outside 1..5 itself: include/gnomix_hip.h)
+    cap = max(T, 1) * (2 ** (min(max(int(max_depth), 1), 5) + 1) - 1)
+    wt0 = np.zeros(W + 1, np.int32); tree_off = np.zeros(max(T, 0) + 1, np.int32); tree_class = np.zeros(max(T, 1), np.int32)
+    left = np.zeros(cap, np.int32); right = np.zeros(cap, np.int32); feat = np.zeros(cap, np.int32)
+    cond = np.zeros(cap, np.float32); dleft = np.zeros(cap, np.uint8); loss = np.zeros(max(int(n_rounds), 0) + 1, np.float64)
+    nn = C.c_int64(0)
+    P = _lib.GbtParams(int(n_rounds), int(max_depth), 256, 0, float(learning_rate), float(reg_lambda), float(gamma), float(min_child_weight),
+                       float(base_score))
+    ctx.check(fn(ctx.h, x_ptr, int(N), int(ldx), y_ptr, int(Cn), int(M), int(context), int(A), C.byref(P), wt0.ctypes.data, tree_off.ctypes.data,
+                 left.ctypes.data, right.ctypes.data, feat.ctypes.data, cond.ctypes.data, dleft.ctypes.data, tree_class.ctypes.data,
+                 C.addressof(nn), loss.ctypes.data))
+    n = nn.value
+    trees = dict(fb_win_tree0=wt0, fb_tree_off=tree_off, fb_left=left[:n].copy(), fb_right=right[:n].copy(), fb_feat=feat[:n].copy(),
+                 fb_cond=cond[:n].copy(), fb_default_left=dleft[:n].copy(), fb_tree_class=tree_class[:T].copy())
+    return trees, loss
+
+
+def train_forest_base(data: GnxModelData, X, y, **kw) -> np.ndarray:
+    """fit the boosted-tree base of `data` in place (base_kind "forest", fb_* arrays, fb_missing = 2, fb_base_score) -> losses per round"""
+    trees, loss = train_forest_arrays(X, y, data.M, data.context, data.A, **kw)
+    data.base_kind, data.fb_missing = "forest", 2
+    data.fb_base_score = float(kw.get("base_score", 0.5))
+    for k, v in trees.items():
+        setattr(data, k, v)
+    return loss
+
+
+def forest_placeholder(W, A):
+    """one stump per window and class (a split on the window's first SNP, two zero leaves): every class gets probability 1 / A"""
+    K = 1 if A == 2 else A
+    T = W * K
+    return dict(fb_win_tree0=(np.arange(W + 1) * K).astype(np.int32), fb_tree_off=(3 * np.arange(T + 1)).astype(np.int32),
+                fb_left=np.tile(np.array([1, -1, -1], np.int32), T), fb_right=np.tile(np.array([2, -1, -1], np.int32), T),
+                fb_feat=np.zeros(3 * T, np.int32), fb_cond=np.tile(np.array([0.5, 0.0, 0.0], np.float32), T),
+                fb_default_left=np.zeros(3 * T, np.uint8), fb_tree_class=(np.arange(T) % K).astype(np.int32))
+
+
 def cnn_init(A, S, seed=None):
     """nn.Conv1d(A, A, S)'s default initialisation (torch.nn.modules.conv._ConvNd.reset_parameters): kaiming_uniform_(a = sqrt 5)
     on the weight and uniform(+-1/sqrt(fan_in)) on the bias are both uniform(+-1/sqrt(A * S)); numpy's generator, not torch's"""
@@ -317,7 +382,7 @@ def train_svc_base(data: GnxModelData, X, y, ctx=None, seeds=None, kernel="CovRS
 def untrained_model(C, M, A, S, context, mode, seed=None, meta=None, base=None):
     """an untrained model of a mode's kinds (the reference's config model.inference: "default", "fast", "large", "best"), ready to
     be loaded and then trained in place: zero logistic weights or, for "best", one placeholder SVC per window (A zero rows, zero
-    coefficients); the smoother's starting point: one placeholder tree, zero CRF weights, Conv1d's default initialisation.
+    coefficients), or with base="xgb" one zero-valued stump per window and class; the smoother's starting point: one placeholder tree, zero CRF weights, Conv1d's default initialisation.
     meta: optional dict with snp_pos, snp_ref, snp_alt, pop_order (the simulation's metadata)"""
     from . import synth
     from .convert import cov_sample
@@ -329,9 +394,14 @@ def untrained_model(C, M, A, S, context, mode, seed=None, meta=None, base=None):
         kw = dict(snp_pos=np.asarray(meta["snp_pos"]), snp_ref=np.asarray(meta["snp_ref"]), snp_alt=np.asarray(meta["snp_alt"]),
                   population_order=list(meta["pop_order"]))
     d = GnxModelData(C=C, M=M, A=A, S=S, context=context, **kw)
-    if base not in (None, "svm"):
-        raise ValueError("base must be None (the mode's own base) or \"svm\" (SVMBase: the RBF SVC), got %r" % (base,))
-    if base == "svm":   # SVMBase (src/Base/models.py:148-159) in place of the mode's base; the smoother stays the mode's
+    if base not in (None, "svm", "xgb"):
+        raise ValueError("base must be None (the mode's own base), \"svm\" (SVMBase: the RBF SVC) or \"xgb\" (XGBBase: boosted trees), "
+                         "got %r" % (base,))
+    if base == "xgb":   # XGBBase (src/Base/models.py:24-35) in place of the mode's base; the smoother stays the mode's
+        d.base_kind, d.fb_missing, d.fb_base_score = "forest", 2, 0.5
+        for k, v in forest_placeholder(W, A).items():
+            setattr(d, k, v)
+    elif base == "svm":   # SVMBase (src/Base/models.py:148-159) in place of the mode's base; the smoother stays the mode's
         P = A * (A - 1) // 2
         d.base_kind, d.svc = "covrsk", []
         for w in range(W):

@@ -15,6 +15,7 @@
  *   gnx_train_logistic    <- Base.train(X, y) of LogisticRegressionBase   src/Base/base.py:104-127, src/model.py:113,155
  *   gnx_train_svc         <- Base.train(X, y) of CovRSKBase (mode "best") src/Base/base.py:104-127, src/Base/models.py:195-215
  *   gnx_train_svc2        <- the same, and Base.train(X, y) of SVMBase (RBF)  src/Base/models.py:148-159
+ *   gnx_train_gbt_base    <- Base.train(X, y) of XGBBase (boosted trees)  src/Base/base.py:104-127, src/Base/models.py:24-35
  *   gnx_train_gbt         <- Smoother.train(B, y) of XGB_Smoother         src/Smooth/smooth.py:28-38, src/model.py:137
  *   gnx_train_crf         <- Smoother.train(B, y) of CRF_Smoother         src/Smooth/crf.py:51-58, src/Smooth/models.py:27-32
  *   gnx_train_cnn         <- Smoother.train(B, y) of CNN_Smoother         src/Smooth/cnn.py:104-118, src/Smooth/models.py:35-42
@@ -439,6 +440,36 @@ int gnx_train_gbt(gnx_ctx* ctx, const void* B, int32_t b_is_f64, const int32_t* 
 int gnx_train_gbt_dev(gnx_ctx* ctx, const void* dB, int32_t b_is_f64, const int32_t* dy, int64_t N, int32_t W, int32_t A, int32_t S,
                       const gnx_gbt_params* params, int32_t* tree_off, int32_t* tree_class, int32_t* left, int32_t* right,
                       int32_t* feat, float* cond, int64_t* n_nodes, double* loss);
+
+/* ---- training the boosted-tree base: Base.train of XGBBase (src/Base/base.py:104-127, src/Base/models.py:24-35: per window
+ *      XGBClassifier(n_estimators=20, max_depth=4, learning_rate=0.1, reg_lambda=1, reg_alpha=0, missing=2).fit(Xw, yw)).
+ * Second-order boosting on the window's SNP codes, all W = C / M windows in one launch sequence per round (forest/k_train_gbt_base.hip, whose
+ * header states the algorithm completely).  As for gnx_train_gbt, xgboost is a third-party fitter outside the reference tree: what is
+ * reproduced is the algorithm that call asks for, NOT xgboost's floating-point trajectory (parity with xgboost itself is unpinned);
+ * gradient sums are fixed point (2^-30) in int64, so the trees do not depend on scheduling and equal the CPU restatement bit for bit.
+ *   X (N, ldx) int8 codes 0, 1 and 2 = missing (fb_missing), y (N, W) int32 labels in [0, A).  gnx_train_gbt_base rejects any other
+ *     code and any label outside the range (GNX_EINVAL).  gnx_train_gbt_base_dev (arrays already in HBM) reads neither back: a code
+ *     other than 1 or 2 trains as a 0 (codes are only compared, never used as an index) and, as in gnx_train_gbt_dev, a label outside
+ *     [0, A) belongs to no class.
+ *   A >= 3: multi:softprob, A trees per round, tree t of a window adds to class t % A;  A == 2: binary:logistic, one tree per round.
+ *   params: n_rounds (20 for XGBBase), max_depth (4; 1..5), eta, lambda, gamma, min_child_weight, base_score (0.5).  max_bin and
+ *     tree_method are ignored: a SNP has two present values, so xgboost's "hist" and "exact" enumerate the same splits.
+ *   outputs (HOST, caller-allocated), the forest base's own layout, ready for gnx_model_desc (fb_*): win_tree0[W+1], tree_off[T+1],
+ *     tree_class[T], left / right / feat (int32, feat = SNP index within the window's padded slice), cond (float32: 0.5 or 1.5, a
+ *     leaf's value at leaves) and default_left (uint8) with room for (2^(max_depth+1) - 1) T nodes, T = W * n_rounds * (A == 2 ? 1 : A);
+ *     *n_nodes = nodes written; loss[n_rounds + 1] (optional) = mean log loss over the N * W problems before each round and after
+ *     the last (float64).
+ * gnx_train_gbt_base_phases(enable, ms): enable = 1 / 0 makes later calls time their phases (one stream synchronisation per phase) or
+ *   stops that, -1 leaves the switch; ms (5 doubles, may be NULL) receives the last timed call's milliseconds in gradients + loss,
+ *   per-level sums, split search, row partition, leaves + margins.  Process-wide, for scripts/bench_train_forest.py. */
+int gnx_train_gbt_base(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t ldx, const int32_t* y, int64_t C, int64_t M, int64_t ctx_snps,
+                       int32_t A, const gnx_gbt_params* params, int32_t* win_tree0, int32_t* tree_off, int32_t* left, int32_t* right,
+                       int32_t* feat, float* cond, uint8_t* default_left, int32_t* tree_class, int64_t* n_nodes, double* loss);
+int gnx_train_gbt_base_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const int32_t* dy, int64_t C, int64_t M,
+                           int64_t ctx_snps, int32_t A, const gnx_gbt_params* params, int32_t* win_tree0, int32_t* tree_off, int32_t* left,
+                           int32_t* right, int32_t* feat, float* cond, uint8_t* default_left, int32_t* tree_class, int64_t* n_nodes,
+                           double* loss);
+int gnx_train_gbt_base_phases(int32_t enable, double* ms);
 
 /* ---- training the convolutional smoother: CNN.fit (src/Smooth/cnn.py:104-118) as Smoother.train calls it for CNN_Smoother
  *      (src/Smooth/smooth.py:28-38, src/Smooth/models.py:35-42).  nn.Conv1d(A, A, S, padding = (S-1)/2) with zero padding,

@@ -29,7 +29,7 @@ MUST_BE_CLEAN = [
     r"k_smooth_xgb_rk<3, 8, 4, true, ", r"k_smooth_crf_ck<", r"k_smooth_crf_row16<", r"k_crf_psi<", r"k_smooth_cnn<",
     r"k_gnofix<", r"k_gnofix_ranks", r"k_gnofix_dif", r"k_gnofix_swap", r"k_gnofix_pmax", r"k_gnofix_count", r"k_gnofix_scan", r"k_gnofix_scatter", r"k_covrsk_dec_fast<\d+, 7>", r"k_covrsk_dec_fast<\d+, 0>", r"k_covrsk_dec<", r"k_svc_couple", r"k_calibrate",
     r"k_base_forest2<", r"k_base_forest<1, true, 8, 1>", r"k_base_forest<1, true, 16, 1>",
-    r"k_unpack2<", r"k_gt2_to_x<", r"k_x_to_gt2", r"k_tr_forward<", r"k_tr_backward<", r"k_gbt_", r"k_sim_admix", r"k_sim_check_",
+    r"k_unpack2<", r"k_gt2_to_x<", r"k_x_to_gt2", r"k_tr_forward<", r"k_tr_backward<", r"k_gbt_", r"k_fbt_", r"k_sim_admix", r"k_sim_check_",
     r"k_svc_pack", r"k_svc_gram", r"k_svc_smo", r"k_svc_heldout", r"k_svc_sigmoid",
     r"k_rbf_dec<", r"k_rbf_stage", r"k_rbf_norm", r"k_rbf_gram",
 ]
