@@ -14,9 +14,9 @@ import weakref
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("GNX_LIBRARY") or os.path.join(_HERE, "libgnomix_hip.so")   # GNX_LIBRARY: another build of the same ABI (kernel A/B timing, scripts/dev)
 
-GNX_ABI_VERSION = 15
+GNX_ABI_VERSION = 16
 GNX_OK, GNX_EINVAL, GNX_ENOMEM, GNX_EHIP, GNX_EUNSUPPORTED, GNX_ESTATE, GNX_ESTALE = 0, -1, -2, -3, -4, -5, -6
-BASE_NONE, BASE_LOGISTIC, BASE_COVRSK_SVC, BASE_FOREST, BASE_RFOREST = 0, 1, 2, 3, 4
+BASE_NONE, BASE_LOGISTIC, BASE_COVRSK_SVC, BASE_FOREST, BASE_RFOREST, BASE_KNN = 0, 1, 2, 3, 4, 5
 SVC_KERNEL_SUBSTRINGS, SVC_KERNEL_POLY, SVC_KERNEL_ALL_LENGTHS, SVC_KERNEL_RBF = 0, 1, 2, 3
 SMOOTH_NONE, SMOOTH_XGB, SMOOTH_CRF, SMOOTH_CNN = 0, 1, 2, 3
 K_BASE_LOGISTIC, K_SMOOTH_XGB, K_BASE_COVRSK, K_SMOOTH_CRF, K_GNOFIX, K_SMOOTH_ROWS, K_CALIBRATE, K_BASE_FOREST, K_SMOOTH_CNN = range(9)
@@ -43,6 +43,10 @@ class SvcWindow(C.Structure):
                 ("kernel_kind", C.c_int32), ("poly_p", C.c_double), ("run_value", C.c_void_p), ("gamma", C.c_double)]
 
 
+class KnnWindow(C.Structure):
+    _fields_ = [("xfit", C.c_void_p), ("y", C.c_void_p), ("n_fit", C.c_int32), ("width", C.c_int32)]
+
+
 class ModelDesc(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("A", C.c_int32), ("C", C.c_int64), ("M", C.c_int64), ("ctx", C.c_int64),
                 ("S", C.c_int32), ("base_kind", C.c_int32), ("smooth_kind", C.c_int32), ("reserved0", C.c_int32),
@@ -61,7 +65,8 @@ class ModelDesc(C.Structure):
                 ("rf_n_trees", C.c_int32), ("rf_n_nodes", C.c_int32), ("rf_win_tree0", C.c_void_p), ("rf_tree_off", C.c_void_p),
                 ("rf_left", C.c_void_p), ("rf_right", C.c_void_p), ("rf_feat", C.c_void_p), ("rf_thr", C.c_void_p),
                 ("rf_value", C.c_void_p), ("cnn_weight", C.c_void_p), ("cnn_bias", C.c_void_p),
-                ("prepared", C.c_void_p), ("prepared_bytes", C.c_int64)]
+                ("prepared", C.c_void_p), ("prepared_bytes", C.c_int64),
+                ("knn", C.c_void_p)]
 
 
 class TrainInfo(C.Structure):

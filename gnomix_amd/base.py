@@ -33,17 +33,20 @@ class HipBase:
         BaseLibSVM.fit; later windows from the state each CovRSK kernel call leaves), and the global generator is left where the
         reference leaves it.  RBF windows (SVMBase): every window's SVC(C=100, gamma, probability=True), one seed per window drawn
         from numpy's global generator in window order.  Forest base (XGBBase): every window's 20 rounds of depth-4 boosted
-        trees (train.train_forest_base)."""
+        trees (train.train_forest_base).  1-NN base (KNNBase): the rows are stored (train.train_knn_base; there is nothing to fit)."""
         from .train import train_logistic_base, train_svc_base, svc_seed_chain, svc_rng_after_kernel, SVC_SEED_HIGH
         from .model import DeviceModel, svc_window_is_rbf
         d = self.dev.data
         if d.base_kind == "rforest":
             raise NotImplementedError("on-device training is not built for the random-forest base (RFBase: scikit-learn's bootstrap "
                                       "stream); the logistic, SVC (CovRSK, RBF) and boosted-tree (XGBBase) bases are")
-        if d.base_kind not in (None, "logistic", "covrsk", "forest"):
+        if d.base_kind not in (None, "logistic", "covrsk", "forest", "knn"):
             raise NotImplementedError("on-device training is built for the logistic, the SVC (CovRSK, RBF) and the boosted-tree bases")
         t = time()
-        if d.base_kind == "forest":
+        if d.base_kind == "knn":
+            from .train import train_knn_base
+            self.train_info = train_knn_base(d, X, y, ctx=self.dev.ctx)
+        elif d.base_kind == "forest":
             # XGBBase: every window's XGBClassifier(n_estimators=20, max_depth=4) (the algorithm, not xgboost's own trajectory)
             from .train import train_forest_base
             self.train_info = {"loss": train_forest_base(d, X, y, ctx=self.dev.ctx)}

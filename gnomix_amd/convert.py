@@ -80,6 +80,43 @@ def svc_rbf_window_from_sklearn(svc, width):
                 n_support=np.asarray(svc._n_support).astype(np.int32), kernel=np.array("rbf"), gamma=np.float64(gamma))
 
 
+def knn_window_from_sklearn(knn, width, n_class):
+    """One fitted KNeighborsClassifier(n_neighbors=1) (or a stubbed pickle's attribute bag with the same attributes) -> the dict
+    GnxModelData.knn holds: xfit = _fit_X as int8, y = classes_[_y] as int32.  Refused: n_neighbors != 1, non-uniform weights,
+    a metric other than Euclidean (Minkowski with p = 2), fit data that are not the whole-number SNP codes 0..2 (the kernel's
+    distances are integers), labels outside 0..n_class-1."""
+    k = getattr(knn, "n_neighbors", None)
+    if k is None or int(k) != 1:
+        raise NotImplementedError(f"KNeighborsClassifier with n_neighbors = {k!r}: only n_neighbors = 1 (KNNBase) is built")
+    wts = getattr(knn, "weights", "uniform")
+    if wts is not None and (not isinstance(wts, str) or wts != "uniform"):
+        raise NotImplementedError(f"KNeighborsClassifier with weights = {wts!r}: only uniform weights are built")
+    metric, p = getattr(knn, "metric", "minkowski"), getattr(knn, "p", 2)
+    eff = getattr(knn, "effective_metric_", None)
+    euclid = (isinstance(metric, str) and metric in ("euclidean", "l2")) or \
+             (isinstance(metric, str) and metric == "minkowski" and p is not None and float(p) == 2.0)
+    if not euclid or (eff is not None and eff not in ("euclidean", "l2", "minkowski")):
+        raise NotImplementedError(f"KNeighborsClassifier with metric = {metric!r}, p = {p!r}: only the Euclidean metric "
+                                  "(minkowski, p = 2) is built")
+    fx = knn._fit_X
+    if hasattr(fx, "toarray"):
+        fx = fx.toarray()
+    fx = np.asarray(fx)
+    if fx.ndim != 2 or fx.shape[1] != int(width) or fx.shape[0] < 1:
+        raise ValueError(f"_fit_X must be (n_fit >= 1, {int(width)}), got {fx.shape}")
+    f64 = fx.astype(np.float64)
+    if not np.all(np.isfinite(f64)) or np.any(f64 != np.rint(f64)) or f64.min() < 0 or f64.max() > 2:
+        raise ValueError("_fit_X must hold the SNP codes 0, 1, 2 (whole numbers): the 1-NN base computes |x - y|^2 in integers")
+    classes = np.asarray(knn.classes_)
+    yi = np.asarray(knn._y).reshape(-1)
+    if len(yi) != fx.shape[0] or yi.min() < 0 or yi.max() >= len(classes):
+        raise ValueError("_y must index classes_ for every row of _fit_X")
+    lab = classes[yi]
+    if np.any(lab != np.rint(np.asarray(lab, dtype=np.float64))) or lab.min() < 0 or lab.max() >= int(n_class):
+        raise ValueError(f"classes_ must be whole numbers in 0..{int(n_class) - 1}, got {classes.tolist()}")
+    return dict(xfit=np.ascontiguousarray(f64, dtype=np.int8), y=np.ascontiguousarray(lab, dtype=np.int32))
+
+
 def poly_run_values(width, p=1.2):
     """what a run of L equal SNPs contributes to the polynomial string kernel (string_kernel.py:52: contigs ** p), computed
     by numpy exactly as the reference computes it (int64 array ** float)"""
@@ -435,6 +472,9 @@ def from_reference_model(model) -> GnxModelData:
         d.base_kind = "covrsk"
         kname = getattr(getattr(model.base, "kernel", None), "__name__", "CovRSK")
         d.svc = [svc_window_from_sklearn(m, d.window_width(i), kname) for i, m in enumerate(models)]
+    elif first == "KNeighborsClassifier":  # KNNBase (src/Base/models.py:135-146); the per-window arrays are kept as fitted
+        d.base_kind = "knn"
+        d.knn = [knn_window_from_sklearn(m, d.window_width(i), A) for i, m in enumerate(models)]
     elif first == "XGBClassifier":  # XGBBase (src/Base/models.py:24-35)
         d.base_kind = "forest"
         parts = [xgb_trees_of(m, A) for m in models]

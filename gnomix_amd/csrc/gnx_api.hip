@@ -369,6 +369,7 @@ int gnx_model_load(gnx_ctx* ctx, const gnx_model_desc* d, gnx_model** out) {
       break;
     case GNX_BASE_FOREST: rc = gnx_build_forest(m, d); break;
     case GNX_BASE_RFOREST: rc = gnx_build_rforest(m, d); break;
+    case GNX_BASE_KNN: rc = gnx_build_knn(m, d); break;
     default: rc = fail(ctx, GNX_EINVAL, "unknown base_kind");
   }
   if (rc == GNX_OK) switch (d->smooth_kind) {
@@ -447,6 +448,7 @@ int gnx_base_predict_dev(gnx_model* m, const int8_t* dX, int64_t N, int64_t ldx,
   if (N < 0 || ldx < m->info.C || (N > 0 && !dX)) return fail(ctx, GNX_EINVAL, "base_predict: bad X / N / ldx");
   if (N == 0 || (!d_b32 && !d_b64)) return GNX_OK;
   GNX_BIND_DEVICE(ctx);
+  if (m->info.base_kind == GNX_BASE_KNN) return gnx_base_predict_knn(m, dX, N, ldx, d_b32, d_b64);
   if (m->info.base_kind == GNX_BASE_COVRSK_SVC && m->rbf) {
     ProfScope ps(ctx, GNX_K_BASE_COVRSK);
     return gnx_base_predict_rbf(m, dX, N, ldx, d_b32, d_b64);

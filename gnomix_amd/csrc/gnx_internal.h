@@ -417,6 +417,7 @@ struct ForestLaunch {
 };
 
 struct SvcRbfModel;  // svm/k_base_rbf.hip
+struct KnnModel;     // knn/k_base_knn.hip
 
 struct gnx_model {
   gnx_ctx* ctx = nullptr;
@@ -432,6 +433,7 @@ struct gnx_model {
   SmoothXGBDev xgb;
   CovRSKDev svc;
   std::shared_ptr<SvcRbfModel> rbf;  // set instead of `svc` when the windows are GNX_SVC_KERNEL_RBF (svm/k_base_rbf.hip)
+  std::shared_ptr<KnnModel> knn;     // GNX_BASE_KNN (knn/k_base_knn.hip)
   ForestDev forest;
   // class-major xgboost-schema copy for the rows kernel
   const int32_t* class_tree0 = nullptr;  // device [A+1]
@@ -490,6 +492,9 @@ int gnx_build_covrsk(gnx_model* m, const gnx_model_desc* d);
 // the RBF SVC base (svm/k_base_rbf.hip): model preparation and pass 2a (distances on the int8 matrix cores -> r_ij) + pass 2b
 int gnx_build_svc_rbf(gnx_model* m, const gnx_model_desc* d);
 int gnx_base_predict_rbf(gnx_model* m, const int8_t* dX, int64_t N, int64_t ldx, float* d_b32, double* d_b64);
+// the 1-nearest-neighbour base (knn/k_base_knn.hip): model preparation and the argmin pass -> one-hot b32 / b64
+int gnx_build_knn(gnx_model* m, const gnx_model_desc* d);
+int gnx_base_predict_knn(gnx_model* m, const int8_t* dX, int64_t N, int64_t ldx, float* d_b32, double* d_b64);
 int gnx_build_forest(gnx_model* m, const gnx_model_desc* d);
 int gnx_build_rforest(gnx_model* m, const gnx_model_desc* d);
 int gnx_build_xgb(gnx_model* m, const gnx_model_desc* d);

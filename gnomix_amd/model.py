@@ -33,7 +33,7 @@ class GnxModelData:
     A: int
     S: int = 75
     context: int = 0                      # SNPs each side = int(M*context_ratio) (src/model.py:47)
-    base_kind: str | None = None          # "logistic" | "covrsk" | "forest" | "rforest"
+    base_kind: str | None = None          # "logistic" | "covrsk" | "forest" | "rforest" | "knn"
     smooth_kind: str | None = None        # "xgb" | "crf" | "cnn"
     # logistic base: coef_ / intercept_ of LogisticRegression per window (src/Base/models.py:12-21)
     lr_coef: np.ndarray | None = None     # (W, A, ldc) float64, window i uses [:, :width_i]
@@ -41,6 +41,12 @@ class GnxModelData:
     # CovRSK base: per-window fitted SVC (src/Base/models.py:195-215)
     svc: list | None = None               # list of dicts: xfit, support, dual_coef, intercept, prob_a, prob_b, n_support, ms
                                           # (SVMBase windows: kernel = "rbf" and gamma instead of ms)
+    # knn base: per-window KNeighborsClassifier(n_neighbors=1) (src/Base/models.py:135-146).  Either the shared form that training
+    # produces (every window's fit rows are the same haplotypes: window w's rows are knn_X[:, window_columns(w)], its labels
+    # knn_y[:, w]) or, for a converted pickle, the per-window arrays as they were fitted
+    knn_X: np.ndarray | None = None       # (n_fit, C) int8, codes 0..2
+    knn_y: np.ndarray | None = None       # (n_fit, W) int32 labels in [0, A)
+    knn: list | None = None               # list of dicts: xfit (n_fit_w, width_w) int8, y (n_fit_w,) int32
     # forest base: per-window XGBClassifier (src/Base/models.py:24-35), xgboost model schema, all windows concatenated
     fb_win_tree0: np.ndarray | None = None   # (W+1,) first tree of each window
     fb_tree_off: np.ndarray | None = None
@@ -113,7 +119,7 @@ class GnxModelData:
         chr22 model shrinks by a few percent) and inflating them costs the command line 0.6 s of its ~1.4 s; load reads both."""
         d = {"gnx_version": GNX_FILE_VERSION}
         for k, v in self.__dict__.items():
-            if v is None or k in ("svc", "extra"):
+            if v is None or k in ("svc", "knn", "extra"):
                 continue
             if k == "population_order":
                 d[k] = np.array([str(p) for p in v])
@@ -124,6 +130,11 @@ class GnxModelData:
             for i, w in enumerate(self.svc):
                 for kk, vv in w.items():
                     d[f"svc{i}_{kk}"] = np.asarray(vv)
+        if self.knn is not None:
+            d["knn_n"] = len(self.knn)
+            for i, w in enumerate(self.knn):
+                for kk, vv in w.items():
+                    d[f"knn{i}_{kk}"] = np.asarray(vv)
         with open(path, "wb") as f:
             (np.savez_compressed if compress else np.savez)(f, **d)
 
@@ -153,7 +164,25 @@ class GnxModelData:
             for i in range(int(z["svc_n"])):
                 pre = f"svc{i}_"
                 m.svc.append({k[len(pre):]: z[k] for k in z.files if k.startswith(pre)})
+        if "knn_n" in z.files:
+            m.knn = [{"xfit": z[f"knn{i}_xfit"], "y": z[f"knn{i}_y"]} for i in range(int(z["knn_n"]))]
         return m
+
+    def knn_windows(self):
+        """the knn base's per-window (xfit (n_fit, width) int8, y (n_fit,) int32) pairs: the per-window arrays of a converted
+        model, or the shared form cut with train.window_columns"""
+        if self.knn is not None:
+            if len(self.knn) != self.W:
+                raise ValueError("knn must list one fitted window per window")
+            return [(_c(w["xfit"], np.int8), _c(w["y"], np.int32).reshape(-1)) for w in self.knn]
+        if self.knn_X is None or self.knn_y is None:
+            raise ValueError("knn base: neither knn (per window) nor knn_X / knn_y (shared) is set")
+        from .train import window_columns
+        X, y = _c(self.knn_X, np.int8), _c(self.knn_y, np.int32)
+        if X.ndim != 2 or X.shape[1] != self.C or y.shape != (X.shape[0], self.W):
+            raise ValueError(f"knn_X must be (n_fit, C={self.C}) and knn_y (n_fit, W={self.W}), got {X.shape} and {y.shape}")
+        return [(np.ascontiguousarray(X[:, window_columns(self.C, self.M, self.context, w)]), np.ascontiguousarray(y[:, w]))
+                for w in range(self.W)]
 
     # ---- C ABI description ---------------------------------------------------------------------------
     def to_desc(self):
@@ -169,7 +198,7 @@ class GnxModelData:
         d.abi_version = _lib.GNX_ABI_VERSION
         d.A, d.C, d.M, d.ctx, d.S = int(self.A), int(self.C), int(self.M), int(self.context), int(self.S)
         d.base_kind = {None: _lib.BASE_NONE, "logistic": _lib.BASE_LOGISTIC, "covrsk": _lib.BASE_COVRSK_SVC,
-                       "forest": _lib.BASE_FOREST, "rforest": _lib.BASE_RFOREST}[self.base_kind]
+                       "forest": _lib.BASE_FOREST, "rforest": _lib.BASE_RFOREST, "knn": _lib.BASE_KNN}[self.base_kind]
         d.smooth_kind = {None: _lib.SMOOTH_NONE, "xgb": _lib.SMOOTH_XGB, "crf": _lib.SMOOTH_CRF, "cnn": _lib.SMOOTH_CNN}[self.smooth_kind]
         W, A = self.W, self.A
         if self.base_kind == "logistic":
@@ -209,6 +238,15 @@ class GnxModelData:
                     s.ms, s.n_ms = ptr(ms, np.int32), len(ms)
             keep.append(arr)
             d.svc = C.addressof(arr)
+        elif self.base_kind == "knn":
+            arr = (_lib.KnnWindow * W)()
+            for i, (xf, yw) in enumerate(self.knn_windows()):
+                if xf.ndim != 2 or len(yw) != xf.shape[0]:
+                    raise ValueError(f"knn window {i}: xfit must be (n_fit, width) and y (n_fit,), got {xf.shape} and {yw.shape}")
+                k = arr[i]
+                k.xfit, k.y, k.n_fit, k.width = ptr(xf, np.int8), ptr(yw, np.int32), xf.shape[0], xf.shape[1]
+            keep.append(arr)
+            d.knn = C.addressof(arr)
         elif self.base_kind == "forest":
             wt0 = _c(self.fb_win_tree0, np.int32)
             if wt0.shape != (W + 1,):

@@ -379,10 +379,34 @@ def train_svc_base(data: GnxModelData, X, y, ctx=None, seeds=None, kernel="CovRS
     return info
 
 
+# ---- the 1-nearest-neighbour base (KNNBase) ------------------------------------------------------------------------------------
+def train_knn_base(data: GnxModelData, X, y, ctx=None) -> dict:
+    """fit the 1-NN base of `data` in place (base_kind "knn") -> info.  KNeighborsClassifier(n_neighbors=1).fit stores its
+    training set, so fitting is storing: no training kernel exists or is needed.  Every window's fit rows are the same
+    haplotypes, so the model keeps X (n_fit, C) and y (n_fit, W) once (the shared form) and windows are cut when the model is
+    loaded.  X must hold the codes 0..2, y labels in [0, A)."""
+    X = np.asarray(X)
+    if X.ndim != 2 or X.shape[1] != data.C or X.shape[0] < 1:
+        raise ValueError(f"X must be (N >= 1, C={data.C}), got {X.shape}")
+    if X.dtype.kind == "f" and np.any(X != np.rint(X)):
+        raise ValueError("X must hold whole numbers (the SNP codes 0, 1, 2)")
+    if X.min() < 0 or X.max() > 2:
+        raise ValueError("X must hold the SNP codes 0, 1, 2 (2 = missing)")
+    y = np.asarray(y)
+    if y.shape != (X.shape[0], data.W):
+        raise ValueError(f"y must be (N, W) = ({X.shape[0]}, {data.W}), got {y.shape}")
+    if y.min() < 0 or y.max() >= data.A:
+        raise ValueError(f"y must hold labels in 0..{data.A - 1}")
+    data.base_kind, data.knn = "knn", None
+    data.knn_X, data.knn_y = np.ascontiguousarray(X, dtype=np.int8), np.ascontiguousarray(y, dtype=np.int32)
+    return {"n_fit": int(X.shape[0])}
+
+
 def untrained_model(C, M, A, S, context, mode, seed=None, meta=None, base=None):
     """an untrained model of a mode's kinds (the reference's config model.inference: "default", "fast", "large", "best"), ready to
     be loaded and then trained in place: zero logistic weights or, for "best", one placeholder SVC per window (A zero rows, zero
-    coefficients), or with base="xgb" one zero-valued stump per window and class; the smoother's starting point: one placeholder tree, zero CRF weights, Conv1d's default initialisation.
+    coefficients), or with base="xgb" one zero-valued stump per window and class, or with base="knn" one fit row of zeros with label 0
+    per window; the smoother's starting point: one placeholder tree, zero CRF weights, Conv1d's default initialisation.
     meta: optional dict with snp_pos, snp_ref, snp_alt, pop_order (the simulation's metadata)"""
     from . import synth
     from .convert import cov_sample
@@ -394,10 +418,12 @@ def untrained_model(C, M, A, S, context, mode, seed=None, meta=None, base=None):
         kw = dict(snp_pos=np.asarray(meta["snp_pos"]), snp_ref=np.asarray(meta["snp_ref"]), snp_alt=np.asarray(meta["snp_alt"]),
                   population_order=list(meta["pop_order"]))
     d = GnxModelData(C=C, M=M, A=A, S=S, context=context, **kw)
-    if base not in (None, "svm", "xgb"):
-        raise ValueError("base must be None (the mode's own base), \"svm\" (SVMBase: the RBF SVC) or \"xgb\" (XGBBase: boosted trees), "
-                         "got %r" % (base,))
-    if base == "xgb":   # XGBBase (src/Base/models.py:24-35) in place of the mode's base; the smoother stays the mode's
+    if base not in (None, "svm", "xgb", "knn"):
+        raise ValueError("base must be None (the mode's own base), \"svm\" (SVMBase: the RBF SVC), \"xgb\" (XGBBase: boosted trees) "
+                         "or \"knn\" (KNNBase: 1-nearest neighbour), got %r" % (base,))
+    if base == "knn":   # KNNBase (src/Base/models.py:135-146) in place of the mode's base; the smoother stays the mode's
+        d.base_kind, d.knn_X, d.knn_y = "knn", np.zeros((1, C), np.int8), np.zeros((1, W), np.int32)
+    elif base == "xgb":   # XGBBase (src/Base/models.py:24-35) in place of the mode's base; the smoother stays the mode's
         d.base_kind, d.fb_missing, d.fb_base_score = "forest", 2, 0.5
         for k, v in forest_placeholder(W, A).items():
             setattr(d, k, v)

@@ -16,6 +16,8 @@
  *   gnx_train_svc         <- Base.train(X, y) of CovRSKBase (mode "best") src/Base/base.py:104-127, src/Base/models.py:195-215
  *   gnx_train_svc2        <- the same, and Base.train(X, y) of SVMBase (RBF)  src/Base/models.py:148-159
  *   gnx_train_gbt_base    <- Base.train(X, y) of XGBBase (boosted trees)  src/Base/base.py:104-127, src/Base/models.py:24-35
+ *   (no entry point)      <- Base.train(X, y) of KNNBase: a 1-NN fit stores its rows; the caller puts them into
+ *                            gnx_model_desc.knn and loads the model                src/Base/models.py:135-146
  *   gnx_train_gbt         <- Smoother.train(B, y) of XGB_Smoother         src/Smooth/smooth.py:28-38, src/model.py:137
  *   gnx_train_crf         <- Smoother.train(B, y) of CRF_Smoother         src/Smooth/crf.py:51-58, src/Smooth/models.py:27-32
  *   gnx_train_cnn         <- Smoother.train(B, y) of CNN_Smoother         src/Smooth/cnn.py:104-118, src/Smooth/models.py:35-42
@@ -55,7 +57,7 @@
 extern "C" {
 #endif
 
-#define GNX_ABI_VERSION 15
+#define GNX_ABI_VERSION 16
 
 typedef struct gnx_ctx gnx_ctx;
 typedef struct gnx_model gnx_model;
@@ -73,7 +75,8 @@ enum {
 
 enum { GNX_SVC_KERNEL_SUBSTRINGS = 0, GNX_SVC_KERNEL_POLY = 1, GNX_SVC_KERNEL_ALL_LENGTHS = 2 /* gnx_train_svc only */,
        GNX_SVC_KERNEL_RBF = 3 /* SVMBase: exp(-gamma |x - y|^2) on the SNP codes as numbers */ };
-enum { GNX_BASE_NONE = 0, GNX_BASE_LOGISTIC = 1, GNX_BASE_COVRSK_SVC = 2, GNX_BASE_FOREST = 3, GNX_BASE_RFOREST = 4 };
+enum { GNX_BASE_NONE = 0, GNX_BASE_LOGISTIC = 1, GNX_BASE_COVRSK_SVC = 2, GNX_BASE_FOREST = 3, GNX_BASE_RFOREST = 4,
+       GNX_BASE_KNN = 5 /* KNNBase: 1-nearest neighbour per window */ };
 enum { GNX_SMOOTH_NONE = 0, GNX_SMOOTH_XGB = 1, GNX_SMOOTH_CRF = 2, GNX_SMOOTH_CNN = 3 };
 
 /* kernel ids for gnx_profile_get */
@@ -124,6 +127,23 @@ typedef struct gnx_svc_window {
   const double* run_value;  /* POLY: (width+1,) value of a run of L equal SNPs = L ** p as numpy computed it */
   double gamma;             /* RBF: sklearn's _gamma */
 } gnx_svc_window;
+
+/* Per-window 1-nearest-neighbour classifier of KNNBase (src/Base/models.py:135-146 -> sklearn
+ * KNeighborsClassifier(n_neighbors=1): uniform weights, Euclidean metric).  B[n, w, c] = 1 if c is the label of the fit row
+ * nearest to the query's window slice, else 0 (float32 and float64 outputs hold exactly 0 and 1; a class absent from a
+ * window's labels gets a zero column).  The squared distance is an exact integer over the SNP codes as numbers (2 = missing is
+ * the number 2; a QUERY code 3, the largest a 2-bit packed row can hold, is the number 3, identically through the int8 and the
+ * 2-bit entry points).  TIES GO TO THE LOWEST FIT-ROW INDEX: a rule of this library and a deviation, since scikit-learn's
+ * choice among equidistant neighbours is unspecified (it depends on the algorithm it resolves to); the outputs agree wherever
+ * the minimum-distance rows carry one label.
+ * GNX_EINVAL: a code outside 0..2 in xfit, a label outside [0, A), n_fit < 1, width != the window's width.
+ * GNX_EUNSUPPORTED: windows wider than GNX_RBF_MAX_WIDTH SNPs. */
+typedef struct gnx_knn_window {
+  const int8_t* xfit;  /* (n_fit, width) fit rows, row-major, codes 0..2 (sklearn _fit_X) */
+  const int32_t* y;    /* (n_fit,) labels in [0, A) (classes_[_y]) */
+  int32_t n_fit;       /* >= 1 */
+  int32_t width;       /* M_ (or M_+rem for the last window), <= GNX_RBF_MAX_WIDTH */
+} gnx_knn_window;
 
 /* Everything a pickled src.model.Gnomix carries for inference (src/model.py:28-88), as flat host
  * arrays.  W = C / M (src/model.py:32); the reference requires C % M != 0 (gnomix.py:124-125). */
@@ -215,6 +235,9 @@ typedef struct gnx_model_desc {
    * does not match -> GNX_ESTALE, nothing loaded.  NULL / 0: prepare from lr_coef. */
   const void* prepared;
   int64_t prepared_bytes;
+
+  /* GNX_BASE_KNN */
+  const gnx_knn_window* knn;  /* (W,) */
 } gnx_model_desc;
 
 typedef struct gnx_model_info {

@@ -32,6 +32,7 @@ MUST_BE_CLEAN = [
     r"k_unpack2<", r"k_gt2_to_x<", r"k_x_to_gt2", r"k_tr_forward<", r"k_tr_backward<", r"k_gbt_", r"k_fbt_", r"k_sim_admix", r"k_sim_check_",
     r"k_svc_pack", r"k_svc_gram", r"k_svc_smo", r"k_svc_heldout", r"k_svc_sigmoid",
     r"k_rbf_dec<", r"k_rbf_stage", r"k_rbf_norm", r"k_rbf_gram",
+    r"k_knn_",
 ]
 
 
