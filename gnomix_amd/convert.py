@@ -117,6 +117,90 @@ def knn_window_from_sklearn(knn, width, n_class):
     return dict(xfit=np.ascontiguousarray(f64, dtype=np.int8), y=np.ascontiguousarray(lab, dtype=np.int32))
 
 
+NB_KINDS = {"BernoulliNB": "bernoulli", "MultinomialNB": "multinomial", "GaussianNB": "gaussian"}
+
+
+def nb_tables(kind, attrs, n_class):
+    """fitted attributes of ONE window -> (table (width, 4, A), bias (A,)) float64 as gnx_nb_window takes them.  attrs: classes_ and,
+    for "bernoulli" / "multinomial", feature_log_prob_ (k, width) and class_log_prior_ (k,); for "gaussian" theta_, var_ (k, width)
+    and class_prior_ (k,).  Class column c = classes_[k]; a class absent from classes_ gets bias -inf and zero table rows.
+      bernoulli:    T[p,0,c] = log(1 - exp(flp[c,p])), T[p,v>=1,c] = flp[c,p];  bias = class_log_prior_
+      multinomial:  T[p,v,c] = v * flp[c,p];                                    bias = class_log_prior_
+      gaussian:     T[p,v,c] = -0.5 (v - theta_[c,p])^2 / var_[c,p];           bias = log(class_prior_) - 0.5 sum_p log(2 pi var_)
+    (scikit-learn's _joint_log_likelihood of each estimator, evaluated at the four codes.)"""
+    A = int(n_class)
+    classes = np.asarray(attrs["classes_"])
+    cf = np.asarray(classes, dtype=np.float64)
+    if classes.ndim != 1 or len(classes) < 1 or np.any(cf != np.rint(cf)) or cf.min() < 0 or cf.max() >= A or len(set(cf.tolist())) != len(cf):
+        raise ValueError(f"classes_ must be distinct whole numbers in 0..{A - 1}, got {classes.tolist()}")
+    cols = cf.astype(np.int64)
+    v = np.arange(4, dtype=np.float64)
+    if kind in ("bernoulli", "multinomial"):
+        flp = np.asarray(attrs["feature_log_prob_"], dtype=np.float64)
+        prior = np.asarray(attrs["class_log_prior_"], dtype=np.float64).reshape(-1)
+        if flp.ndim != 2 or flp.shape[0] != len(cols) or prior.shape != (len(cols),):
+            raise ValueError("feature_log_prob_ must be (n_classes, width) and class_log_prior_ (n_classes,)")
+        if not np.all(np.isfinite(flp)):
+            raise ValueError("feature_log_prob_ is not finite: alpha=0 under scikit-learn >= 1.4 leaves log 0 on a class-monomorphic SNP "
+                             "(no smoothing is applied), and scikit-learn itself then returns NaN probabilities; refit with alpha > 0 "
+                             "(scikit-learn <= 1.3 raised alpha=0 to 1e-10, which gnomix_amd.train.train_nb_base does)")
+        if kind == "bernoulli":
+            with np.errstate(divide="ignore"):
+                neg = np.log(1.0 - np.exp(flp))
+            if not np.all(np.isfinite(neg)):
+                raise ValueError("log(1 - exp(feature_log_prob_)) is not finite: a SNP is non-zero in every row of a class and no "
+                                 "smoothing was applied (alpha=0 under scikit-learn >= 1.4 leaves log 0 there, and scikit-learn itself "
+                                 "then returns NaN probabilities); refit with alpha > 0")
+            t = np.stack([neg, flp, flp, flp], axis=0)                      # (4, k, width)
+        else:
+            t = v[:, None, None] * flp[None]
+        b = prior
+    elif kind == "gaussian":
+        theta = np.asarray(attrs["theta_"], dtype=np.float64)
+        var = np.asarray(attrs["var_"], dtype=np.float64)
+        cp = np.asarray(attrs["class_prior_"], dtype=np.float64).reshape(-1)
+        if theta.ndim != 2 or theta.shape != var.shape or theta.shape[0] != len(cols) or cp.shape != (len(cols),):
+            raise ValueError("theta_ / var_ must be (n_classes, width) and class_prior_ (n_classes,)")
+        if not (np.all(np.isfinite(theta)) and np.all(np.isfinite(var)) and np.all(var > 0) and np.all(np.isfinite(cp)) and np.all(cp > 0)):
+            raise ValueError("theta_ / var_ / class_prior_ must be finite, var_ and class_prior_ positive")
+        t = -0.5 * (v[:, None, None] - theta[None]) ** 2 / var[None]
+        b = np.log(cp) - 0.5 * np.sum(np.log(2.0 * np.pi * var), axis=1)
+    else:
+        raise ValueError(f"nb kind must be one of {sorted(NB_KINDS.values())}, got {kind!r}")
+    if not np.all(np.isfinite(t)) or not np.all(np.isfinite(b)):
+        raise ValueError("the Naive-Bayes table / bias of a present class is not finite")
+    width = t.shape[2]
+    table = np.zeros((width, 4, A))
+    bias = np.full(A, -np.inf)
+    table[:, :, cols] = np.transpose(t, (2, 0, 1))
+    bias[cols] = b
+    return table, bias
+
+
+def nb_window_from_sklearn(nb, width, n_class, kind=None):
+    """One fitted BernoulliNB / MultinomialNB / GaussianNB (or a stubbed pickle's attribute bag with the same attributes; then pass
+    `kind`) -> (table (width, 4, A), bias (A,)).  Refused: BernoulliNB with binarize != 0.0 (ValueError), non-finite
+    feature_log_prob_ (ValueError: see nb_tables), a width that is not the window's."""
+    kind = kind or NB_KINDS.get(type(nb).__name__)
+    if kind is None:
+        raise NotImplementedError(f"{type(nb).__name__} is not a Naive-Bayes estimator this library converts")
+    if kind == "bernoulli":
+        bz = getattr(nb, "binarize", 0.0)
+        if bz is None or float(bz) != 0.0:
+            raise ValueError(f"BernoulliNB with binarize = {bz!r}: only binarize = 0.0 (a SNP code counts as set when it is non-zero) is built")
+    names = ("classes_", "feature_log_prob_", "class_log_prior_") if kind != "gaussian" else ("classes_", "theta_", "var_", "class_prior_")
+    attrs = {}
+    for k in names:
+        if not hasattr(nb, k) and k == "var_" and hasattr(nb, "sigma_"):   # scikit-learn < 1.0 named it sigma_
+            attrs[k] = nb.sigma_
+        else:
+            attrs[k] = getattr(nb, k)
+    table, bias = nb_tables(kind, attrs, n_class)
+    if table.shape[0] != int(width):
+        raise ValueError(f"the estimator was fitted on {table.shape[0]} features, the window is {int(width)} wide")
+    return table, bias
+
+
 def poly_run_values(width, p=1.2):
     """what a run of L equal SNPs contributes to the polynomial string kernel (string_kernel.py:52: contigs ** p), computed
     by numpy exactly as the reference computes it (int64 array ** float)"""
@@ -475,6 +559,17 @@ def from_reference_model(model) -> GnxModelData:
     elif first == "KNeighborsClassifier":  # KNNBase (src/Base/models.py:135-146); the per-window arrays are kept as fitted
         d.base_kind = "knn"
         d.knn = [knn_window_from_sklearn(m, d.window_width(i), A) for i, m in enumerate(models)]
+    elif first in NB_KINDS:  # NBBernoulliBase / NBMultinomialBase / NBGaussianBase (src/Base/models.py:96-132) -> likelihood tables
+        d.base_kind, d.nb_kind = "nb", NB_KINDS[first]
+        d.nb_table = np.zeros((W, d.M_ + d.rem, 4, A))
+        d.nb_bias = np.zeros((W, A))
+        for i, m in enumerate(models):
+            try:
+                t, b = nb_window_from_sklearn(m, d.window_width(i), A, kind=d.nb_kind)
+            except ValueError as e:
+                raise ValueError(f"window {i}: {e}") from e
+            d.nb_table[i, :t.shape[0]] = t
+            d.nb_bias[i] = b
     elif first == "XGBClassifier":  # XGBBase (src/Base/models.py:24-35)
         d.base_kind = "forest"
         parts = [xgb_trees_of(m, A) for m in models]

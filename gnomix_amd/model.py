@@ -33,7 +33,7 @@ class GnxModelData:
     A: int
     S: int = 75
     context: int = 0                      # SNPs each side = int(M*context_ratio) (src/model.py:47)
-    base_kind: str | None = None          # "logistic" | "covrsk" | "forest" | "rforest" | "knn"
+    base_kind: str | None = None          # "logistic" | "covrsk" | "forest" | "rforest" | "knn" | "nb"
     smooth_kind: str | None = None        # "xgb" | "crf" | "cnn"
     # logistic base: coef_ / intercept_ of LogisticRegression per window (src/Base/models.py:12-21)
     lr_coef: np.ndarray | None = None     # (W, A, ldc) float64, window i uses [:, :width_i]
@@ -47,6 +47,11 @@ class GnxModelData:
     knn_X: np.ndarray | None = None       # (n_fit, C) int8, codes 0..2
     knn_y: np.ndarray | None = None       # (n_fit, W) int32 labels in [0, A)
     knn: list | None = None               # list of dicts: xfit (n_fit_w, width_w) int8, y (n_fit_w,) int32
+    # nb base: per-window BernoulliNB / MultinomialNB / GaussianNB (src/Base/models.py:96-132) as likelihood tables: for codes
+    # x in {0, 1, 2, 3}  jll[c] = nb_bias[w, c] + sum_p nb_table[w, p, x[p], c]  (include/gnomix_hip.h, gnx_nb_window)
+    nb_kind: str | None = None            # "bernoulli" | "multinomial" | "gaussian" (what the tables were built from)
+    nb_table: np.ndarray | None = None    # (W, ldw, 4, A) float64, ldw = M + 2 ctx + rem; window i uses [:width_i]; finite
+    nb_bias: np.ndarray | None = None     # (W, A) float64; -inf = the class is absent from the window
     # forest base: per-window XGBClassifier (src/Base/models.py:24-35), xgboost model schema, all windows concatenated
     fb_win_tree0: np.ndarray | None = None   # (W+1,) first tree of each window
     fb_tree_off: np.ndarray | None = None
@@ -153,7 +158,7 @@ class GnxModelData:
                     v = float(v)
                 elif k == "calib_is_f32":
                     v = bool(v)
-                elif k in ("base_kind", "smooth_kind"):
+                elif k in ("base_kind", "smooth_kind", "nb_kind"):
                     v = str(v)
                 elif k == "population_order":
                     v = [str(p) for p in v]
@@ -184,6 +189,19 @@ class GnxModelData:
         return [(np.ascontiguousarray(X[:, window_columns(self.C, self.M, self.context, w)]), np.ascontiguousarray(y[:, w]))
                 for w in range(self.W)]
 
+    def nb_windows(self):
+        """-> (gnx_nb_window array, keepalive list) for gnx_model_load_nb: window i's (width_i, 4, A) table and (A,) bias"""
+        W, A, ldw = self.W, self.A, self.M_ + self.rem
+        if self.nb_table is None or self.nb_bias is None:
+            raise ValueError("nb base: nb_table / nb_bias is not set")
+        tab, bias = _c(self.nb_table, np.float64), _c(self.nb_bias, np.float64)
+        if tab.shape != (W, ldw, 4, A) or bias.shape != (W, A):
+            raise ValueError(f"nb_table must be (W, ldw, 4, A) = ({W}, {ldw}, 4, {A}) and nb_bias (W, A), got {tab.shape} and {bias.shape}")
+        arr = (_lib.NbWindow * W)()
+        for i in range(W):
+            arr[i].table, arr[i].bias, arr[i].width = tab[i].ctypes.data, bias[i].ctypes.data, self.window_width(i)
+        return arr, [tab, bias]
+
     # ---- C ABI description ---------------------------------------------------------------------------
     def to_desc(self):
         """-> (gnx_model_desc, keepalive list of the arrays the pointers refer to)"""
@@ -198,7 +216,7 @@ class GnxModelData:
         d.abi_version = _lib.GNX_ABI_VERSION
         d.A, d.C, d.M, d.ctx, d.S = int(self.A), int(self.C), int(self.M), int(self.context), int(self.S)
         d.base_kind = {None: _lib.BASE_NONE, "logistic": _lib.BASE_LOGISTIC, "covrsk": _lib.BASE_COVRSK_SVC,
-                       "forest": _lib.BASE_FOREST, "rforest": _lib.BASE_RFOREST, "knn": _lib.BASE_KNN}[self.base_kind]
+                       "forest": _lib.BASE_FOREST, "rforest": _lib.BASE_RFOREST, "knn": _lib.BASE_KNN, "nb": _lib.BASE_NB}[self.base_kind]
         d.smooth_kind = {None: _lib.SMOOTH_NONE, "xgb": _lib.SMOOTH_XGB, "crf": _lib.SMOOTH_CRF, "cnn": _lib.SMOOTH_CNN}[self.smooth_kind]
         W, A = self.W, self.A
         if self.base_kind == "logistic":
@@ -247,6 +265,9 @@ class GnxModelData:
                 k.xfit, k.y, k.n_fit, k.width = ptr(xf, np.int8), ptr(yw, np.int32), xf.shape[0], xf.shape[1]
             keep.append(arr)
             d.knn = C.addressof(arr)
+        elif self.base_kind == "nb":   # the tables travel beside the description (gnx_model_load_nb): checked here, built by nb_windows
+            if self.nb_table is None or self.nb_bias is None:
+                raise ValueError("nb base: nb_table / nb_bias is not set")
         elif self.base_kind == "forest":
             wt0 = _c(self.fb_win_tree0, np.int32)
             if wt0.shape != (W + 1,):
@@ -323,7 +344,12 @@ class DeviceModel:
             keep.append(pb)
             desc.prepared, desc.prepared_bytes = pb.ctypes.data, pb.size
         h = C.c_void_p()
-        self.ctx.check(self.lib.gnx_model_load(self.ctx.h, C.byref(desc), C.byref(h)))
+        if data.base_kind == "nb":
+            nb, nb_keep = data.nb_windows()
+            keep.append(nb_keep)
+            self.ctx.check(self.lib.gnx_model_load_nb(self.ctx.h, C.byref(desc), nb, C.byref(h)))
+        else:
+            self.ctx.check(self.lib.gnx_model_load(self.ctx.h, C.byref(desc), C.byref(h)))
         del keep
         self.h = h
         self.ctx._models.add(self)

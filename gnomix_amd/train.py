@@ -402,11 +402,109 @@ def train_knn_base(data: GnxModelData, X, y, ctx=None) -> dict:
     return {"n_fit": int(X.shape[0])}
 
 
+# ---- the three Naive-Bayes bases (NBBernoulliBase, NBMultinomialBase, NBGaussianBase) -------------------------------------------
+NB_TRAIN_KINDS = ("bernoulli", "multinomial", "gaussian")
+
+
+def nb_counts(X, y, M, context, A, ctx=None, device=0):
+    """the integer counts every Naive-Bayes closed form needs, on the device (gnx_train_nb_counts): X (N, C) int8 codes 0..2, y (N, W)
+    labels in [0, A) -> n1, n2 (W, A, ldw) int32 (rows of class c whose SNP at window position p is 1 / 2; positions past a window's
+    width hold 0) and class_count (W, A) int32"""
+    ctx = ctx or _lib.default_context(device)
+    X = np.ascontiguousarray(X, dtype=np.int8)
+    N, Cn = X.shape
+    W = Cn // int(M)
+    y = np.ascontiguousarray(y, dtype=np.int32)
+    if y.shape != (N, W):
+        raise ValueError(f"y must be (N, W) = ({N}, {W}), got {y.shape}")
+    ldw = int(M) + 2 * int(context) + Cn - int(M) * W
+    n1, n2, cc = np.zeros((W, int(A), ldw), np.int32), np.zeros((W, int(A), ldw), np.int32), np.zeros((W, int(A)), np.int32)
+    ctx.check(ctx.lib.gnx_train_nb_counts(ctx.h, X.ctypes.data, N, Cn, y.ctypes.data, Cn, int(M), int(context), int(A), n1.ctypes.data,
+                                          n2.ctypes.data, cc.ctypes.data))
+    return n1, n2, cc
+
+
+def nb_fit_from_counts(kind, n1, n2, cc, alpha=1e-10, var_smoothing=1e-9):
+    """ONE window's fitted attributes from its counts, by scikit-learn's own expressions (so they come out equal to scikit-learn's):
+    n1, n2 (A, width) and cc (A,) integers -> dict with classes_ (the classes that have rows) and, per kind,
+      bernoulli:    fc = n1 + n2;    feature_log_prob_ = log(fc + alpha) - log((cc + 2 alpha)[:, None])
+      multinomial:  fc = n1 + 2 n2;  sf = fc + alpha;  feature_log_prob_ = log(sf) - log(sf.sum(axis=1)[:, None])
+      both:         class_log_prior_ = log(cc) - log(cc.sum())
+      gaussian:     theta_ = (n1 + 2 n2) / cc;  var_ = (n0 theta^2 + n1 (1 - theta)^2 + n2 (2 - theta)^2) / cc + eps,
+                    eps = var_smoothing * (largest whole-window variance over positions, from the pooled counts);
+                    class_prior_ = cc / cc.sum()"""
+    n1, n2, cc = np.asarray(n1, dtype=np.int64), np.asarray(n2, dtype=np.int64), np.asarray(cc, dtype=np.int64)
+    present = np.flatnonzero(cc > 0)
+    n1, n2, cc = n1[present], n2[present], cc[present].astype(np.float64)
+    out = {"classes_": present.astype(np.int64)}
+    if kind == "bernoulli":
+        fc = (n1 + n2).astype(np.float64)
+        out["feature_log_prob_"] = np.log(fc + alpha) - np.log((cc + alpha * 2).reshape(-1, 1))
+        out["class_log_prior_"] = np.log(cc) - np.log(cc.sum())
+    elif kind == "multinomial":
+        sf = (n1 + 2 * n2).astype(np.float64) + alpha
+        out["feature_log_prob_"] = np.log(sf) - np.log(sf.sum(axis=1).reshape(-1, 1))
+        out["class_log_prior_"] = np.log(cc) - np.log(cc.sum())
+    elif kind == "gaussian":
+        n = cc.sum()
+        s1, s2 = (n1 + 2 * n2).sum(axis=0).astype(np.float64), (n1 + 4 * n2).sum(axis=0).astype(np.float64)
+        mu = s1 / n
+        n0a, n1a, n2a = n - (n1 + n2).sum(axis=0), n1.sum(axis=0).astype(np.float64), n2.sum(axis=0).astype(np.float64)
+        pooled = (n0a * mu ** 2 + n1a * (1.0 - mu) ** 2 + n2a * (2.0 - mu) ** 2) / n
+        eps = var_smoothing * pooled.max()
+        theta = (n1 + 2 * n2).astype(np.float64) / cc[:, None]
+        n0 = cc[:, None] - (n1 + n2)
+        var = (n0 * theta ** 2 + n1 * (1.0 - theta) ** 2 + n2 * (2.0 - theta) ** 2) / cc[:, None]
+        out["theta_"], out["var_"], out["class_prior_"] = theta, var + eps, cc / n
+    else:
+        raise ValueError(f"kind must be one of {NB_TRAIN_KINDS}, got {kind!r}")
+    return out
+
+
+def train_nb_base(data: GnxModelData, X, y, kind, alpha=1e-10, var_smoothing=1e-9, ctx=None) -> dict:
+    """fit a Naive-Bayes base of `data` in place (base_kind "nb", nb_kind, nb_table, nb_bias) -> info.  The device counts
+    (gnx_train_nb_counts: exact integers), the closed forms finish in numpy (nb_fit_from_counts), the converter's nb_tables builds the
+    tables.  alpha = 1e-10 is a decision: the reference asks for alpha=0, which the scikit-learn it pins (1.0.1) raises to 1e-10;
+    newer scikit-learn keeps a true 0 and returns NaN on real genotype data.  A class with no rows in a window becomes an absent
+    class of that window.  X must hold the codes 0..2, y labels in [0, A)."""
+    from .convert import nb_tables
+    if kind not in NB_TRAIN_KINDS:
+        raise ValueError(f"kind must be one of {NB_TRAIN_KINDS}, got {kind!r}")
+    X = np.asarray(X)
+    if X.ndim != 2 or X.shape[1] != data.C or X.shape[0] < 1:
+        raise ValueError(f"X must be (N >= 1, C={data.C}), got {X.shape}")
+    if X.dtype.kind == "f" and np.any(X != np.rint(X)):
+        raise ValueError("X must hold whole numbers (the SNP codes 0, 1, 2)")
+    if X.min() < 0 or X.max() > 2:
+        raise ValueError("X must hold the SNP codes 0, 1, 2 (2 = missing)")
+    y = np.asarray(y)
+    if y.shape != (X.shape[0], data.W):
+        raise ValueError(f"y must be (N, W) = ({X.shape[0]}, {data.W}), got {y.shape}")
+    if y.min() < 0 or y.max() >= data.A:
+        raise ValueError(f"y must hold labels in 0..{data.A - 1}")
+    n1, n2, cc = nb_counts(X, y, data.M, data.context, data.A, ctx=ctx)
+    W, A = data.W, data.A
+    table, bias = np.zeros((W, data.M_ + data.rem, 4, A)), np.zeros((W, A))
+    fits = []
+    for w in range(W):
+        width = data.window_width(w)
+        fit = nb_fit_from_counts(kind, n1[w, :, :width], n2[w, :, :width], cc[w], alpha=alpha, var_smoothing=var_smoothing)
+        try:
+            t, b = nb_tables(kind, fit, A)
+        except ValueError as e:
+            raise ValueError(f"window {w}: {e}") from e
+        table[w, :width], bias[w] = t, b
+        fits.append(fit)
+    data.base_kind, data.nb_kind, data.nb_table, data.nb_bias = "nb", kind, table, bias
+    return {"n_fit": int(X.shape[0]), "fits": fits, "n1": n1, "n2": n2, "class_count": cc}
+
+
 def untrained_model(C, M, A, S, context, mode, seed=None, meta=None, base=None):
     """an untrained model of a mode's kinds (the reference's config model.inference: "default", "fast", "large", "best"), ready to
     be loaded and then trained in place: zero logistic weights or, for "best", one placeholder SVC per window (A zero rows, zero
     coefficients), or with base="xgb" one zero-valued stump per window and class, or with base="knn" one fit row of zeros with label 0
-    per window; the smoother's starting point: one placeholder tree, zero CRF weights, Conv1d's default initialisation.
+    per window, or with base="nb_bernoulli" / "nb_multinomial" / "nb_gaussian" zero Naive-Bayes tables and zero bias (every class
+    gets 1 / A); the smoother's starting point: one placeholder tree, zero CRF weights, Conv1d's default initialisation.
     meta: optional dict with snp_pos, snp_ref, snp_alt, pop_order (the simulation's metadata)"""
     from . import synth
     from .convert import cov_sample
@@ -418,10 +516,15 @@ def untrained_model(C, M, A, S, context, mode, seed=None, meta=None, base=None):
         kw = dict(snp_pos=np.asarray(meta["snp_pos"]), snp_ref=np.asarray(meta["snp_ref"]), snp_alt=np.asarray(meta["snp_alt"]),
                   population_order=list(meta["pop_order"]))
     d = GnxModelData(C=C, M=M, A=A, S=S, context=context, **kw)
-    if base not in (None, "svm", "xgb", "knn"):
-        raise ValueError("base must be None (the mode's own base), \"svm\" (SVMBase: the RBF SVC), \"xgb\" (XGBBase: boosted trees) "
-                         "or \"knn\" (KNNBase: 1-nearest neighbour), got %r" % (base,))
-    if base == "knn":   # KNNBase (src/Base/models.py:135-146) in place of the mode's base; the smoother stays the mode's
+    nb_names = {"nb_" + k: k for k in NB_TRAIN_KINDS}
+    if base not in (None, "svm", "xgb", "knn") and base not in nb_names:
+        raise ValueError("base must be None (the mode's own base), \"svm\" (SVMBase: the RBF SVC), \"xgb\" (XGBBase: boosted trees), "
+                         "\"knn\" (KNNBase: 1-nearest neighbour) or \"nb_bernoulli\" / \"nb_multinomial\" / \"nb_gaussian\" (the "
+                         "Naive-Bayes bases), got %r" % (base,))
+    if base in nb_names:   # NB*Base (src/Base/models.py:96-132) in place of the mode's base; the smoother stays the mode's
+        d.base_kind, d.nb_kind = "nb", nb_names[base]
+        d.nb_table, d.nb_bias = np.zeros((W, M + 2 * context + C - M * W, 4, A)), np.zeros((W, A))
+    elif base == "knn":   # KNNBase (src/Base/models.py:135-146) in place of the mode's base; the smoother stays the mode's
         d.base_kind, d.knn_X, d.knn_y = "knn", np.zeros((1, C), np.int8), np.zeros((1, W), np.int32)
     elif base == "xgb":   # XGBBase (src/Base/models.py:24-35) in place of the mode's base; the smoother stays the mode's
         d.base_kind, d.fb_missing, d.fb_base_score = "forest", 2, 0.5

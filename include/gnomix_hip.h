@@ -18,6 +18,9 @@
  *   gnx_train_gbt_base    <- Base.train(X, y) of XGBBase (boosted trees)  src/Base/base.py:104-127, src/Base/models.py:24-35
  *   (no entry point)      <- Base.train(X, y) of KNNBase: a 1-NN fit stores its rows; the caller puts them into
  *                            gnx_model_desc.knn and loads the model                src/Base/models.py:135-146
+ *   gnx_train_nb_counts   <- Base.train(X, y) of NBBernoulliBase / NBMultinomialBase / NBGaussianBase: the integer counts
+ *                            every closed form needs; the caller finishes in float64 and loads the tables through
+ *                            gnx_model_load_nb                                     src/Base/models.py:96-132
  *   gnx_train_gbt         <- Smoother.train(B, y) of XGB_Smoother         src/Smooth/smooth.py:28-38, src/model.py:137
  *   gnx_train_crf         <- Smoother.train(B, y) of CRF_Smoother         src/Smooth/crf.py:51-58, src/Smooth/models.py:27-32
  *   gnx_train_cnn         <- Smoother.train(B, y) of CNN_Smoother         src/Smooth/cnn.py:104-118, src/Smooth/models.py:35-42
@@ -76,7 +79,8 @@ enum {
 enum { GNX_SVC_KERNEL_SUBSTRINGS = 0, GNX_SVC_KERNEL_POLY = 1, GNX_SVC_KERNEL_ALL_LENGTHS = 2 /* gnx_train_svc only */,
        GNX_SVC_KERNEL_RBF = 3 /* SVMBase: exp(-gamma |x - y|^2) on the SNP codes as numbers */ };
 enum { GNX_BASE_NONE = 0, GNX_BASE_LOGISTIC = 1, GNX_BASE_COVRSK_SVC = 2, GNX_BASE_FOREST = 3, GNX_BASE_RFOREST = 4,
-       GNX_BASE_KNN = 5 /* KNNBase: 1-nearest neighbour per window */ };
+       GNX_BASE_KNN = 5 /* KNNBase: 1-nearest neighbour per window */,
+       GNX_BASE_NB = 6 /* the three Naive-Bayes bases: per-window likelihood tables, loaded through gnx_model_load_nb */ };
 enum { GNX_SMOOTH_NONE = 0, GNX_SMOOTH_XGB = 1, GNX_SMOOTH_CRF = 2, GNX_SMOOTH_CNN = 3 };
 
 /* kernel ids for gnx_profile_get */
@@ -144,6 +148,34 @@ typedef struct gnx_knn_window {
   int32_t n_fit;       /* >= 1 */
   int32_t width;       /* M_ (or M_+rem for the last window), <= GNX_RBF_MAX_WIDTH */
 } gnx_knn_window;
+
+/* Per-window Naive-Bayes classifier of NBBernoulliBase / NBMultinomialBase / NBGaussianBase (src/Base/models.py:96-132 -> sklearn
+ * BernoulliNB(alpha=0) / MultinomialNB(alpha=0) / GaussianNB()).  On SNP codes x in {0, 1, 2, 3} all three have one form:
+ *   jll[n, c] = bias[c] + sum_p table[p, x[n, col(p)], c]     p = 0 .. width-1 in this order, col = the window's slice of the
+ *   B[n, w, :] = softmax_c(jll)                                reflect-padded query (base.py:41-44, 146-164)
+ * The sum is a plain sequential float64 sum that starts at bias[c]: one rounding per position, in position order (the kernel adds
+ * each table row with one v_mfma_f64_16x16x4_f64 whose other three products are exact zeros).
+ * Normalisation: m = max_c jll over the present classes; e_c = exp(jll_c - m); B_c = e_c / sum(e) (one reciprocal per row).
+ * The float32 output is the float32 rounding of the float64 output.
+ * Table construction is the caller's (gnomix_amd.convert.nb_window_from_sklearn), class column c = classes_[k]:
+ *   Bernoulli   (binarize = 0):  table[p,0,c] = log(1 - exp(flp[c,p])), table[p,v>=1,c] = flp[c,p];  bias = class_log_prior_
+ *   Multinomial:                 table[p,v,c] = v * flp[c,p];                                        bias = class_log_prior_
+ *   Gaussian:                    table[p,v,c] = -0.5 (v - theta_[c,p])^2 / var_[c,p];
+ *                                bias[c] = log(class_prior_[c]) - 0.5 sum_p log(2 pi var_[c,p])
+ *   (flp = feature_log_prob_.)
+ * Codes are numbers: 2 = missing is the number 2; a query code 3 (the largest a 2-bit packed row can hold) reads table row 3, which
+ * is the number 3 for Multinomial and Gaussian and "non-zero" for Bernoulli.  Other int8 values are outside the contract: the kernel
+ * uses their two low bits, so nothing is read out of bounds.
+ * A class absent from a window has bias = -inf: its table rows are ignored (taken as zero) and its output column is exactly 0.
+ * -inf is allowed only in bias; at least one class per window must be present.
+ * GNX_EINVAL: a non-finite table entry (the message names the window), NaN or +inf in bias, a window with no class present,
+ *   width != the window's width, a NULL pointer.  GNX_EUNSUPPORTED: A > 16 (the class columns are one 16-wide MFMA tile). */
+typedef struct gnx_nb_window {
+  const double* table;  /* (width, 4, A) row-major: [position][code][class], finite */
+  const double* bias;   /* (A,) finite, or -inf for a class absent from the window */
+  int32_t width;        /* M_ (or M_+rem for the last window) */
+  int32_t reserved;
+} gnx_nb_window;
 
 /* Everything a pickled src.model.Gnomix carries for inference (src/model.py:28-88), as flat host
  * arrays.  W = C / M (src/model.py:32); the reference requires C % M != 0 (gnomix.py:124-125). */
@@ -282,6 +314,10 @@ int gnx_debug_ws_devices(gnx_ctx* ctx, int32_t* out, int32_t n);
 
 /* model */
 int gnx_model_load(gnx_ctx* ctx, const gnx_model_desc* desc, gnx_model** out);
+/* A model whose base is GNX_BASE_NB: desc->base_kind must be GNX_BASE_NB, nb lists the W windows' tables (gnx_nb_window above);
+ * everything else in desc (geometry, smoother, calibrator) means what it means to gnx_model_load.  gnx_model_load itself answers
+ * GNX_EINVAL to GNX_BASE_NB and names this entry: gnx_model_desc has no field for the tables. */
+int gnx_model_load_nb(gnx_ctx* ctx, const gnx_model_desc* desc, const gnx_nb_window* nb /* (W,) */, gnx_model** out);
 void gnx_model_free(gnx_model* model);
 int gnx_model_get_info(const gnx_model* model, gnx_model_info* out);
 /* smooth.calibrate (gnomix.py:367): when on AND the model carries a calibrator, smoother outputs (probabilities and the
@@ -493,6 +529,22 @@ int gnx_train_gbt_base_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ld
                            int32_t* right, int32_t* feat, float* cond, uint8_t* default_left, int32_t* tree_class, int64_t* n_nodes,
                            double* loss);
 int gnx_train_gbt_base_phases(int32_t enable, double* ms);
+
+/* ---- fitting the Naive-Bayes bases: the counting half of Base.train(X, y) for NBBernoulliBase / NBMultinomialBase /
+ *      NBGaussianBase (src/Base/base.py:104-127, src/Base/models.py:96-132).  Every fitted attribute of the three estimators is a
+ *      closed form of three integer tables, and the integers are exact:
+ *        n1[w, c, p] = rows n with y[n, w] == c and X[n, col(w, p)] == 1        (W, A, ldw) int32, ldw = M + 2 ctx + (C - M W)
+ *        n2[w, c, p] = the same for code 2                                       (W, A, ldw) int32; positions >= width_w hold 0
+ *        class_count[w, c] = rows n with y[n, w] == c                            (W, A) int32
+ *      (n0 = class_count - n1 - n2.)  col(w, p) is the window's slice of the reflect-padded row.  The float64 closed forms are the
+ *      caller's (gnomix_amd.train.train_nb_base: scikit-learn's own expressions).
+ *      X (N, ldx) int8 codes 0..2, y (N, W) labels in [0, A), 2 <= A <= 32, N < 2^31.  The host form checks X and y (GNX_EINVAL); the
+ *      _dev form takes device pointers for inputs AND outputs, runs asynchronously on the context's stream, counts only codes 1 and
+ *      2 and ignores rows whose label is outside [0, A). */
+int gnx_train_nb_counts(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t ldx, const int32_t* y, int64_t C, int64_t M, int64_t ctx_snps,
+                        int32_t A, int32_t* n1, int32_t* n2, int32_t* class_count);
+int gnx_train_nb_counts_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const int32_t* dy, int64_t C, int64_t M,
+                            int64_t ctx_snps, int32_t A, int32_t* d_n1, int32_t* d_n2, int32_t* d_class_count);
 
 /* ---- training the convolutional smoother: CNN.fit (src/Smooth/cnn.py:104-118) as Smoother.train calls it for CNN_Smoother
  *      (src/Smooth/smooth.py:28-38, src/Smooth/models.py:35-42).  nn.Conv1d(A, A, S, padding = (S-1)/2) with zero padding,

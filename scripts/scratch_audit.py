@@ -33,6 +33,7 @@ MUST_BE_CLEAN = [
     r"k_svc_pack", r"k_svc_gram", r"k_svc_smo", r"k_svc_heldout", r"k_svc_sigmoid",
     r"k_rbf_dec<", r"k_rbf_stage", r"k_rbf_norm", r"k_rbf_gram",
     r"k_knn_",
+    r"k_nb_",
 ]
 
 
