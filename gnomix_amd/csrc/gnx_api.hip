@@ -619,8 +619,20 @@ static int smooth_raw_dev(gnx_model* m, const void* dB, int b_is_f64, int64_t N,
     if (h64) HIPCHK(ctx, gnx_launch_smooth_xgb_h64(L, (uint16_t*)ctx->ws_rank.p, ctx->tune, ctx->stream));
     else
 #endif
-    if (m->xgb.rk_packed) HIPCHK(ctx, gnx_launch_smooth_xgb_rk(L, ctx->tune, ctx->stream));
-    else HIPCHK(ctx, gnx_launch_smooth_xgb(L, ctx->tune, ctx->stream));
+    if (m->xgb.rk_packed) {
+      // lane = haplotype, 32 per half-wave (k_smooth_xgb_h32) where the model has its tables and two blocks fit a CU's LDS; every
+      // other shape silently takes the rank kernel with pointer nodes.  GNX_SMOOTH_IMPL=h32 forces it for any batch.
+      // By default only for batches of at least one 32-haplotype block per CU: below that the rank kernel's 8-haplotype blocks
+      // spread over more CUs.
+      const bool h32 = (m->xgb.impl == 5 || (m->xgb.impl == 6 && (N + 31) / 32 * ((L.W + GNX_H32_WPB - 1) / GNX_H32_WPB) >= ctx->n_cu)) &&
+                       gnx_smooth_h32_fits(m->xgb, L.A, L.S);
+      if (h32) {
+        HIPCHK(ctx, gnx_launch_smooth_xgb_h32(L, ctx->stream));
+        return GNX_OK;
+      }
+      if (L.d.impl == 5 || L.d.impl == 6) L.d.impl = 3;
+      HIPCHK(ctx, gnx_launch_smooth_xgb_rk(L, ctx->tune, ctx->stream));
+    } else HIPCHK(ctx, gnx_launch_smooth_xgb(L, ctx->tune, ctx->stream));
     return GNX_OK;
   }
   if (m->info.smooth_kind == GNX_SMOOTH_CRF) {

@@ -193,7 +193,17 @@ struct SmoothXGBDev {
   const int32_t* rp_group_tree0 = nullptr;
   const int32_t* rp_group_class = nullptr;
   int32_t rp_tree_bytes = 0, rp_n_groups = 0, rp_max_group = 0;
-  int32_t impl = 0;                      // 1 rk, 2 h64, 3 rk with pointer nodes (GNX_SMOOTH_IMPL at model load)
+  int32_t impl = 0;                      // 1 rk, 2 h64, 3 rk with pointer nodes, 5 h32, 6 unset: h32 for batches that fill the chip, else 3 (GNX_SMOOTH_IMPL at model load)
+  // pointer-node copy for k_smooth_xgb_h32 (depth 4 only; lane = haplotype, 32 per half-wave; same ranks, rk_thr / rk_lut).  The
+  // strip is [slot pair][class][32 haplotypes] dwords, slot 2q in the low half and 2q + 1 in the high half.  Per tree 320 bytes:
+  // 16 node slots of 8 bytes for windows at an EVEN strip position (w0 = rank field << 16 | byte offset of slot s of class a,
+  // ((s >> 1) * A + a) * 128 + (s & 1) * 2; w1 and the 16-byte tree top as in rp_packed), 16 float leaves, and the 16 node slots
+  // again for windows at an ODD position (offsets of slot s + 1, counted from the even position before the window; the children
+  // of its last level are the same leaves)
+  const uint8_t* h3_packed = nullptr;
+  const int32_t* h3_group_tree0 = nullptr;
+  const int32_t* h3_group_class = nullptr;
+  int32_t h3_n_groups = 0, h3_max_group = 0;
   // rank copy for k_gnofix: per tree 2^D node words (heap order; rank field << 16 | byte offset (a * gf_pitch + s) * 2 of feature
   // s * A + a in the [class][gf_pitch] u16 tile) followed by 2^D float leaves; class-major tree order (class_tree0)
   const uint32_t* gf_packed = nullptr;
@@ -229,6 +239,13 @@ GnxBsLayout gnx_bs_layout(int A, int S, int wc, int nbins);  // k_smooth_xgb_bs.
 __host__ __device__ inline int gnx_gf_tree_words(int D) { return 2 << D; }
 constexpr int GNX_GF_PAD_TREES = 24;
 
+constexpr int GNX_H32_WPB = 96;          // windows per block of k_smooth_xgb_h32: 16 waves x 2 half-waves x 3 windows per lane
+constexpr int GNX_H32_TREE_BYTES = 320;  // SmoothXGBDev::h3_packed
+constexpr int GNX_H32_MAX_GROUP = 16;    // trees per staging group at most (5 KB: one 16-byte piece per thread)
+// LDS bytes of a k_smooth_xgb_h32 block: two staging buffers of G trees and the strip of WPB + S - 1 slots
+inline size_t gnx_h32_lds_bytes(int A, int S, int G) {
+  return (size_t)2 * G * GNX_H32_TREE_BYTES + (size_t)((GNX_H32_WPB + S) / 2) * A * 128;
+}
 constexpr int GNX_RK_RPL_MAX = 6;  // most 64-window segments per strip the rank kernel is instantiated for
 
 static inline int gnx_tree_bytes(int D) {
@@ -549,6 +566,11 @@ hipError_t gnx_launch_fb_emit(const float* d_proba, int64_t N, int64_t W, int A,
                               const int64_t* d_line_off, char* d_body, hipStream_t s);
 hipError_t gnx_launch_smooth_xgb(const SmoothXGBLaunch& L, const gnx_tune& tune, hipStream_t s);
 hipError_t gnx_launch_smooth_xgb_rk(const SmoothXGBLaunch& L, const gnx_tune& tune, hipStream_t s);
+// lane = haplotype, 32 per half-wave (k_smooth_xgb_h32.hip, GNX_SMOOTH_IMPL=h32).  gnx_smooth_h32_fits: the model has the h3_* tables
+// and two blocks fit a CU's LDS; where it says no the caller takes k_smooth_xgb_rk (the launcher checks again and declines with
+// hipErrorInvalidValue before it launches anything)
+bool gnx_smooth_h32_fits(const SmoothXGBDev& d, int A, int S);
+hipError_t gnx_launch_smooth_xgb_h32(const SmoothXGBLaunch& L, hipStream_t s);
 #ifdef GNX_EXPERIMENTS
 // bit-sliced tree smoother (scripts/dev/rejected/k_smooth_xgb_bs.hip, GNX_SMOOTH_IMPL=bs); bins = gnx_smooth_bs_scratch_bytes() of
 // device scratch (the rank pre-pass's output)

@@ -672,6 +672,62 @@ static int build_xgb_rk(gnx_model* m, const gnx_model_desc* d, const std::vector
     if ((rc = gnx_dev_upload(m, gp_class, &m->xgb.rp_group_class)) != GNX_OK) return rc;
     m->xgb.rp_tree_bytes = tbp; m->xgb.rp_n_groups = (int32_t)gp_class.size(); m->xgb.rp_max_group = Gp;
   }
+  // ---- the same trees for k_smooth_xgb_h32 (lane = haplotype, 32 per half-wave): pointer nodes, one copy of the node slots for
+  // windows at an even strip position and one for windows at an odd position (layout in gnx_internal.h: SmoothXGBDev::h3_packed)
+  if (D == 4 && ((size_t)(S >> 1) * A + A) * 128 <= 65536) {
+    constexpr int tb3 = GNX_H32_TREE_BYTES;
+    // a staging group = as many trees as leave room for two blocks per CU beside the strip (chr22, A = 7: 8), even: pair walks
+    int G3 = 2;
+    {
+      const size_t strip = gnx_h32_lds_bytes(A, S, 0);
+      if (strip + 4 * (size_t)tb3 <= (size_t)80 * 1024) G3 = std::min(GNX_H32_MAX_GROUP, (int)((((size_t)80 * 1024 - strip) / 2) / tb3) & ~1);
+    }
+    std::vector<int32_t> g3_tree0, g3_class;
+    {
+      int in_group = 0, cur = -1;
+      for (size_t k = 0; k < order.size(); ++k) {
+        const int c = d->tree_class[order[k]];
+        if (c != cur || in_group == G3) { g3_tree0.push_back((int32_t)k); g3_class.push_back(c); in_group = 0; cur = c; }
+        ++in_group;
+      }
+      g3_tree0.push_back((int32_t)order.size());
+    }
+    std::vector<uint8_t> p3(order.size() * (size_t)tb3, 0);
+    std::vector<uint32_t> nodes(16);
+    std::vector<float> leaves(16);
+    size_t g = 0;
+    for (size_t k = 0; k < order.size(); ++k) {
+      while ((size_t)g3_tree0[g + 1] <= k) ++g;
+      const uint32_t base = (uint32_t)(k - (size_t)g3_tree0[g]) * (uint32_t)tb3;  // the tree's first byte inside its group
+      std::fill(nodes.begin(), nodes.end(), 0u);
+      tree_fill_rk(d, d->tree_off[order[k]], 0, 1, 0, 4, U, stride, nodes.data(), leaves.data());  // (field << 16) | rank-strip offset
+      for (uint32_t odd = 0; odd < 2; ++odd) {
+        const uint32_t nb = base + odd * 192u;  // this copy's node slots; the leaves sit at base + 128 for both
+        uint32_t* o = reinterpret_cast<uint32_t*>(p3.data() + k * tb3 + odd * 192u);
+        auto w0 = [&](uint32_t j) {
+          // the rank layout's byte offset (a * stride + s) * 2 back to (s, a); an early leaf's word (offset 0) reads slot 0
+          const uint32_t hw = (nodes[j] & 0xffffu) / 2, a = hw / (uint32_t)stride, s = hw - a * (uint32_t)stride + odd;
+          return (nodes[j] & 0xffff0000u) | (((s >> 1) * (uint32_t)A + a) * 128u + (s & 1u) * 2u);
+        };
+        auto kids = [&](uint32_t j) {
+          const uint32_t l = 2 * j < 16u ? nb + 8u * (2 * j) : base + 128u + 4u * (2 * j - 16u);
+          const uint32_t step = 2 * j < 16u ? 8u : 4u;
+          return l | ((l + step) << 16);
+        };
+        for (uint32_t j = 2; j < 16u; ++j) { o[2 * j] = w0(j); o[2 * j + 1] = kids(j); }
+        o[0] = w0(2); o[1] = w0(3); o[2] = w0(1); o[3] = kids(2);
+      }
+      memcpy(p3.data() + k * tb3 + 128, leaves.data(), 64);
+    }
+    if ((rc = gnx_dev_upload(m, p3, &m->xgb.h3_packed, 64)) != GNX_OK) return rc;
+    if ((rc = gnx_dev_upload(m, g3_tree0, &m->xgb.h3_group_tree0)) != GNX_OK) return rc;
+    if ((rc = gnx_dev_upload(m, g3_class, &m->xgb.h3_group_class)) != GNX_OK) return rc;
+    m->xgb.h3_n_groups = (int32_t)g3_class.size(); m->xgb.h3_max_group = G3;
+    // measured (chr22, A = 7, 10 000 haplotypes, MI355X): faster than the rank kernel -> what an unset GNX_SMOOTH_IMPL
+    // runs for batches that fill the chip (gnx_api.hip); "h32" forces it, "rp" / "rk" keep the rank kernel
+    if (!impl || !*impl) m->xgb.impl = 6;
+    else if (std::string(impl) == "h32") m->xgb.impl = 5;
+  }
 #ifdef GNX_EXPERIMENTS
   // ---- the same trees for k_smooth_xgb_h64 (lane = haplotype): pointer nodes whose w0 carries the feature's SLOT s * A + a --------
   if (D >= 2 && D <= 6 && (size_t)S * A < 65536) {

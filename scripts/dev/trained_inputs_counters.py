@@ -31,11 +31,11 @@ subprocess.run(["rocprofv3", "--pmc", "SQ_LDS_IDX_ACTIVE", "SQ_LDS_BANK_CONFLICT
 agg = {}
 for f in glob.glob(out + "/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
-        if "k_smooth_xgb_rk" in r["Kernel_Name"]:
+        if "k_smooth_xgb_rk" in r["Kernel_Name"] or "k_smooth_xgb_h32" in r["Kernel_Name"]:  # whichever the dispatch ran
             agg.setdefault(r["Counter_Name"], []).append(float(r["Counter_Value"]))
 a = {k: sum(v) / len(v) for k, v in agg.items()}
 from bench import kernel_src_sha16
-res = {"source": "scripts/dev/trained_inputs_counters.py (rocprofv3 --pmc SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT; k_smooth_xgb_rk on a gnx_train_gbt ensemble, tract inputs, 10 000 haplotypes x 370 windows)",
+res = {"source": "scripts/dev/trained_inputs_counters.py (rocprofv3 --pmc SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT; the default tree smoother (k_smooth_xgb_h32 at this shape) on a gnx_train_gbt ensemble, tract inputs, 10 000 haplotypes x 370 windows)",
        "SQ_LDS_IDX_ACTIVE": a.get("SQ_LDS_IDX_ACTIVE"), "SQ_LDS_BANK_CONFLICT": a.get("SQ_LDS_BANK_CONFLICT"),
        "lds_conflict_frac_of_active": a["SQ_LDS_BANK_CONFLICT"] / a["SQ_LDS_IDX_ACTIVE"] if a.get("SQ_LDS_IDX_ACTIVE") else None,
        "launches": len(agg.get("SQ_LDS_IDX_ACTIVE", [])), "kernel_src_sha16": kernel_src_sha16()}

@@ -32,7 +32,7 @@ def short(name):
 TRAFFIC_KEYS = {
     "k_base_logistic_i8": "k_base_logistic", "k_base_logistic_i8_dl": "k_base_logistic",   # the int8-resident base pass (one of the two runs)
     "k_base_logistic_p2": "k_base_logistic_p2",
-    "k_smooth_xgb_rk": "k_smooth_xgb",                                                       # the default tree smoother
+    "k_smooth_xgb_rk": "k_smooth_xgb", "k_smooth_xgb_h32": "k_smooth_xgb",                   # the default tree smoother (one of the two runs)
     "k_smooth_xgb": "k_smooth_xgb_f32", "k_smooth_xgb_bs": "k_smooth_xgb_bs", "k_bs_ranks": "k_bs_ranks",
 }
 
