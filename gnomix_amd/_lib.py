@@ -114,6 +114,37 @@ class VcfInfo(C.Structure):
                 ("n_threads", C.c_int32), ("compression", C.c_int32), ("region_fallback", C.c_int32), ("gt2_pinned", C.c_int32)]
 
 
+class GnofixOpts(C.Structure):
+    """gnx_gnofix_opts (include/gnomix_hip.h)"""
+    _fields_ = [("struct_bytes", C.c_int32), ("max_it", C.c_int32), ("check_criterion", C.c_int32), ("max_center_offset", C.c_int32),
+                ("non_lin_s", C.c_int32), ("prob_comp", C.c_int32), ("padding", C.c_int32), ("reserved", C.c_int32),
+                ("prior_switch_prob", C.c_double)]
+
+
+GNOFIX_CHECKS = {"disc_smooth": 0, "all": 1, "disc_base": 2, "disc_either": 3}   # GNX_GNOFIX_CHECK_*
+GNOFIX_PROB_COMPS = {"max": 0, "prod": 1}                                        # GNX_GNOFIX_PROB_*
+GNOFIX_UNBUILT = ("naive_switch", "end_naive_switch", "d")                      # gnofix() arguments that are not built
+
+
+def gnofix_opts(max_it=50, **kw):
+    """The reference's gnofix() keyword arguments -> GnofixOpts.  check_criterion / prob_comp are the reference's strings."""
+    for name in GNOFIX_UNBUILT:
+        if kw.get(name) is not None:
+            raise NotImplementedError(f"gnofix: {name} is not built (the naive switch is out of scope; d is dead code in the reference)")
+        kw.pop(name, None)
+    cc, pc = kw.pop("check_criterion", "disc_smooth"), kw.pop("prob_comp", "max")
+    if cc not in GNOFIX_CHECKS:
+        raise ValueError(f"gnofix: unknown check_criterion {cc!r} (one of {sorted(GNOFIX_CHECKS)})")
+    if pc not in GNOFIX_PROB_COMPS:
+        raise ValueError(f"gnofix: unknown prob_comp {pc!r} (one of {sorted(GNOFIX_PROB_COMPS)})")
+    off, nls = kw.pop("max_center_offset", 0), kw.pop("non_lin_s", 0)
+    prior, padding = kw.pop("prior_switch_prob", 0.5), kw.pop("padding", True)
+    if kw:
+        raise TypeError(f"gnofix: unknown option(s) {sorted(kw)}")
+    return GnofixOpts(C.sizeof(GnofixOpts), int(max_it), GNOFIX_CHECKS[cc], int(off), int(nls), GNOFIX_PROB_COMPS[pc],
+                      1 if padding else 0, 0, float(prior))
+
+
 class ModelInfo(C.Structure):
     _fields_ = [("C", C.c_int64), ("M", C.c_int64), ("ctx", C.c_int64), ("W", C.c_int64), ("A", C.c_int32),
                 ("S", C.c_int32), ("base_kind", C.c_int32), ("smooth_kind", C.c_int32), ("n_trees", C.c_int32),
@@ -159,6 +190,8 @@ SYMBOLS = {
     "gnx_gnofix": (C.c_int, [_VP, _VP, _I64, _VP, _I64, C.c_int32, _VP, _VP]),
     "gnx_gnofix_dev": (C.c_int, [_VP, _VP, _I64, _VP, _I64, C.c_int32, _VP, _VP]),
     "gnx_gnofix_packed_dev": (C.c_int, [_VP, _VP, _I64, _VP, _I64, C.c_int32, _VP, _VP]),
+    "gnx_gnofix_ex": (C.c_int, [_VP, _VP, _I64, _VP, _I64, C.POINTER(GnofixOpts), _VP, _VP]),
+    "gnx_gnofix_ex_dev": (C.c_int, [_VP, _VP, _I64, _VP, _I64, C.POINTER(GnofixOpts), _VP, _VP]),
     "gnx_train_logistic": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, C.c_double, C.c_double, C.c_int32, _VP, _I64, _VP,
                                      C.POINTER(TrainInfo)]),
     "gnx_train_logistic_dev": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, C.c_double, C.c_double, C.c_int32, _VP, _I64,

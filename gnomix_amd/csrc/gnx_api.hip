@@ -1066,8 +1066,8 @@ static int gnofix_check(gnx_model* m, int64_t ldx, int64_t n_ind, int32_t max_it
 
 // scratch of one device-resident batch of n individuals (grows only).  ws_misc: [hist | par | dif | ranks] (rank kernel) or
 // [hist | float32 strips] (fallback, strips that do not fit the LDS)
-struct GnofixWs { size_t par = 0, dif = 0, rk = 0, pm = 0, ord = 0, bp = 0; };
-static int gnofix_ws_reserve(gnx_model* m, int64_t n, int32_t max_it, bool in_lds, GnofixWs* out) {
+struct GnofixWs { size_t par = 0, dif = 0, rk = 0, pm = 0, ord = 0, bp = 0, am = 0; };
+static int gnofix_ws_reserve(gnx_model* m, int64_t n, int32_t max_it, bool in_lds, GnofixWs* out, bool with_opts = false) {
   gnx_ctx* ctx = m->ctx;
   const int W = (int)m->info.W, A = m->info.A, S = m->info.S, pad = (S + 1) / 2;
   const size_t WA = (size_t)W * A, NWD = (size_t)(W + 31) / 32;
@@ -1083,6 +1083,7 @@ static int gnofix_ws_reserve(gnx_model* m, int64_t n, int32_t max_it, bool in_ld
     o.rk = misc; misc += up((size_t)2 * n * WA * 2);
     o.pm = misc; misc += up((size_t)2 * n * W * 4);
     o.ord = misc; misc += up(((size_t)2 * n + 2 * ((size_t)W + 1)) * 4);
+    if (with_opts) { o.am = misc; misc += up((size_t)2 * n * W); }  // k_gnofix_opts: argmax of B per (haplotype, window)
   } else if (!in_lds) {
     o.bp = misc; misc += (size_t)n * 2 * (W + 2 * pad) * A * 4;
   }
@@ -1094,14 +1095,15 @@ static int gnofix_ws_reserve(gnx_model* m, int64_t n, int32_t max_it, bool in_ld
 // side_stream: run the input-only pre-passes beside the smoother.  Not from the host-pointer pipeline: a fifth stream makes two of
 // them share a hardware queue (HIP maps streams onto 4 by default), and when those two are the copy-in and copy-out streams the
 // pipeline's H2D and D2H stop overlapping (measured: 13.3 k -> 9.2 k individuals/s through host pointers).
+// opts: NULL = the default loop (k_gnofix / k_gnofix_f32); else non-default options for k_gnofix_opts (validated by gnofix_opts_check)
 static int gnofix_run_dev(gnx_model* m, int8_t* dX, int64_t ldx, const double* dB, int64_t n, int32_t max_it, int32_t* dY,
-                          int32_t* dNs, bool in_lds, bool side_stream, bool packed = false) {
+                          int32_t* dNs, bool in_lds, bool side_stream, bool packed = false, const gnx_gnofix_opts* opts = nullptr) {
   gnx_ctx* ctx = m->ctx;
   GNX_BIND_DEVICE(ctx);
   const int W = (int)m->info.W, A = m->info.A, S = m->info.S;
   int rc;
   GnofixWs ws;
-  if ((rc = gnofix_ws_reserve(m, n, max_it, in_lds, &ws)) != GNX_OK) return rc;
+  if ((rc = gnofix_ws_reserve(m, n, max_it, in_lds, &ws, opts != nullptr)) != GNX_OK) return rc;
   int32_t* dY0 = (int32_t*)ctx->ws_y0.p;
   GnofixLaunch L{};
   L.X = dX; L.ldx = ldx; L.C = m->info.C; L.B = dB; L.Y0 = dY0; L.Yout = dY; L.n_switches = dNs;
@@ -1135,6 +1137,10 @@ static int gnofix_run_dev(gnx_model* m, int8_t* dX, int64_t ldx, const double* d
   if (rk && side_stream) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_aux[1], 0));  // (also on failure: the side stream is joined)
   if (rc != GNX_OK) return rc;
   ProfScope ps(ctx, GNX_K_GNOFIX);
+  if (rk && opts) {
+    HIPCHK(ctx, gnx_launch_gnofix_opts(L, n, *opts, (uint8_t*)ctx->ws_misc.p + ws.am, ctx->stream));
+    return GNX_OK;
+  }
   if (rk) {
     HIPCHK(ctx, gnx_launch_gnofix(L, n, gnofix_threads(m), ctx->stream));
     return GNX_OK;
@@ -1167,13 +1173,11 @@ int gnx_gnofix_dev(gnx_model* m, int8_t* dX, int64_t ldx, const double* dB, int6
   return gnofix_run_dev(m, dX, ldx, dB, n_ind, max_it, dY, d_n_switches, in_lds, true);
 }
 
-int gnx_gnofix(gnx_model* m, int8_t* X, int64_t ldx, const double* B, int64_t n_ind, int32_t max_it, int32_t* Y,
-               int32_t* n_switches) {
-  if (!m) return GNX_EINVAL;
+// the host-pointer pipeline of gnx_gnofix / gnx_gnofix_ex after their checks (opts: see gnofix_run_dev)
+static int gnofix_host(gnx_model* m, int8_t* X, int64_t ldx, const double* B, int64_t n_ind, int32_t max_it, int32_t* Y,
+                       int32_t* n_switches, bool in_lds, const gnx_gnofix_opts* opts) {
   gnx_ctx* ctx = m->ctx;
-  bool in_lds = true;
-  int rc = gnofix_check(m, ldx, n_ind, max_it, X && B && Y, &in_lds);
-  if (rc != GNX_OK || n_ind == 0) return rc;
+  int rc;
   GNX_BIND_DEVICE(ctx);
   const int W = (int)m->info.W;
   const size_t WA = (size_t)W * m->info.A;
@@ -1195,7 +1199,7 @@ int gnx_gnofix(gnx_model* m, int8_t* X, int64_t ldx, const double* B, int64_t n_
   if ((rc = ws_reserve(ctx, ctx->ws_lab, y_b * nbuf)) != GNX_OK) return rc;
   // what a batch grows on the compute stream must not move while a copy stream is busy: size it now, with one individual run through
   // the smoother so that its own workspaces exist at full size too
-  if ((rc = gnofix_ws_reserve(m, nb, max_it, in_lds, nullptr)) != GNX_OK) return rc;
+  if ((rc = gnofix_ws_reserve(m, nb, max_it, in_lds, nullptr, opts != nullptr)) != GNX_OK) return rc;
   hipStream_t sc = ctx->stream, si = nbuf == 2 ? ctx->s_in : ctx->stream, so = nbuf == 2 ? ctx->s_out : ctx->stream;
   const int64_t n_batches = (n_ind + nb - 1) / nb;
   auto issue_h2d = [&](int64_t i) -> int {
@@ -1217,7 +1221,7 @@ int gnx_gnofix(gnx_model* m, int8_t* X, int64_t ldx, const double* B, int64_t n_
     int32_t* dY = (int32_t*)((char*)ctx->ws_lab.p + (size_t)b * y_b);
     int32_t* dNs = dY + (size_t)2 * nb * W;
     if (nbuf == 2) HIPCHK(ctx, hipStreamWaitEvent(sc, ctx->ev_in[b], 0));
-    if ((rc = gnofix_run_dev(m, dX, ldx, dB, n, max_it, dY, dNs, in_lds, nbuf == 1)) != GNX_OK) return rc;
+    if ((rc = gnofix_run_dev(m, dX, ldx, dB, n, max_it, dY, dNs, in_lds, nbuf == 1, false, opts)) != GNX_OK) return rc;
     if (nbuf == 2) HIPCHK(ctx, hipEventRecord(ctx->ev_done[b], sc));
     // (two halves: the next batch goes up before this one's results are awaited; one half: X is both input and output of it)
     if (nbuf == 2 && i + 1 < n_batches && (rc = issue_h2d(i + 1)) != GNX_OK) return rc;
@@ -1237,6 +1241,71 @@ int gnx_gnofix(gnx_model* m, int8_t* X, int64_t ldx, const double* B, int64_t n_
   }
   HIPCHK(ctx, hipStreamSynchronize(sc));
   return GNX_OK;
+}
+
+int gnx_gnofix(gnx_model* m, int8_t* X, int64_t ldx, const double* B, int64_t n_ind, int32_t max_it, int32_t* Y,
+               int32_t* n_switches) {
+  if (!m) return GNX_EINVAL;
+  bool in_lds = true;
+  int rc = gnofix_check(m, ldx, n_ind, max_it, X && B && Y, &in_lds);
+  if (rc != GNX_OK || n_ind == 0) return rc;
+  return gnofix_host(m, X, ldx, B, n_ind, max_it, Y, n_switches, in_lds, nullptr);
+}
+
+// ---- gnofix() with the reference's search options (gnofix.py:58-208) -----------------------------------------------
+// Validates the options; *is_default: they equal the reference's defaults (the caller runs the default kernels).  Nothing is
+// written before this returns GNX_OK.
+static int gnofix_opts_check(gnx_model* m, const gnx_gnofix_opts* o, bool* is_default) {
+  gnx_ctx* ctx = m->ctx;
+  if (!o) return fail(ctx, GNX_EINVAL, "gnofix_ex: opts is NULL");
+  if (o->struct_bytes != (int32_t)sizeof(gnx_gnofix_opts)) return fail(ctx, GNX_EINVAL, "gnofix_ex: opts->struct_bytes != sizeof(gnx_gnofix_opts)");
+  if (o->max_it < 0) return fail(ctx, GNX_EINVAL, "gnofix_ex: max_it < 0");
+  if (o->check_criterion < GNX_GNOFIX_CHECK_DISC_SMOOTH || o->check_criterion > GNX_GNOFIX_CHECK_DISC_EITHER)
+    return fail(ctx, GNX_EINVAL, "gnofix_ex: unknown check_criterion");
+  if (o->prob_comp != GNX_GNOFIX_PROB_MAX && o->prob_comp != GNX_GNOFIX_PROB_PROD) return fail(ctx, GNX_EINVAL, "gnofix_ex: unknown prob_comp");
+  if (o->padding != 0 && o->padding != 1) return fail(ctx, GNX_EINVAL, "gnofix_ex: padding is 0 or 1");
+  if (m->info.smooth_kind != GNX_SMOOTH_XGB)  // src/model.py:194
+    return fail(ctx, GNX_EUNSUPPORTED, "Type of Smoother does not currently support re-phasing");
+  const int half = (m->info.S - 1) / 2;
+  if (o->max_center_offset < 0 || o->max_center_offset > half)  // beyond: ragged permutations, the reference raises
+    return fail(ctx, GNX_EINVAL, "gnofix_ex: max_center_offset outside [0, (S-1)/2]");
+  if (o->non_lin_s < 0 || o->non_lin_s > half) return fail(ctx, GNX_EINVAL, "gnofix_ex: non_lin_s outside [0, (S-1)/2]");
+  if (!std::isfinite(o->prior_switch_prob) || !(o->prior_switch_prob > 0.0) || !(o->prior_switch_prob < 1.0))
+    return fail(ctx, GNX_EINVAL, "gnofix_ex: prior_switch_prob must be finite and strictly inside (0, 1)");
+  *is_default = o->check_criterion == GNX_GNOFIX_CHECK_DISC_SMOOTH && o->max_center_offset == 0 && o->non_lin_s == 0 &&
+                o->prob_comp == GNX_GNOFIX_PROB_MAX && o->padding == 1 && o->prior_switch_prob == 0.5;
+  if (*is_default) return GNX_OK;
+  if (!gnofix_use_rk(m))
+    return fail(ctx, GNX_EUNSUPPORTED, "gnofix_ex: non-default options need the smoother's rank-quantised copy (k_gnofix_opts); this model runs the float32 Gnofix kernel");
+  if (m->info.S < 3) return fail(ctx, GNX_EUNSUPPORTED, "gnofix_ex: non-default options need S >= 3");
+  int rows = 0;
+  if (gnx_gnofix_opts_lds_bytes((int)m->info.W, m->info.A, m->info.S, m->xgb.gf_pitch, m->xgb.n_trees, &rows) > (size_t)160 * 1024 || rows < 1)
+    return fail(ctx, GNX_EUNSUPPORTED, "gnofix_ex: W / n_trees too large for the LDS working set of k_gnofix_opts");
+  return GNX_OK;
+}
+
+int gnx_gnofix_ex_dev(gnx_model* m, int8_t* dX, int64_t ldx, const double* dB, int64_t n_ind, const gnx_gnofix_opts* opts, int32_t* dY,
+                      int32_t* d_n_switches) {
+  if (!m) return GNX_EINVAL;
+  GNX_BIND_DEVICE(m->ctx);
+  bool is_default = true, in_lds = true;
+  int rc = gnofix_opts_check(m, opts, &is_default);
+  if (rc != GNX_OK) return rc;
+  rc = gnofix_check(m, ldx, n_ind, opts->max_it, dX && dB && dY, &in_lds);
+  if (rc != GNX_OK || n_ind == 0) return rc;
+  return gnofix_run_dev(m, dX, ldx, dB, n_ind, opts->max_it, dY, d_n_switches, in_lds, true, false, is_default ? nullptr : opts);
+}
+
+int gnx_gnofix_ex(gnx_model* m, int8_t* X, int64_t ldx, const double* B, int64_t n_ind, const gnx_gnofix_opts* opts, int32_t* Y,
+                  int32_t* n_switches) {
+  if (!m) return GNX_EINVAL;
+  GNX_BIND_DEVICE(m->ctx);
+  bool is_default = true, in_lds = true;
+  int rc = gnofix_opts_check(m, opts, &is_default);
+  if (rc != GNX_OK) return rc;
+  rc = gnofix_check(m, ldx, n_ind, opts->max_it, X && B && Y, &in_lds);
+  if (rc != GNX_OK || n_ind == 0) return rc;
+  return gnofix_host(m, X, ldx, B, n_ind, opts->max_it, Y, n_switches, in_lds, is_default ? nullptr : opts);
 }
 
 // ---- training --------------------------------------------------------------------------------------------

@@ -590,6 +590,11 @@ hipError_t gnx_launch_gnofix_prep(const GnofixLaunch& L, int64_t n_ind, hipStrea
 hipError_t gnx_launch_gnofix(const GnofixLaunch& L, int64_t n_ind, int threads, hipStream_t s);
 size_t gnx_gnofix_lds_bytes(int W, int A, int S, int pitch, int cap, int D, int threads, int n_trees);
 int gnx_gnofix_cap(int max_class_trees, int D, int S, int threads);
+hipError_t gnx_launch_gnofix_pmax(const GnofixLaunch& L, int64_t n_ind, hipStream_t s);  // k_gnofix.hip: proba0 -> pmax0
+hipError_t gnx_launch_gnofix_swap(const GnofixLaunch& L, int64_t n_ind, hipStream_t s);  // k_gnofix.hip: the final parity applied to X
+// gnofix/k_gnofix_opts.hip: the loop with the reference's search options (am: [2 n_ind][W] bytes of scratch)
+hipError_t gnx_launch_gnofix_opts(const GnofixLaunch& L, int64_t n_ind, const gnx_gnofix_opts& O, uint8_t* am, hipStream_t s);
+size_t gnx_gnofix_opts_lds_bytes(int W, int A, int S, int pitch, int n_trees, int* rows_side_by_side);
 hipError_t gnx_launch_gnofix_f32(const GnofixLaunch& L, int64_t n_ind, hipStream_t s);
 size_t gnx_gnofix_f32_lds_bytes(int W, int A, int S, int n_trees, int tree_bytes, bool bp_in_lds);
 hipError_t gnx_launch_calibrate(const CalibLaunch& L, hipStream_t s);

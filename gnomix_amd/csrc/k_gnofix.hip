@@ -1079,14 +1079,27 @@ hipError_t gnx_launch_gnofix(const GnofixLaunch& L, int64_t n_ind, int threads, 
     hipLaunchKernelGGL(k_gnofix_count, dim3((unsigned)n_ind), dim3(256), 0, s, L.Y0, L.W, cnt, hist);
     hipLaunchKernelGGL(k_gnofix_scan, dim3(1), dim3(256), 0, s, hist, L.W, start);
     hipLaunchKernelGGL(k_gnofix_scatter, dim3((unsigned)((n_ind + 255) / 256)), dim3(256), 0, s, cnt, n_ind, start, const_cast<int32_t*>(L.order));
-    hipLaunchKernelGGL(k_gnofix_pmax, dim3((unsigned)((2 * n_ind * L.W + 255) / 256)), dim3(256), 0, s, L.proba0, 2 * n_ind * (int64_t)L.W, L.A,
-                       const_cast<float*>(L.pmax0));
+    if ((e0 = gnx_launch_gnofix_pmax(L, n_ind, s)) != hipSuccess) return e0;
   }
   hipError_t e;
   if (threads == 256) e = launch_t<256>(L, n_ind, s);
   else if (threads == 1024) e = launch_t<1024>(L, n_ind, s);
   else e = launch_t<512>(L, n_ind, s);
   if (e != hipSuccess) return e;
+  return gnx_launch_gnofix_swap(L, n_ind, s);
+}
+
+// the row maxima of the initial smoother pass (the cache of the candidates' original rows), for k_gnofix_opts
+hipError_t gnx_launch_gnofix_pmax(const GnofixLaunch& L, int64_t n_ind, hipStream_t s) {
+  if (n_ind <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_gnofix_pmax, dim3((unsigned)((2 * n_ind * L.W + 255) / 256)), dim3(256), 0, s, L.proba0, 2 * n_ind * (int64_t)L.W, L.A,
+                     const_cast<float*>(L.pmax0));
+  return hipGetLastError();
+}
+
+// post-pass of both per-individual kernels: the final parity (L.par) applied to the SNPs
+hipError_t gnx_launch_gnofix_swap(const GnofixLaunch& L, int64_t n_ind, hipStream_t s) {
+  if (n_ind <= 0) return hipSuccess;
   const int NWD = (L.W + 31) / 32;
   const uint32_t ws = (uint32_t)(L.C / L.W);
   for (int64_t i0 = 0; i0 < n_ind; i0 += 65535) {  // the individual is grid.y: at most 65535 per launch

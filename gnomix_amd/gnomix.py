@@ -124,12 +124,14 @@ class HipGnomix:
         p, _ = self.dev.infer(X, want_proba=True, want_labels=False)
         return p
 
-    def phase(self, X, B=None, verbose=False):
-        """Gnofix re-phasing (model.py:188-214): -> X_phased (N, C) int, Y_phased (N, W) int"""
+    def phase(self, X, B=None, verbose=False, **gnofix_kw):
+        """Gnofix re-phasing (model.py:188-214): -> X_phased (N, C) int, Y_phased (N, W) int.  `gnofix_kw`: gnofix()'s search
+        options (check_criterion, max_center_offset, non_lin_s, prob_comp, prior_switch_prob, padding, max_it); the reference's
+        Gnomix.phase passes none, which is the default here too."""
         assert self.smooth is not None, "Smoother is not trained, returning original haplotypes"
         assert self.smooth.gnofix, "Type of Smoother ({}) does not currently support re-phasing".format(self.smooth)
         X = np.asarray(X)
         if B is None:
             B = self.base.predict_proba(X)
-        Xp, Y, _ = self.dev.gnofix(X, B)
+        Xp, Y, _ = self.dev.gnofix(X, B, **gnofix_kw)
         return Xp.astype(int), Y.astype(int)

@@ -554,8 +554,11 @@ class DeviceModel:
                                                    out.ctypes.data))
         return out
 
-    def gnofix(self, X, B, max_it=50, inplace=False, out=None):
+    def gnofix(self, X, B, max_it=50, inplace=False, out=None, **opts):
         """Re-phase individuals (rows 2i, 2i+1 of X and B).  Returns (X re-phased, labels i32 (2n, W), n_switches i32 (n,)).
+        `opts`: the reference's gnofix() arguments check_criterion ("disc_smooth", "all", "disc_base", "disc_either"),
+        max_center_offset, non_lin_s, prob_comp ("max", "prod"), prior_switch_prob, padding (gnx_gnofix_ex); with none given
+        the call is gnx_gnofix as before.  naive_switch, end_naive_switch and d raise NotImplementedError.
         `inplace=True` re-phases the caller's C-contiguous int8 X itself (what the C ABI does; no host copy of X — keep X, B
         and `out=(Y, nsw)` in `ctx.pinned_empty` arrays and batches overlap on three streams); the default works on a copy."""
         if inplace:
@@ -578,6 +581,11 @@ class DeviceModel:
         else:
             Y = np.empty((2 * n_ind, self.W), np.int32)
             nsw = np.empty((n_ind,), np.int32)
+        if opts:
+            o = _lib.gnofix_opts(max_it, **opts)
+            self.ctx.check(self.lib.gnx_gnofix_ex(self.h, X.ctypes.data, X.shape[1], B.ctypes.data, n_ind, C.byref(o),
+                                                  Y.ctypes.data, nsw.ctypes.data))
+            return X, Y, nsw
         self.ctx.check(self.lib.gnx_gnofix(self.h, X.ctypes.data, X.shape[1], B.ctypes.data, n_ind, int(max_it),
                                            Y.ctypes.data, nsw.ctypes.data))
         return X, Y, nsw
@@ -650,15 +658,21 @@ class DeviceModel:
                                                      None, lab.data_ptr() if want_labels else None))
         return p, lab
 
-    def gnofix_device(self, X_t, B_t, max_it=50):
-        """X_t (2n, C) int8 CUDA tensor re-phased IN PLACE, B_t (2n, W, A) float64 -> (labels i32 (2n, W), n_switches i32 (n,))"""
+    def gnofix_device(self, X_t, B_t, max_it=50, **opts):
+        """X_t (2n, C) int8 CUDA tensor re-phased IN PLACE, B_t (2n, W, A) float64 -> (labels i32 (2n, W), n_switches i32 (n,)).
+        `opts`: the reference's gnofix() arguments as in gnofix() (gnx_gnofix_ex_dev); none given: gnx_gnofix_dev as before."""
         import torch
+        o = _lib.gnofix_opts(max_it, **opts) if opts else None
         assert X_t.is_cuda and X_t.dtype == torch.int8 and X_t.stride(1) == 1
         assert B_t.is_cuda and B_t.dtype == torch.float64 and B_t.is_contiguous()
         self._bind_torch_stream()
         n_ind = X_t.shape[0] // 2
         Y = torch.empty((2 * n_ind, self.W), dtype=torch.int32, device=X_t.device)
         ns = torch.empty((n_ind,), dtype=torch.int32, device=X_t.device)
+        if o is not None:
+            self.ctx.check(self.lib.gnx_gnofix_ex_dev(self.h, X_t.data_ptr(), X_t.stride(0), B_t.data_ptr(), n_ind, C.byref(o),
+                                                      Y.data_ptr(), ns.data_ptr()))
+            return Y, ns
         self.ctx.check(self.lib.gnx_gnofix_dev(self.h, X_t.data_ptr(), X_t.stride(0), B_t.data_ptr(), n_ind, int(max_it),
                                                Y.data_ptr(), ns.data_ptr()))
         return Y, ns

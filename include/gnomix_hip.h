@@ -12,6 +12,7 @@
  *   gnx_infer             <- Gnomix.predict_proba(X) / .predict(X)      src/model.py:169-179, gnomix.py:72
  *   gnx_smooth_rows       <- smoother.model.predict_proba(rows)         src/Gnofix/gnofix.py:157
  *   gnx_gnofix            <- Gnomix.phase(X, B) -> gnofix() per indiv.  src/model.py:188-214, src/Gnofix/gnofix.py:58-208
+ *   gnx_gnofix_ex         <- gnofix(..., check_criterion, max_center_offset, non_lin_s, prob_comp, prior_switch_prob, padding)
  *   gnx_train_logistic    <- Base.train(X, y) of LogisticRegressionBase   src/Base/base.py:104-127, src/model.py:113,155
  *   gnx_train_svc         <- Base.train(X, y) of CovRSKBase (mode "best") src/Base/base.py:104-127, src/Base/models.py:195-215
  *   gnx_train_svc2        <- the same, and Base.train(X, y) of SVMBase (RBF)  src/Base/models.py:148-159
@@ -391,6 +392,37 @@ int gnx_gnofix_dev(gnx_model* model, int8_t* dX, int64_t ldx, const double* dB, 
  * windows with odd final switch parity are exchanged in the packed rows (a quarter of the bytes of the int8 matrix) */
 int gnx_gnofix_packed_dev(gnx_model* model, uint8_t* d_packed, int64_t ldp, const double* dB, int64_t n_ind, int32_t max_it,
                           int32_t* dY, int32_t* d_n_switches);
+
+/* gnofix() with the reference's search options (src/Gnofix/gnofix.py:58-208).  Options equal to the defaults (criterion
+ * DISC_SMOOTH, max_center_offset 0, non_lin_s 0, prob_comp MAX, padding 1, prior_switch_prob exactly 0.5) run the same kernels as
+ * gnx_gnofix and give the same bits; every other setting runs k_gnofix_opts, which reproduces the reference's behaviour:
+ *   - candidates of a window w inside the centers, in np.argmax order (first maximum wins): single switches at
+ *     w-max_center_offset .. w+max_center_offset, double switches [w-j, w) for j = 1 .. non_lin_s-1, [w, w+j+1) for j = 0 .. non_lin_s-1;
+ *   - acceptance best * prior > orig * (1 - prior) with both products in float32 (numpy >= 2, NEP 50: the Python float is "weak");
+ *   - an accepted double switch exchanges B on [j1, j2) but X only from j2 on; a single switch at window 0 exchanges B alone.
+ * GNX_EINVAL (nothing written): unknown enum value, max_center_offset or non_lin_s outside [0, (S-1)/2], prior_switch_prob not
+ * finite or not strictly inside (0, 1), max_it < 0, struct_bytes != sizeof(gnx_gnofix_opts).
+ * GNX_EUNSUPPORTED: a smoother that is not the tree smoother (with any options, the defaults included: gnx_gnofix reports the
+ * same model as GNX_ESTATE, the two entries differ in this code); non-default options with a model whose smoother has no
+ * rank-quantised copy (the models the float32 Gnofix kernel serves) or whose geometry does not fit the kernel's LDS.
+ * naive_switch / end_naive_switch / d of the reference are not built. */
+enum { GNX_GNOFIX_CHECK_DISC_SMOOTH = 0, GNX_GNOFIX_CHECK_ALL = 1, GNX_GNOFIX_CHECK_DISC_BASE = 2, GNX_GNOFIX_CHECK_DISC_EITHER = 3 };
+enum { GNX_GNOFIX_PROB_MAX = 0, GNX_GNOFIX_PROB_PROD = 1 };
+typedef struct gnx_gnofix_opts {
+  int32_t struct_bytes;        /* sizeof(gnx_gnofix_opts): lets the struct grow */
+  int32_t max_it;
+  int32_t check_criterion;     /* gnofix.py:25-45 */
+  int32_t max_center_offset;   /* gnofix.py:134 */
+  int32_t non_lin_s;           /* gnofix.py:135-136 */
+  int32_t prob_comp;           /* gnofix.py:160-163 */
+  int32_t padding;             /* gnofix.py:84: 1 = windows 1..W-1, 0 = centers only */
+  int32_t reserved;
+  double  prior_switch_prob;   /* gnofix.py:171 */
+} gnx_gnofix_opts;
+int gnx_gnofix_ex(gnx_model* model, int8_t* X, int64_t ldx, const double* B, int64_t n_ind, const gnx_gnofix_opts* opts,
+                  int32_t* Y, int32_t* n_switches);
+int gnx_gnofix_ex_dev(gnx_model* model, int8_t* dX, int64_t ldx, const double* dB, int64_t n_ind, const gnx_gnofix_opts* opts,
+                      int32_t* dY, int32_t* d_n_switches);
 
 /* Base.train for the logistic base (src/Base/base.py:104-127 -> per window
  * LogisticRegression(penalty="l2", C=3., solver="liblinear", max_iter=1000).fit(X_w, y_w), src/Base/models.py:12-21; called
