@@ -16,7 +16,7 @@ SO_PATH = os.environ.get("GNX_LIBRARY") or os.path.join(_HERE, "libgnomix_hip.so
 
 GNX_ABI_VERSION = 16
 GNX_OK, GNX_EINVAL, GNX_ENOMEM, GNX_EHIP, GNX_EUNSUPPORTED, GNX_ESTATE, GNX_ESTALE = 0, -1, -2, -3, -4, -5, -6
-BASE_NONE, BASE_LOGISTIC, BASE_COVRSK_SVC, BASE_FOREST, BASE_RFOREST, BASE_KNN, BASE_NB = 0, 1, 2, 3, 4, 5, 6
+BASE_NONE, BASE_LOGISTIC, BASE_COVRSK_SVC, BASE_FOREST, BASE_RFOREST, BASE_KNN, BASE_NB, BASE_LDA = 0, 1, 2, 3, 4, 5, 6, 7
 SVC_KERNEL_SUBSTRINGS, SVC_KERNEL_POLY, SVC_KERNEL_ALL_LENGTHS, SVC_KERNEL_RBF = 0, 1, 2, 3
 SMOOTH_NONE, SMOOTH_XGB, SMOOTH_CRF, SMOOTH_CNN = 0, 1, 2, 3
 K_BASE_LOGISTIC, K_SMOOTH_XGB, K_BASE_COVRSK, K_SMOOTH_CRF, K_GNOFIX, K_SMOOTH_ROWS, K_CALIBRATE, K_BASE_FOREST, K_SMOOTH_CNN = range(9)
@@ -49,6 +49,10 @@ class KnnWindow(C.Structure):
 
 class NbWindow(C.Structure):
     _fields_ = [("table", C.c_void_p), ("bias", C.c_void_p), ("width", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LdaWindow(C.Structure):
+    _fields_ = [("coef", C.c_void_p), ("intercept", C.c_void_p), ("width", C.c_int32), ("n_rows", C.c_int32)]
 
 
 class ModelDesc(C.Structure):
@@ -169,6 +173,7 @@ SYMBOLS = {
     "gnx_synchronize": (C.c_int, [_VP]),
     "gnx_model_load": (C.c_int, [_VP, C.POINTER(ModelDesc), C.POINTER(_VP)]),
     "gnx_model_load_nb": (C.c_int, [_VP, C.POINTER(ModelDesc), C.POINTER(NbWindow), C.POINTER(_VP)]),
+    "gnx_model_load_lda": (C.c_int, [_VP, C.POINTER(ModelDesc), C.POINTER(LdaWindow), C.POINTER(_VP)]),
     "gnx_model_free": (None, [_VP]),
     "gnx_model_get_info": (C.c_int, [_VP, C.POINTER(ModelInfo)]),
     "gnx_model_set_calibrate": (C.c_int, [_VP, _I]),
@@ -208,6 +213,8 @@ SYMBOLS = {
     "gnx_train_gbt_base_phases": (C.c_int, [C.c_int32, _VP]),
     "gnx_train_nb_counts": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, _VP, _VP, _VP]),
     "gnx_train_nb_counts_dev": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, _VP, _VP, _VP]),
+    "gnx_train_lda_gram": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, _I64, _I64, _VP, _VP, _VP]),
+    "gnx_train_lda_gram_dev": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, _I64, _I64, _VP, _VP, _VP]),
     "gnx_train_crf": (C.c_int, [_VP, _VP, C.c_int32, _VP, _I64, C.c_int32, C.c_int32, C.POINTER(CrfParams), _VP, _VP, C.POINTER(CrfInfo)]),
     "gnx_train_cnn": (C.c_int, [_VP, _VP, C.c_int32, _VP, _I64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CnnParams), _VP, _VP, _VP, _VP]),
     "gnx_train_gbt_dev": (C.c_int, [_VP, _VP, C.c_int32, _VP, _I64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(GbtParams)] + [_VP] * 8),

@@ -34,18 +34,23 @@ class HipBase:
         reference leaves it.  RBF windows (SVMBase): every window's SVC(C=100, gamma, probability=True), one seed per window drawn
         from numpy's global generator in window order.  Forest base (XGBBase): every window's 20 rounds of depth-4 boosted
         trees (train.train_forest_base).  1-NN base (KNNBase): the rows are stored (train.train_knn_base; there is nothing to fit).
-        Naive-Bayes bases (NB*Base): counts on the device, closed forms on the host (train.train_nb_base; alpha = 1e-10)."""
+        Naive-Bayes bases (NB*Base): counts on the device, closed forms on the host (train.train_nb_base; alpha = 1e-10).
+        LDA base (LDABase): the exact Gram matrix, class sums and counts on the device, scikit-learn's svd solver restated on them in
+        float64 on the host (train.train_lda_base)."""
         from .train import train_logistic_base, train_svc_base, svc_seed_chain, svc_rng_after_kernel, SVC_SEED_HIGH
         from .model import DeviceModel, svc_window_is_rbf
         d = self.dev.data
         if d.base_kind == "rforest":
             raise NotImplementedError("on-device training is not built for the random-forest base (RFBase: scikit-learn's bootstrap "
-                                      "stream); the logistic, SVC (CovRSK, RBF), boosted-tree (XGBBase), 1-NN (KNNBase) and Naive-Bayes bases are")
-        if d.base_kind not in (None, "logistic", "covrsk", "forest", "knn", "nb"):
-            raise NotImplementedError("on-device training is built for the logistic, the SVC (CovRSK, RBF), the boosted-tree, the 1-NN and the "
-                                      "Naive-Bayes bases")
+                                      "stream); the logistic, SVC (CovRSK, RBF), boosted-tree (XGBBase), 1-NN (KNNBase), Naive-Bayes and LDA bases are")
+        if d.base_kind not in (None, "logistic", "covrsk", "forest", "knn", "nb", "lda"):
+            raise NotImplementedError("on-device training is built for the logistic, the SVC (CovRSK, RBF), the boosted-tree, the 1-NN, the "
+                                      "Naive-Bayes and the LDA bases")
         t = time()
-        if d.base_kind == "nb":
+        if d.base_kind == "lda":
+            from .train import train_lda_base
+            self.train_info = train_lda_base(d, X, y, ctx=self.dev.ctx)
+        elif d.base_kind == "nb":
             # NB*Base: integer counts on the device, scikit-learn's closed forms on the host (train.train_nb_base)
             from .train import train_nb_base
             self.train_info = train_nb_base(d, X, y, d.nb_kind, ctx=self.dev.ctx)

@@ -201,6 +201,32 @@ def nb_window_from_sklearn(nb, width, n_class, kind=None):
     return table, bias
 
 
+def lda_from_sklearn(m, width, n_class=None):
+    """One fitted LinearDiscriminantAnalysis (or a stubbed pickle's attribute bag with the same attributes) -> (coef (A or 1, width),
+    intercept (A or 1,)) float64 as gnx_lda_window takes them: coef_ and intercept_ as scikit-learn keeps them (for two classes the one
+    row coef_[1] - coef_[0]).  Refused (ValueError): a solver other than "svd", shrinkage, classes_ that are not 0 .. A-1 (the
+    reference's vectorized path has no remap), a width that is not the window's, non-finite values."""
+    solver = getattr(m, "solver", "svd")
+    if solver != "svd":
+        raise ValueError(f"LinearDiscriminantAnalysis with solver = {solver!r}: only the default \"svd\" (what LDABase builds) is converted")
+    if getattr(m, "shrinkage", None) is not None:
+        raise ValueError(f"LinearDiscriminantAnalysis with shrinkage = {m.shrinkage!r}: LDABase builds none")
+    classes = np.asarray(m.classes_)
+    A = int(n_class) if n_class is not None else len(classes)
+    if classes.ndim != 1 or len(classes) != A or np.any(np.asarray(classes, dtype=np.float64) != np.arange(A)):
+        raise ValueError(f"classes_ != 0..{A - 1} (the vectorized reference path has no remap, base.py:176), got {classes.tolist()}")
+    coef = np.asarray(m.coef_, dtype=np.float64)
+    icpt = np.asarray(m.intercept_, dtype=np.float64).reshape(-1)
+    R = 1 if A == 2 else A
+    if coef.ndim != 2 or coef.shape[0] != R or icpt.shape != (R,):
+        raise ValueError(f"coef_ must be ({R}, width) and intercept_ ({R},) for {A} classes, got {coef.shape} and {icpt.shape}")
+    if coef.shape[1] != int(width):
+        raise ValueError(f"the estimator was fitted on {coef.shape[1]} features, the window is {int(width)} wide")
+    if not (np.all(np.isfinite(coef)) and np.all(np.isfinite(icpt))):
+        raise ValueError("coef_ / intercept_ is not finite")
+    return np.ascontiguousarray(coef), icpt
+
+
 def poly_run_values(width, p=1.2):
     """what a run of L equal SNPs contributes to the polynomial string kernel (string_kernel.py:52: contigs ** p), computed
     by numpy exactly as the reference computes it (int64 array ** float)"""
@@ -570,6 +596,18 @@ def from_reference_model(model) -> GnxModelData:
                 raise ValueError(f"window {i}: {e}") from e
             d.nb_table[i, :t.shape[0]] = t
             d.nb_bias[i] = b
+    elif first == "LinearDiscriminantAnalysis":  # LDABase (src/Base/models.py:83-94): coef_ / intercept_ as fitted
+        R = 1 if A == 2 else A
+        d.base_kind = "lda"
+        d.lda_coef = np.zeros((W, R, d.M_ + d.rem))
+        d.lda_intercept = np.zeros((W, R))
+        for i, m in enumerate(models):
+            try:
+                coef, icpt = lda_from_sklearn(m, d.window_width(i), A)
+            except ValueError as e:
+                raise ValueError(f"window {i}: {e}") from e
+            d.lda_coef[i, :, :coef.shape[1]] = coef
+            d.lda_intercept[i] = icpt
     elif first == "XGBClassifier":  # XGBBase (src/Base/models.py:24-35)
         d.base_kind = "forest"
         parts = [xgb_trees_of(m, A) for m in models]

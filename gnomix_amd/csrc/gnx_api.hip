@@ -371,6 +371,7 @@ int gnx_model_load(gnx_ctx* ctx, const gnx_model_desc* d, gnx_model** out) {
     case GNX_BASE_RFOREST: rc = gnx_build_rforest(m, d); break;
     case GNX_BASE_KNN: rc = gnx_build_knn(m, d); break;
     case GNX_BASE_NB: rc = fail(ctx, GNX_EINVAL, "GNX_BASE_NB: the Naive-Bayes tables are loaded through gnx_model_load_nb"); break;
+    case GNX_BASE_LDA: rc = fail(ctx, GNX_EINVAL, "GNX_BASE_LDA: the LDA coefficients are loaded through gnx_model_load_lda"); break;
     default: rc = fail(ctx, GNX_EINVAL, "unknown base_kind");
   }
   if (rc == GNX_OK) switch (d->smooth_kind) {
@@ -451,6 +452,7 @@ int gnx_base_predict_dev(gnx_model* m, const int8_t* dX, int64_t N, int64_t ldx,
   GNX_BIND_DEVICE(ctx);
   if (m->info.base_kind == GNX_BASE_KNN) return gnx_base_predict_knn(m, dX, N, ldx, d_b32, d_b64);
   if (m->info.base_kind == GNX_BASE_NB) return gnx_base_predict_nb(m, dX, N, ldx, d_b32, d_b64);
+  if (m->info.base_kind == GNX_BASE_LDA) return gnx_base_predict_lda(m, dX, N, ldx, d_b32, d_b64);
   if (m->info.base_kind == GNX_BASE_COVRSK_SVC && m->rbf) {
     ProfScope ps(ctx, GNX_K_BASE_COVRSK);
     return gnx_base_predict_rbf(m, dX, N, ldx, d_b32, d_b64);

@@ -436,6 +436,7 @@ struct ForestLaunch {
 struct SvcRbfModel;  // svm/k_base_rbf.hip
 struct KnnModel;     // knn/k_base_knn.hip
 struct NbModel;      // nb/k_base_nb.hip
+struct LdaModel;     // lda/k_base_lda.hip
 
 struct gnx_model {
   gnx_ctx* ctx = nullptr;
@@ -453,6 +454,7 @@ struct gnx_model {
   std::shared_ptr<SvcRbfModel> rbf;  // set instead of `svc` when the windows are GNX_SVC_KERNEL_RBF (svm/k_base_rbf.hip)
   std::shared_ptr<KnnModel> knn;     // GNX_BASE_KNN (knn/k_base_knn.hip)
   std::shared_ptr<NbModel> nb;       // GNX_BASE_NB (nb/k_base_nb.hip; set by gnx_model_load_nb)
+  std::shared_ptr<LdaModel> lda;     // GNX_BASE_LDA (lda/k_base_lda.hip; set by gnx_model_load_lda)
   ForestDev forest;
   // class-major xgboost-schema copy for the rows kernel
   const int32_t* class_tree0 = nullptr;  // device [A+1]
@@ -516,6 +518,8 @@ int gnx_build_knn(gnx_model* m, const gnx_model_desc* d);
 int gnx_base_predict_knn(gnx_model* m, const int8_t* dX, int64_t N, int64_t ldx, float* d_b32, double* d_b64);
 // the Naive-Bayes bases (nb/k_base_nb.hip): the table pass -> b32 / b64 (model preparation is gnx_model_load_nb's, in the same file)
 int gnx_base_predict_nb(gnx_model* m, const int8_t* dX, int64_t N, int64_t ldx, float* d_b32, double* d_b64);
+// the LDA base (lda/k_base_lda.hip): the decision + softmax pass -> b32 / b64 (model preparation is gnx_model_load_lda's, in the same file)
+int gnx_base_predict_lda(gnx_model* m, const int8_t* dX, int64_t N, int64_t ldx, float* d_b32, double* d_b64);
 int gnx_build_forest(gnx_model* m, const gnx_model_desc* d);
 int gnx_build_rforest(gnx_model* m, const gnx_model_desc* d);
 int gnx_build_xgb(gnx_model* m, const gnx_model_desc* d);

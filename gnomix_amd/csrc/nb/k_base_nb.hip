@@ -51,6 +51,7 @@
 // window.
 #include "../gnx_internal.h"
 #include "../gnx_exp.h"
+#include "../gnx_window.h"
 
 #include <cmath>
 #include <cstring>
@@ -95,11 +96,7 @@ constexpr int NB_WAVES = 4;
 constexpr int NB_ROWS = NB_WAVES * NB_MT * 16;  // query rows per block
 constexpr int NB_PC = 16;                 // positions per X chunk (one 16-byte load per lane)
 
-__device__ __forceinline__ int64_t pad_src(int64_t p, int64_t C, int64_t ctx) {
-  if (p < ctx) return ctx - 1 - p;
-  if (p < ctx + C) return p - ctx;
-  return C - 1 - (p - ctx - C);
-}
+__device__ __forceinline__ int64_t pad_src(int64_t p, int64_t C, int64_t ctx) { return gnx_pad_src(p, C, ctx); }
 
 __device__ __forceinline__ xbytes16 load_x16(const int8_t* p) {  // unaligned global_load_dwordx4
   xbytes16 r;

@@ -33,7 +33,7 @@ class GnxModelData:
     A: int
     S: int = 75
     context: int = 0                      # SNPs each side = int(M*context_ratio) (src/model.py:47)
-    base_kind: str | None = None          # "logistic" | "covrsk" | "forest" | "rforest" | "knn" | "nb"
+    base_kind: str | None = None          # "logistic" | "covrsk" | "forest" | "rforest" | "knn" | "nb" | "lda"
     smooth_kind: str | None = None        # "xgb" | "crf" | "cnn"
     # logistic base: coef_ / intercept_ of LogisticRegression per window (src/Base/models.py:12-21)
     lr_coef: np.ndarray | None = None     # (W, A, ldc) float64, window i uses [:, :width_i]
@@ -52,6 +52,10 @@ class GnxModelData:
     nb_kind: str | None = None            # "bernoulli" | "multinomial" | "gaussian" (what the tables were built from)
     nb_table: np.ndarray | None = None    # (W, ldw, 4, A) float64, ldw = M + 2 ctx + rem; window i uses [:width_i]; finite
     nb_bias: np.ndarray | None = None     # (W, A) float64; -inf = the class is absent from the window
+    # lda base: per-window LinearDiscriminantAnalysis() (src/Base/models.py:83-94): decision = Xw @ lda_coef[w].T + lda_intercept[w],
+    # softmax over the A rows, or for A == 2 the one row scikit-learn keeps (coef_[1] - coef_[0]) through the sigmoid
+    lda_coef: np.ndarray | None = None       # (W, A or 1, ldw) float64, ldw = M + 2 ctx + rem; zero beyond a window's width; finite
+    lda_intercept: np.ndarray | None = None  # (W, A or 1) float64, finite
     # forest base: per-window XGBClassifier (src/Base/models.py:24-35), xgboost model schema, all windows concatenated
     fb_win_tree0: np.ndarray | None = None   # (W+1,) first tree of each window
     fb_tree_off: np.ndarray | None = None
@@ -202,6 +206,21 @@ class GnxModelData:
             arr[i].table, arr[i].bias, arr[i].width = tab[i].ctypes.data, bias[i].ctypes.data, self.window_width(i)
         return arr, [tab, bias]
 
+    def lda_windows(self):
+        """-> (gnx_lda_window array, keepalive list) for gnx_model_load_lda: window i's (n_rows, width_i) coefficients and intercepts"""
+        W, ldw, R = self.W, self.M_ + self.rem, (1 if self.A == 2 else self.A)
+        if self.lda_coef is None or self.lda_intercept is None:
+            raise ValueError("lda base: lda_coef / lda_intercept is not set")
+        coef, icpt = _c(self.lda_coef, np.float64), _c(self.lda_intercept, np.float64)
+        if coef.shape != (W, R, ldw) or icpt.shape != (W, R):
+            raise ValueError(f"lda_coef must be (W, A or 1, ldw) = ({W}, {R}, {ldw}) and lda_intercept (W, A or 1), got {coef.shape} and {icpt.shape}")
+        arr, keep = (_lib.LdaWindow * W)(), [icpt]
+        for i in range(W):
+            cw = np.ascontiguousarray(coef[i, :, :self.window_width(i)])
+            keep.append(cw)
+            arr[i].coef, arr[i].intercept, arr[i].width, arr[i].n_rows = cw.ctypes.data, icpt[i].ctypes.data, self.window_width(i), R
+        return arr, keep
+
     # ---- C ABI description ---------------------------------------------------------------------------
     def to_desc(self):
         """-> (gnx_model_desc, keepalive list of the arrays the pointers refer to)"""
@@ -216,7 +235,8 @@ class GnxModelData:
         d.abi_version = _lib.GNX_ABI_VERSION
         d.A, d.C, d.M, d.ctx, d.S = int(self.A), int(self.C), int(self.M), int(self.context), int(self.S)
         d.base_kind = {None: _lib.BASE_NONE, "logistic": _lib.BASE_LOGISTIC, "covrsk": _lib.BASE_COVRSK_SVC,
-                       "forest": _lib.BASE_FOREST, "rforest": _lib.BASE_RFOREST, "knn": _lib.BASE_KNN, "nb": _lib.BASE_NB}[self.base_kind]
+                       "forest": _lib.BASE_FOREST, "rforest": _lib.BASE_RFOREST, "knn": _lib.BASE_KNN, "nb": _lib.BASE_NB,
+                       "lda": _lib.BASE_LDA}[self.base_kind]
         d.smooth_kind = {None: _lib.SMOOTH_NONE, "xgb": _lib.SMOOTH_XGB, "crf": _lib.SMOOTH_CRF, "cnn": _lib.SMOOTH_CNN}[self.smooth_kind]
         W, A = self.W, self.A
         if self.base_kind == "logistic":
@@ -268,6 +288,9 @@ class GnxModelData:
         elif self.base_kind == "nb":   # the tables travel beside the description (gnx_model_load_nb): checked here, built by nb_windows
             if self.nb_table is None or self.nb_bias is None:
                 raise ValueError("nb base: nb_table / nb_bias is not set")
+        elif self.base_kind == "lda":   # the coefficients travel beside the description (gnx_model_load_lda), built by lda_windows
+            if self.lda_coef is None or self.lda_intercept is None:
+                raise ValueError("lda base: lda_coef / lda_intercept is not set")
         elif self.base_kind == "forest":
             wt0 = _c(self.fb_win_tree0, np.int32)
             if wt0.shape != (W + 1,):
@@ -348,6 +371,10 @@ class DeviceModel:
             nb, nb_keep = data.nb_windows()
             keep.append(nb_keep)
             self.ctx.check(self.lib.gnx_model_load_nb(self.ctx.h, C.byref(desc), nb, C.byref(h)))
+        elif data.base_kind == "lda":
+            lda, lda_keep = data.lda_windows()
+            keep.append(lda_keep)
+            self.ctx.check(self.lib.gnx_model_load_lda(self.ctx.h, C.byref(desc), lda, C.byref(h)))
         else:
             self.ctx.check(self.lib.gnx_model_load(self.ctx.h, C.byref(desc), C.byref(h)))
         del keep

@@ -499,12 +499,145 @@ def train_nb_base(data: GnxModelData, X, y, kind, alpha=1e-10, var_smoothing=1e-
     return {"n_fit": int(X.shape[0]), "fits": fits, "n1": n1, "n2": n2, "class_count": cc}
 
 
+# ---- the LDA base (LDABase) --------------------------------------------------------------------------------------------------------
+def lda_gram(X, y, M, context, A, w0, w1, ctx=None, device=0):
+    """the exact integers the LDA fit needs for the windows [w0, w1), on the device (gnx_train_lda_gram): X (N, C) int8 codes 0..2, y
+    (N, W) labels in [0, A) -> G (w1 - w0, ldw, ldw) int32 (Xw^T Xw, full symmetric), S (w1 - w0, A, ldw) int32 (class sums) and
+    n (w1 - w0, A) int32 (class counts); ldw = the widest window, positions past a window's width hold 0"""
+    ctx = ctx or _lib.default_context(device)
+    X = np.ascontiguousarray(X, dtype=np.int8)
+    N, Cn = X.shape
+    W = Cn // int(M)
+    y = np.ascontiguousarray(y, dtype=np.int32)
+    if y.shape != (N, W):
+        raise ValueError(f"y must be (N, W) = ({N}, {W}), got {y.shape}")
+    ldw, nw = int(M) + 2 * int(context) + Cn - int(M) * W, int(w1) - int(w0)
+    if not 0 <= int(w0) < int(w1) <= W:
+        raise ValueError(f"the window range [{w0}, {w1}) is not inside [0, {W})")
+    G, S, n = np.zeros((nw, ldw, ldw), np.int32), np.zeros((nw, int(A), ldw), np.int32), np.zeros((nw, int(A)), np.int32)
+    ctx.check(ctx.lib.gnx_train_lda_gram(ctx.h, X.ctypes.data, N, Cn, y.ctypes.data, Cn, int(M), int(context), int(A), int(w0), int(w1),
+                                         G.ctypes.data, S.ctypes.data, n.ctypes.data))
+    return G, S, n
+
+
+def lda_finish(G, S, n, N, tol=1e-4):
+    """ONE window's LinearDiscriminantAnalysis(solver="svd", tol) fit from its integers -> (coef (A or 1, width), intercept (A or 1,),
+    info).  G (width, width) = Xw^T Xw, S (A, width) class sums, n (A,) class counts, N rows; priors are the class frequencies.
+    scikit-learn's _solve_svd, step by step, with the one SVD of the (N, width) scaled, class-centred data replaced by the
+    eigen-decomposition of its Gram matrix, which the integers give exactly:
+      scatter = G - sum_k S_k S_k^T / n_k;  std = sqrt(diag(scatter) / N), 1 where a column is constant within every class;
+      fac / (std std^T) * scatter = V diag(s^2) V^T  (numpy.linalg.eigh), s descending;  rank = #(s > tol);
+      scalings = (V[:, :rank] / std[:, None]) / s[:rank];
+      the (A, rank) between-class matrix sqrt(N priors / (A - 1)) (means - xbar) @ scalings goes through a real SVD, rank2 =
+      #(s2 > tol s2[0]); coef_ and intercept_ follow as in scikit-learn; for A == 2 row 1 minus row 0 is kept.
+    A column is constant within every class exactly when its scatter is 0; a column that is not has scatter >= 1/2 (integer codes),
+    and the float64 evaluation of the scatter is exact for the former, so the test is scatter < 1/4.
+    info: rank, rank2, sv (all width values of s), sv2.  ValueError: a class without rows, N - A < 1."""
+    G, S, n = np.asarray(G, dtype=np.float64), np.asarray(S, dtype=np.float64), np.asarray(n, dtype=np.float64)
+    A, width = S.shape
+    if np.any(n < 1):
+        raise ValueError("class %d has no row" % int(np.flatnonzero(n < 1)[0]))
+    if N - A < 1:
+        raise ValueError(f"N - A = {N - A} < 1: the pooled covariance needs more rows than classes")
+    priors = n / float(N)
+    means = S / n[:, None]
+    xbar = priors @ means
+    scatter = G - (S / n[:, None]).T @ S
+    diag = np.diagonal(scatter).copy()
+    const = diag < 0.25
+    std = np.sqrt(np.where(const, 0.0, diag) / float(N))
+    std[const] = 1.0
+    fac = 1.0 / (N - A)
+    scaled = fac * (scatter / std[:, None] / std[None, :])
+    scaled[const, :] = 0.0
+    scaled[:, const] = 0.0
+    lam, V = np.linalg.eigh(0.5 * (scaled + scaled.T))
+    lam, V = lam[::-1], V[:, ::-1]
+    sv = np.sqrt(np.maximum(lam, 0.0))
+    rank = int(np.sum(sv > tol))
+    scalings = (V[:, :rank] / std[:, None]) / sv[:rank]
+    fac2 = 1.0 if A == 1 else 1.0 / (A - 1)
+    Xb = (np.sqrt((N * priors) * fac2) * (means - xbar).T).T @ scalings
+    _, sv2, Vt2 = np.linalg.svd(Xb, full_matrices=False)
+    rank2 = int(np.sum(sv2 > tol * sv2[0])) if len(sv2) else 0
+    scalings = scalings @ Vt2.T[:, :rank2]
+    coef = (means - xbar) @ scalings
+    intercept = -0.5 * np.sum(coef ** 2, axis=1) + np.log(priors)
+    coef = coef @ scalings.T
+    intercept -= xbar @ coef.T
+    if A == 2:
+        coef, intercept = coef[1:2] - coef[0:1], intercept[1:2] - intercept[0:1]
+    return coef, intercept, {"rank": rank, "rank2": rank2, "sv": sv, "sv2": sv2}
+
+
+def host_threads():
+    """the CPUs this process may use: OMP_NUM_THREADS when it is set (a job's allowance), else the scheduler's affinity mask"""
+    import os
+    try:
+        v = int(os.environ.get("OMP_NUM_THREADS", "0"))
+    except ValueError:
+        v = 0
+    return max(1, v if v > 0 else len(os.sched_getaffinity(0)))
+
+
+def train_lda_base(data: GnxModelData, X, y, ctx=None, tol=1e-4, windows_per_call=None) -> dict:
+    """fit the LDA base of `data` in place (base_kind "lda", lda_coef, lda_intercept) -> info.  The device computes every window's exact
+    Gram matrix, class sums and counts (lda_gram, windows_per_call windows at a time: by default as many as keep G under 1 GiB); the
+    host finishes each window in float64 (lda_finish), the windows of a call in parallel over the allowed host threads.
+    ValueError (naming the window): a class of range(A) without rows in a window (the reference's predict_proba_vectorized cannot
+    stack such a model either), N - A < 1.  X must hold the codes 0..2, y labels in [0, A)."""
+    from concurrent.futures import ThreadPoolExecutor
+    X = np.asarray(X)
+    if X.ndim != 2 or X.shape[1] != data.C or X.shape[0] < 1:
+        raise ValueError(f"X must be (N >= 1, C={data.C}), got {X.shape}")
+    if X.dtype.kind == "f" and np.any(X != np.rint(X)):
+        raise ValueError("X must hold whole numbers (the SNP codes 0, 1, 2)")
+    if X.min() < 0 or X.max() > 2:
+        raise ValueError("X must hold the SNP codes 0, 1, 2 (2 = missing)")
+    y = np.asarray(y)
+    N, W, A = X.shape[0], data.W, data.A
+    if y.shape != (N, W):
+        raise ValueError(f"y must be (N, W) = ({N}, {W}), got {y.shape}")
+    if y.min() < 0 or y.max() >= A:
+        raise ValueError(f"y must hold labels in 0..{A - 1}")
+    if N - A < 1:
+        raise ValueError(f"N - A = {N - A} < 1: the pooled covariance needs more rows than classes")
+    ldw, R = data.M_ + data.rem, (1 if A == 2 else A)
+    per_call = int(windows_per_call) if windows_per_call else max(1, min(W, (1 << 30) // (4 * ldw * ldw)))
+    if per_call < 1:
+        raise ValueError("windows_per_call must be at least 1")
+    coef, icpt = np.zeros((W, R, ldw)), np.zeros((W, R))
+    ranks = np.zeros((W, 2), np.int64)
+    X8, y32 = np.ascontiguousarray(X, dtype=np.int8), np.ascontiguousarray(y, dtype=np.int32)
+    workers = min(host_threads(), per_call)
+
+    def one(w, G, S, n):
+        width = data.window_width(w)
+        try:
+            c, b, info = lda_finish(G[:width, :width], S[:, :width], n, N, tol)
+        except ValueError as e:
+            raise ValueError(f"window {w}: {e}") from e
+        coef[w, :, :width], icpt[w] = c, b
+        ranks[w] = info["rank"], info["rank2"]
+
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        for w0 in range(0, W, per_call):
+            w1 = min(W, w0 + per_call)
+            G, S, n = lda_gram(X8, y32, data.M, data.context, A, w0, w1, ctx=ctx)
+            for f in [pool.submit(one, w, G[w - w0], S[w - w0], n[w - w0]) for w in range(w0, w1)]:
+                f.result()
+    data.base_kind, data.lda_coef, data.lda_intercept = "lda", coef, icpt
+    return {"n_fit": int(N), "ranks": ranks, "windows_per_call": per_call}
+
+
 def untrained_model(C, M, A, S, context, mode, seed=None, meta=None, base=None):
     """an untrained model of a mode's kinds (the reference's config model.inference: "default", "fast", "large", "best"), ready to
     be loaded and then trained in place: zero logistic weights or, for "best", one placeholder SVC per window (A zero rows, zero
     coefficients), or with base="xgb" one zero-valued stump per window and class, or with base="knn" one fit row of zeros with label 0
     per window, or with base="nb_bernoulli" / "nb_multinomial" / "nb_gaussian" zero Naive-Bayes tables and zero bias (every class
-    gets 1 / A); the smoother's starting point: one placeholder tree, zero CRF weights, Conv1d's default initialisation.
+    gets 1 / A), or with base="lda_svd" (LDABase: LinearDiscriminantAnalysis with its default svd solver; the bare name "lda" stays refused, as it
+    was before the base existed) zero LDA coefficients and intercepts (every class gets 1 / A); the smoother's starting point:
+    one placeholder tree, zero CRF weights, Conv1d's default initialisation.
     meta: optional dict with snp_pos, snp_ref, snp_alt, pop_order (the simulation's metadata)"""
     from . import synth
     from .convert import cov_sample
@@ -517,11 +650,14 @@ def untrained_model(C, M, A, S, context, mode, seed=None, meta=None, base=None):
                   population_order=list(meta["pop_order"]))
     d = GnxModelData(C=C, M=M, A=A, S=S, context=context, **kw)
     nb_names = {"nb_" + k: k for k in NB_TRAIN_KINDS}
-    if base not in (None, "svm", "xgb", "knn") and base not in nb_names:
+    if base not in (None, "svm", "xgb", "knn", "lda_svd") and base not in nb_names:
         raise ValueError("base must be None (the mode's own base), \"svm\" (SVMBase: the RBF SVC), \"xgb\" (XGBBase: boosted trees), "
-                         "\"knn\" (KNNBase: 1-nearest neighbour) or \"nb_bernoulli\" / \"nb_multinomial\" / \"nb_gaussian\" (the "
-                         "Naive-Bayes bases), got %r" % (base,))
-    if base in nb_names:   # NB*Base (src/Base/models.py:96-132) in place of the mode's base; the smoother stays the mode's
+                         "\"knn\" (KNNBase: 1-nearest neighbour), \"nb_bernoulli\" / \"nb_multinomial\" / \"nb_gaussian\" (the "
+                         "Naive-Bayes bases) or \"lda_svd\" (LDABase: linear discriminant analysis, svd solver), got %r" % (base,))
+    if base == "lda_svd":   # LDABase (src/Base/models.py:83-94) in place of the mode's base; the smoother stays the mode's
+        d.base_kind = "lda"
+        d.lda_coef, d.lda_intercept = np.zeros((W, 1 if A == 2 else A, M + 2 * context + C - M * W)), np.zeros((W, 1 if A == 2 else A))
+    elif base in nb_names:   # NB*Base (src/Base/models.py:96-132) in place of the mode's base; the smoother stays the mode's
         d.base_kind, d.nb_kind = "nb", nb_names[base]
         d.nb_table, d.nb_bias = np.zeros((W, M + 2 * context + C - M * W, 4, A)), np.zeros((W, A))
     elif base == "knn":   # KNNBase (src/Base/models.py:135-146) in place of the mode's base; the smoother stays the mode's

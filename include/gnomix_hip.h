@@ -22,6 +22,9 @@
  *   gnx_train_nb_counts   <- Base.train(X, y) of NBBernoulliBase / NBMultinomialBase / NBGaussianBase: the integer counts
  *                            every closed form needs; the caller finishes in float64 and loads the tables through
  *                            gnx_model_load_nb                                     src/Base/models.py:96-132
+ *   gnx_train_lda_gram    <- Base.train(X, y) of LDABase: the exact integer Gram matrix, class sums and class counts of every
+ *                            window; the caller finishes scikit-learn's svd solver in float64 and loads coef_ / intercept_
+ *                            through gnx_model_load_lda                            src/Base/models.py:83-94
  *   gnx_train_gbt         <- Smoother.train(B, y) of XGB_Smoother         src/Smooth/smooth.py:28-38, src/model.py:137
  *   gnx_train_crf         <- Smoother.train(B, y) of CRF_Smoother         src/Smooth/crf.py:51-58, src/Smooth/models.py:27-32
  *   gnx_train_cnn         <- Smoother.train(B, y) of CNN_Smoother         src/Smooth/cnn.py:104-118, src/Smooth/models.py:35-42
@@ -81,7 +84,8 @@ enum { GNX_SVC_KERNEL_SUBSTRINGS = 0, GNX_SVC_KERNEL_POLY = 1, GNX_SVC_KERNEL_AL
        GNX_SVC_KERNEL_RBF = 3 /* SVMBase: exp(-gamma |x - y|^2) on the SNP codes as numbers */ };
 enum { GNX_BASE_NONE = 0, GNX_BASE_LOGISTIC = 1, GNX_BASE_COVRSK_SVC = 2, GNX_BASE_FOREST = 3, GNX_BASE_RFOREST = 4,
        GNX_BASE_KNN = 5 /* KNNBase: 1-nearest neighbour per window */,
-       GNX_BASE_NB = 6 /* the three Naive-Bayes bases: per-window likelihood tables, loaded through gnx_model_load_nb */ };
+       GNX_BASE_NB = 6 /* the three Naive-Bayes bases: per-window likelihood tables, loaded through gnx_model_load_nb */,
+       GNX_BASE_LDA = 7 /* LDABase: per-window linear discriminant, loaded through gnx_model_load_lda */ };
 enum { GNX_SMOOTH_NONE = 0, GNX_SMOOTH_XGB = 1, GNX_SMOOTH_CRF = 2, GNX_SMOOTH_CNN = 3 };
 
 /* kernel ids for gnx_profile_get */
@@ -177,6 +181,23 @@ typedef struct gnx_nb_window {
   int32_t width;        /* M_ (or M_+rem for the last window) */
   int32_t reserved;
 } gnx_nb_window;
+
+/* Per-window linear discriminant of LDABase (src/Base/models.py -> sklearn LinearDiscriminantAnalysis(), solver "svd").  On the
+ * window's slice x of the reflect-padded query, the SNP codes as numbers (2 = missing is the number 2):
+ *   d[n, r] = sum_p coef[r, p] * x[n, col(p)] + intercept[r]       r = 0 .. n_rows - 1
+ *   A > 2:   n_rows = A, B[n, w, :] = softmax_r(d)     (row maximum subtracted; one reciprocal per row)
+ *   A == 2:  n_rows = 1 (scikit-learn keeps coef_[1] - coef_[0]);  p = 1 / (1 + exp(-d));  B[n, w, :] = [1 - p, p]
+ * The sum runs in float64 on v_mfma_f64_16x16x4_f64 with coef as the float64 it is (nothing is quantised); the order of the
+ * additions is the instruction's, so d differs from a numpy evaluation by at most (width + 2) 2^-53 (sum_p |coef x| + |intercept|).
+ * The float32 output is the float32 rounding of the float64 output.
+ * GNX_EINVAL: a non-finite coefficient or intercept (the message names the window), width != the window's width, n_rows != A
+ *   (1 for A == 2), a NULL pointer.  GNX_EUNSUPPORTED: A > 16 (the decision columns are one 16-wide MFMA tile). */
+typedef struct gnx_lda_window {
+  const double* coef;       /* (n_rows, width) row-major, finite */
+  const double* intercept;  /* (n_rows,) finite */
+  int32_t width;            /* M_ (or M_+rem for the last window) */
+  int32_t n_rows;           /* A, or 1 when A == 2 */
+} gnx_lda_window;
 
 /* Everything a pickled src.model.Gnomix carries for inference (src/model.py:28-88), as flat host
  * arrays.  W = C / M (src/model.py:32); the reference requires C % M != 0 (gnomix.py:124-125). */
@@ -319,6 +340,10 @@ int gnx_model_load(gnx_ctx* ctx, const gnx_model_desc* desc, gnx_model** out);
  * everything else in desc (geometry, smoother, calibrator) means what it means to gnx_model_load.  gnx_model_load itself answers
  * GNX_EINVAL to GNX_BASE_NB and names this entry: gnx_model_desc has no field for the tables. */
 int gnx_model_load_nb(gnx_ctx* ctx, const gnx_model_desc* desc, const gnx_nb_window* nb /* (W,) */, gnx_model** out);
+/* A model whose base is GNX_BASE_LDA: desc->base_kind must be GNX_BASE_LDA, lda lists the W windows' coefficients (gnx_lda_window
+ * above); the rest of desc means what it means to gnx_model_load, which itself answers GNX_EINVAL to GNX_BASE_LDA and names this
+ * entry. */
+int gnx_model_load_lda(gnx_ctx* ctx, const gnx_model_desc* desc, const gnx_lda_window* lda /* (W,) */, gnx_model** out);
 void gnx_model_free(gnx_model* model);
 int gnx_model_get_info(const gnx_model* model, gnx_model_info* out);
 /* smooth.calibrate (gnomix.py:367): when on AND the model carries a calibrator, smoother outputs (probabilities and the
@@ -577,6 +602,24 @@ int gnx_train_nb_counts(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t ldx, c
                         int32_t A, int32_t* n1, int32_t* n2, int32_t* class_count);
 int gnx_train_nb_counts_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const int32_t* dy, int64_t C, int64_t M,
                             int64_t ctx_snps, int32_t A, int32_t* d_n1, int32_t* d_n2, int32_t* d_class_count);
+
+/* ---- fitting the LDA base: the integer half of Base.train(X, y) for LDABase (LinearDiscriminantAnalysis(), solver "svd").
+ *      Everything scikit-learn's _solve_svd consumes is a function of three exact integer quantities per window:
+ *        G[w]    = Xw^T Xw                                  (ldw, ldw) int32, full symmetric, ldw = M + 2 ctx + (C - M W)
+ *        S[w, k] = sum of the rows n with y[n, w] == k      (A, ldw) int32
+ *        n[w, k] = number of those rows                     (A,) int32
+ *      Xw = the window's slice of the reflect-padded row; positions >= width_w hold 0.  The within-class scatter is
+ *      G - sum_k S_k S_k^T / n_k; the float64 rest (std, the two truncated decompositions, coef_ / intercept_) is the caller's
+ *      (gnomix_amd.train.lda_finish).  One v_mfma_i32_16x16x64_i8 product of [Xw | onehot(y)] with itself gives all three.
+ *      The outputs cover the windows [w0, w1) only — window w0 first — so that the caller bounds memory: (w1 - w0) ldw^2 int32.
+ *      X (N, ldx) int8 codes 0..2, y (N, W) labels in [0, A), 2 <= A <= 32.  GNX_EINVAL: 4 N >= 2^31 (an int32 sum could overflow),
+ *      a bad range, a NULL pointer; the host form also checks X and the range's labels (GNX_EINVAL) before anything is launched.
+ *      The _dev form takes device pointers for inputs AND outputs, runs asynchronously on the context's stream, and a row whose
+ *      label is outside [0, A) enters G but no class sum or count. */
+int gnx_train_lda_gram(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t ldx, const int32_t* y, int64_t C, int64_t M, int64_t ctx_snps,
+                       int32_t A, int64_t w0, int64_t w1, int32_t* G, int32_t* S, int32_t* n);
+int gnx_train_lda_gram_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const int32_t* dy, int64_t C, int64_t M,
+                           int64_t ctx_snps, int32_t A, int64_t w0, int64_t w1, int32_t* d_G, int32_t* d_S, int32_t* d_n);
 
 /* ---- training the convolutional smoother: CNN.fit (src/Smooth/cnn.py:104-118) as Smoother.train calls it for CNN_Smoother
  *      (src/Smooth/smooth.py:28-38, src/Smooth/models.py:35-42).  nn.Conv1d(A, A, S, padding = (S-1)/2) with zero padding,

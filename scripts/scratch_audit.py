@@ -34,6 +34,7 @@ MUST_BE_CLEAN = [
     r"k_rbf_dec<", r"k_rbf_stage", r"k_rbf_norm", r"k_rbf_gram",
     r"k_knn_",
     r"k_nb_",
+    r"k_lda_",
 ]
 
 
