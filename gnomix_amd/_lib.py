@@ -211,6 +211,9 @@ SYMBOLS = {
     "gnx_train_gbt_base": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, C.POINTER(GbtParams)] + [_VP] * 10),
     "gnx_train_gbt_base_dev": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, C.POINTER(GbtParams)] + [_VP] * 10),
     "gnx_train_gbt_base_phases": (C.c_int, [C.c_int32, _VP]),
+    "gnx_train_rforest": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, C.c_int32, C.c_int32] + [_VP] * 10),
+    "gnx_train_rforest_dev": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, C.c_int32, C.c_int32] + [_VP] * 10),
+    "gnx_train_rforest_phases": (C.c_int, [C.c_int32, _VP]),
     "gnx_train_nb_counts": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, _VP, _VP, _VP]),
     "gnx_train_nb_counts_dev": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, _VP, _VP, _VP]),
     "gnx_train_lda_gram": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, _I64, _I64, _VP, _VP, _VP]),

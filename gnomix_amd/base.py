@@ -36,18 +36,26 @@ class HipBase:
         trees (train.train_forest_base).  1-NN base (KNNBase): the rows are stored (train.train_knn_base; there is nothing to fit).
         Naive-Bayes bases (NB*Base): counts on the device, closed forms on the host (train.train_nb_base; alpha = 1e-10).
         LDA base (LDABase): the exact Gram matrix, class sums and counts on the device, scikit-learn's svd solver restated on them in
-        float64 on the host (train.train_lda_base)."""
+        float64 on the host (train.train_lda_base).  Random-forest base (RFBase) of a model made by untrained_model(base="rf"): every window's
+        20 depth-4 trees as scikit-learn builds them (train.train_rforest_base); an rforest model without rf_train (a converted pickle,
+        a loaded .gnx) has no hyper-parameters and is refused."""
         from .train import train_logistic_base, train_svc_base, svc_seed_chain, svc_rng_after_kernel, SVC_SEED_HIGH
         from .model import DeviceModel, svc_window_is_rbf
         d = self.dev.data
-        if d.base_kind == "rforest":
+        if d.base_kind == "rforest" and not getattr(d, "rf_train", None):
+            # a converted pickle, a synthetic model or a loaded .gnx carries no hyper-parameters to fit with
             raise NotImplementedError("on-device training is not built for the random-forest base (RFBase: scikit-learn's bootstrap "
                                       "stream); the logistic, SVC (CovRSK, RBF), boosted-tree (XGBBase), 1-NN (KNNBase), Naive-Bayes and LDA bases are")
-        if d.base_kind not in (None, "logistic", "covrsk", "forest", "knn", "nb", "lda"):
+        if d.base_kind not in (None, "logistic", "covrsk", "forest", "rforest", "knn", "nb", "lda"):
             raise NotImplementedError("on-device training is built for the logistic, the SVC (CovRSK, RBF), the boosted-tree, the 1-NN, the "
                                       "Naive-Bayes and the LDA bases")
         t = time()
-        if d.base_kind == "lda":
+        if d.base_kind == "rforest":
+            # RFBase: every window's RandomForestClassifier(n_estimators=20, max_depth=4), scikit-learn's own trees; one forest seed per
+            # window from numpy's global generator, in window order (the reference's workers fit with unseeded generators)
+            from .train import train_rforest_base
+            self.train_info = train_rforest_base(d, X, y, ctx=self.dev.ctx)
+        elif d.base_kind == "lda":
             from .train import train_lda_base
             self.train_info = train_lda_base(d, X, y, ctx=self.dev.ctx)
         elif d.base_kind == "nb":

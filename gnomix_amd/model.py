@@ -75,6 +75,7 @@ class GnxModelData:
     rf_feat: np.ndarray | None = None
     rf_thr: np.ndarray | None = None         # float64
     rf_value: np.ndarray | None = None       # (n_nodes, A) float64: predict_proba row of each node
+    rf_train: dict | None = None             # n_trees, max_depth for HipBase.train (train.untrained_model(base="rf")); in memory only
     # xgb smoother in xgboost's model schema (src/Smooth/models.py:14-20)
     tree_off: np.ndarray | None = None
     left: np.ndarray | None = None
@@ -128,7 +129,7 @@ class GnxModelData:
         chr22 model shrinks by a few percent) and inflating them costs the command line 0.6 s of its ~1.4 s; load reads both."""
         d = {"gnx_version": GNX_FILE_VERSION}
         for k, v in self.__dict__.items():
-            if v is None or k in ("svc", "knn", "extra"):
+            if v is None or k in ("svc", "knn", "extra", "rf_train"):
                 continue
             if k == "population_order":
                 d[k] = np.array([str(p) for p in v])

@@ -570,6 +570,127 @@ def lda_finish(G, S, n, N, tol=1e-4):
     return coef, intercept, {"rank": rank, "rank2": rank2, "sv": sv, "sv2": sv2}
 
 
+# ---- the random-forest base (RFBase) ---------------------------------------------------------------------------------------------
+RF_SEED_HIGH = 2 ** 31 - 1                      # sklearn.ensemble._base._set_random_states: randint(np.iinfo(np.int32).max)
+
+
+def rforest_seeds_unchained(W):
+    """forest seeds for RFBase's window fits: the reference fits them in spawned workers with unseeded generators, so there is no
+    stream to reproduce; one seed per window from numpy's global generator, in window order, in one call -> int64 (W,)"""
+    return np.random.randint(RF_SEED_HIGH, size=int(W)).astype(np.int64)
+
+
+def rforest_bootstrap(seeds, n_trees, N):
+    """what numpy's generator decides in RandomForestClassifier(n_estimators=n_trees, random_state=seed).fit on N rows, per window
+    seed: the tree seeds RandomState(seed).randint(2**31 - 1) in order; per tree the bootstrap rows RandomState(ts).randint(0, N, N,
+    dtype=int32) as row weights (bincount) and the splitter's state, the first randint(0, 2**31 - 1) of a FRESH RandomState(ts)
+    -> (weight (W, n_trees, N) int64, state (W, n_trees) uint32)"""
+    seeds = np.asarray(seeds).reshape(-1)
+    W, T, N = len(seeds), int(n_trees), int(N)
+    weight, state = np.zeros((W, T, N), np.int64), np.zeros((W, T), np.uint32)
+    for w in range(W):
+        rs = np.random.RandomState(int(seeds[w]))
+        for t in range(T):
+            ts = rs.randint(RF_SEED_HIGH)
+            weight[w, t] = np.bincount(np.random.RandomState(ts).randint(0, N, N, dtype=np.int32), minlength=N)
+            state[w, t] = np.random.RandomState(ts).randint(0, RF_SEED_HIGH)
+    return weight, state
+
+
+def train_rforest_arrays(X, y, M, context, A, seeds, n_trees=20, max_depth=4, ctx=None, device=0):
+    """RFBase's per-window RandomForestClassifier(n_estimators=n_trees, max_depth=max_depth, random_state=seeds[w]).fit on the device,
+    the same trees as scikit-learn 1.7.2 builds (gnx_train_rforest; the chain is stated in forest/k_train_rforest.hip).  X (N, C) int8
+    codes {0, 1, 2} — a numpy array, or a CUDA int8 tensor that stays on the device — y (N, W) labels, seeds (W,) -> dict of rf_* arrays
+    as GnxModelData takes them (convert.rforest_from_sklearn's layout).  The bootstrap is drawn here with numpy (rforest_bootstrap)."""
+    ctx = ctx or _lib.default_context(device)
+    on_dev = hasattr(X, "is_cuda") and X.is_cuda
+    A, T, D = int(A), int(n_trees), int(max_depth)
+    N, Cn = X.shape
+    W = Cn // int(M)
+    seeds = np.asarray(seeds).reshape(-1)
+    if seeds.shape != (W,):
+        raise ValueError(f"seeds must be (W,) = ({W},), got {seeds.shape}")
+    if T < 1 or not 1 <= D <= 5:
+        raise ValueError("n_trees >= 1 and 1 <= max_depth <= 5")
+    weight, state = rforest_bootstrap(seeds, T, N)
+    if weight.max() > 127:
+        raise _lib.GnxError(_lib.GNX_EINVAL, "train_rforest: a bootstrap weight above 127")
+    weight = weight.astype(np.uint8)
+    keep = []
+    if on_dev:
+        import torch
+        assert X.dtype == torch.int8 and X.dim() == 2 and X.stride(1) == 1
+        ldx = X.stride(0) if N > 1 else Cn
+        y = y if (hasattr(y, "is_cuda") and y.is_cuda) else torch.as_tensor(np.ascontiguousarray(y, dtype=np.int32), device=X.device)
+        assert y.dtype == torch.int32 and y.is_contiguous() and tuple(y.shape) == (N, W)
+        dw, ds = torch.as_tensor(weight, device=X.device), torch.as_tensor(state.view(np.int32), device=X.device)
+        keep = [dw, ds]
+        x_ptr, y_ptr, w_ptr, s_ptr, fn = X.data_ptr(), y.data_ptr(), dw.data_ptr(), ds.data_ptr(), ctx.lib.gnx_train_rforest_dev
+        ctx.set_stream(torch.cuda.current_stream(ctx.device).cuda_stream)
+        torch.cuda.current_stream(ctx.device).synchronize()
+    else:
+        X = np.ascontiguousarray(X, dtype=np.int8)
+        ldx = Cn
+        y = np.ascontiguousarray(y, dtype=np.int32)
+        if y.shape != (N, W):
+            raise ValueError(f"y must be (N, W) = ({N}, {W}), got {y.shape}")
+        x_ptr, y_ptr, w_ptr, s_ptr, fn = X.ctypes.data, y.ctypes.data, weight.ctypes.data, state.ctypes.data, ctx.lib.gnx_train_rforest
+    cap = max(W * T, 1) * (2 ** (D + 1) - 1)
+    wt0, tree_off = np.zeros(W + 1, np.int32), np.zeros(W * T + 1, np.int32)
+    left, right, feat = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+    thr, value = np.zeros(cap, np.float64), np.zeros((cap, A), np.float64)
+    nn = C.c_int64(0)
+    ctx.check(fn(ctx.h, x_ptr, int(N), int(ldx), y_ptr, int(Cn), int(M), int(context), A, T, D, w_ptr, s_ptr, wt0.ctypes.data,
+                 tree_off.ctypes.data, left.ctypes.data, right.ctypes.data, feat.ctypes.data, thr.ctypes.data, value.ctypes.data,
+                 C.addressof(nn)))
+    del keep
+    n = nn.value
+    return dict(rf_win_tree0=wt0, rf_tree_off=tree_off, rf_left=left[:n].copy(), rf_right=right[:n].copy(), rf_feat=feat[:n].copy(),
+                rf_thr=thr[:n].copy(), rf_value=value[:n].copy())
+
+
+def rforest_placeholder(W, A):
+    """one single-leaf tree per window: every class gets probability 1 / A"""
+    return dict(rf_win_tree0=np.arange(W + 1, dtype=np.int32), rf_tree_off=np.arange(W + 1, dtype=np.int32),
+                rf_left=np.full(W, -1, np.int32), rf_right=np.full(W, -1, np.int32), rf_feat=np.zeros(W, np.int32),
+                rf_thr=np.full(W, -2.0, np.float64), rf_value=np.full((W, A), 1.0 / A, np.float64))
+
+
+def train_rforest_base(data: GnxModelData, X, y, seeds=None, ctx=None) -> dict:
+    """fit the random-forest base of `data` in place (base_kind "rforest", rf_* arrays) -> info.  Hyper-parameters are data.rf_train
+    (n_trees, max_depth; RFBase's 20 and 4 when absent).  seeds (W,): one forest seed per window; by default drawn from numpy's global
+    generator in window order (rforest_seeds_unchained).  ValueError (naming the window): a class of range(A) without rows in a window
+    (scikit-learn would fit fewer classes and the reference's predict_proba_vectorized cannot stack such a model).  X must hold the
+    codes 0..2, y labels in [0, A)."""
+    X = np.asarray(X)
+    if X.ndim != 2 or X.shape[1] != data.C or X.shape[0] < 1:
+        raise ValueError(f"X must be (N >= 1, C={data.C}), got {X.shape}")
+    if X.dtype.kind == "f" and np.any(X != np.rint(X)):
+        raise ValueError("X must hold whole numbers (the SNP codes 0, 1, 2)")
+    if X.min() < 0 or X.max() > 2:
+        raise ValueError("X must hold the SNP codes 0, 1, 2 (2 = missing)")
+    y = np.asarray(y)
+    N, W, A = X.shape[0], data.W, data.A
+    if y.shape != (N, W):
+        raise ValueError(f"y must be (N, W) = ({N}, {W}), got {y.shape}")
+    if y.min() < 0 or y.max() >= A:
+        raise ValueError(f"y must hold labels in 0..{A - 1}")
+    y32 = np.ascontiguousarray(y, dtype=np.int32)
+    for w in range(W):
+        cc = np.bincount(y32[:, w], minlength=A)
+        if np.any(cc < 1):
+            raise ValueError("window %d: class %d has no row" % (w, int(np.flatnonzero(cc < 1)[0])))
+    hp = {"n_trees": 20, "max_depth": 4, **(getattr(data, "rf_train", None) or {})}
+    if seeds is None:
+        seeds = rforest_seeds_unchained(W)
+    trees = train_rforest_arrays(np.ascontiguousarray(X, dtype=np.int8), y32, data.M, data.context, A, seeds, n_trees=hp["n_trees"],
+                                 max_depth=hp["max_depth"], ctx=ctx)
+    data.base_kind = "rforest"
+    for k, v in trees.items():
+        setattr(data, k, v)
+    return {"n_fit": int(N), "seeds": np.asarray(seeds, dtype=np.int64), "n_nodes": int(len(trees["rf_left"])), **hp}
+
+
 def host_threads():
     """the CPUs this process may use: OMP_NUM_THREADS when it is set (a job's allowance), else the scheduler's affinity mask"""
     import os
@@ -633,7 +754,8 @@ def train_lda_base(data: GnxModelData, X, y, ctx=None, tol=1e-4, windows_per_cal
 def untrained_model(C, M, A, S, context, mode, seed=None, meta=None, base=None):
     """an untrained model of a mode's kinds (the reference's config model.inference: "default", "fast", "large", "best"), ready to
     be loaded and then trained in place: zero logistic weights or, for "best", one placeholder SVC per window (A zero rows, zero
-    coefficients), or with base="xgb" one zero-valued stump per window and class, or with base="knn" one fit row of zeros with label 0
+    coefficients), or with base="rf" (RFBase: the random forest) one single-leaf tree per window with value 1 / A and
+    rf_train = dict(n_trees=20, max_depth=4) (the hyper-parameters HipBase.train fits with; kept in memory, not in the .gnx), or with base="xgb" one zero-valued stump per window and class, or with base="knn" one fit row of zeros with label 0
     per window, or with base="nb_bernoulli" / "nb_multinomial" / "nb_gaussian" zero Naive-Bayes tables and zero bias (every class
     gets 1 / A), or with base="lda_svd" (LDABase: LinearDiscriminantAnalysis with its default svd solver; the bare name "lda" stays refused, as it
     was before the base existed) zero LDA coefficients and intercepts (every class gets 1 / A); the smoother's starting point:
@@ -650,9 +772,9 @@ def untrained_model(C, M, A, S, context, mode, seed=None, meta=None, base=None):
                   population_order=list(meta["pop_order"]))
     d = GnxModelData(C=C, M=M, A=A, S=S, context=context, **kw)
     nb_names = {"nb_" + k: k for k in NB_TRAIN_KINDS}
-    if base not in (None, "svm", "xgb", "knn", "lda_svd") and base not in nb_names:
+    if base not in (None, "svm", "xgb", "rf", "knn", "lda_svd") and base not in nb_names:
         raise ValueError("base must be None (the mode's own base), \"svm\" (SVMBase: the RBF SVC), \"xgb\" (XGBBase: boosted trees), "
-                         "\"knn\" (KNNBase: 1-nearest neighbour), \"nb_bernoulli\" / \"nb_multinomial\" / \"nb_gaussian\" (the "
+                         "\"rf\" (RFBase: the random forest), \"knn\" (KNNBase: 1-nearest neighbour), \"nb_bernoulli\" / \"nb_multinomial\" / \"nb_gaussian\" (the "
                          "Naive-Bayes bases) or \"lda_svd\" (LDABase: linear discriminant analysis, svd solver), got %r" % (base,))
     if base == "lda_svd":   # LDABase (src/Base/models.py:83-94) in place of the mode's base; the smoother stays the mode's
         d.base_kind = "lda"
@@ -662,6 +784,10 @@ def untrained_model(C, M, A, S, context, mode, seed=None, meta=None, base=None):
         d.nb_table, d.nb_bias = np.zeros((W, M + 2 * context + C - M * W, 4, A)), np.zeros((W, A))
     elif base == "knn":   # KNNBase (src/Base/models.py:135-146) in place of the mode's base; the smoother stays the mode's
         d.base_kind, d.knn_X, d.knn_y = "knn", np.zeros((1, C), np.int8), np.zeros((1, W), np.int32)
+    elif base == "rf":   # RFBase (src/Base/models.py:54-66) in place of the mode's base; the smoother stays the mode's
+        d.base_kind, d.rf_train = "rforest", dict(n_trees=20, max_depth=4)
+        for k, v in rforest_placeholder(W, A).items():
+            setattr(d, k, v)
     elif base == "xgb":   # XGBBase (src/Base/models.py:24-35) in place of the mode's base; the smoother stays the mode's
         d.base_kind, d.fb_missing, d.fb_base_score = "forest", 2, 0.5
         for k, v in forest_placeholder(W, A).items():

@@ -17,6 +17,7 @@
  *   gnx_train_svc         <- Base.train(X, y) of CovRSKBase (mode "best") src/Base/base.py:104-127, src/Base/models.py:195-215
  *   gnx_train_svc2        <- the same, and Base.train(X, y) of SVMBase (RBF)  src/Base/models.py:148-159
  *   gnx_train_gbt_base    <- Base.train(X, y) of XGBBase (boosted trees)  src/Base/base.py:104-127, src/Base/models.py:24-35
+ *   gnx_train_rforest     <- Base.train(X, y) of RFBase                   src/Base/models.py:54-66
  *   (no entry point)      <- Base.train(X, y) of KNNBase: a 1-NN fit stores its rows; the caller puts them into
  *                            gnx_model_desc.knn and loads the model                src/Base/models.py:135-146
  *   gnx_train_nb_counts   <- Base.train(X, y) of NBBernoulliBase / NBMultinomialBase / NBGaussianBase: the integer counts
@@ -586,6 +587,31 @@ int gnx_train_gbt_base_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ld
                            int32_t* right, int32_t* feat, float* cond, uint8_t* default_left, int32_t* tree_class, int64_t* n_nodes,
                            double* loss);
 int gnx_train_gbt_base_phases(int32_t enable, double* ms);
+
+/* ---- training the random-forest base: Base.train of RFBase (src/Base/base.py:104-127, src/Base/models.py:54-66: per window
+ *      RandomForestClassifier(n_estimators=20, max_depth=4).fit(Xw, yw)), tree for tree as scikit-learn 1.7.2 builds them
+ *      (forest/k_train_rforest.hip, whose header states the chain; tests/rf_exact.py restates it and is held to live scikit-learn).
+ *      What numpy's generator decides is the caller's (gnomix_amd.train.rforest_bootstrap): for tree t of window w
+ *        weight[w, t, n] = how often the bootstrap drew row n (uint8; GNX_EINVAL above 127: the int8 operand of the count product),
+ *        state[w, t]     = the splitter's 32-bit generator state (uint32).
+ *      X (N, ldx) int8 codes 0..2, y (N, W) int32 labels in [0, A), 2 <= A <= 32, N < 2^24 (GNX_EINVAL beyond: an int32 sum of
+ *      weights could overflow), 1 <= max_depth <= 5.  gnx_train_rforest checks X and y (GNX_EINVAL); gnx_train_rforest_dev (X, y,
+ *      weight, state already in HBM) reads neither back: codes are only compared, a label outside [0, A) belongs to no class.
+ *      Outputs (HOST, caller-allocated), the rforest base's own layout, ready for gnx_model_desc (rf_*): win_tree0[W+1],
+ *      tree_off[W n_trees + 1], left / right / feat (int32; children are indices inside the tree, -1 at leaves; feat = SNP index
+ *      within the window's padded slice, 0 at leaves), thr (float64: 0.5, 1.0 or 1.5, -2 at leaves) with room for
+ *      (2^(max_depth+1) - 1) W n_trees nodes and value with A times as many (float64, a node's class frequencies); *n_nodes = nodes
+ *      written.  Trees do not depend on scheduling.
+ * gnx_train_rforest_phases(enable, ms): as gnx_train_gbt_base_phases; ms (3 doubles, may be NULL) receives the last timed call's
+ *   milliseconds in the count product, the draw and the row partition.  Process-wide, for scripts/bench_train_rforest.py. */
+int gnx_train_rforest(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t ldx, const int32_t* y, int64_t C, int64_t M, int64_t ctx_snps,
+                      int32_t A, int32_t n_trees, int32_t max_depth, const uint8_t* weight, const uint32_t* state, int32_t* win_tree0,
+                      int32_t* tree_off, int32_t* left, int32_t* right, int32_t* feat, double* thr, double* value, int64_t* n_nodes);
+int gnx_train_rforest_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const int32_t* dy, int64_t C, int64_t M,
+                          int64_t ctx_snps, int32_t A, int32_t n_trees, int32_t max_depth, const uint8_t* d_weight,
+                          const uint32_t* d_state, int32_t* win_tree0, int32_t* tree_off, int32_t* left, int32_t* right, int32_t* feat,
+                          double* thr, double* value, int64_t* n_nodes);
+int gnx_train_rforest_phases(int32_t enable, double* ms);
 
 /* ---- fitting the Naive-Bayes bases: the counting half of Base.train(X, y) for NBBernoulliBase / NBMultinomialBase /
  *      NBGaussianBase (src/Base/base.py:104-127, src/Base/models.py:96-132).  Every fitted attribute of the three estimators is a

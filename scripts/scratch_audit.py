@@ -35,6 +35,7 @@ MUST_BE_CLEAN = [
     r"k_knn_",
     r"k_nb_",
     r"k_lda_",
+    r"k_rf_",
 ]
 
 
