@@ -32,14 +32,17 @@ class HipBase:
         probability=True), seeded as the reference's sequential fits are (window 0 from numpy's global generator, like
         BaseLibSVM.fit; later windows from the state each CovRSK kernel call leaves), and the global generator is left where the
         reference leaves it.  RBF windows (SVMBase): every window's SVC(C=100, gamma, probability=True), one seed per window drawn
-        from numpy's global generator in window order.  Forest base (XGBBase): every window's 20 rounds of depth-4 boosted
+        from numpy's global generator in window order.  Windows tagged "string_kernel" / "poly_kernel" (StringKernelBase /
+        PolynomialStringKernelBase): every window's SVC(kernel=<that kernel>, probability=True) with the window's own lengths / exponent,
+        seeded likewise (the reference fits them sequentially and their kernels draw nothing), the generator left there; untagged
+        string-kernel windows are fitted as CovRSK.  Forest base (XGBBase): every window's 20 rounds of depth-4 boosted
         trees (train.train_forest_base).  1-NN base (KNNBase): the rows are stored (train.train_knn_base; there is nothing to fit).
         Naive-Bayes bases (NB*Base): counts on the device, closed forms on the host (train.train_nb_base; alpha = 1e-10).
         LDA base (LDABase): the exact Gram matrix, class sums and counts on the device, scikit-learn's svd solver restated on them in
         float64 on the host (train.train_lda_base).  Random-forest base (RFBase) of a model made by untrained_model(base="rf"): every window's
         20 depth-4 trees as scikit-learn builds them (train.train_rforest_base); an rforest model without rf_train (a converted pickle,
         a loaded .gnx) has no hyper-parameters and is refused."""
-        from .train import train_logistic_base, train_svc_base, svc_seed_chain, svc_rng_after_kernel, SVC_SEED_HIGH
+        from .train import train_logistic_base, train_svc_base, svc_seed_chain, svc_rng_after_kernel, svc_window_kernel, SVC_SEED_HIGH
         from .model import DeviceModel, svc_window_is_rbf
         d = self.dev.data
         if d.base_kind == "rforest" and not getattr(d, "rf_train", None):
@@ -72,6 +75,12 @@ class HipBase:
         elif d.base_kind == "covrsk" and d.svc and svc_window_is_rbf(d.svc[0]):
             # SVMBase: the reference's workers fit with unseeded generators; one seed per window from the global generator, in order
             self.train_info = train_svc_base(d, X, y, ctx=self.dev.ctx, kernel="rbf", gamma=float(d.svc[0]["gamma"]))
+        elif d.base_kind == "covrsk" and d.svc and svc_window_kernel(d.svc[0]) in ("string_kernel", "poly_kernel"):
+            # StringKernelBase / PolynomialStringKernelBase (windows tagged by train_svc_base / untrained_model): sequential fits whose
+            # kernels leave numpy's global generator alone, so window w's seed is the w-th value drawn from it; no CovRSK seed chain
+            kernel = svc_window_kernel(d.svc[0])
+            kw = dict(p=float(d.svc[0]["poly_p"])) if kernel == "poly_kernel" else {}
+            self.train_info = train_svc_base(d, X, y, ctx=self.dev.ctx, kernel=kernel, **kw)
         elif d.base_kind == "covrsk":
             widths = [d.window_width(w) for w in range(d.W)]
             seeds = svc_seed_chain(widths, np.random.randint(SVC_SEED_HIGH))

@@ -12,6 +12,8 @@
 //    runs of equal symbols are peeled with ctz and each adds g(L) = sum_{m in Ms, m <= L} (L - m + 1) from an LDS table.
 //    Values are exact integers below 2^24 (checked on the host from g(width)), so the float Gram equals libsvm's Qfloat
 //    and its double diagonal QD.
+//  * k_svc_gram_poly (GNX_SVC_KERNEL_POLY, PolynomialStringKernelBase): the same planes and Gram layout; the value of a pair is
+//    (long long)(np.sum(run_value[run lengths]) / p) in numpy's summation order, again an exact integer below 2^24.
 //  * k_svc_smo: one wave per solve (a class pair's full problem or one of its fold problems, any window of the batch).
 //    libsvm's Solver::Solve for C-SVC (C = 1, eps = 1e-3, shrinking, no iteration cap beyond a hang guard) restated:
 //    WSS3 second-order working-set selection with libsvm's tie rules (`>=` / `<=`: the LAST index wins, so the parallel
@@ -44,6 +46,7 @@
 //   OF THE POSSIBILITY OF SUCH DAMAGE.
 #include "../gnx_internal.h"
 #include "gnx_svc_rbf.h"
+#include "gnx_np_pairwise.h"
 
 #include <cmath>
 #include <random>
@@ -58,6 +61,11 @@
 namespace {
 
 constexpr int SVC_MAX_WIDTH = 16384;          // g table in LDS: (width + 1) * 4 bytes
+// The polynomial kernel's run values are doubles: (width + 1) * 8 bytes.  Its budget is the 64 KiB a block gets without asking
+// for more, which also leaves room for two blocks on a CU's 160 KiB: the pass is bound by the latency of dependent LDS lookups,
+// so resident waves are what it runs on.
+constexpr int SVC_POLY_LDS_BUDGET = 64 * 1024;
+constexpr int SVC_POLY_MAX_WIDTH = SVC_POLY_LDS_BUDGET / 8 - 1;  // 8191 SNPs
 constexpr int SVC_FOLDS = 5;                  // svm_binary_svc_probability
 constexpr int SVC_MAX_BATCH = 256;            // windows per batch (grid z, per-element workspace)
 constexpr double SVC_EPS = 1e-3;              // sklearn SVC(tol=1e-3)
@@ -139,6 +147,59 @@ __global__ __launch_bounds__(256) void k_svc_gram(const uint32_t* planes, int64_
   float* G = gram + (size_t)wl * N * N;
   G[i * N + j] = (float)K;
   G[j * N + i] = (float)K;
+}
+
+// The polynomial string kernel (PolynomialStringKernelBase, string_kernel.py:40-61): K = (long long)(np.sum(contigs ** p) / p),
+// contigs = the length of the run of equal SNPs before every mismatch plus the run the window ends with (zero-length runs count).
+// Same tiling and output as k_svc_gram; the run values (width + 1 doubles, the host's np.arange(width + 1) ** p) sit in LDS and are
+// added in numpy's pairwise order (gnx_np_pairwise.h), so the truncated value is the reference's.  Two sweeps over the pair's words:
+// the first counts the elements (the order depends on the count), the second streams them.
+__global__ __launch_bounds__(256) void k_svc_gram_poly(const uint32_t* planes, int64_t N, int nwm, int w_first, int W, int width_main,
+                                                        int width_last, const double* run_value, double poly_p, float* gram) {
+  extern __shared__ double rv_lds[];
+  const int wl = blockIdx.z;
+  const int w = w_first + wl;
+  const int width = (w == W - 1) ? width_last : width_main;
+  if (blockIdx.y < blockIdx.x) return;  // block-uniform: every column index < every row index
+  for (int t = threadIdx.x; t <= width; t += blockDim.x) rv_lds[t] = run_value[t];
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * 16 + (threadIdx.x & 15);
+  const int64_t j = (int64_t)blockIdx.y * 16 + (threadIdx.x >> 4);
+  if (i >= N || j >= N || j < i) return;
+  const int NW = (width + 31) >> 5;
+  const int tail_bits = (width & 31) ? (width & 31) : 32;
+  const uint32_t tail_mask = (width & 31) ? ((1u << (width & 31)) - 1u) : 0xffffffffu;
+  const uint32_t* xi = planes + (((int64_t)wl * N + i) * 2) * nwm;
+  const uint32_t* xj = planes + (((int64_t)wl * N + j) * 2) * nwm;
+  auto mismatches = [&](int q) -> uint32_t {  // bit t: SNP 32 q + t differs (bits past the window are clear)
+    const uint32_t d = (xi[q] ^ xj[q]) | (xi[nwm + q] ^ xj[nwm + q]);
+    return q == NW - 1 ? (d & tail_mask) : d;
+  };
+  int n_el = 1;
+  for (int q = 0; q < NW; ++q) n_el += __builtin_popcount(mismatches(q));
+  // generator: the word in hand is q, its mismatches from bit b on are mm (shifted down), run is the length of the open run
+  int q = -1, b = 0, bits = 0, run = 0;
+  uint32_t mm = 0;
+  auto next_val = [&]() -> double {
+    while (mm == 0u) {
+      run += bits - b;  // the rest of the word matches
+      if (++q == NW) { q = NW - 1; b = bits; return rv_lds[run]; }  // the run the window ends with (the last element)
+      mm = mismatches(q);
+      bits = (q == NW - 1) ? tail_bits : 32;
+      b = 0;
+    }
+    const int z = __builtin_ctz(mm);
+    const double v = rv_lds[run + z];
+    run = 0;
+    mm = (mm >> z) >> 1;
+    b += z + 1;
+    return v;
+  };
+  const double S = gnx_np_pairwise_sum(n_el, next_val);
+  const float K = (float)(long long)(S / poly_p);  // numpy float -> int assignment truncates toward zero; < 2^24 (host check)
+  float* G = gram + (size_t)wl * N * N;
+  G[i * N + j] = K;
+  G[j * N + i] = K;
 }
 
 struct SvcSolve {
@@ -555,6 +616,58 @@ std::vector<int32_t> kernel_lengths(int32_t kernel_kind, int width) {
   return ms;
 }
 
+// g(L) over the kernel's lengths (prefix-stable in the width: one table serves both widths); < 2^24: svc_kernel_check bounds g(width)
+std::vector<uint32_t> run_table(int32_t kernel_kind, int width) {
+  const std::vector<int32_t> ms = kernel_lengths(kernel_kind, width);
+  std::vector<uint32_t> g(width + 1, 0);
+  for (int L = 1; L <= width; ++L) {
+    uint64_t s = 0;
+    for (int32_t m : ms)
+      if (m <= L) s += (uint64_t)(L - m + 1);
+    g[L] = (uint32_t)s;
+  }
+  return g;
+}
+
+struct SvcPoly {  // GNX_SVC_KERNEL_POLY: the exponent and the caller's (host) table np.arange(n) ** p
+  double p;
+  const double* run_value;
+  int64_t n;
+};
+
+// the string kernels' Gram pass of one batch of windows: k_svc_pack, then k_svc_gram (g table) or k_svc_gram_poly (run values)
+struct GramPass {
+  int64_t N;
+  int nwm, W, width_main, width_last;
+  const uint32_t* dg;  // device, width_last + 1 (the integer kernels)
+  const double* drv;   // device, width_last + 1 (the polynomial kernel), or NULL
+  double poly_p;
+  size_t lds() const { return (size_t)(width_last + 1) * (drv ? 8 : 4); }
+};
+
+hipError_t gram_pass_prepare(const GramPass& gp) {
+  if (!gp.drv && gp.lds() > 64 * 1024)  // (the polynomial kernel's table stays within SVC_POLY_LDS_BUDGET)
+    return hipFuncSetAttribute((const void*)k_svc_gram, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gp.lds());
+  return hipSuccess;
+}
+
+hipError_t gram_pass(const GramPass& gp, const int8_t* dX, int64_t ldx, int64_t C, int64_t M, int64_t cx, int w0, int nb, uint32_t* dPl,
+                     float* dGram, hipStream_t s) {
+  const int64_t n_words = (int64_t)nb * gp.N * gp.nwm;
+  hipLaunchKernelGGL(k_svc_pack, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, s, dX, gp.N, ldx, C, M, cx, w0, nb, gp.W,
+                     (int)(C % M), gp.nwm, dPl);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const unsigned tiles = (unsigned)((gp.N + 15) / 16);
+  if (gp.drv)
+    hipLaunchKernelGGL(k_svc_gram_poly, dim3(tiles, tiles, (unsigned)nb), dim3(256), gp.lds(), s, dPl, gp.N, gp.nwm, w0, gp.W, gp.width_main,
+                       gp.width_last, gp.drv, gp.poly_p, dGram);
+  else
+    hipLaunchKernelGGL(k_svc_gram, dim3(tiles, tiles, (unsigned)nb), dim3(256), gp.lds(), s, dPl, gp.N, gp.nwm, w0, gp.W, gp.width_main,
+                       gp.width_last, gp.dg, dGram);
+  return hipGetLastError();
+}
+
 // sklearn's newrand.h: mt19937 + the tweaked Lemire post-processor
 uint32_t bounded_rand_int(std::mt19937& mt, uint32_t range) {
   uint32_t x = mt();
@@ -606,21 +719,14 @@ struct PairTask {  // one (window, class pair) of a batch
 };
 
 int train_svc_impl(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const int32_t* y, int64_t C, int64_t M, int64_t cx,
-                   int32_t A, const gnx_svc_params& prm, const uint32_t* seeds, int32_t* n_sv, int32_t* n_support, int32_t* support,
-                   double* dual_coef, double* intercept, double* prob_a, double* prob_b, gnx_svc_train_info* info) {
+                   int32_t A, const gnx_svc_params& prm, const SvcPoly* poly, const uint32_t* seeds, int32_t* n_sv, int32_t* n_support,
+                   int32_t* support, double* dual_coef, double* intercept, double* prob_a, double* prob_b, gnx_svc_train_info* info) {
   const int32_t kernel_kind = prm.kernel_kind;
   const bool rbf = kernel_kind == GNX_SVC_KERNEL_RBF;
   const int W = (int)(C / M), rem = (int)(C % M), P = A * (A - 1) / 2;
   const int width_main = (int)(M + 2 * cx), width_last = width_main + rem;
   // g(L) over the kernel's lengths (prefix-stable in the width: one table serves both widths)
-  const std::vector<int32_t> ms = rbf ? std::vector<int32_t>() : kernel_lengths(kernel_kind, width_last);
-  std::vector<uint32_t> g(width_last + 1, 0);
-  for (int L = 1; L <= width_last; ++L) {
-    uint64_t s = 0;
-    for (int32_t m : ms)
-      if (m <= L) s += (uint64_t)(L - m + 1);
-    g[L] = (uint32_t)s;  // < 2^24: train_svc_check bounds g(width_last)
-  }
+  const std::vector<uint32_t> g = (rbf || poly) ? std::vector<uint32_t>(width_last + 1, 0) : run_table(kernel_kind, width_last);
   const int nwm = (width_last + 31) / 32;
   // RBF: staged int8 rows (Np x kp per window) instead of bit-planes, the int32 distances beside the float Gram, one exp table
   const int64_t Np = (N + 63) / 64 * 64;
@@ -641,10 +747,11 @@ int train_svc_impl(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const
   const size_t bXw = rbf ? up256((size_t)wb * Np * kp) : 0, bNrm = rbf ? up256((size_t)wb * Np * 4) : 0;
   const size_t bD2 = rbf ? up256((size_t)wb * gram_w) : 0, bTab = rbf ? up256(tab.size() * 8) : 0;
   const size_t bPl = rbf ? 0 : up256((size_t)wb * N * 2 * nwm * 4), bGram = up256((size_t)wb * gram_w), bG = up256((size_t)(width_last + 1) * 4);
+  const size_t bRv = poly ? up256((size_t)(width_last + 1) * 8) : 0;
   const size_t bSol = up256(max_solves * sizeof(SvcSolve)), bE8 = up256(max_elems * 8), bE4 = up256(max_elems * 4), bE1 = up256(max_elems);
   const size_t bS8 = up256(max_solves * 8), bS4 = up256(max_solves * 4);
   const size_t bT4 = up256(max_rows * 4), bT8 = up256(max_rows * 8), bP8 = up256(max_pairs * 8), bP4 = up256(max_pairs * 4);
-  const size_t total = bPl + bGram + bG + bSol + 4 * bE8 + 2 * bE4 + 3 * bE1 + bS8 + 2 * bS4 + 2 * bT4 + 2 * bT8 + 3 * bP8 + 2 * bP4 + bXw + bNrm + bD2 + bTab;
+  const size_t total = bPl + bGram + bG + bSol + 4 * bE8 + 2 * bE4 + 3 * bE1 + bS8 + 2 * bS4 + 2 * bT4 + 2 * bT8 + 3 * bP8 + 2 * bP4 + bXw + bNrm + bD2 + bTab + bRv;
   DevBlock blk;
   hipError_t e = hipMalloc(&blk.p, total);
   if (e != hipSuccess) {
@@ -682,14 +789,16 @@ int train_svc_impl(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const
   int32_t* dNrm = (int32_t*)take(bNrm);
   int32_t* dD2 = rbf ? (int32_t*)take(bD2) : nullptr;
   double* dTab = rbf ? (double*)take(bTab) : nullptr;
+  double* dRv = poly ? (double*)take(bRv) : nullptr;
 
   hipStream_t s = ctx->stream;
   DevEvents ev;
   for (auto& x : ev.e) HIPCHK(ctx, hipEventCreate(&x));
   HIPCHK(ctx, hipMemcpyAsync(dg, g.data(), (size_t)(width_last + 1) * 4, hipMemcpyHostToDevice, s));
   if (rbf) HIPCHK(ctx, hipMemcpyAsync(dTab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
-  const size_t lds_g = (size_t)(width_last + 1) * 4;
-  if (!rbf && lds_g > 64 * 1024) HIPCHK(ctx, hipFuncSetAttribute((const void*)k_svc_gram, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g));
+  if (poly) HIPCHK(ctx, hipMemcpyAsync(dRv, poly->run_value, (size_t)(width_last + 1) * 8, hipMemcpyHostToDevice, s));
+  const GramPass gp{N, nwm, W, width_main, width_last, dg, dRv, poly ? poly->p : 0.0};
+  if (!rbf) HIPCHK(ctx, gram_pass_prepare(gp));
 
   gnx_svc_train_info inf{};
   std::vector<std::vector<int32_t>> cls_rows(A);
@@ -769,12 +878,7 @@ int train_svc_impl(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const
       HIPCHK(ctx, gnx_launch_rbf_stage(dX, N, ldx, C, M, cx, w0, nb, W, rem, Np, kp, dXw, dNrm, s));
       HIPCHK(ctx, gnx_launch_rbf_gram(dXw, dNrm, N, Np, kp, nb, dTab, (int32_t)tab.size() - 1, dGram, dD2, s));
     } else {
-      const int64_t n_words = (int64_t)nb * N * nwm;
-      hipLaunchKernelGGL(k_svc_pack, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, s, dX, N, ldx, C, M, cx, w0, nb, W, rem, nwm, dPl);
-      HIPCHK(ctx, hipGetLastError());
-      const unsigned tiles = (unsigned)((N + 15) / 16);
-      hipLaunchKernelGGL(k_svc_gram, dim3(tiles, tiles, (unsigned)nb), dim3(256), lds_g, s, dPl, N, nwm, w0, W, width_main, width_last, dg, dGram);
-      HIPCHK(ctx, hipGetLastError());
+      HIPCHK(ctx, gram_pass(gp, dX, ldx, C, M, cx, w0, nb, dPl, dGram, s));
     }
     HIPCHK(ctx, hipEventRecord(ev.e[1], s));
     // ---- SMO ----
@@ -862,9 +966,52 @@ int train_svc_impl(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const
   return GNX_OK;
 }
 
+// what a kernel kind asks of the geometry: widths the tables fit, kernel values that are exact floats, a Gram within the budget
+int svc_kernel_check(gnx_ctx* ctx, const char* who, int64_t N, int64_t C, int64_t M, int64_t cx, int32_t kernel_kind, double gamma,
+                     const SvcPoly* poly) {
+  const std::string pre = std::string(who) + ": ";
+  const int64_t width = M + 2 * cx + C % M;
+  if (kernel_kind == GNX_SVC_KERNEL_RBF) {
+    if (!(gamma > 0.0) || !std::isfinite(gamma)) return gnx_fail(ctx, GNX_EINVAL, pre + "gamma must be finite and > 0");
+    if (width > GNX_RBF_MAX_WIDTH) return gnx_fail(ctx, GNX_EINVAL, pre + "window wider than GNX_RBF_MAX_WIDTH SNPs");
+    if ((uint64_t)N * N * 8 > GNX_SVC_GRAM_BUDGET)
+      return gnx_fail(ctx, GNX_EINVAL, pre + "one window's Gram and distances (2 N^2 words) exceed GNX_SVC_GRAM_BUDGET");
+    return GNX_OK;
+  }
+  uint64_t gw = 0;
+  if (kernel_kind == GNX_SVC_KERNEL_POLY) {
+    if (!(poly->p > 0.0) || !std::isfinite(poly->p)) return gnx_fail(ctx, GNX_EINVAL, pre + "poly_p must be finite and > 0");
+    if (!poly->run_value) return gnx_fail(ctx, GNX_EINVAL, pre + "run_value is NULL");
+    if (width > SVC_POLY_MAX_WIDTH)
+      return gnx_fail(ctx, GNX_EINVAL, pre + "window of " + std::to_string(width) + " SNPs: the polynomial kernel's run values (8 bytes each) "
+                                         "must fit " + std::to_string(SVC_POLY_LDS_BUDGET >> 10) + " KiB of LDS: at most " +
+                                         std::to_string(SVC_POLY_MAX_WIDTH) + " SNPs");
+    if (poly->n < width + 1)
+      return gnx_fail(ctx, GNX_EINVAL, pre + "run_value holds " + std::to_string(poly->n) + " values, a window of " + std::to_string(width) +
+                                         " SNPs needs " + std::to_string(width + 1));
+    for (int64_t L = 0; L <= width; ++L)
+      if (!(poly->run_value[L] >= 0.0) || !std::isfinite(poly->run_value[L]))
+        return gnx_fail(ctx, GNX_EINVAL, pre + "run_value[" + std::to_string(L) + "] is negative or not finite");
+    // the largest kernel value: K(x, x) = run_value[width] / p for p >= 1 (L^p is superadditive); below 1 runs of one SNP add up to
+    // at most width / p
+    const double top = std::max(poly->run_value[width], poly->p < 1.0 ? (double)width : 0.0) / poly->p;
+    gw = top < 1.8e19 ? (uint64_t)(long long)top : ~(uint64_t)0;
+  } else {
+    if (width > SVC_MAX_WIDTH) return gnx_fail(ctx, GNX_EINVAL, pre + "window wider than " + std::to_string(SVC_MAX_WIDTH) + " SNPs");
+    // the largest kernel value is K(x, x) = g(width): it must be an exact float
+    for (int32_t m : kernel_lengths(kernel_kind, (int)width)) gw += (uint64_t)(width - m + 1);
+  }
+  if (gw >= ((uint64_t)1 << 24))
+    return gnx_fail(ctx, GNX_EINVAL, pre + "window of " + std::to_string(width) + " SNPs: kernel values reach " + std::to_string(gw) +
+                                       " >= 2^24, not exact in float");
+  if ((uint64_t)N * N * 4 > GNX_SVC_GRAM_BUDGET)
+    return gnx_fail(ctx, GNX_EINVAL, pre + "one window's Gram (N^2 floats) exceeds GNX_SVC_GRAM_BUDGET");
+  return GNX_OK;
+}
+
 int train_svc_check(gnx_ctx* ctx, int64_t N, int64_t ldx, int64_t C, int64_t M, int64_t cx, int32_t A, const gnx_svc_params* prm,
-                    const void* X, const void* y, const uint32_t* seeds, const void* o1, const void* o2, const void* o3, const void* o4,
-                    const void* o5, const void* o6, const void* o7) {
+                    const SvcPoly* poly, const void* X, const void* y, const uint32_t* seeds, const void* o1, const void* o2, const void* o3,
+                    const void* o4, const void* o5, const void* o6, const void* o7) {
   if (!ctx->usable) return gnx_fail(ctx, GNX_ESTATE, "context has no device (gnx_init failed)");
   if (!prm) return gnx_fail(ctx, GNX_EINVAL, "train_svc: params is NULL");
   const int32_t kernel_kind = prm->kernel_kind;
@@ -872,29 +1019,15 @@ int train_svc_check(gnx_ctx* ctx, int64_t N, int64_t ldx, int64_t C, int64_t M, 
   if (A < 2 || A > 32) return gnx_fail(ctx, GNX_EINVAL, "A (ancestries) must be in [2, 32]");
   if (N < 2 || N > INT32_MAX || M <= 0 || C < M || cx < 0 || cx > C || ldx < C || C > INT32_MAX)
     return gnx_fail(ctx, GNX_EINVAL, "train_svc: bad N / C / M / ctx / ldx");
-  if (kernel_kind == GNX_SVC_KERNEL_POLY)
-    return gnx_fail(ctx, GNX_EUNSUPPORTED, "train_svc: the polynomial string kernel (GNX_SVC_KERNEL_POLY) has no trainer");
-  if (kernel_kind != GNX_SVC_KERNEL_SUBSTRINGS && kernel_kind != GNX_SVC_KERNEL_ALL_LENGTHS && kernel_kind != GNX_SVC_KERNEL_RBF)
+  if (poly && kernel_kind != GNX_SVC_KERNEL_POLY)
+    return gnx_fail(ctx, GNX_EINVAL, "train_svc_poly: kernel_kind must be GNX_SVC_KERNEL_POLY (the other kinds: gnx_train_svc2)");
+  if (kernel_kind == GNX_SVC_KERNEL_POLY && !poly)
+    return gnx_fail(ctx, GNX_EUNSUPPORTED, "train_svc: the polynomial string kernel (GNX_SVC_KERNEL_POLY) takes its exponent and run "
+                                           "values through gnx_train_svc_poly");
+  if (kernel_kind != GNX_SVC_KERNEL_SUBSTRINGS && kernel_kind != GNX_SVC_KERNEL_ALL_LENGTHS && kernel_kind != GNX_SVC_KERNEL_RBF && !poly)
     return gnx_fail(ctx, GNX_EINVAL, "train_svc: kernel_kind must be GNX_SVC_KERNEL_SUBSTRINGS, GNX_SVC_KERNEL_ALL_LENGTHS or GNX_SVC_KERNEL_RBF");
   if (!(prm->C > 0.0) || !std::isfinite(prm->C)) return gnx_fail(ctx, GNX_EINVAL, "train_svc: C must be finite and > 0");
-  const int64_t width = M + 2 * cx + C % M;
-  if (kernel_kind == GNX_SVC_KERNEL_RBF) {
-    if (!(prm->gamma > 0.0) || !std::isfinite(prm->gamma)) return gnx_fail(ctx, GNX_EINVAL, "train_svc: gamma must be finite and > 0");
-    if (width > GNX_RBF_MAX_WIDTH) return gnx_fail(ctx, GNX_EINVAL, "train_svc: window wider than GNX_RBF_MAX_WIDTH SNPs");
-    if ((uint64_t)N * N * 8 > GNX_SVC_GRAM_BUDGET)
-      return gnx_fail(ctx, GNX_EINVAL, "train_svc: one window's Gram and distances (2 N^2 words) exceed GNX_SVC_GRAM_BUDGET");
-    return GNX_OK;
-  }
-  if (width > SVC_MAX_WIDTH) return gnx_fail(ctx, GNX_EINVAL, "train_svc: window wider than " + std::to_string(SVC_MAX_WIDTH) + " SNPs");
-  // the largest kernel value is K(x, x) = g(width): it must be an exact float
-  uint64_t gw = 0;
-  for (int32_t m : kernel_lengths(kernel_kind, (int)width)) gw += (uint64_t)(width - m + 1);
-  if (gw >= ((uint64_t)1 << 24))
-    return gnx_fail(ctx, GNX_EINVAL, "train_svc: window of " + std::to_string(width) + " SNPs: kernel values reach " + std::to_string(gw) +
-                                       " >= 2^24, not exact in float");
-  if ((uint64_t)N * N * 4 > GNX_SVC_GRAM_BUDGET)
-    return gnx_fail(ctx, GNX_EINVAL, "train_svc: one window's Gram (N^2 floats) exceeds GNX_SVC_GRAM_BUDGET");
-  return GNX_OK;
+  return svc_kernel_check(ctx, "train_svc", N, C, M, cx, kernel_kind, prm->gamma, poly);
 }
 
 int train_svc_labels(gnx_ctx* ctx, const int32_t* y, int64_t N, int W, int32_t A) {
@@ -920,12 +1053,13 @@ extern "C" int gnx_svc_fold_permutation(uint32_t seed, int32_t l, int32_t* perm)
   return GNX_OK;
 }
 
-extern "C" int gnx_train_svc2_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const int32_t* dy, int64_t C, int64_t M,
-                                  int64_t ctx_snps, int32_t A, const gnx_svc_params* params, const uint32_t* seeds, int32_t* n_sv,
-                                  int32_t* n_support, int32_t* support, double* dual_coef, double* intercept, double* prob_a,
-                                  double* prob_b, gnx_svc_train_info* info) {
+namespace {
+
+int train_svc_dev_any(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const int32_t* dy, int64_t C, int64_t M, int64_t ctx_snps,
+                      int32_t A, const gnx_svc_params* params, const SvcPoly* poly, const uint32_t* seeds, int32_t* n_sv, int32_t* n_support,
+                      int32_t* support, double* dual_coef, double* intercept, double* prob_a, double* prob_b, gnx_svc_train_info* info) {
   if (!ctx) return GNX_EINVAL;
-  int rc = train_svc_check(ctx, N, ldx, C, M, ctx_snps, A, params, dX, dy, seeds, n_sv, n_support, support, dual_coef, intercept,
+  int rc = train_svc_check(ctx, N, ldx, C, M, ctx_snps, A, params, poly, dX, dy, seeds, n_sv, n_support, support, dual_coef, intercept,
                            prob_a, prob_b);
   if (rc != GNX_OK) return rc;
   GNX_BIND_DEVICE(ctx);
@@ -934,16 +1068,15 @@ extern "C" int gnx_train_svc2_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int
   HIPCHK(ctx, hipMemcpyAsync(y.data(), dy, y.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   if ((rc = train_svc_labels(ctx, y.data(), N, W, A)) != GNX_OK) return rc;
-  return train_svc_impl(ctx, dX, N, ldx, y.data(), C, M, ctx_snps, A, *params, seeds, n_sv, n_support, support, dual_coef, intercept,
+  return train_svc_impl(ctx, dX, N, ldx, y.data(), C, M, ctx_snps, A, *params, poly, seeds, n_sv, n_support, support, dual_coef, intercept,
                         prob_a, prob_b, info);
 }
 
-extern "C" int gnx_train_svc2(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t ldx, const int32_t* y, int64_t C, int64_t M,
-                              int64_t ctx_snps, int32_t A, const gnx_svc_params* params, const uint32_t* seeds, int32_t* n_sv,
-                              int32_t* n_support, int32_t* support, double* dual_coef, double* intercept, double* prob_a, double* prob_b,
-                              gnx_svc_train_info* info) {
+int train_svc_host_any(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t ldx, const int32_t* y, int64_t C, int64_t M, int64_t ctx_snps,
+                       int32_t A, const gnx_svc_params* params, const SvcPoly* poly, const uint32_t* seeds, int32_t* n_sv, int32_t* n_support,
+                       int32_t* support, double* dual_coef, double* intercept, double* prob_a, double* prob_b, gnx_svc_train_info* info) {
   if (!ctx) return GNX_EINVAL;
-  int rc = train_svc_check(ctx, N, ldx, C, M, ctx_snps, A, params, X, y, seeds, n_sv, n_support, support, dual_coef, intercept,
+  int rc = train_svc_check(ctx, N, ldx, C, M, ctx_snps, A, params, poly, X, y, seeds, n_sv, n_support, support, dual_coef, intercept,
                            prob_a, prob_b);
   if (rc != GNX_OK) return rc;
   if ((rc = train_svc_labels(ctx, y, N, (int)(C / M), A)) != GNX_OK) return rc;
@@ -955,8 +1088,98 @@ extern "C" int gnx_train_svc2(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t 
     return gnx_fail(ctx, GNX_ENOMEM, std::string("train_svc: hipMalloc: ") + hipGetErrorString(e));
   }
   HIPCHK(ctx, hipMemcpy2DAsync(xb.p, (size_t)C, X, (size_t)ldx, (size_t)C, (size_t)N, hipMemcpyHostToDevice, ctx->stream));
-  return train_svc_impl(ctx, (const int8_t*)xb.p, N, C, y, C, M, ctx_snps, A, *params, seeds, n_sv, n_support, support, dual_coef,
+  return train_svc_impl(ctx, (const int8_t*)xb.p, N, C, y, C, M, ctx_snps, A, *params, poly, seeds, n_sv, n_support, support, dual_coef,
                         intercept, prob_a, prob_b, info);
+}
+
+}  // namespace
+
+extern "C" int gnx_train_svc2_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const int32_t* dy, int64_t C, int64_t M,
+                                  int64_t ctx_snps, int32_t A, const gnx_svc_params* params, const uint32_t* seeds, int32_t* n_sv,
+                                  int32_t* n_support, int32_t* support, double* dual_coef, double* intercept, double* prob_a,
+                                  double* prob_b, gnx_svc_train_info* info) {
+  return train_svc_dev_any(ctx, dX, N, ldx, dy, C, M, ctx_snps, A, params, nullptr, seeds, n_sv, n_support, support, dual_coef, intercept,
+                           prob_a, prob_b, info);
+}
+
+extern "C" int gnx_train_svc2(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t ldx, const int32_t* y, int64_t C, int64_t M,
+                              int64_t ctx_snps, int32_t A, const gnx_svc_params* params, const uint32_t* seeds, int32_t* n_sv,
+                              int32_t* n_support, int32_t* support, double* dual_coef, double* intercept, double* prob_a, double* prob_b,
+                              gnx_svc_train_info* info) {
+  return train_svc_host_any(ctx, X, N, ldx, y, C, M, ctx_snps, A, params, nullptr, seeds, n_sv, n_support, support, dual_coef, intercept,
+                            prob_a, prob_b, info);
+}
+
+// PolynomialStringKernelBase: params->kernel_kind = GNX_SVC_KERNEL_POLY, the exponent and the run values beside it
+extern "C" int gnx_train_svc_poly_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const int32_t* dy, int64_t C, int64_t M,
+                                      int64_t ctx_snps, int32_t A, const gnx_svc_params* params, double poly_p, const double* run_value,
+                                      int64_t n_run_value, const uint32_t* seeds, int32_t* n_sv, int32_t* n_support, int32_t* support,
+                                      double* dual_coef, double* intercept, double* prob_a, double* prob_b, gnx_svc_train_info* info) {
+  const SvcPoly poly{poly_p, run_value, n_run_value};
+  return train_svc_dev_any(ctx, dX, N, ldx, dy, C, M, ctx_snps, A, params, &poly, seeds, n_sv, n_support, support, dual_coef, intercept,
+                           prob_a, prob_b, info);
+}
+
+extern "C" int gnx_train_svc_poly(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t ldx, const int32_t* y, int64_t C, int64_t M,
+                                  int64_t ctx_snps, int32_t A, const gnx_svc_params* params, double poly_p, const double* run_value,
+                                  int64_t n_run_value, const uint32_t* seeds, int32_t* n_sv, int32_t* n_support, int32_t* support,
+                                  double* dual_coef, double* intercept, double* prob_a, double* prob_b, gnx_svc_train_info* info) {
+  const SvcPoly poly{poly_p, run_value, n_run_value};
+  return train_svc_host_any(ctx, X, N, ldx, y, C, M, ctx_snps, A, params, &poly, seeds, n_sv, n_support, support, dual_coef, intercept,
+                            prob_a, prob_b, info);
+}
+
+// the float Gram matrices of windows [w0, w1) as the trainers compute them (k_svc_pack + k_svc_gram / k_svc_gram_poly): host pointers
+extern "C" int gnx_svc_gram(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t ldx, int64_t C, int64_t M, int64_t ctx_snps, int32_t kernel_kind,
+                            double poly_p, const double* run_value, int64_t n_run_value, int64_t w0, int64_t w1, float* gram) {
+  if (!ctx) return GNX_EINVAL;
+  if (!ctx->usable) return gnx_fail(ctx, GNX_ESTATE, "context has no device (gnx_init failed)");
+  if (!X || !gram) return gnx_fail(ctx, GNX_EINVAL, "svc_gram: NULL array");
+  if (N < 1 || N > INT32_MAX || M <= 0 || C < M || ctx_snps < 0 || ctx_snps > C || ldx < C || C > INT32_MAX)
+    return gnx_fail(ctx, GNX_EINVAL, "svc_gram: bad N / C / M / ctx / ldx");
+  const int W = (int)(C / M);
+  if (w0 < 0 || w1 <= w0 || w1 > W) return gnx_fail(ctx, GNX_EINVAL, "svc_gram: windows [w0, w1) must lie in [0, W) and hold at least one");
+  if (kernel_kind != GNX_SVC_KERNEL_SUBSTRINGS && kernel_kind != GNX_SVC_KERNEL_ALL_LENGTHS && kernel_kind != GNX_SVC_KERNEL_POLY)
+    return gnx_fail(ctx, GNX_EINVAL, "svc_gram: kernel_kind must be GNX_SVC_KERNEL_SUBSTRINGS, GNX_SVC_KERNEL_POLY or GNX_SVC_KERNEL_ALL_LENGTHS");
+  const bool is_poly = kernel_kind == GNX_SVC_KERNEL_POLY;
+  const SvcPoly poly{poly_p, run_value, n_run_value};
+  int rc = svc_kernel_check(ctx, "svc_gram", N, C, M, ctx_snps, kernel_kind, 0.0, is_poly ? &poly : nullptr);
+  if (rc != GNX_OK) return rc;
+  const size_t gram_w = (size_t)N * N * 4;
+  if ((uint64_t)(w1 - w0) * gram_w > GNX_SVC_GRAM_BUDGET)
+    return gnx_fail(ctx, GNX_EINVAL, "svc_gram: the Gram matrices of the range exceed GNX_SVC_GRAM_BUDGET: ask for fewer windows");
+  GNX_BIND_DEVICE(ctx);
+  const int width_main = (int)(M + 2 * ctx_snps), width_last = width_main + (int)(C % M), nwm = (width_last + 31) / 32;
+  const int wb = (int)std::min<int64_t>(w1 - w0, SVC_MAX_BATCH);
+  const std::vector<uint32_t> g = is_poly ? std::vector<uint32_t>(width_last + 1, 0) : run_table(kernel_kind, width_last);
+  const size_t bX = up256((size_t)N * C + 64), bPl = up256((size_t)wb * N * 2 * nwm * 4), bGram = up256((size_t)wb * gram_w);
+  const size_t bG = up256((size_t)(width_last + 1) * 4), bRv = is_poly ? up256((size_t)(width_last + 1) * 8) : 0;
+  DevBlock blk;
+  hipError_t e = hipMalloc(&blk.p, bX + bPl + bGram + bG + bRv);
+  if (e != hipSuccess) {
+    blk.p = nullptr;
+    return gnx_fail(ctx, GNX_ENOMEM, std::string("svc_gram: hipMalloc: ") + hipGetErrorString(e));
+  }
+  char* q = (char*)blk.p;
+  auto take = [&](size_t b) { char* r = q; q += b; return r; };
+  int8_t* dX = (int8_t*)take(bX);
+  uint32_t* dPl = (uint32_t*)take(bPl);
+  float* dGram = (float*)take(bGram);
+  uint32_t* dg = (uint32_t*)take(bG);
+  double* dRv = is_poly ? (double*)take(bRv) : nullptr;
+  hipStream_t s = ctx->stream;
+  HIPCHK(ctx, hipMemcpy2DAsync(dX, (size_t)C, X, (size_t)ldx, (size_t)C, (size_t)N, hipMemcpyHostToDevice, s));
+  HIPCHK(ctx, hipMemcpyAsync(dg, g.data(), (size_t)(width_last + 1) * 4, hipMemcpyHostToDevice, s));
+  if (is_poly) HIPCHK(ctx, hipMemcpyAsync(dRv, run_value, (size_t)(width_last + 1) * 8, hipMemcpyHostToDevice, s));
+  const GramPass gp{N, nwm, W, width_main, width_last, dg, dRv, is_poly ? poly_p : 0.0};
+  HIPCHK(ctx, gram_pass_prepare(gp));
+  for (int64_t w = w0; w < w1; w += wb) {
+    const int nb = (int)std::min<int64_t>(wb, w1 - w);
+    HIPCHK(ctx, gram_pass(gp, dX, C, C, M, ctx_snps, (int)w, nb, dPl, dGram, s));
+    HIPCHK(ctx, hipMemcpyAsync(gram + (size_t)(w - w0) * N * N, dGram, (size_t)nb * gram_w, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+  }
+  return GNX_OK;
 }
 
 // the CovRSK entries: C = 1 (sklearn's default)

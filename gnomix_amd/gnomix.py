@@ -103,10 +103,11 @@ class HipGnomix:
             self.accuracies, self.Confusion_Matrices = self._score_splits(
                 {"train": ((X_t1, y_t1), (B_t2, y_t2)), "val": None if X_v is None else ((X_v, y_v), None)})
         if retrain_base:
-            from .model import svc_window_is_rbf
-            if self.dev.data.base_kind == "covrsk" and not svc_window_is_rbf(self.dev.data.svc[0]):
+            from .train import svc_window_kernel
+            if self.dev.data.base_kind == "covrsk" and svc_window_kernel(self.dev.data.svc[0]) == "CovRSK":
                 # the reference's kernel calls between the two fits (its base predictions of train2 / val) leave numpy's global
                 # generator where a CovRSK kernel call on the last window leaves it; this build's predictions do not touch it
+                # (the RBF, plain and polynomial string kernels draw nothing: their models leave the generator alone)
                 from .train import svc_rng_after_kernel
                 svc_rng_after_kernel(self.data.window_width(self.W - 1))
             parts = [(X_t1, y_t1), (X_t2, y_t2)] + ([(X_v, y_v)] if X_v is not None else [])

@@ -22,7 +22,9 @@ def _c(a, dt):
 
 
 def svc_window_is_rbf(w) -> bool:
-    """the kernel tag of a per-window SVC dict: "rbf" = SVMBase's libsvm RBF kernel; no tag (every older .gnx) = a string kernel"""
+    """the kernel tag of a per-window SVC dict: "rbf" = SVMBase's libsvm RBF kernel; no tag (every older .gnx) = a string kernel
+    ("string_kernel" / "poly_kernel" tag the windows of StringKernelBase / PolynomialStringKernelBase for training:
+    train.svc_window_kernel; inference reads ms / poly_p, not the tag)"""
     return "kernel" in w and str(np.asarray(w["kernel"])) == "rbf"
 
 
@@ -40,7 +42,8 @@ class GnxModelData:
     lr_intercept: np.ndarray | None = None  # (W, A)
     # CovRSK base: per-window fitted SVC (src/Base/models.py:195-215)
     svc: list | None = None               # list of dicts: xfit, support, dual_coef, intercept, prob_a, prob_b, n_support, ms
-                                          # (SVMBase windows: kernel = "rbf" and gamma instead of ms)
+                                          # (SVMBase windows: kernel = "rbf" and gamma instead of ms; polynomial string kernel:
+                                          # kernel = "poly_kernel", poly_p and run_value instead of ms; plain: kernel = "string_kernel")
     # knn base: per-window KNeighborsClassifier(n_neighbors=1) (src/Base/models.py:135-146).  Either the shared form that training
     # produces (every window's fit rows are the same haplotypes: window w's rows are knn_X[:, window_columns(w)], its labels
     # knn_y[:, w]) or, for a converted pickle, the per-window arrays as they were fitted

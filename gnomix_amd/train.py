@@ -268,7 +268,8 @@ def train_crf_smoother(data: GnxModelData, B, y, **kw) -> dict:
 # ---- the CovRSK SVC base (mode "best") ---------------------------------------------------------------------------------------
 SVC_SEED_HIGH = int(np.iinfo("i").max)          # BaseLibSVM.fit: seed = rnd.randint(np.iinfo("i").max)
 SVC_KERNEL_KINDS = {"CovRSK": 0, "string_kernel": 2}   # GNX_SVC_KERNEL_SUBSTRINGS (CovSample lengths), GNX_SVC_KERNEL_ALL_LENGTHS
-SVC_TRAIN_KINDS = dict(SVC_KERNEL_KINDS, rbf=3)        # + GNX_SVC_KERNEL_RBF (SVMBase): what train_svc_arrays accepts
+SVC_TRAIN_KINDS = dict(SVC_KERNEL_KINDS, rbf=3, poly_kernel=1)   # + GNX_SVC_KERNEL_RBF (SVMBase), GNX_SVC_KERNEL_POLY (PolynomialStringKernelBase): what train_svc_arrays accepts
+SVC_UNCHAINED_KERNELS = ("rbf", "string_kernel", "poly_kernel")  # kernels that leave numpy's global generator alone: one drawn seed per window
 
 
 def svc_rng_after_kernel(width):
@@ -315,13 +316,17 @@ def window_columns(C, M, context, w):
 def svc_seeds_unchained(W):
     """libsvm seeds for SVMBase's window fits: the reference fits them in spawned workers with unseeded generators
     (base_multithread = True), so there is nothing to reproduce; one seed per window from numpy's global generator, in window
-    order, as BaseLibSVM.fit draws it -> uint32 (W,)"""
+    order, as BaseLibSVM.fit draws it -> uint32 (W,).  StringKernelBase and PolynomialStringKernelBase fit sequentially
+    (base_multithread = False) and their kernels never touch the global generator, so these ARE the seeds the reference's fits draw:
+    the first W values of RandomState(k).randint(SVC_SEED_HIGH) after np.random.seed(k)."""
     return np.asarray([np.random.randint(SVC_SEED_HIGH) for _ in range(int(W))], dtype=np.uint32)
 
 
-def train_svc_arrays(X, y, M, context, A, seeds, kernel="CovRSK", ctx=None, device=0, gamma=0.001, C=None):
+def train_svc_arrays(X, y, M, context, A, seeds, kernel="CovRSK", ctx=None, device=0, gamma=0.001, C=None, p=1.2):
     """SVC(kernel=<kernel>, probability=True).fit of every window on the device (gnx_train_svc2).  kernel "rbf" is SVMBase's
-    SVC(C=100., gamma=0.001) (C defaults to 100 for "rbf" and to sklearn's 1 for the string kernels).  X (N, C) int8 {0,1,2}, y (N, W)
+    SVC(C=100., gamma=0.001) (C defaults to 100 for "rbf" and to sklearn's 1 for the string kernels); "poly_kernel" is
+    PolynomialStringKernelBase's poly_kernel(X, Y, p) (gnx_train_svc_poly, with the run values of convert.poly_run_values).
+    X (N, C) int8 {0,1,2}, y (N, W)
     labels, seeds (W,) libsvm seeds -> dict of (W, ...) arrays in sklearn's layout (support / dual_coef padded to N columns, n_sv
     valid) and an info dict"""
     import ctypes as ct   # (the libsvm cost parameter of this function is named C, as sklearn's)
@@ -343,26 +348,72 @@ def train_svc_arrays(X, y, M, context, A, seeds, kernel="CovRSK", ctx=None, devi
                prob_a=np.zeros((W, P), np.float64), prob_b=np.zeros((W, P), np.float64))
     info = _lib.SvcTrainInfo()
     prm = _lib.SvcParams(SVC_TRAIN_KINDS[kernel], 0, float((100.0 if kernel == "rbf" else 1.0) if C is None else C), float(gamma))
-    ctx.check(ctx.lib.gnx_train_svc2(ctx.h, X.ctypes.data, N, Cn, y.ctypes.data, Cn, int(M), int(context), A, ct.byref(prm),
-                                    seeds.ctypes.data, *(out[k].ctypes.data for k in ("n_sv", "n_support", "support", "dual_coef",
-                                                                                      "intercept", "prob_a", "prob_b")), ct.byref(info)))
+    outs = [out[k].ctypes.data for k in ("n_sv", "n_support", "support", "dual_coef", "intercept", "prob_a", "prob_b")]
+    if kernel == "poly_kernel":
+        from .convert import poly_run_values
+        rv = np.ascontiguousarray(poly_run_values(int(M) + 2 * int(context) + Cn % int(M), p)["run_value"], dtype=np.float64)
+        ctx.check(ctx.lib.gnx_train_svc_poly(ctx.h, X.ctypes.data, N, Cn, y.ctypes.data, Cn, int(M), int(context), A, ct.byref(prm),
+                                            float(p), rv.ctypes.data, len(rv), seeds.ctypes.data, *outs, ct.byref(info)))
+    else:
+        ctx.check(ctx.lib.gnx_train_svc2(ctx.h, X.ctypes.data, N, Cn, y.ctypes.data, Cn, int(M), int(context), A, ct.byref(prm),
+                                        seeds.ctypes.data, *outs, ct.byref(info)))
     return out, dict(smo_iterations=info.smo_iterations, n_solves=info.n_solves, n_guarded=info.n_guarded, gram_ms=info.gram_ms,
                      smo_ms=info.smo_ms, platt_ms=info.platt_ms)
 
 
+def svc_gram(X, M, context, kernel="CovRSK", p=1.2, w0=0, w1=None, ctx=None, device=0):
+    """the float Gram matrices K(Xw, Xw) of windows [w0, w1) as the string-kernel trainers compute them (gnx_svc_gram) ->
+    (w1 - w0, N, N) float32.  kernel: "CovRSK", "string_kernel" or "poly_kernel" (with exponent p)"""
+    if kernel not in SVC_TRAIN_KINDS or kernel == "rbf":
+        raise ValueError("kernel must be \"CovRSK\", \"string_kernel\" or \"poly_kernel\"")
+    ctx = ctx or _lib.default_context(device)
+    X = np.ascontiguousarray(X, dtype=np.int8)
+    N, Cn = X.shape
+    w1 = Cn // int(M) if w1 is None else int(w1)
+    rv = None
+    if kernel == "poly_kernel":
+        from .convert import poly_run_values
+        rv = np.ascontiguousarray(poly_run_values(int(M) + 2 * int(context) + Cn % int(M), p)["run_value"], dtype=np.float64)
+    G = np.zeros((max(w1 - int(w0), 0), N, N), np.float32)
+    ctx.check(ctx.lib.gnx_svc_gram(ctx.h, X.ctypes.data, N, Cn, Cn, int(M), int(context), SVC_TRAIN_KINDS[kernel], float(p),
+                                  None if rv is None else rv.ctypes.data, 0 if rv is None else len(rv), int(w0), w1, G.ctypes.data))
+    return G
+
+
+def svc_window_kernel(w) -> str:
+    """the kernel of a per-window SVC dict, by its tag: "rbf" (SVMBase), "string_kernel" (StringKernelBase), "poly_kernel"
+    (PolynomialStringKernelBase); no tag (a converted pickle, an older .gnx) = "CovRSK", whatever lengths it carries"""
+    k = str(np.asarray(w["kernel"])) if "kernel" in w else "CovRSK"
+    if k not in SVC_TRAIN_KINDS:
+        raise ValueError(f"unknown SVC window kernel tag {k!r}")
+    return k
+
+
 def train_svc_base(data: GnxModelData, X, y, ctx=None, seeds=None, kernel="CovRSK", **kw) -> dict:
     """fit the SVC base of `data` in place (data.svc, base_kind "covrsk") -> info: the CovRSK string kernel, or kernel="rbf"
-    (SVMBase; gamma=0.001, C=100.0 unless given).  Each window keeps only its support
+    (SVMBase; gamma=0.001, C=100.0 unless given), kernel="string_kernel" (StringKernelBase: every length) or kernel="poly_kernel"
+    (PolynomialStringKernelBase; p=1.2 unless given); the windows of the last three carry the tag `kernel` and one seed per window
+    drawn from numpy's global generator when `seeds` is None.  Each window keeps only its support
     rows as `xfit` (support = arange(n_sv)): the full training window would put N x width bytes per window into the .gnx.  The
     sklearn-order support_ indices (rows of X) are info["support"]."""
     from .convert import string_kernel_lengths
     W = data.W
     rbf = kernel == "rbf"
     if seeds is None:
-        seeds = svc_seeds_unchained(W) if rbf else svc_seed_chain([data.window_width(w) for w in range(W)], np.random.randint(SVC_SEED_HIGH))
+        seeds = (svc_seeds_unchained(W) if kernel in SVC_UNCHAINED_KERNELS else
+                 svc_seed_chain([data.window_width(w) for w in range(W)], np.random.randint(SVC_SEED_HIGH)))
     X = np.ascontiguousarray(X, dtype=np.int8)
     res, info = train_svc_arrays(X, y, data.M, data.context, data.A, seeds, kernel=kernel, ctx=ctx, **kw)
-    tag = dict(kernel=np.array("rbf"), gamma=np.float64(kw.get("gamma", 0.001))) if rbf else None
+    from .convert import poly_run_values
+
+    def extras(width):   # what a window carries besides the fitted arrays: the kernel's tag and parameters
+        if rbf:
+            return dict(kernel=np.array("rbf"), gamma=np.float64(kw.get("gamma", 0.001)))
+        if kernel == "poly_kernel":
+            return dict(kernel=np.array("poly_kernel"), **poly_run_values(width, kw.get("p", 1.2)))
+        if kernel == "string_kernel":
+            return dict(kernel=np.array("string_kernel"), ms=string_kernel_lengths(width, kernel))
+        return dict(ms=string_kernel_lengths(width, kernel))
     svc, sup_raw = [], []
     for w in range(W):
         n = int(res["n_sv"][w])
@@ -371,7 +422,7 @@ def train_svc_base(data: GnxModelData, X, y, ctx=None, seeds=None, kernel="CovRS
         svc.append(dict(xfit=np.ascontiguousarray(X[sup][:, cols]), support=np.arange(n, dtype=np.int32),
                         dual_coef=np.ascontiguousarray(res["dual_coef"][w, :, :n]), intercept=res["intercept"][w].copy(),
                         prob_a=res["prob_a"][w].copy(), prob_b=res["prob_b"][w].copy(), n_support=res["n_support"][w].copy(),
-                        **(tag if rbf else dict(ms=string_kernel_lengths(len(cols), kernel)))))
+                        **extras(len(cols))))
         sup_raw.append(sup)
     data.base_kind, data.svc = "covrsk", svc
     info["support"] = sup_raw
@@ -757,7 +808,8 @@ def untrained_model(C, M, A, S, context, mode, seed=None, meta=None, base=None):
     coefficients), or with base="rf" (RFBase: the random forest) one single-leaf tree per window with value 1 / A and
     rf_train = dict(n_trees=20, max_depth=4) (the hyper-parameters HipBase.train fits with; kept in memory, not in the .gnx), or with base="xgb" one zero-valued stump per window and class, or with base="knn" one fit row of zeros with label 0
     per window, or with base="nb_bernoulli" / "nb_multinomial" / "nb_gaussian" zero Naive-Bayes tables and zero bias (every class
-    gets 1 / A), or with base="lda_svd" (LDABase: LinearDiscriminantAnalysis with its default svd solver; the bare name "lda" stays refused, as it
+    gets 1 / A), or with base="string_kernel" / "poly_string_kernel" (StringKernelBase / PolynomialStringKernelBase) placeholder SVC
+    windows tagged with the kernel and carrying its parameters, or with base="lda_svd" (LDABase: LinearDiscriminantAnalysis with its default svd solver; the bare name "lda" stays refused, as it
     was before the base existed) zero LDA coefficients and intercepts (every class gets 1 / A); the smoother's starting point:
     one placeholder tree, zero CRF weights, Conv1d's default initialisation.
     meta: optional dict with snp_pos, snp_ref, snp_alt, pop_order (the simulation's metadata)"""
@@ -772,10 +824,11 @@ def untrained_model(C, M, A, S, context, mode, seed=None, meta=None, base=None):
                   population_order=list(meta["pop_order"]))
     d = GnxModelData(C=C, M=M, A=A, S=S, context=context, **kw)
     nb_names = {"nb_" + k: k for k in NB_TRAIN_KINDS}
-    if base not in (None, "svm", "xgb", "rf", "knn", "lda_svd") and base not in nb_names:
+    if base not in (None, "svm", "xgb", "rf", "knn", "lda_svd", "string_kernel", "poly_string_kernel") and base not in nb_names:
         raise ValueError("base must be None (the mode's own base), \"svm\" (SVMBase: the RBF SVC), \"xgb\" (XGBBase: boosted trees), "
                          "\"rf\" (RFBase: the random forest), \"knn\" (KNNBase: 1-nearest neighbour), \"nb_bernoulli\" / \"nb_multinomial\" / \"nb_gaussian\" (the "
-                         "Naive-Bayes bases) or \"lda_svd\" (LDABase: linear discriminant analysis, svd solver), got %r" % (base,))
+                         "Naive-Bayes bases), \"lda_svd\" (LDABase: linear discriminant analysis, svd solver), \"string_kernel\" (StringKernelBase: the plain "
+                         "string-kernel SVC) or \"poly_string_kernel\" (PolynomialStringKernelBase: the polynomial string-kernel SVC), got %r" % (base,))
     if base == "lda_svd":   # LDABase (src/Base/models.py:83-94) in place of the mode's base; the smoother stays the mode's
         d.base_kind = "lda"
         d.lda_coef, d.lda_intercept = np.zeros((W, 1 if A == 2 else A, M + 2 * context + C - M * W)), np.zeros((W, 1 if A == 2 else A))
@@ -799,6 +852,19 @@ def untrained_model(C, M, A, S, context, mode, seed=None, meta=None, base=None):
             d.svc.append(dict(xfit=np.zeros((A, d.window_width(w)), np.int8), support=np.arange(A, dtype=np.int32),
                               dual_coef=np.zeros((A - 1, A)), intercept=np.zeros(P), prob_a=np.zeros(P), prob_b=np.zeros(P),
                               n_support=np.ones(A, np.int32), kernel=np.array("rbf"), gamma=np.float64(0.001)))
+    elif base in ("string_kernel", "poly_string_kernel"):
+        # StringKernelBase / PolynomialStringKernelBase (src/Base/models.py:161-193) in place of the mode's base: placeholder windows
+        # with the kernel's tag and parameters (every length / p = 1.2 and its run values); the smoother stays the mode's
+        from .convert import poly_run_values, string_kernel_lengths
+        P = A * (A - 1) // 2
+        d.base_kind, d.svc = "covrsk", []
+        for w in range(W):
+            width = d.window_width(w)
+            par = (dict(kernel=np.array("string_kernel"), ms=string_kernel_lengths(width, "string_kernel")) if base == "string_kernel" else
+                   dict(kernel=np.array("poly_kernel"), **poly_run_values(width)))
+            d.svc.append(dict(xfit=np.zeros((A, width), np.int8), support=np.arange(A, dtype=np.int32),
+                              dual_coef=np.zeros((A - 1, A)), intercept=np.zeros(P), prob_a=np.zeros(P), prob_b=np.zeros(P),
+                              n_support=np.ones(A, np.int32), **par))
     elif mode == "best":
         P = A * (A - 1) // 2
         d.base_kind, d.svc = "covrsk", []

@@ -16,6 +16,10 @@
  *   gnx_train_logistic    <- Base.train(X, y) of LogisticRegressionBase   src/Base/base.py:104-127, src/model.py:113,155
  *   gnx_train_svc         <- Base.train(X, y) of CovRSKBase (mode "best") src/Base/base.py:104-127, src/Base/models.py:195-215
  *   gnx_train_svc2        <- the same, and Base.train(X, y) of SVMBase (RBF)  src/Base/models.py:148-159
+ *                            (gnx_train_svc with GNX_SVC_KERNEL_ALL_LENGTHS: Base.train(X, y) of StringKernelBase, models.py:161-176)
+ *   gnx_train_svc_poly    <- Base.train(X, y) of PolynomialStringKernelBase  src/Base/models.py:178-193, string_kernel.py:40-61
+ *   gnx_svc_gram          <- the kernel callables themselves on a window's training rows: CovRSK_DP_triangular_numbers(Xw, Xw),
+ *                            string_kernel_DP_triangular_numbers(Xw, Xw), poly_kernel(Xw, Xw)   src/Base/string_kernel.py
  *   gnx_train_gbt_base    <- Base.train(X, y) of XGBBase (boosted trees)  src/Base/base.py:104-127, src/Base/models.py:24-35
  *   gnx_train_rforest     <- Base.train(X, y) of RFBase                   src/Base/models.py:54-66
  *   (no entry point)      <- Base.train(X, y) of KNNBase: a 1-NN fit stores its rows; the caller puts them into
@@ -487,7 +491,7 @@ int gnx_train_logistic_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ld
  *     sklearn's support_ (rows of X, class-major); dual_coef (W, A - 1, N): the first n_sv[w] columns of each row are _dual_coef_;
  *     intercept / prob_a / prob_b (W, P) = _intercept_ / _probA / _probB
  * Refused before anything is written: a window without a row of some class (GNX_EINVAL: the reference's fit fails there), a label
- * outside [0, A) (GNX_EINVAL), GNX_SVC_KERNEL_POLY (GNX_EUNSUPPORTED), a window whose largest kernel value g(width) is not below 2^24
+ * outside [0, A) (GNX_EINVAL), GNX_SVC_KERNEL_POLY (GNX_EUNSUPPORTED: its entry is gnx_train_svc_poly), a window whose largest kernel value g(width) is not below 2^24
  * (not exact in float) or wider than 16 384 SNPs (GNX_EINVAL), N whose Gram (N^2 floats) exceeds GNX_SVC_GRAM_BUDGET (GNX_EINVAL).
  * Windows are batched so that a batch's Gram matrices stay within GNX_SVC_GRAM_BUDGET.  The _dev form takes device X / y; it reads
  * y back to the host (the problems are laid out there).  Both are synchronous. */
@@ -524,6 +528,29 @@ int gnx_train_svc2_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, c
 /* the Platt fold permutation of an l-row class-pair problem fitted with libsvm seed `seed` (svm_binary_svc_probability: sklearn's
  * mt19937 + bounded_rand_int); host only, no context */
 int gnx_svc_fold_permutation(uint32_t seed, int32_t l, int32_t* perm);
+/* PolynomialStringKernelBase.train (src/Base/models.py:178-193: per window SVC(kernel=poly_kernel, probability=True).fit): arguments
+ * and outputs of gnx_train_svc2 with params->kernel_kind = GNX_SVC_KERNEL_POLY (anything else: GNX_EINVAL) and params->C the cost
+ * (the reference: sklearn's 1.0), plus the kernel's exponent poly_p (1.2 in the reference) and run_value, a HOST table (also for the
+ * _dev form) of n_run_value >= width + 1 doubles, np.arange(n) ** p as numpy computes it (width = the last, widest window).  A pair's
+ * kernel value is (long long)(np.sum(run_value[contigs]) / poly_p), contigs = the run of equal SNPs before every mismatch and the one
+ * the window ends with, summed in numpy's pairwise order (k_svc_gram_poly); the solver, the Platt folds and the sigmoid fit are
+ * gnx_train_svc2's.  Refused before anything is written, besides gnx_train_svc2's refusals: poly_p not finite or <= 0, run_value NULL,
+ * shorter than width + 1 or with a negative or non-finite entry, a window wider than 8 191 SNPs (the run values, 8 bytes each, take
+ * at most 64 KiB of LDS), kernel values (run_value[width] / poly_p) not below 2^24 (all GNX_EINVAL). */
+int gnx_train_svc_poly(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t ldx, const int32_t* y, int64_t C, int64_t M, int64_t ctx_snps,
+                       int32_t A, const gnx_svc_params* params, double poly_p, const double* run_value, int64_t n_run_value,
+                       const uint32_t* seeds, int32_t* n_sv, int32_t* n_support, int32_t* support, double* dual_coef, double* intercept,
+                       double* prob_a, double* prob_b, gnx_svc_train_info* info);
+int gnx_train_svc_poly_dev(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const int32_t* dy, int64_t C, int64_t M,
+                           int64_t ctx_snps, int32_t A, const gnx_svc_params* params, double poly_p, const double* run_value,
+                           int64_t n_run_value, const uint32_t* seeds, int32_t* n_sv, int32_t* n_support, int32_t* support,
+                           double* dual_coef, double* intercept, double* prob_a, double* prob_b, gnx_svc_train_info* info);
+/* The Gram matrices the string-kernel trainers solve on: gram (w1 - w0, N, N) float (HOST) = K(Xw, Xw) of windows [w0, w1), by the same
+ * pack and Gram kernels.  kernel_kind GNX_SVC_KERNEL_SUBSTRINGS, GNX_SVC_KERNEL_ALL_LENGTHS (poly_p / run_value / n_run_value unread)
+ * or GNX_SVC_KERNEL_POLY (as in gnx_train_svc_poly).  The trainers' bounds on the window width and the kernel values hold (GNX_EINVAL);
+ * so does GNX_SVC_GRAM_BUDGET for the whole range.  Synchronous. */
+int gnx_svc_gram(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t ldx, int64_t C, int64_t M, int64_t ctx_snps, int32_t kernel_kind,
+                 double poly_p, const double* run_value, int64_t n_run_value, int64_t w0, int64_t w1, float* gram);
 
 /* ---- training the tree smoother: Smoother.train of XGB_Smoother (src/Smooth/smooth.py:28-38, src/Smooth/models.py:14-20:
  *      XGBClassifier(n_estimators=100, max_depth=4, learning_rate=0.1, reg_lambda=1, objective='multi:softprob').fit(slide_window(B), y))
