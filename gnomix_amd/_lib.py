@@ -210,6 +210,7 @@ SYMBOLS = {
     "gnx_train_svc_poly_dev": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, C.POINTER(SvcParams), C.c_double, _VP, _I64] + [_VP] * 8 + [C.POINTER(SvcTrainInfo)]),
     "gnx_svc_gram": (C.c_int, [_VP, _VP, _I64, _I64, _I64, _I64, _I64, C.c_int32, C.c_double, _VP, _I64, _I64, _I64, _VP]),
     "gnx_fit_isotonic_f32": (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP]),
+    "gnx_fit_isotonic_f64": (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP]),
     "gnx_train_gbt": (C.c_int, [_VP, _VP, C.c_int32, _VP, _I64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(GbtParams)] + [_VP] * 8),
     "gnx_train_gbt_base": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, C.POINTER(GbtParams)] + [_VP] * 10),
     "gnx_train_gbt_base_dev": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I64, C.c_int32, C.POINTER(GbtParams)] + [_VP] * 10),

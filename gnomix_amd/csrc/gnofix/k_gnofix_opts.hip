@@ -28,10 +28,17 @@
 // After an accepted switch on [j1, j2): smoother rows that see only exchanged windows exchange their two labels and cache entries,
 // rows that see windows on both sides of j1 or j2 are re-evaluated at once, the others keep what they have.
 //
+// A calibrated model (Smoother.calibrate with a fitted Calibrator) runs this kernel for EVERY option set, the defaults included:
+// smoother.predict (gnofix.py:80,190) goes through Smoother.predict_proba and is argmax(Calibrator.transform(raw)), so every label of
+// a smoother row — the initial ones (Y0, from a labels-only k_calibrate launch) and the re-evaluated ones — is the calibrated label
+// of gnx_calibrate.h.  smoother.model.predict_proba (gnofix.py:157) is the raw model: the cache of largest probabilities, prob_comp
+// and the acceptance test stay on the raw float32 softmax.  The maps are read from global memory (a few KB, L2-resident).
+//
 // One 256-thread workgroup per individual; every decision is block-uniform (taken from LDS after a barrier).
 #include "../gnx_internal.h"
 #include "../gnx_rank.h"
 #include "../gnx_exp.h"
+#include "../gnx_calibrate.h"
 
 namespace {
 
@@ -88,6 +95,7 @@ struct GnofixOptsK {
   int32_t W, A, S, max_it, D, NT, GP;
   int32_t criterion, off, nls, prod, padding;
   float base_score, prior, one_minus_prior;
+  CalibMaps cal;          // cal.off != NULL: smoother rows carry calibrated labels
 };
 
 // ---- pre-pass: np.argmax(B, axis=-1) on the float64 base probabilities (first maximum; a NaN counts as the maximum) ----
@@ -198,8 +206,11 @@ __global__ __launch_bounds__(OT) void k_gnofix_opts(GnofixOptsK L) {
   // The smoother on rows desc[0 .. nrows) of the tile: rmax / rlab.  Row = haplotype h of the tile, shifted by `shift` positions,
   // reading the OTHER haplotype at tile positions [f1, f2).  RC rows at a time: lane = (tree, row) walks one tree on one row and
   // parks the leaf; one lane per (row, class) adds the class's leaves in tree order (float32: bit-identical to the sequential
-  // predictor); one lane per row takes xgboost's Softmax.  Called by all threads; ends with a barrier.
-  auto eval_rows = [&](int nrows) {
+  // predictor); one lane per row takes xgboost's Softmax.  want_lab: the rows' labels are used (re-evaluated smoother rows; the
+  // candidates of a window are compared by probability only) — a calibrated model then pays the maps for those rows alone.
+  // Called by all threads; ends with a barrier.
+  const bool calibrated = L.cal.off != nullptr;
+  auto eval_rows = [&](int nrows, bool want_lab) {
     for (int c0 = 0; c0 < nrows; c0 += RC) {
       const int nr = min(RC, nrows - c0);
       const uint32_t invN = nr > 1 ? 0xFFFFFFFFu / (uint32_t)nr + 1u : 0u;  // e / nr = umulhi(e, invN): nr * NT <= 12288 < 65536 (the 48 KB of leaves).
@@ -239,7 +250,9 @@ __global__ __launch_bounds__(OT) void k_gnofix_opts(GnofixOptsK L) {
         int best = 0;
         float bv = mr[0] / fs;
         for (int a = 1; a < A; ++a) { const float v = mr[a] / fs; if (v > bv) { bv = v; best = a; } }
-        rmax[c0 + r] = bv;
+        rmax[c0 + r] = bv;   // raw, calibrated or not
+        if (calibrated && want_lab)   // the float32 quotients are what the batched smoother stores and k_calibrate reads
+          best = gnx_calib_row(L.cal, A, false, [&](int c) -> double { return (double)(mr[c] / fs); }, [](int, double) {});
         rlab[c0 + r] = (uint8_t)best;
       }
       __syncthreads();
@@ -288,7 +301,7 @@ __global__ __launch_bounds__(OT) void k_gnofix_opts(GnofixOptsK L) {
         desc[2 * r + 1] = f1 | (f2 << 16);
       }
       __syncthreads();
-      eval_rows(2 * K);
+      eval_rows(2 * K, false);
       // np.argmax over the candidates, then gnofix.py:171 in float32
       float best = 0.f;
       int kb = 0;
@@ -355,7 +368,7 @@ __global__ __launch_bounds__(OT) void k_gnofix_opts(GnofixOptsK L) {
           }
         }
         __syncthreads();
-        eval_rows(2 * nwin);
+        eval_rows(2 * nwin, true);
         for (int r = tid; r < 2 * nwin; r += OT) {
           const int h = r >= nwin ? 1 : 0, rk = r - h * nwin;
           reinterpret_cast<uint8_t*>(Y)[2 * (gb + rk) + h] = rlab[r];
@@ -385,7 +398,9 @@ size_t gnx_gnofix_opts_lds_bytes(int W, int A, int S, int pitch, int n_trees, in
 }
 
 // after the initial smoother pass (Y0, proba0) and gnx_launch_gnofix_prep; am: [2 n_ind][W] bytes of scratch
-hipError_t gnx_launch_gnofix_opts(const GnofixLaunch& G, int64_t n_ind, const gnx_gnofix_opts& O, uint8_t* am, hipStream_t s) {
+// cal: the maps of a calibrated model (Y0 then holds calibrated labels, proba0 the RAW probabilities), or NULL
+hipError_t gnx_launch_gnofix_opts(const GnofixLaunch& G, int64_t n_ind, const gnx_gnofix_opts& O, uint8_t* am, const CalibMaps* cal,
+                                  hipStream_t s) {
   if (n_ind <= 0) return hipSuccess;
   int rc = 0;
   const size_t lds = gnx_gnofix_opts_lds_bytes(G.W, G.A, G.S, G.gf_pitch, G.d.n_trees, &rc);
@@ -397,7 +412,8 @@ hipError_t gnx_launch_gnofix_opts(const GnofixLaunch& G, int64_t n_ind, const gn
   const float prior = (float)O.prior_switch_prob, omp = (float)(1.0 - O.prior_switch_prob);
   const GnofixOptsK L{G.R, G.dif, G.par, G.gf, G.class_tree0, G.Y0, G.pmax0, am, G.Yout, G.n_switches, G.hist, G.W, G.A, G.S, G.max_it,
                       G.d.D, G.d.n_trees, G.gf_pitch, O.check_criterion, O.max_center_offset, O.non_lin_s,
-                      O.prob_comp == GNX_GNOFIX_PROB_PROD ? 1 : 0, O.padding ? 1 : 0, G.d.base_score, prior, omp};
+                      O.prob_comp == GNX_GNOFIX_PROB_PROD ? 1 : 0, O.padding ? 1 : 0, G.d.base_score, prior, omp,
+                      cal ? *cal : CalibMaps{nullptr, nullptr, nullptr, 0}};
   GNX_LDS_OPTIN(lds, k_gnofix_opts);
   hipLaunchKernelGGL(k_gnofix_opts, dim3((unsigned)n_ind), dim3(OT), lds, s, L);
   if ((e = hipGetLastError()) != hipSuccess) return e;

@@ -1045,16 +1045,28 @@ static bool gnofix_use_rk(const gnx_model* m) {
   return gnx_gnofix_lds_bytes(W, A, S, m->xgb.gf_pitch, gnx_gnofix_cap(m->xgb.gf_max_class, m->xgb.D, S, T), m->xgb.D, T, m->xgb.n_trees) <= (size_t)160 * 1024;
 }
 
+// smoother.predict inside gnofix() (gnofix.py:80,103,190,200) goes through Smoother.predict_proba: with the calibrate switch on and
+// a fitted calibrator its labels are calibrated ones.  Such a model runs k_gnofix_opts for every option set (its calibrated
+// labelling mode); k_gnofix and k_gnofix_f32 never see it.
+static bool gnofix_calibrated(const gnx_model* m) { return m->calibrate_on && m->calib_off; }
+
 static int gnofix_check(gnx_model* m, int64_t ldx, int64_t n_ind, int32_t max_it, bool ptrs_ok, bool* in_lds) {
   gnx_ctx* ctx = m->ctx;
   // src/model.py:194: only a smoother with .gnofix == True (XGB_Smoother) supports re-phasing
   if (m->info.smooth_kind != GNX_SMOOTH_XGB)
     return fail(ctx, GNX_ESTATE, "Type of Smoother does not currently support re-phasing");
   if (n_ind < 0 || ldx < m->info.C || max_it < 0 || (n_ind > 0 && !ptrs_ok)) return fail(ctx, GNX_EINVAL, "gnofix: bad arguments");
-  if (m->calibrate_on && m->calib_off)  // smoother.predict inside the loop would be calibrated (gnofix.py:80,190); the kernel's is not
-    return fail(ctx, GNX_EUNSUPPORTED, "gnofix with calibrate=True is not built: switch calibration off for re-phasing");
   const int W = (int)m->info.W, A = m->info.A, S = m->info.S;
   *in_lds = true;
+  if (gnofix_calibrated(m)) {  // the bounds of k_gnofix_opts, whatever the options
+    if (!gnofix_use_rk(m))
+      return fail(ctx, GNX_EUNSUPPORTED, "gnofix on a calibrated model needs the smoother's rank-quantised copy (k_gnofix_opts); this model runs the float32 Gnofix kernel");
+    if (S < 3) return fail(ctx, GNX_EUNSUPPORTED, "gnofix on a calibrated model needs S >= 3 (k_gnofix_opts)");
+    int rows = 0;
+    if (gnx_gnofix_opts_lds_bytes(W, A, S, m->xgb.gf_pitch, m->xgb.n_trees, &rows) > (size_t)160 * 1024 || rows < 1)
+      return fail(ctx, GNX_EUNSUPPORTED, "gnofix on a calibrated model: W / n_trees too large for the LDS working set of k_gnofix_opts");
+    return GNX_OK;
+  }
   if (gnofix_use_rk(m)) {
     if (gnx_gnofix_lds_bytes(W, A, S, m->xgb.gf_pitch, gnx_gnofix_cap(m->xgb.gf_max_class, m->xgb.D, S, gnofix_threads(m)), m->xgb.D, gnofix_threads(m), m->xgb.n_trees) > (size_t)160 * 1024)
       return fail(ctx, GNX_EUNSUPPORTED, "gnofix: W too large for the LDS working set (labels: 2 bytes per window)");
@@ -1074,6 +1086,7 @@ static int gnofix_ws_reserve(gnx_model* m, int64_t n, int32_t max_it, bool in_ld
   const int W = (int)m->info.W, A = m->info.A, S = m->info.S, pad = (S + 1) / 2;
   const size_t WA = (size_t)W * A, NWD = (size_t)(W + 31) / 32;
   int rc;
+  with_opts = with_opts || gnofix_calibrated(m);
   if ((rc = ws_reserve(ctx, ctx->ws_p32, (size_t)2 * n * WA * 4)) != GNX_OK) return rc;
   if ((rc = ws_reserve(ctx, ctx->ws_y0, (size_t)2 * n * W * 4)) != GNX_OK) return rc;
   auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
@@ -1098,6 +1111,7 @@ static int gnofix_ws_reserve(gnx_model* m, int64_t n, int32_t max_it, bool in_ld
 // them share a hardware queue (HIP maps streams onto 4 by default), and when those two are the copy-in and copy-out streams the
 // pipeline's H2D and D2H stop overlapping (measured: 13.3 k -> 9.2 k individuals/s through host pointers).
 // opts: NULL = the default loop (k_gnofix / k_gnofix_f32); else non-default options for k_gnofix_opts (validated by gnofix_opts_check)
+// A calibrated model (gnofix_calibrated; gnofix_check has verified k_gnofix_opts' bounds) runs k_gnofix_opts with either.
 static int gnofix_run_dev(gnx_model* m, int8_t* dX, int64_t ldx, const double* dB, int64_t n, int32_t max_it, int32_t* dY,
                           int32_t* dNs, bool in_lds, bool side_stream, bool packed = false, const gnx_gnofix_opts* opts = nullptr) {
   gnx_ctx* ctx = m->ctx;
@@ -1105,6 +1119,12 @@ static int gnofix_run_dev(gnx_model* m, int8_t* dX, int64_t ldx, const double* d
   const int W = (int)m->info.W, A = m->info.A, S = m->info.S;
   int rc;
   GnofixWs ws;
+  const bool cal = gnofix_calibrated(m);
+  gnx_gnofix_opts defaults{};  // gnofix()'s own defaults (gnofix.py:58): what opts == NULL means to k_gnofix_opts
+  defaults.struct_bytes = (int32_t)sizeof(gnx_gnofix_opts); defaults.max_it = max_it;
+  defaults.check_criterion = GNX_GNOFIX_CHECK_DISC_SMOOTH; defaults.prob_comp = GNX_GNOFIX_PROB_MAX;
+  defaults.padding = 1; defaults.prior_switch_prob = 0.5;
+  if (cal && !opts) opts = &defaults;
   if ((rc = gnofix_ws_reserve(m, n, max_it, in_lds, &ws, opts != nullptr)) != GNX_OK) return rc;
   int32_t* dY0 = (int32_t*)ctx->ws_y0.p;
   GnofixLaunch L{};
@@ -1135,12 +1155,26 @@ static int gnofix_run_dev(gnx_model* m, int8_t* dX, int64_t ldx, const double* d
     }
   }
   // initial labels = smoother.predict(B) for every haplotype at once (gnofix.py:80)
-  rc = gnx_smooth_predict_dev(m, dB, 1, 2 * n, (float*)ctx->ws_p32.p, nullptr, dY0);
+  if (!cal) rc = gnx_smooth_predict_dev(m, dB, 1, 2 * n, (float*)ctx->ws_p32.p, nullptr, dY0);
+  else {
+    // the loop compares RAW probabilities (smoother.model.predict_proba, gnofix.py:157) and carries CALIBRATED labels: the raw pass
+    // fills ws_p32 (-> pmax0), a labels-only k_calibrate launch turns those rows into Y0
+    rc = smooth_raw_dev(m, dB, 1, 2 * n, (float*)ctx->ws_p32.p, nullptr, nullptr);
+    if (rc == GNX_OK) {
+      CalibLaunch CL{};
+      CL.in = ctx->ws_p32.p; CL.in_is_f64 = 0; CL.R = 2 * n * (int64_t)W; CL.A = A;
+      CL.off = m->calib_off; CL.x = m->calib_x; CL.y = m->calib_y; CL.thr_f32 = m->calib_f32;
+      CL.labels = dY0;
+      ProfScope pc(ctx, GNX_K_CALIBRATE);
+      if (gnx_launch_calibrate(CL, ctx->stream) != hipSuccess) rc = fail(ctx, GNX_EHIP, "gnofix: the labels-only k_calibrate launch failed");
+    }
+  }
   if (rk && side_stream) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_aux[1], 0));  // (also on failure: the side stream is joined)
   if (rc != GNX_OK) return rc;
   ProfScope ps(ctx, GNX_K_GNOFIX);
   if (rk && opts) {
-    HIPCHK(ctx, gnx_launch_gnofix_opts(L, n, *opts, (uint8_t*)ctx->ws_misc.p + ws.am, ctx->stream));
+    const CalibMaps maps{m->calib_off, m->calib_x, m->calib_y, m->calib_f32 ? 1 : 0};
+    HIPCHK(ctx, gnx_launch_gnofix_opts(L, n, *opts, (uint8_t*)ctx->ws_misc.p + ws.am, cal ? &maps : nullptr, ctx->stream));
     return GNX_OK;
   }
   if (rk) {
@@ -1443,6 +1477,81 @@ int gnx_fit_isotonic_f32(const float* x, const float* y, int64_t n, float* x_thr
     for (size_t i = 0; i < m; ++i) {
       const bool keep = (i == 0 || i + 1 == m) ? true : (fy[i] != fy[i - 1] || fy[i] != fy[i + 1]);
       if (keep) { x_thr[k] = ux[i]; y_thr[k] = fy[i]; ++k; }
+    }
+    *n_thr = k;
+  } catch (...) {
+    return GNX_ENOMEM;
+  }
+  return GNX_OK;
+}
+
+// The same fit on float64 inputs (the CRF smoother's probabilities; Calibration.py:55 passes y as float64 one-hot columns):
+// np.lexsort((y, X)); _make_unique with eps = np.finfo(np.float64).resolution = 1e-15, sums and quotient in float64;
+// scipy.optimize.isotonic_regression's pool-adjacent-violators in ITS order of operations (a block is kept as (mean, weight); a
+// merge rebuilds the sum as weight * mean, looks ahead while the next value is <= the block's mean, then back while the previous
+// block's mean is >= it; ties pool); threshold pruning as above.  Every intermediate is a float64 and nothing is contracted.
+int gnx_fit_isotonic_f64(const double* x, const double* y, int64_t n, double* x_thr, double* y_thr, int64_t* n_thr) {
+  if (n <= 0 || !x || !y || !x_thr || !y_thr || !n_thr) return GNX_EINVAL;
+  try {
+    std::vector<int64_t> order((size_t)n);
+    for (int64_t i = 0; i < n; ++i) order[(size_t)i] = i;
+    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return x[a] < x[b] || (x[a] == x[b] && y[a] < y[b]); });
+    std::vector<double> ux, v, w;  // unique x, their mean y (then the blocks' means), their weights
+    const double eps = 1e-15;      // np.finfo(np.float64).resolution
+    double cx = x[order[0]], cy = 0.0, cw = 0.0;
+    for (int64_t j = 0; j < n; ++j) {
+      const double xv = x[order[(size_t)j]], yv = y[order[(size_t)j]];
+      if (xv - cx >= eps) {
+        ux.push_back(cx); w.push_back(cw); v.push_back(cy / cw);
+        cx = xv; cw = 1.0; cy = yv * 1.0;
+      } else {
+        cw += 1.0;
+        cy += yv * 1.0;
+      }
+    }
+    ux.push_back(cx); w.push_back(cw); v.push_back(cy / cw);
+    const int64_t m = (int64_t)ux.size();
+    // pava (scipy/optimize/_pava): v / w are overwritten block by block, r[b] = first index of block b
+    std::vector<int64_t> r((size_t)m + 1, -1);
+    r[0] = 0; r[1] = 1;
+    int64_t b = 0;
+    double xb_prev = v[0], wb_prev = w[0];
+    for (int64_t i = 1; i < m; ++i) {
+      ++b;
+      double xb = v[(size_t)i], wb = w[(size_t)i];
+      if (xb_prev >= xb) {
+        --b;
+        double sb = wb_prev * xb_prev + wb * xb;
+        wb += wb_prev;
+        xb = sb / wb;
+        while (i < m - 1 && xb >= v[(size_t)i + 1]) {
+          ++i;
+          sb += w[(size_t)i] * v[(size_t)i];
+          wb += w[(size_t)i];
+          xb = sb / wb;
+        }
+        while (b > 0 && v[(size_t)b - 1] >= xb) {
+          --b;
+          sb += w[(size_t)b] * v[(size_t)b];
+          wb += w[(size_t)b];
+          xb = sb / wb;
+        }
+      }
+      v[(size_t)b] = xb_prev = xb;
+      w[(size_t)b] = wb_prev = wb;
+      r[(size_t)b + 1] = i + 1;
+    }
+    int64_t f = m - 1;
+    for (int64_t k = b; k >= 0; --k) {
+      const int64_t t = r[(size_t)k];
+      const double vk = v[(size_t)k];
+      for (int64_t i = f; i >= t; --i) v[(size_t)i] = vk;
+      f = t - 1;
+    }
+    int64_t k = 0;
+    for (int64_t i = 0; i < m; ++i) {
+      const bool keep = (i == 0 || i + 1 == m) ? true : (v[(size_t)i] != v[(size_t)i - 1] || v[(size_t)i] != v[(size_t)i + 1]);
+      if (keep) { x_thr[k] = ux[(size_t)i]; y_thr[k] = v[(size_t)i]; ++k; }
     }
     *n_thr = k;
   } catch (...) {

@@ -1,0 +1,61 @@
+// gnx_calibrate.h — "the calibrated probabilities / the calibrated label of one row": the ONE definition that k_calibrate.hip
+// (Smoother.predict_proba with a calibrator) and k_gnofix_opts.hip (smoother.predict inside gnofix(), gnofix.py:80,190) share.
+// Reference: src/Smooth/Calibration.py:57-69 -> sklearn IsotonicRegression(out_of_bounds="clip").transform per class, then
+// Calibrator.normalize (:26-41), then np.argmax (src/Smooth/smooth.py:61).
+//   per class c: x clipped to [X_min, X_max]; linear interpolation on (X_thresholds_, y_thresholds_) exactly as
+//   scipy interp1d(kind="linear") evaluates it: k = clip(searchsorted(x_thr, x, side="left"), 1, n-1),
+//   slope = (y[k]-y[k-1])/(x[k]-x[k-1]),  y = slope*(x - x[k-1]) + y[k-1];
+//   normalize: 2 classes -> p0 = 1 - p1; else p /= sum(p); NaN -> 1/A; (1, 1+1e-5] -> 1;  the first maximum wins.
+// Arithmetic type follows sklearn/scipy: maps fitted on float32 probabilities (the xgb smoother) applied to float32
+// inputs are evaluated entirely in float32 (clip, slope, interpolant), anything else in float64 with the thresholds
+// widened; the result is then a float64 and normalised in float64.
+// No per-thread array: a run-time-indexed double p[32] lives in scratch (272 B per lane).  A class's value is evaluated twice
+// instead (once for the row sum, once for the output) — a few binary searches, and the same bits.
+#pragma once
+#include "gnx_internal.h"  // CalibMaps
+
+// one class's interpolated value of the raw probability x (in_is_f64: x is a float64 input, else a widened float32)
+__device__ __forceinline__ double gnx_calib_value(const CalibMaps& M, int c, double x, bool in_is_f64) {
+  const int o0 = M.off[c], n = M.off[c + 1] - o0;
+  const double* xs = M.x + o0;
+  const double* ys = M.y + o0;
+  if (n == 1) return ys[0];
+  x = fmin(fmax(x, xs[0]), xs[n - 1]);
+  int lo = 0, hi = n;  // searchsorted(side="left"): first index with xs[idx] >= x
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (xs[mid] < x) lo = mid + 1; else hi = mid;
+  }
+  const int k = lo < 1 ? 1 : (lo > n - 1 ? n - 1 : lo);
+  if (M.thr_f32 && !in_is_f64) {  // all operands are float32 values: same operations in float32
+    const float xf = (float)x, x0 = (float)xs[k - 1], x1 = (float)xs[k], y0 = (float)ys[k - 1], y1 = (float)ys[k];
+    const float slope = (y1 - y0) / (x1 - x0);
+    return (double)(slope * (xf - x0) + y0);
+  }
+  if (M.thr_f32) {                // float64 input, float32 maps: the slope is a float32 quantity
+    const float slope = ((float)ys[k] - (float)ys[k - 1]) / ((float)xs[k] - (float)xs[k - 1]);
+    return (double)slope * (x - xs[k - 1]) + ys[k - 1];
+  }
+  const double slope = (ys[k] - ys[k - 1]) / (xs[k] - xs[k - 1]);
+  return slope * (x - xs[k - 1]) + ys[k - 1];
+}
+
+// The calibrated row: raw(c) -> the row's raw probability of class c as a double (called up to twice per class, every class before
+// the first emit), emit(c, p) receives the calibrated probability of class c in class order.  Returns the calibrated label.
+template <class Raw, class Emit>
+__device__ __forceinline__ int gnx_calib_row(const CalibMaps& M, int A, bool in_is_f64, Raw raw, Emit emit) {
+  double sum = 0.0;
+  if (A != 2)
+    for (int c = 0; c < A; ++c) sum += gnx_calib_value(M, c, raw(c), in_is_f64);
+  const double p1 = (A == 2) ? gnx_calib_value(M, 1, raw(1), in_is_f64) : 0.0;
+  int best = 0;
+  double pbest = 0.0;
+  for (int c = 0; c < A; ++c) {
+    double pc = (A == 2) ? (c == 0 ? 1.0 - p1 : p1) : gnx_calib_value(M, c, raw(c), in_is_f64) / sum;
+    if (pc != pc) pc = 1.0 / A;
+    if (pc > 1.0 && pc <= 1.0 + 1e-5) pc = 1.0;
+    if (c == 0 || pc > pbest) { best = c; pbest = pc; }   // first maximum wins, as np.argmax
+    emit(c, pc);
+  }
+  return best;
+}

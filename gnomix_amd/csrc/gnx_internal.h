@@ -389,7 +389,13 @@ struct GnofixLaunch {
   int32_t gf_pitch, gf_cap;
 };
 
-// ---- calibrator (k_calibrate.hip) -----------------------------------------------------------------------
+// ---- calibrator (k_calibrate.hip; the row arithmetic both users share: gnx_calibrate.h) ------------------------
+struct CalibMaps {
+  const int32_t* off;    // device (A+1): class c owns thresholds [off[c], off[c+1]); NULL = no calibration
+  const double* x;       // device thresholds (float32 values widened when thr_f32)
+  const double* y;
+  int32_t thr_f32;       // the maps were fitted in float32
+};
 struct CalibLaunch {
   const void* in;        // (R, A) probabilities, float32 or float64
   int32_t in_is_f64;
@@ -597,7 +603,9 @@ int gnx_gnofix_cap(int max_class_trees, int D, int S, int threads);
 hipError_t gnx_launch_gnofix_pmax(const GnofixLaunch& L, int64_t n_ind, hipStream_t s);  // k_gnofix.hip: proba0 -> pmax0
 hipError_t gnx_launch_gnofix_swap(const GnofixLaunch& L, int64_t n_ind, hipStream_t s);  // k_gnofix.hip: the final parity applied to X
 // gnofix/k_gnofix_opts.hip: the loop with the reference's search options (am: [2 n_ind][W] bytes of scratch)
-hipError_t gnx_launch_gnofix_opts(const GnofixLaunch& L, int64_t n_ind, const gnx_gnofix_opts& O, uint8_t* am, hipStream_t s);
+// cal: NULL, or the maps of a calibrated model: smoother rows are then labelled as Smoother.predict labels them (gnx_calibrate.h)
+hipError_t gnx_launch_gnofix_opts(const GnofixLaunch& L, int64_t n_ind, const gnx_gnofix_opts& O, uint8_t* am, const CalibMaps* cal,
+                                  hipStream_t s);
 size_t gnx_gnofix_opts_lds_bytes(int W, int A, int S, int pitch, int n_trees, int* rows_side_by_side);
 hipError_t gnx_launch_gnofix_f32(const GnofixLaunch& L, int64_t n_ind, hipStream_t s);
 size_t gnx_gnofix_f32_lds_bytes(int W, int A, int S, int n_trees, int tree_bytes, bool bp_in_lds);

@@ -92,13 +92,10 @@ class HipSmoother:
 
     def train_calibrator(self, B, y, frac=0.05):
         """Smoother.train_calibrator (smooth.py:81-92): uncalibrated probabilities of a random `frac` of the haplotypes (numpy's
-        global generator, as the reference), one isotonic map per class (gnomix_amd.calibrate), device model re-loaded with them"""
+        global generator, as the reference), one isotonic map per class (gnomix_amd.calibrate), device model re-loaded with them.
+        The fit follows the dtype the smoother returns: float32 for the tree and the CNN smoother, float64 for the CRF smoother."""
         from .calibrate import fit_calibrator
         from .model import DeviceModel
-        if self.dev.data.smooth_kind != "xgb":
-            # Calibrator.fit on a float64 smoother (CRF) fits sklearn's isotonic maps on float64 inputs without the float32
-            # tie merging gnx_fit_isotonic_f32 reproduces: not built, and not silently approximated
-            raise NotImplementedError("train_calibrator is built for the tree smoother (float32 probabilities)")
         B = np.asarray(B)
         y = np.asarray(y)
         calibrate = self.calibrate

@@ -413,7 +413,12 @@ int gnx_calibrate_rows(gnx_model* model, const void* proba, int proba_is_f64, in
 /* Gnomix.phase: for each of n_ind individuals (haplotype rows 2i, 2i+1 of X and of B) run the
  * Gnofix loop with the reference's default arguments.  X (2*n_ind, ldx) int8 is re-phased IN
  * PLACE, B (2*n_ind, W, A) float64 is read only, Y (2*n_ind, W) receives Gnofix's labels and
- * n_switches (n_ind,) (may be NULL) the number of accepted switches. */
+ * n_switches (n_ind,) (may be NULL) the number of accepted switches.
+ * A calibrated model (gnx_model_set_calibrate(model, 1) with calib_* loaded) re-phases as the reference's gnofix() does with a
+ * calibrated Smoother: labels are argmax(Calibrator.transform(raw)) (smoother.predict, gnofix.py:80,190), candidates are compared
+ * by the RAW probabilities (smoother.model.predict_proba, gnofix.py:157).  Every gnx_gnofix* / gnx_phase_gt2* entry then runs
+ * k_gnofix_opts; GNX_EUNSUPPORTED (the message names the reason) for such a model without the rank-quantised smoother copy, with
+ * S < 3, or with a geometry beyond that kernel's LDS working set. */
 int gnx_gnofix(gnx_model* model, int8_t* X, int64_t ldx, const double* B, int64_t n_ind, int32_t max_it,
                int32_t* Y, int32_t* n_switches);
 int gnx_gnofix_dev(gnx_model* model, int8_t* dX, int64_t ldx, const double* dB, int64_t n_ind, int32_t max_it,
@@ -718,6 +723,10 @@ int gnx_train_crf(gnx_ctx* ctx, const void* B, int32_t b_is_f64, const int32_t* 
  * Host arithmetic (no context, no device): x, y (n,) float32 in any order -> thresholds x_thr / y_thr (caller-allocated, n each),
  * *n_thr of them; they go into gnx_model_desc.calib_x / calib_y (as float64) with calib_is_f32 = 1. */
 int gnx_fit_isotonic_f32(const float* x, const float* y, int64_t n, float* x_thr, float* y_thr, int64_t* n_thr);
+/* The same fit on float64 probabilities (the CRF smoother's; the CNN smoother's are float32 and use the entry above): ties are
+ * merged below 1e-15 (numpy's float64 resolution), every sum, mean and block mean is a float64 in scikit-learn's / scipy's order of
+ * operations; the thresholds go into calib_x / calib_y as they are, with calib_is_f32 = 0. */
+int gnx_fit_isotonic_f64(const double* x, const double* y, int64_t n, double* x_thr, double* y_thr, int64_t* n_thr);
 
 /* ---- the admixture simulator's training data: LAIDataset.simulate (src/laidataset.py:362-428) + admix (:119-176) write each
  *      simulated haplotype as founder slices; write_output (:180-201) stacks them; window_reshape / data_process
