@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/gnomix_hip.h"
+#include "gnx_rank_table.h"
 
 // ------------------------------------------------------------------------------------------------
 // context / model
@@ -174,10 +175,11 @@ struct SmoothXGBDev {
   // followed by 2^D float leaves.
   const uint8_t* rk_packed = nullptr;
   const float* rk_thr = nullptr;         // [rk_K] sorted distinct finite thresholds
-  const uint32_t* rk_lut = nullptr;      // [1024] first | (last << 16) candidate index per 1/1024-wide bucket
+  const GnxRankEntry* rk_lut = nullptr;  // [1 << rk_bits] 16-byte entries, bucket count chosen per model (gnx_rank_table.h)
   const int32_t* rk_group_tree0 = nullptr;
   const int32_t* rk_group_class = nullptr;
   int32_t rk_K = 0, rk_steps = 0, rk_stride = 0, rk_tree_bytes = 0, rk_n_groups = 0, rk_max_group = 0;
+  int32_t rk_bits = 0;                   // log2 of rk_lut's bucket count; rk_steps = bisections behind an entry (0: none needed)
   int32_t rk_rpl = 0;                    // 64-window segments per strip the node offsets were laid out for
   // lane = haplotype copy for k_smooth_xgb_h64 (same ranks, rk_thr / rk_lut): per tree 2^D nodes of 8 bytes {byte offset of the
   // feature's slot = (s * A + a) * 128, rank field} (heap slot 0 unused) followed by 2^D float leaves, padded to 16 bytes

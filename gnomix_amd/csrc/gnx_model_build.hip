@@ -571,18 +571,11 @@ static int build_xgb_rk(gnx_model* m, const gnx_model_desc* d, const std::vector
   if (U.size() > 65000 || (size_t)A * stride * 2 > 65535) return GNX_OK;  // does not fit 16 bits: float kernel only
   if (U.empty()) U.push_back(0.5f);
   const int K = (int)U.size();
-  // bucket b covers [b/1024, (b+1)/1024) (bucket 0 also everything below, bucket 1023 everything above):
-  // rank(p) lies in [#{U < lower edge}, #{U < upper edge}]
-  std::vector<uint32_t> lut(1024);
-  int steps = 0;
-  for (int b = 0; b < 1024; ++b) {
-    const int lo = b == 0 ? 0 : (int)(std::lower_bound(U.begin(), U.end(), (float)b / 1024.0f) - U.begin());
-    const int hi = b == 1023 ? K : (int)(std::lower_bound(U.begin(), U.end(), (float)(b + 1) / 1024.0f) - U.begin());
-    lut[(size_t)b] = (uint32_t)lo | ((uint32_t)hi << 16);
-    int st = 0;
-    while ((1 << st) < hi - lo + 1) ++st;
-    steps = std::max(steps, st);
-  }
+  // the lookup table of the ranks, sized to the thresholds (gnx_rank_table.h; GNX_RK_BITS: a bucket count of one's own, development)
+  GnxRankTable rt;
+  gnx_rank_table_build(U, std::getenv("GNX_RK_BITS") ? std::atoi(std::getenv("GNX_RK_BITS")) : 0, rt);
+  const std::vector<GnxRankEntry>& lut = rt.lut;
+  const int steps = rt.steps;
   const int tree_bytes = 8 << D;
   int group_bytes = 4096;  // per staging buffer; two of them per block
   if (const char* e = std::getenv("GNX_RK_GROUP_BYTES")) group_bytes = std::max(tree_bytes, std::min(8192, std::atoi(e)));
@@ -609,7 +602,7 @@ static int build_xgb_rk(gnx_model* m, const gnx_model_desc* d, const std::vector
   if ((rc = gnx_dev_upload(m, lut, &m->xgb.rk_lut)) != GNX_OK) return rc;
   if ((rc = gnx_dev_upload(m, group_tree0, &m->xgb.rk_group_tree0)) != GNX_OK) return rc;
   if ((rc = gnx_dev_upload(m, group_class, &m->xgb.rk_group_class)) != GNX_OK) return rc;
-  m->xgb.rk_K = K; m->xgb.rk_steps = steps; m->xgb.rk_stride = stride; m->xgb.rk_tree_bytes = tree_bytes;
+  m->xgb.rk_K = K; m->xgb.rk_bits = rt.bits; m->xgb.rk_steps = steps; m->xgb.rk_stride = stride; m->xgb.rk_tree_bytes = tree_bytes;
   m->xgb.rk_n_groups = (int32_t)group_class.size(); m->xgb.rk_max_group = G; m->xgb.rk_rpl = rpl;
   // measured (chr22, 10 000 haplotypes, MI355X): rk 1.83 ms; h64 2.22 ms + 0.23 ms of rank pre-pass — conflict-free, and slower
   // (DESIGN.md 4.2b): the rank kernel stays the default, h64 is what GNX_SMOOTH_IMPL=h64 selects

@@ -59,7 +59,7 @@ __device__ __forceinline__ bool neq(const snp16& a, const snp16& b) { return ((a
 
 // ---- pre-pass 1: base probabilities -> ranks (float32 cast first: Smooth/utils.py:20) ----
 __global__ __launch_bounds__(256) void k_gnofix_ranks(const double* __restrict__ B, int64_t n, const float* __restrict__ U,
-                                                      const uint32_t* __restrict__ lut, int K, int steps, uint16_t* __restrict__ R) {
+                                                      const GnxRankEntry* __restrict__ lut, int K, int bits, int steps, uint16_t* __restrict__ R) {
   constexpr int NV = 4;
   const int64_t e0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * NV;
   if (e0 >= n) return;
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void k_gnofix_ranks(const double* __restrict__
   uint32_t r[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) p[i] = (float)B[min(e0 + i, n - 1)];
-  ranks<NV>(U, lut, K, steps, p, r);
+  ranks<NV>(U, lut, K, bits, steps, p, r);
 #pragma unroll
   for (int i = 0; i < NV; ++i)
     if (e0 + i < n) R[e0 + i] = (uint16_t)r[i];
@@ -1054,7 +1054,7 @@ hipError_t gnx_launch_gnofix_prep(const GnofixLaunch& L, int64_t n_ind, hipStrea
   const int NWD = (L.W + 31) / 32;
   const int64_t n = 2 * n_ind * (int64_t)L.W * L.A;
   hipLaunchKernelGGL(k_gnofix_ranks, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, s, L.B, n, L.d.rk_thr, L.d.rk_lut, L.d.rk_K,
-                     L.d.rk_steps, const_cast<uint16_t*>(L.R));
+                     L.d.rk_bits, L.d.rk_steps, const_cast<uint16_t*>(L.R));
   for (int64_t i0 = 0; i0 < n_ind; i0 += 65535) {  // the individual is grid.y: at most 65535 per launch
     const unsigned ny = (unsigned)std::min<int64_t>(65535, n_ind - i0);
     uint32_t* dif = const_cast<uint32_t*>(L.dif) + (size_t)i0 * NWD;

@@ -127,6 +127,9 @@ __global__ __launch_bounds__(THREADS, 8) void k_smooth_xgb_h32(SmoothXGBLaunch L
   // a wave takes 16 haplotypes x 4 consecutive (slot, class) elements at a time: 16-byte runs of B on the way in, and on the way
   // out the 8 haplotypes of a half-wave spread over 8 banks (4 rows each: the transposition's conflicts, 4-way instead of 32-way).
   // A thread keeps its haplotype; its elements are 32 apart, so (slot, class) advance by a fixed step: no division per element
+  // Only a haplotype's first and last window block touch the reflection; a block whose slots all lie inside the chromosome reads
+  // its strip as ONE run of P * A elements per haplotype (element rr of the strip is element rr of the run): no slide_src, no
+  // clamps of the slot, no index arithmetic per element.  blockIdx.x decides, so the branch is uniform.
   {
     constexpr int NV = 4;
     const int per_h = P * A;
@@ -135,24 +138,39 @@ __global__ __launch_bounds__(THREADS, 8) void k_smooth_xgb_h32(SmoothXGBLaunch L
     const int dq = 32 / A, da = 32 - dq * A;
     int rr = (wave >> 1) * 4 + (lane & 3);
     int q = rr / A, a = rr - q * A;
+    const bool interior = w0 >= pad && w0 + P <= pad + W;
+    const size_t run0 = (row + (size_t)(interior ? w0 - pad : 0)) * A;
     for (; rr < per_h; rr += NV * 32) {
       float p[NV];
       uint32_t r[NV];
       int dst[NV];
       bool ok[NV];
+      if (interior) {
 #pragma unroll
-      for (int i = 0; i < NV; ++i) {
-        ok[i] = rr + i * 32 < per_h;
-        const int qc = ok[i] ? q : P - 1, ac = ok[i] ? a : A - 1;  // clamped: loads stay unconditional
-        const int j = min(w0 + qc, W + 2 * pad - 1);
-        const size_t idx = (row + slide_src(j, W, pad)) * A + ac;
-        p[i] = L.b_is_f64 ? (float)reinterpret_cast<const double*>(L.B)[idx] : reinterpret_cast<const float*>(L.B)[idx];
-        dst[i] = ((qc >> 1) * A + ac) * 128 + hl * 4 + (qc & 1) * 2;
-        a += da;
-        q += dq;
-        if (a >= A) { a -= A; ++q; }
+        for (int i = 0; i < NV; ++i) {
+          ok[i] = rr + i * 32 < per_h;
+          const size_t idx = run0 + (size_t)min(rr + i * 32, per_h - 1);  // clamped: loads stay unconditional
+          p[i] = L.b_is_f64 ? (float)reinterpret_cast<const double*>(L.B)[idx] : reinterpret_cast<const float*>(L.B)[idx];
+          dst[i] = ((q >> 1) * A + a) * 128 + hl * 4 + (q & 1) * 2;  // never stored when !ok
+          a += da;
+          q += dq;
+          if (a >= A) { a -= A; ++q; }
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+          ok[i] = rr + i * 32 < per_h;
+          const int qc = ok[i] ? q : P - 1, ac = ok[i] ? a : A - 1;  // clamped: loads stay unconditional
+          const int j = min(w0 + qc, W + 2 * pad - 1);
+          const size_t idx = (row + slide_src(j, W, pad)) * A + ac;
+          p[i] = L.b_is_f64 ? (float)reinterpret_cast<const double*>(L.B)[idx] : reinterpret_cast<const float*>(L.B)[idx];
+          dst[i] = ((qc >> 1) * A + ac) * 128 + hl * 4 + (qc & 1) * 2;
+          a += da;
+          q += dq;
+          if (a >= A) { a -= A; ++q; }
+        }
       }
-      ranks<NV>(L.d.rk_thr, L.d.rk_lut, L.d.rk_K, L.d.rk_steps, p, r);
+      ranks<NV>(L.d.rk_thr, L.d.rk_lut, L.d.rk_K, L.d.rk_bits, L.d.rk_steps, p, r);
 #pragma unroll
       for (int i = 0; i < NV; ++i)
         if (ok[i]) *reinterpret_cast<uint16_t*>(strip + dst[i]) = (uint16_t)r[i];

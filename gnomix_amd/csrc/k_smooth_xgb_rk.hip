@@ -390,7 +390,7 @@ __global__ __launch_bounds__(NWAVE * 64) void k_smooth_xgb_rk(SmoothXGBLaunch L)
         p[i] = L.b_is_f64 ? (float)reinterpret_cast<const double*>(L.B)[idx] : reinterpret_cast<const float*>(L.B)[idx];
         dst[i] = (hl * A + a) * stride + q;
       }
-      ranks<NV>(L.d.rk_thr, L.d.rk_lut, L.d.rk_K, L.d.rk_steps, p, r);
+      ranks<NV>(L.d.rk_thr, L.d.rk_lut, L.d.rk_K, L.d.rk_bits, L.d.rk_steps, p, r);
 #pragma unroll
       for (int i = 0; i < NV; ++i)
         if (e0 + i * THREADS < total) reinterpret_cast<uint16_t*>(strip)[dst[i]] = (uint16_t)r[i];

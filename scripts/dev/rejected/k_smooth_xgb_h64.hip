@@ -25,50 +25,14 @@
 #include <cstdlib>
 
 #include "gnx_internal.h"
+#include "gnx_rank.h"
 
 namespace {
 
 constexpr int HB = 64;       // haplotypes per block = lanes
 constexpr int RW = 3;        // windows per lane
 
-__device__ __forceinline__ int slide_src(int j, int W, int pad) {  // reflect padding of slide_window (src/Smooth/utils.py:14-17)
-  if (j < pad) return pad - 1 - j;
-  if (j < pad + W) return j - pad;
-  return W - 1 - (j - pad - W);
-}
-
-// r = #{U[k] <= p} for NV values side by side (the rank kernel's search); NaN -> 0xFFFF ("never less than a threshold")
-template <int NV>
-__device__ __forceinline__ void ranks(const float* __restrict__ U, const uint32_t* __restrict__ lut, int K, int steps, const float* p,
-                                      uint32_t* r) {
-  int lo[NV], hi[NV];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const float sc = p[i] * 1024.0f;
-    const int b = (int)fminf(fmaxf(sc, 0.0f), 1023.0f);
-    const uint32_t e = lut[b];
-    lo[i] = (int)(e & 0xffffu);
-    hi[i] = (int)(e >> 16);
-  }
-  for (int s = 0; s < steps; ++s) {
-    float u[NV];
-    int mid[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      mid[i] = (lo[i] + hi[i]) >> 1;
-      u[i] = U[min(mid[i], K - 1)];
-    }
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const bool open = lo[i] < hi[i];
-      const bool up = open && (u[i] <= p[i]);
-      hi[i] = (open && !up) ? mid[i] : hi[i];
-      lo[i] = up ? mid[i] + 1 : lo[i];
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < NV; ++i) r[i] = (p[i] != p[i]) ? 0xFFFFu : (uint32_t)lo[i];
-}
+// slide_src and ranks<NV> (r = #{U[k] <= p}, NaN -> 0xFFFF): gnx_rank.h, the rank kernel's own
 
 // byte offset of haplotype h inside a 128-byte slot
 __device__ __forceinline__ int hap_off(int h) { return (h & 31) * 4 + (h >> 5) * 2; }
@@ -100,7 +64,7 @@ __global__ __launch_bounds__(256) void k_smooth_ranks(SmoothXGBLaunch L, uint16_
       p[i] = L.b_is_f64 ? (float)reinterpret_cast<const double*>(L.B)[idx] : reinterpret_cast<const float*>(L.B)[idx];
       dst[i] = q * 128 + ((((h & 31) + q) & 31) << 2) + (h >> 5) * 2;
     }
-    ranks<NV>(L.d.rk_thr, L.d.rk_lut, L.d.rk_K, L.d.rk_steps, p, r);
+    ranks<NV>(L.d.rk_thr, L.d.rk_lut, L.d.rk_K, L.d.rk_bits, L.d.rk_steps, p, r);
 #pragma unroll
     for (int i = 0; i < NV; ++i)
       if (e0 + i * 256 < total) *reinterpret_cast<uint16_t*>(lds + dst[i]) = (uint16_t)r[i];
