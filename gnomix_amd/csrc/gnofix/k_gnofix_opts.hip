@@ -252,7 +252,7 @@ __global__ __launch_bounds__(OT) void k_gnofix_opts(GnofixOptsK L) {
         for (int a = 1; a < A; ++a) { const float v = mr[a] / fs; if (v > bv) { bv = v; best = a; } }
         rmax[c0 + r] = bv;   // raw, calibrated or not
         if (calibrated && want_lab)   // the float32 quotients are what the batched smoother stores and k_calibrate reads
-          best = gnx_calib_row(L.cal, A, false, [&](int c) -> double { return (double)(mr[c] / fs); }, [](int, double) {});
+          best = gnx_calib_row(L.cal, A, [&](int c) -> double { return (double)(mr[c] / fs); }, [](int, double) {});
         rlab[c0 + r] = (uint8_t)best;
       }
       __syncthreads();

@@ -15,7 +15,7 @@ __global__ __launch_bounds__(256) void k_calibrate(CalibLaunch L) {
   // (out64 may alias `in`: gnx_calib_row has read every input of the row for the sum before the first emit, and re-reads class
   //  c's own value before emit(c) overwrites it)
   const int best = gnx_calib_row(
-      M, A, L.in_is_f64 != 0,
+      M, A,
       [&](int c) -> double {
         return L.in_is_f64 ? reinterpret_cast<const double*>(L.in)[r * A + c] : (double)reinterpret_cast<const float*>(L.in)[r * A + c];
       },

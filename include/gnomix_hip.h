@@ -247,8 +247,10 @@ typedef struct gnx_model_desc {
   const int32_t* calib_off;  /* (A+1,) */
   const double* calib_x;
   const double* calib_y;
-  int32_t calib_is_f32;      /* the isotonic maps were fitted on float32 probabilities (the xgb smoother's output): sklearn then
-                                interpolates in float32, and so does the kernel for float32 inputs */
+  int32_t calib_is_f32;      /* the isotonic maps were fitted on float32 probabilities (the xgb and CNN smoothers' output): sklearn then
+                                casts its input to float32 and interpolates in float32, and so does the kernel, narrowing float64
+                                inputs first; maps fitted in float64 are evaluated in float64 by np.interp's rules (float32 inputs
+                                widened, a value exactly on a threshold returns that threshold's y) */
   int32_t reserved3;
 
   /* GNX_BASE_FOREST: one gradient-boosted tree ensemble per window (XGBBase, src/Base/models.py:24-35:
