@@ -227,6 +227,8 @@ SYMBOLS = {
     "gnx_train_gbt_dev": (C.c_int, [_VP, _VP, C.c_int32, _VP, _I64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(GbtParams)] + [_VP] * 8),
     "gnx_simulate_admix_dev": (C.c_int, [_VP, _VP, _I64, _I64, _I64, _I64, _VP, _VP, _VP, _VP, C.c_int32, _I64, _VP, _I64, _VP, _VP]),
     "gnx_simulate_admix": (C.c_int, [_VP, _VP, _I64, _I64, _I64, _I64, _VP, _VP, _VP, _VP, C.c_int32, _I64, _VP, _I64, _VP, _VP]),
+    "gnx_confusion_dev": (C.c_int, [_VP, _VP, _VP, _I, _I64, C.c_int32, _VP, _I64, C.POINTER(_I64)]),
+    "gnx_confusion": (C.c_int, [_VP, _VP, _VP, _I, _I64, C.c_int32, _VP, _I64, C.POINTER(_I64)]),
     # include/gnomix_io.h: the file side
     "gnx_io_last_error": (C.c_char_p, []),
     "gnx_vcf_read": (C.c_int, [_VP, C.c_char_p, C.c_char_p, _I, C.POINTER(_VP)]),
@@ -305,6 +307,9 @@ def load():
     return lib
 
 
+OWN_STREAM = "own"   # Context.bound_stream while the context works on the non-blocking stream it created itself
+
+
 class Context:
     """One gnx_ctx (one per device / per process under torch.distributed)."""
 
@@ -315,6 +320,7 @@ class Context:
         self.h = h
         self.device = int(device)
         self._models = weakref.WeakSet()
+        self.bound_stream = OWN_STREAM   # what set_stream last bound (a hipStream_t as an int, None = HIP's null stream)
         _live_contexts.add(self)
         if rc != GNX_OK:
             msg = self.lib.gnx_last_error(h).decode() if h else "gnx_init failed"
@@ -329,9 +335,11 @@ class Context:
 
     def set_stream(self, stream_ptr):
         self.check(self.lib.gnx_set_stream(self.h, C.c_void_p(stream_ptr)))
+        self.bound_stream = stream_ptr
 
     def reset_stream(self):
         self.check(self.lib.gnx_reset_stream(self.h))
+        self.bound_stream = OWN_STREAM
 
     def synchronize(self):
         self.check(self.lib.gnx_synchronize(self.h))

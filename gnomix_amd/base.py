@@ -44,7 +44,14 @@ class HipBase:
         a loaded .gnx) has no hyper-parameters and is refused."""
         from .train import train_logistic_base, train_svc_base, svc_seed_chain, svc_rng_after_kernel, svc_window_kernel, SVC_SEED_HIGH
         from .model import DeviceModel, svc_window_is_rbf
+        from . import resident
         d = self.dev.data
+        if resident.all_on_device([X, y], "HipBase.train: (X, y)") and d.base_kind not in (None, "logistic"):
+            # CUDA tensors: the logistic base fits them in place (gnx_train_logistic_dev); every other base takes the host path
+            import warnings
+            warnings.warn("HipBase.train: the %s base has no device-resident training path; X and y are copied to the host once and "
+                          "the host-array path runs" % d.base_kind, RuntimeWarning, stacklevel=2)
+            X, y = resident.to_host(X), resident.to_host(y)
         if d.base_kind == "rforest" and not getattr(d, "rf_train", None):
             # a converted pickle, a synthetic model or a loaded .gnx carries no hyper-parameters to fit with
             raise NotImplementedError("on-device training is not built for the random-forest base (RFBase: scikit-learn's bootstrap "
@@ -94,7 +101,14 @@ class HipBase:
 
     def evaluate(self, X=None, y=None, B=None):
         """(accuracy %, balanced accuracy %) rounded to two decimals, from SNPs or from base probabilities (base.py:214-228)"""
-        from .metrics import accuracy_pair
+        from .metrics import accuracy_pair, accuracy_pair_from_counts
+        from . import resident
+        if resident.all_on_device([X, y, B], "HipBase.evaluate: (X, y, B)"):
+            # device-resident: the kernel takes the argmax of the probabilities itself and only the A x A counts come back
+            if X is None and B is None:
+                raise ValueError("Need either SNP input or estimated probabilities to evaluate.")
+            B = self.predict_proba(X) if X is not None else B
+            return accuracy_pair_from_counts(resident.confusion_counts(self.dev.ctx, y, B, self.A))
         if X is not None:
             y_pred = self.predict(X)
         elif B is not None:
@@ -104,9 +118,15 @@ class HipBase:
         return accuracy_pair(y, y_pred)
 
     def predict_proba(self, X):
-        """X (N, C) int8-like -> B (N, W, A) float64, as Base.predict_proba (base.py:129-180)."""
+        """X (N, C) int8-like -> B (N, W, A) float64, as Base.predict_proba (base.py:129-180).  A CUDA int8 tensor (rows contiguous,
+        any row stride) gives a CUDA float64 tensor and nothing crosses the host link."""
+        from . import resident
         t = time()
-        _, B = self.dev.base_predict(X, want_f32=False, want_f64=True)
+        if resident.is_cuda(X):
+            with resident.torch_stream(self.dev.ctx):
+                B = self.dev.base_predict_device(resident.check_x(X, self.C, self.dev.ctx.device), f64=True)
+        else:
+            _, B = self.dev.base_predict(X, want_f32=False, want_f64=True)
         self.time["inference"] = time() - t
         return B
 
@@ -116,4 +136,5 @@ class HipBase:
         return b32
 
     def predict(self, X):
-        return np.argmax(self.predict_proba(X), axis=-1)  # base.py:214-216
+        B = self.predict_proba(X)
+        return B.argmax(dim=-1) if hasattr(B, "is_cuda") else np.argmax(B, axis=-1)  # base.py:214-216 (both: first maximum)

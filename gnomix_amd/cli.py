@@ -232,10 +232,10 @@ def _since_process_start():
 def main(argv=None):
     argv = list(sys.argv if argv is None else argv)
     t_startup = _since_process_start() if os.environ.get("GNX_CLI_TIMING") else None
+    if len(argv) in (8, 9):
+        return train_main(argv)   # (decides about torch itself: the device-resident training path hands it tensors)
     if "torch" not in sys.modules:
         os.environ.setdefault("GNX_NO_TORCH", "1")   # the command line needs no torch: do not pay for its import
-    if len(argv) in (8, 9):
-        return train_main(argv)
     if len(argv) != 6:
         if len(argv) > 1:
             print("Error: Incorrect number of arguments.")
@@ -319,6 +319,22 @@ def training_setup(argv):
     return base_args, config, None
 
 
+def train_resident(config, environ=None):
+    """whether training mode simulates into HBM and trains from there (SimPlan.materialise_dev + the CUDA-tensor form of
+    HipGnomix.train): mode "default" (the logistic base with the tree smoother: the pair that trains without leaving the device),
+    data that are simulated now (not read from simulation.path) and NOT kept (simulation.rm_data: generated data that must be
+    written to <output>/generated_data are host arrays anyway), torch importable, and neither GNX_TRAIN_RESIDENT=0 nor
+    GNX_NO_TORCH set"""
+    environ = os.environ if environ is None else environ
+    sim, mode = config["simulation"], config["model"].get("inference") or "default"
+    if environ.get("GNX_TRAIN_RESIDENT", "1") == "0" or environ.get("GNX_NO_TORCH"):
+        return False
+    if mode != "default" or not sim.get("rm_data") or (sim.get("run") is False and sim.get("path") is not None):
+        return False
+    import importlib.util
+    return importlib.util.find_spec("torch") is not None
+
+
 def _initial_model(C, M, A, S, context, mode, seed, meta):
     """an untrained model of the mode's kinds (gnomix_amd.train.untrained_model)"""
     from .train import untrained_model
@@ -341,6 +357,11 @@ def train_main(argv):
         print("Error: " + err)
         return 2
     from time import perf_counter as clock
+    resident = train_resident(config)
+    if resident:
+        import torch  # noqa: F401  (before the library is loaded: both then share one HIP runtime, gnomix_amd/_lib.py)
+    elif "torch" not in sys.modules:
+        os.environ.setdefault("GNX_NO_TORCH", "1")   # the host-array path needs no torch: do not pay for its import
     from . import simulate as sim_mod
     from . import _lib
     from .gnomix import HipGnomix
@@ -375,8 +396,11 @@ def train_main(argv):
         t0 = clock()
         ctx = _lib.default_context(0)
         keep = not sim.get("rm_data")
-        (data, anc) = plan.materialise(ctx, M=M, want_anc=True) if keep else (plan.materialise(ctx, M=M), None)
-        T["simulate"] = clock() - t0
+        if resident:   # (implies not keep) the splits are built in HBM and stay there: HipGnomix.train reads them in place
+            data, anc = plan.materialise_dev(ctx, M=M), None
+        else:
+            (data, anc) = plan.materialise(ctx, M=M, want_anc=True) if keep else (plan.materialise(ctx, M=M), None)
+        T["simulate_dev" if resident else "simulate"] = clock() - t0
         if keep:
             t0 = clock()
             X_all = np.concatenate([d[0] for d in data if d[0] is not None])

@@ -7,6 +7,7 @@ import sys
 
 import numpy as np
 
+from . import resident
 from .base import HipBase
 from .model import DeviceModel, GnxModelData
 from .smooth import HipSmoother
@@ -71,6 +72,7 @@ class HipGnomix:
         split's own haplotypes and the smoother on labels predicted from base probabilities: for "train" those are two different
         sets (base: train1; smoother: train2, whose probabilities `train` already holds), for "val" one.  Keys as the reference
         stores them: <base|smooth>_<split>_acc[_bal] in `accuracies`, the split's name in `Confusion_Matrices`."""
+        from .metrics import accuracy_pair_from_counts, confusion_from_counts
         acc, cms = {}, {}
         for name, parts in splits.items():
             if parts is None:
@@ -80,18 +82,77 @@ class HipGnomix:
             labels = self.smooth.predict(B)
             B_s, y_s = smoother_part if smoother_part is not None else (B, y)
             labels_s = labels if smoother_part is None else self.smooth.predict(B_s)
+            if resident.is_cuda(X):
+                # the split was predicted in HBM: three passes of gnx_confusion_dev, 3 A^2 integers to the host, the same formulas
+                import torch
+                ctx = self.dev.ctx
+                counts = resident.confusion_counts(ctx, y, labels.to(torch.int32), self.A)
+                acc["base_%s_acc" % name], acc["base_%s_acc_bal" % name] = accuracy_pair_from_counts(resident.confusion_counts(ctx, y, B, self.A))
+                acc["smooth_%s_acc" % name], acc["smooth_%s_acc_bal" % name] = accuracy_pair_from_counts(
+                    counts if smoother_part is None else resident.confusion_counts(ctx, y_s, labels_s.to(torch.int32), self.A))
+                cms[name] = confusion_from_counts(counts)
+                continue
             acc["base_%s_acc" % name], acc["base_%s_acc_bal" % name] = self.base.evaluate(X=None, y=y, B=B)
             acc["smooth_%s_acc" % name], acc["smooth_%s_acc_bal" % name] = self.smooth.evaluate(B=None, y=y_s, y_pred=labels_s)
             cms[name] = self.conf_matrix(y=y, y_pred=labels)
         return acc, cms
 
+    def _resident_mode(self):
+        """the reference's mode name of this model's base / smoother pair, for messages"""
+        d = self.dev.data
+        return {("logistic", "xgb"): "default", ("logistic", "crf"): "fast", ("logistic", "cnn"): "large",
+                ("covrsk", "xgb"): "best"}.get((d.base_kind, d.smooth_kind), "%s base, %s smoother" % (d.base_kind, d.smooth_kind))
+
+    def _train_resident(self, data, retrain_base, evaluate, **smoother_kw):
+        """train() on CUDA tensors, logistic base and tree smoother: the reference's steps in the reference's order with X, the base
+        probabilities and the labels in HBM throughout.  The host receives the fitted arrays, the calibrator's 5 % sample and the
+        A x A counts of the scored splits."""
+        import torch
+        (X_t1, y_t1), (X_t2, y_t2), (X_v, y_v) = data
+        with resident.torch_stream(self.dev.ctx):
+            self.train_base(X_t1, y_t1)
+            B_t2 = self.base.predict_proba(X_t2)
+            self.train_smoother(B_t2, y_t2, **smoother_kw)
+            if self.calibrate:   # src/model.py:119-124
+                self.smooth.train_calibrator(self.base.predict_proba(X_t1), y_t1)
+                self.dev = self.smooth.dev
+                self.base.dev = self.dev
+            if evaluate:
+                self.accuracies, self.Confusion_Matrices = self._score_splits(
+                    {"train": ((X_t1, y_t1), (B_t2, y_t2)), "val": None if X_v is None else ((X_v, y_v), None)})
+            del B_t2
+            if retrain_base:
+                parts = [(X_t1, y_t1), (X_t2, y_t2)] + ([(X_v, y_v)] if X_v is not None else [])
+                X_all = resident.adjacent_rows([p[0] for p in parts])
+                y_all = resident.adjacent_rows([p[1] for p in parts])
+                if X_all is None:   # not one allocation's consecutive rows: concatenated in HBM
+                    X_all = torch.cat([p[0] for p in parts])
+                if y_all is None:
+                    y_all = torch.cat([p[1] for p in parts])
+                self.train_base(X_all, y_all)
+        return self
+
     def train(self, data, retrain_base=True, evaluate=True, verbose=False, **smoother_kw):
         """Gnomix.train (src/model.py:104-167) on the device: base on train1, smoother on the base's probabilities of train2,
         the reference's accuracies / confusion matrices, base again on all the data.
-        data = ((X_t1, y_t1), (X_t2, y_t2), (X_v, y_v)) with X_v possibly None."""
+        data = ((X_t1, y_t1), (X_t2, y_t2), (X_v, y_v)) with X_v possibly None.  Numpy arrays are staged through the device call
+        by call; CUDA tensors (X torch.int8 with contiguous rows and any row stride, y torch.int32, as SimPlan.materialise_dev
+        returns them) stay in HBM for the logistic base with the tree smoother, and are copied to the host once, with a warning,
+        for every other pair.  A mixture of the two is a TypeError."""
         from time import time
         t0 = time()
         (X_t1, y_t1), (X_t2, y_t2), (X_v, y_v) = data
+        if resident.all_on_device([X_t1, y_t1, X_t2, y_t2, X_v, y_v], "HipGnomix.train: data"):
+            d = self.dev.data
+            if d.base_kind in (None, "logistic") and d.smooth_kind in (None, "xgb"):
+                self._train_resident(data, retrain_base, evaluate, **smoother_kw)
+                self.time["training"] = round(time() - t0, 2)
+                return self
+            import warnings
+            warnings.warn('HipGnomix.train: mode "%s" has no device-resident training path (the logistic base with the tree smoother, '
+                          'mode "default", has); the splits are copied to the host once and the host-array path runs'
+                          % self._resident_mode(), RuntimeWarning, stacklevel=2)
+            (X_t1, y_t1), (X_t2, y_t2), (X_v, y_v) = [(resident.to_host(X), resident.to_host(y)) for X, y in data]
         self.train_base(X_t1, y_t1)
         B_t2 = self.base.predict_proba(X_t2)
         self.train_smoother(B_t2, y_t2, **smoother_kw)
@@ -117,11 +178,23 @@ class HipGnomix:
 
     def predict(self, X):
         """labels (N, W) — base + smoother fused on the device, B never leaves HBM (model.py:169-173)"""
+        if resident.is_cuda(X):   # CUDA in, CUDA out (int64, as the numpy form)
+            import torch
+            with resident.torch_stream(self.dev.ctx):
+                _, lab = self.dev.infer_device(resident.check_x(X, self.C, self.dev.ctx.device), want_proba=False, want_labels=True)
+                return lab.to(torch.int64)
         _, lab = self.dev.infer(X, want_proba=False, want_labels=True)
         return lab.astype(np.int64)
 
     def predict_proba(self, X):
         """probabilities (N, W, A) (model.py:175-179)"""
+        if resident.is_cuda(X):   # CUDA in, CUDA out, the dtype the numpy form returns
+            import torch
+            pd = torch.float64 if self.dev.proba_dtype() == np.float64 else torch.float32
+            with resident.torch_stream(self.dev.ctx):
+                p, _ = self.dev.infer_device(resident.check_x(X, self.C, self.dev.ctx.device), want_proba=True, want_labels=False,
+                                             proba_dtype=pd)
+            return p
         p, _ = self.dev.infer(X, want_proba=True, want_labels=False)
         return p
 

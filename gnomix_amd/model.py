@@ -626,16 +626,21 @@ class DeviceModel:
         import torch
         self.ctx.set_stream(torch.cuda.current_stream(self.ctx.device).cuda_stream)
 
-    def infer_device(self, X_t, want_proba=True, want_labels=True):
-        """X_t: torch int8 CUDA tensor (N, C) resident in HBM -> (proba f32 tensor, labels i32 tensor)."""
+    def infer_device(self, X_t, want_proba=True, want_labels=True, proba_dtype=None):
+        """X_t: torch int8 CUDA tensor (N, C) resident in HBM -> (proba tensor, labels i32 tensor); proba_dtype: torch.float32 (the
+        default) or torch.float64."""
         import torch
         assert X_t.is_cuda and X_t.dtype == torch.int8 and X_t.dim() == 2 and X_t.stride(1) == 1
         self._bind_torch_stream()
         N = X_t.shape[0]
-        p = torch.empty((N, self.W, self.A), dtype=torch.float32, device=X_t.device) if want_proba else None
+        pd = proba_dtype or torch.float32
+        assert pd in (torch.float32, torch.float64)
+        p = torch.empty((N, self.W, self.A), dtype=pd, device=X_t.device) if want_proba else None
         lab = torch.empty((N, self.W), dtype=torch.int32, device=X_t.device) if want_labels else None
-        self.ctx.check(self.lib.gnx_infer_dev(self.h, X_t.data_ptr(), N, X_t.stride(0), p.data_ptr() if want_proba else None,
-                                              None, lab.data_ptr() if want_labels else None))
+        self.ctx.check(self.lib.gnx_infer_dev(self.h, X_t.data_ptr(), N, X_t.stride(0),
+                                              p.data_ptr() if (want_proba and pd == torch.float32) else None,
+                                              p.data_ptr() if (want_proba and pd == torch.float64) else None,
+                                              lab.data_ptr() if want_labels else None))
         return p, lab
 
     def base_predict_device(self, X_t, f64=False):
@@ -722,13 +727,19 @@ class DeviceModel:
                                                       Y.data_ptr(), ns.data_ptr()))
         return Y, ns
 
-    def smooth_predict_device(self, B_t):
+    def smooth_predict_device(self, B_t, want_proba=True, want_labels=True, proba_dtype=None):
+        """B_t (N, W, A) float32 / float64 CUDA tensor -> (proba or None, labels int32 or None); proba_dtype: torch.float32 (the
+        default) or torch.float64, as gnx_smooth_predict_dev writes either"""
         import torch
         assert B_t.is_cuda and B_t.is_contiguous() and B_t.dtype in (torch.float32, torch.float64)
         self._bind_torch_stream()
         N = B_t.shape[0]
-        p = torch.empty((N, self.W, self.A), dtype=torch.float32, device=B_t.device)
-        lab = torch.empty((N, self.W), dtype=torch.int32, device=B_t.device)
+        pd = proba_dtype or torch.float32
+        assert pd in (torch.float32, torch.float64)
+        p = torch.empty((N, self.W, self.A), dtype=pd, device=B_t.device) if want_proba else None
+        lab = torch.empty((N, self.W), dtype=torch.int32, device=B_t.device) if want_labels else None
         self.ctx.check(self.lib.gnx_smooth_predict_dev(self.h, B_t.data_ptr(), int(B_t.dtype == torch.float64), N,
-                                                       p.data_ptr(), None, lab.data_ptr()))
+                                                       p.data_ptr() if (want_proba and pd == torch.float32) else None,
+                                                       p.data_ptr() if (want_proba and pd == torch.float64) else None,
+                                                       lab.data_ptr() if want_labels else None))
         return p, lab

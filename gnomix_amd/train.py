@@ -23,20 +23,36 @@ def train_logistic_arrays(X, y, M, context, A, C_reg=3.0, tol=1e-9, max_iter=100
     Defaults are the reference's (C=3., max_iter=1000); tol is OUR stopping rule |grad| <= tol |grad(0)| (the reference's
     liblinear stops near 1e-4: the default here converges to the optimum it approximates)."""
     ctx = ctx or _lib.default_context(device)
-    X = np.ascontiguousarray(X, dtype=np.int8)
-    N, Cn = X.shape
-    W = Cn // int(M)
-    y = np.ascontiguousarray(y, dtype=np.int32)
-    if y.shape != (N, W):
-        raise ValueError(f"y must be (N, W) = ({N}, {W}), got {y.shape}")
-    if y.min() < 0 or y.max() >= A:
+    from . import resident
+    on_dev = resident.all_on_device([X, y], "train_logistic_arrays: (X, y)")
+    if on_dev:
+        # X / y already in HBM (a CUDA int8 tensor with any row stride, int32 labels): gnx_train_logistic_dev reads them in place
+        N, Cn = X.shape
+        W = Cn // int(M)
+        X, y = resident.check_x(X, Cn, ctx.device), resident.check_y(y, N, W, ctx.device)
+        lo, hi = (int(v) for v in y.aminmax()) if N else (0, 0)
+    else:
+        X = np.ascontiguousarray(X, dtype=np.int8)
+        N, Cn = X.shape
+        W = Cn // int(M)
+        y = np.ascontiguousarray(y, dtype=np.int32)
+        if y.shape != (N, W):
+            raise ValueError(f"y must be (N, W) = ({N}, {W}), got {y.shape}")
+        lo, hi = y.min(), y.max()
+    if lo < 0 or hi >= A:
         raise ValueError("labels must lie in [0, A)")
     ldc = int(M) + 2 * int(context) + (Cn - int(M) * W)
     coef = np.zeros((W, int(A), ldc), np.float64)
     icpt = np.zeros((W, int(A)), np.float64)
     info = _lib.TrainInfo()
-    ctx.check(ctx.lib.gnx_train_logistic(ctx.h, X.ctypes.data, N, X.shape[1], y.ctypes.data, Cn, int(M), int(context), int(A),
-                                         float(C_reg), float(tol), int(max_iter), coef.ctypes.data, ldc, icpt.ctypes.data, C.byref(info)))
+    if on_dev:
+        with resident.torch_stream(ctx):
+            ctx.check(ctx.lib.gnx_train_logistic_dev(ctx.h, X.data_ptr(), N, resident.row_stride(X), y.data_ptr(), Cn, int(M), int(context),
+                                                     int(A), float(C_reg), float(tol), int(max_iter), coef.ctypes.data, ldc,
+                                                     icpt.ctypes.data, C.byref(info)))
+    else:
+        ctx.check(ctx.lib.gnx_train_logistic(ctx.h, X.ctypes.data, N, X.shape[1], y.ctypes.data, Cn, int(M), int(context), int(A),
+                                             float(C_reg), float(tol), int(max_iter), coef.ctypes.data, ldc, icpt.ctypes.data, C.byref(info)))
     out = dict(newton_iterations=info.newton_iterations, cg_iterations=info.cg_iterations, n_problems=info.n_problems,
                worst_rel_gradient=info.worst_rel_gradient, objective_sum=info.objective_sum)
     # the library bounds the Newton steps (at most 200 whatever max_iter says: include/gnomix_hip.h) and returns what it has: a

@@ -754,6 +754,27 @@ int gnx_simulate_admix(gnx_ctx* ctx, const int8_t* F, int64_t n_founder_haps, in
                        const int64_t* seg_off, const int32_t* seg_begin, const int32_t* seg_src, const uint8_t* anc_of_src,
                        int32_t A, int64_t N, int8_t* X, int64_t ldx, int32_t* Y, uint8_t* anc);
 
+/* ---- scoring a split that was predicted on the device: the bookkeeping of Gnomix.train (src/model.py:127-151: accuracy_score,
+ *      balanced_accuracy_score and confusion_matrix of sklearn on label vectors) needs only the A x A counts
+ *        cm[t * A + p] = #{i : y[i] == t and pred[i] == p}
+ *      (gnomix_amd/metrics.py turns them into the reference's figures).  k_confusion.hip counts them in one pass.
+ *   y (n,) int32 true labels;  pred by pred_kind: (n,) int32 labels, or (n, A) float64 / float32 probabilities of which the
+ *     first-maximum argmax is taken as np.argmax(B, -1) does (Base.evaluate, src/Base/base.py:221): a NaN counts as a maximum and
+ *     the first NaN of a row wins;  cm (A * A) int64, overwritten.  n == 0: cm is zeroed, nothing launched.
+ *   A true or predicted label outside [0, A) indexes nothing: such elements are counted apart and, after the launch, reported as
+ *     GNX_EINVAL (the message gives their number); cm then holds the counts of all other elements.
+ *   GNX_EUNSUPPORTED: A > GNX_CONFUSION_MAX_A (the per-workgroup table is A x A 32-bit counters in LDS).
+ *   Debugging arguments (0 / NULL in production): a workgroup adds its table to cm before it has counted more than
+ *     debug_flush_every elements since the last time (built in: 2^31, the bound that keeps a 32-bit counter from overflowing; at least
+ *     one step of 256 elements is always counted); *debug_n_flushes receives the number of such additions over all workgroups.
+ *   Both forms synchronise the context stream once (the verdict on the labels is read back). */
+#define GNX_CONFUSION_MAX_A 32
+enum { GNX_PRED_LABELS_I32 = 0, GNX_PRED_PROBA_F64 = 1, GNX_PRED_PROBA_F32 = 2 };
+int gnx_confusion_dev(gnx_ctx* ctx, const int32_t* d_y, const void* d_pred, int pred_kind, int64_t n, int32_t A, int64_t* d_cm,
+                      int64_t debug_flush_every, int64_t* debug_n_flushes);
+int gnx_confusion(gnx_ctx* ctx, const int32_t* y, const void* pred, int pred_kind, int64_t n, int32_t A, int64_t* cm,
+                  int64_t debug_flush_every, int64_t* debug_n_flushes);
+
 /* per-kernel device time, measured with hipEvents on the context stream around every launch */
 int gnx_profile_enable(gnx_ctx* ctx, int on);
 int gnx_profile_reset(gnx_ctx* ctx);

@@ -36,6 +36,7 @@ MUST_BE_CLEAN = [
     r"k_nb_",
     r"k_lda_",
     r"k_rf_",
+    r"k_confusion<",
 ]
 
 
