@@ -229,6 +229,10 @@ SYMBOLS = {
     "gnx_simulate_admix": (C.c_int, [_VP, _VP, _I64, _I64, _I64, _I64, _VP, _VP, _VP, _VP, C.c_int32, _I64, _VP, _I64, _VP, _VP]),
     "gnx_confusion_dev": (C.c_int, [_VP, _VP, _VP, _I, _I64, C.c_int32, _VP, _I64, C.POINTER(_I64)]),
     "gnx_confusion": (C.c_int, [_VP, _VP, _VP, _I, _I64, C.c_int32, _VP, _I64, C.POINTER(_I64)]),
+    "gnx_mode_filter_dev": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _I64, _I64, C.c_int32, _I64]),
+    "gnx_mode_filter": (C.c_int, [_VP, _VP, _VP, _I64, _I64, C.c_int32, _I64]),
+    "gnx_label_runs_dev": (C.c_int, [_VP, _VP, _I64, _I64, _I64, _VP, _VP, _VP, _I64, C.POINTER(_I64)]),
+    "gnx_label_runs": (C.c_int, [_VP, _VP, _I64, _I64, _I64, _VP, _VP, _VP, _I64, C.POINTER(_I64)]),
     # include/gnomix_io.h: the file side
     "gnx_io_last_error": (C.c_char_p, []),
     "gnx_vcf_read": (C.c_int, [_VP, C.c_char_p, C.c_char_p, _I, C.POINTER(_VP)]),
@@ -249,6 +253,8 @@ SYMBOLS = {
     "gnx_infer_gt2_range": (C.c_int, [_VP, _VP, _I64, _I64, _I64, _I64, _VP, _VP, _VP, _VP]),
     "gnx_phase_gt2_range": (C.c_int, [_VP, _VP, _I64, _I64, _I64, _I64, _VP, C.c_int32, _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP]),
     "gnx_write_msp": (C.c_int, [C.c_char_p, C.c_char_p, _I64, _VP, _VP, _VP, _I64, _I64, _I64, _I]),
+    "gnx_write_lai": (C.c_int, [C.c_char_p, C.c_char_p, _I64, _VP, _I64, _VP, _VP, _I64, _I64, _I64, _I]),
+    "gnx_write_bed": (C.c_int, [C.c_char_p, _VP, _VP, C.c_char_p, _I64, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _I64, _I64, _I]),
     "gnx_write_fb_dev": (C.c_int, [_VP, C.c_char_p, C.c_char_p, _I64, _VP, _VP, _VP, _I64, _I64, _I64]),
     "gnx_write_fb": (C.c_int, [C.c_char_p, C.c_char_p, _I64, _VP, _VP, _VP, _I, _I64, _I64, _I64, _I]),
     "gnx_write_vcf_gt2": (C.c_int, [C.c_char_p, C.c_char_p, _I64, _VP, _VP, _VP, _I64, _I64, _I64, _I, _I]),

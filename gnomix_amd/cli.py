@@ -183,10 +183,15 @@ def _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out,
     from . import postprocess as pp
     from . import vcfio
     chm, output_path = base_args["chm"], base_args["output_basename"]
+    mode_filter = getattr(model.smooth, "mode_filter", 0) if model.smooth is not None else 0
     if not base_args["phase"]:
         proba, labels = runner.infer_gt2(vcf.gt2, N, src, out=out)
+        if mode_filter:   # Smoother.predict's filter: the .msp labels (and .lai / .bed) are filtered, the .fb probabilities are not
+            labels = model.dev.mode_filter(labels, mode_filter)
         T["infer"] = clock() - t0
     else:
+        if mode_filter:
+            raise NotImplementedError("phase with mode_filter != 0: the filter inside the Gnofix loop is not built")
         assert model.smooth is not None, "Smoother is not trained, returning original haplotypes"
         assert model.smooth.gnofix, "Type of Smoother ({}) does not currently support re-phasing".format(model.smooth)
         G_phased, proba, labels, _ = runner.phase_gt2(vcf.gt2, N, src, out_cols=fmt_idx, out=out)
@@ -210,10 +215,15 @@ def _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out,
     t0 = clock()
     pp.write_fb(out_prefix, meta, proba, model.population_order, samples, ctx=model.dev.ctx if os.environ.get("GNX_FB_DEV") == "1" else None)
     T["write_fb"] = clock() - t0
+    # (.lai and .bed from the labels held here: the same bytes as postprocess.msp_to_lai / msp_to_bed make from the .msp text)
     if snp_level:
-        pp.msp_to_lai(out_prefix + ".msp", vcf["variants/POS"], out_prefix + ".lai")
+        t0 = clock()
+        pp.write_lai(out_prefix, meta, labels, vcf["variants/POS"], samples, populations=model.population_order)
+        T["write_lai"] = clock() - t0
     if bed_file_output:
-        pp.msp_to_bed(out_prefix + ".msp", output_path + "/" + "query_results_bed", pop_order=model.population_order)
+        t0 = clock()
+        pp.write_bed(output_path + "/" + "query_results_bed", meta, labels, samples, pop_order=model.population_order, ctx=model.dev.ctx)
+        T["write_bed"] = clock() - t0
     return out_prefix
 
 

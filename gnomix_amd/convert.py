@@ -671,6 +671,9 @@ def from_reference_model(model) -> GnxModelData:
     if cal is not None and all(mm is not None for mm in cal.models):
         for k, v in calibrator_arrays(cal.models).items():
             setattr(d, k, v)
+    mf = getattr(model.smooth, "mode_filter", 0)
+    if mf:   # (0, False and None all mean "off", src/Smooth/smooth.py:63, utils.py:39)
+        d.mode_filter = int(mf)
     d.snp_pos, d.snp_ref, d.snp_alt = model.snp_pos, model.snp_ref, model.snp_alt
     d.population_order = list(model.population_order) if model.population_order is not None else None
     gm = getattr(model, "gen_map_df", None)

@@ -15,7 +15,9 @@ from .smooth import HipSmoother
 
 class HipGnomix:
 
-    def __init__(self, data: GnxModelData, device: int = 0, ctx=None, calibrate=False, verbose=False, prepared=None):
+    def __init__(self, data: GnxModelData, device: int = 0, ctx=None, calibrate=False, verbose=False, prepared=None, mode_filter=None):
+        """mode_filter: Gnomix(..., mode_filter=k) (src/model.py:18, 80); None takes the model's own (GnxModelData.mode_filter, what a
+        converted model.pkl or a .gnx carries), 0 / False switches it off"""
         self.data = data
         self.dev = DeviceModel(data, ctx=ctx, device=device, prepared=prepared)
         self.C, self.M, self.A, self.S = data.C, data.M, data.A, data.S
@@ -34,7 +36,8 @@ class HipGnomix:
             except ImportError:
                 self.gen_map_df = {"pos": data.gen_map_pos, "pos_cm": data.gen_map_cm}
         self.base = HipBase(self.dev, verbose=verbose)
-        self.smooth = HipSmoother(self.dev, calibrate=calibrate, verbose=verbose)
+        self.smooth = HipSmoother(self.dev, calibrate=calibrate, mode_filter=(data.mode_filter if mode_filter is None else mode_filter) or 0,
+                                  verbose=verbose)
         self.time = {}
 
     @classmethod
@@ -177,13 +180,19 @@ class HipGnomix:
         return self
 
     def predict(self, X):
-        """labels (N, W) — base + smoother fused on the device, B never leaves HBM (model.py:169-173)"""
+        """labels (N, W) — base + smoother fused on the device, B never leaves HBM (model.py:169-173); the smoother's mode_filter
+        acts on them as in Smoother.predict"""
+        mf = self.smooth.mode_filter
         if resident.is_cuda(X):   # CUDA in, CUDA out (int64, as the numpy form)
             import torch
             with resident.torch_stream(self.dev.ctx):
                 _, lab = self.dev.infer_device(resident.check_x(X, self.C, self.dev.ctx.device), want_proba=False, want_labels=True)
+                if mf:
+                    lab = self.dev.mode_filter_device(lab, mf)
                 return lab.to(torch.int64)
         _, lab = self.dev.infer(X, want_proba=False, want_labels=True)
+        if mf:
+            lab = self.dev.mode_filter(lab, mf)
         return lab.astype(np.int64)
 
     def predict_proba(self, X):
@@ -204,6 +213,9 @@ class HipGnomix:
         Gnomix.phase passes none, which is the default here too."""
         assert self.smooth is not None, "Smoother is not trained, returning original haplotypes"
         assert self.smooth.gnofix, "Type of Smoother ({}) does not currently support re-phasing".format(self.smooth)
+        if self.smooth.mode_filter:
+            # gnofix() takes its labels from smoother.predict (src/Gnofix/gnofix.py): the filter would act inside its loop
+            raise NotImplementedError("phase: mode_filter != 0 inside the Gnofix loop is not built (predict applies it; phase does not)")
         X = np.asarray(X)
         if B is None:
             B = self.base.predict_proba(X)

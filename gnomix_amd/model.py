@@ -98,6 +98,9 @@ class GnxModelData:
     calib_x: np.ndarray | None = None
     calib_y: np.ndarray | None = None
     calib_is_f32: bool = False            # maps fitted on float32 probabilities (sklearn then interpolates in float32)
+    # Smoother.mode_filter (src/Smooth/smooth.py:18, 63-64): window size of the label filter predict() applies; None (= 0, and not
+    # stored in the .gnx: an archive written without it is byte for byte what it was) or a positive size
+    mode_filter: int | None = None
     # dataset metadata used by the writers (src/model.py:40-44, 88)
     snp_pos: np.ndarray | None = None
     snp_ref: np.ndarray | None = None
@@ -160,7 +163,7 @@ class GnxModelData:
         for k in cls.__dataclass_fields__:
             if k in z.files:
                 v = z[k]
-                if k in ("C", "M", "A", "S", "context", "fb_missing"):
+                if k in ("C", "M", "A", "S", "context", "fb_missing", "mode_filter"):
                     v = int(v)
                 elif k in ("base_score", "fb_base_score"):
                     v = float(v)
@@ -452,6 +455,22 @@ class DeviceModel:
         self.ctx.check(self.lib.gnx_smooth_predict(self.h, B.ctypes.data, int(B.dtype == np.float64), N, p32, p64,
                                                    lab.ctypes.data if want_labels else None))
         return p, lab
+
+    def mode_filter(self, lab, size):
+        """Smoother.predict's mode_filter on (N, W) int32 labels (gnx_mode_filter; gnomix_amd.postprocess.mode_filter)"""
+        from .postprocess import mode_filter
+        return mode_filter(self.ctx, lab, self.A, size)
+
+    def mode_filter_device(self, lab_t, size):
+        """the same on an (N, W) int32 CUDA tensor with contiguous rows (gnx_mode_filter_dev) -> a new tensor"""
+        import torch
+        assert lab_t.is_cuda and lab_t.dtype == torch.int32 and lab_t.dim() == 2 and (lab_t.shape[1] == 0 or lab_t.stride(1) == 1)
+        self._bind_torch_stream()
+        N, W = lab_t.shape
+        out = torch.empty((N, W), dtype=torch.int32, device=lab_t.device)
+        self.ctx.check(self.lib.gnx_mode_filter_dev(self.ctx.h, lab_t.data_ptr(), lab_t.stride(0) if N > 1 else W, out.data_ptr(), W, N, W,
+                                                    self.A, int(size)))
+        return out
 
     def proba_dtype(self):
         """dtype of the probabilities this model's smoother returns: float64 for CRF and for calibrated output, else float32"""

@@ -124,6 +124,87 @@ def write_fb(fb_prefix, meta_data, proba, ancestry, query_samples, n_threads=0, 
                                            int(proba.dtype == np.float64), proba.shape[0], n_rows, proba.shape[2], int(n_threads)))
 
 
+def mode_filter(ctx, labels, A, size):
+    """Smoother.predict's mode_filter (src/Smooth/utils.py:31-46) on (N, W) labels in [0, A), on the device (gnx_mode_filter):
+    -> a new int32 array.  size 0 / None / False: the labels as they came, nothing launched."""
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    if lab.ndim != 2:
+        raise ValueError(f"labels must be (N, W), got {lab.shape}")
+    if not size:
+        return lab
+    out = np.empty_like(lab)
+    ctx.check(ctx.lib.gnx_mode_filter(ctx.h, lab.ctypes.data, out.ctypes.data, lab.shape[0], lab.shape[1], int(A), int(size)))
+    return out
+
+
+def label_runs(ctx, labels):
+    """run-length encoding of every row of (N, W) labels on the device (gnx_label_runs): -> (counts (N,) int64, offsets (N + 1,)
+    int64, triples (total, 3) int32 of (first_window, last_window, label)); row n owns triples offsets[n] .. offsets[n + 1] - 1"""
+    import ctypes as C
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    if lab.ndim != 2:
+        raise ValueError(f"labels must be (N, W), got {lab.shape}")
+    N, W = lab.shape
+    counts, offsets, total = np.zeros(N, np.int64), np.zeros(N + 1, np.int64), C.c_int64(0)
+    triples = np.empty((N * min(W, 8), 3), np.int32)   # room for 8 runs a row; the entry says how many there are when that is too few
+    for _ in range(2):
+        rc = ctx.lib.gnx_label_runs(ctx.h, lab.ctypes.data, W, N, W, counts.ctypes.data, offsets.ctypes.data, triples.ctypes.data,
+                                    triples.shape[0], C.byref(total))
+        if rc == _lib.GNX_EINVAL and total.value > triples.shape[0]:
+            triples = np.empty((total.value, 3), np.int32)
+            continue
+        ctx.check(rc)
+        break
+    return counts, offsets, triples[:total.value]
+
+
+def write_lai(prefix, meta, labels, positions, samples, populations=None, n_threads=0, first_line=None):
+    """<prefix>.lai — the bytes msp_to_lai writes from <prefix>.msp, from the labels themselves (gnx_write_lai): the .msp's first
+    header line (built from `populations`, or given as `first_line`), "position" and the haplotype columns, then one line per query
+    SNP: its position and the N labels of its window (meta["n snps"] positions per window)."""
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    n_snps = np.ascontiguousarray(meta["n snps"], dtype=np.int64)
+    if lab.ndim != 2 or lab.shape[1] != len(n_snps):
+        raise ValueError(f"labels must be (N, W={len(n_snps)}), got {lab.shape}")
+    pos = np.ascontiguousarray(positions, dtype=np.int64)
+    if first_line is None:
+        first_line = "#Subpopulation order/codes: " + "\t".join([str(pop) + "=" + str(i) for i, pop in enumerate(populations)]) + "\n"
+    head = first_line + "position\t" + "\t".join([str(s) for q in samples for s in (str(q) + ".0", str(q) + ".1")]) + "\n"
+    head = head.encode()
+    _lib.io_check(_lib.load().gnx_write_lai((prefix + ".lai").encode(), head, len(head), pos.ctypes.data, len(pos), n_snps.ctypes.data,
+                                            lab.ctypes.data, lab.shape[0], lab.shape[1], lab.shape[1], int(n_threads)))
+
+
+def write_bed_runs(root, meta, offsets, triples, samples, pop_order=None, n_threads=0):
+    """one .bed per haplotype column from a run list (label_runs): the files msp_to_bed writes (gnx_write_bed)"""
+    os.makedirs(root, exist_ok=True)
+    cols = [s for r in _meta_strings(meta) for s in r[:5]]
+    cb, co = _blob(cols)
+    names = [(str(q) + h).replace(".", "_") + ".bed" for q in samples for h in (".0", ".1")]
+    fb, fo = _blob(names)
+    ab, ao = _blob([str(p) for p in pop_order] if pop_order is not None else [])
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    triples = np.ascontiguousarray(triples, dtype=np.int32)
+    if len(offsets) != len(names) + 1:
+        raise ValueError(f"{len(names)} haplotype columns but {len(offsets) - 1} rows of runs")
+    head = b"chm\tspos\tepos\tancestry\tsgpos\tegpos\n"
+    _lib.io_check(_lib.load().gnx_write_bed(root.encode(), fb, fo.ctypes.data, head, len(head), cb, co.ctypes.data, ab, ao.ctypes.data,
+                                            0 if pop_order is None else len(pop_order), offsets.ctypes.data, triples.ctypes.data,
+                                            len(names), len(meta["spos"]), int(n_threads)))
+
+
+def write_bed(root, meta, labels, samples, pop_order=None, ctx=None, n_threads=0):
+    """<root>/<sample>_<0|1>.bed for every haplotype row of labels (N, W): the runs come from the device (k_label_runs), the text
+    and the files from the library's host threads"""
+    if ctx is None:
+        ctx = _lib.default_context(0)
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    if lab.ndim != 2 or lab.shape[1] != len(meta["spos"]):
+        raise ValueError(f"labels must be (N, W={len(meta['spos'])}), got {lab.shape}")
+    _, offsets, triples = label_runs(ctx, lab)
+    write_bed_runs(root, meta, offsets, triples, samples, pop_order, n_threads)
+
+
 def msp_to_lai(msp_file, positions, lai_file=None):
     """SNP-level labels (postprocess.py:128-160): every window row repeated `n snps` times."""
     with open(msp_file) as f:

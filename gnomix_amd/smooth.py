@@ -193,14 +193,17 @@ class HipSmoother:
         return B.contiguous()
 
     def predict(self, B):
-        """argmax labels (N, W) int64, first max wins (smooth.py:58-65)."""
-        if self.mode_filter:
-            raise NotImplementedError("mode_filter != 0 is out of scope (default 0; broken on scipy>=1.11 in the reference)")
+        """argmax labels (N, W) int64, first max wins; with mode_filter = k, each label but the first and last k // 2 of a row
+        becomes the unambiguous mode of the k labels around it (smooth.py:58-65, Smooth/utils.py:31-46; k_mode_filter)."""
         from . import resident
         if resident.is_cuda(B):   # CUDA in, CUDA out (int64, as the numpy form)
             import torch
             with resident.torch_stream(self.dev.ctx):
                 _, lab = self.dev.smooth_predict_device(self._b_dev(B), want_proba=False, want_labels=True)
+                if self.mode_filter:
+                    lab = self.dev.mode_filter_device(lab, self.mode_filter)
                 return lab.to(torch.int64)
         _, lab = self.dev.smooth_predict(B, want_proba=False, want_labels=True)
+        if self.mode_filter:
+            lab = self.dev.mode_filter(lab, self.mode_filter)
         return lab.astype(np.int64)

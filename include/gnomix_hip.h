@@ -35,6 +35,8 @@
  *   gnx_train_cnn         <- Smoother.train(B, y) of CNN_Smoother         src/Smooth/cnn.py:104-118, src/Smooth/models.py:35-42
  *   gnx_simulate_admix    <- LAIDataset.simulate + write_output + data_process   src/laidataset.py:119-201, 362-428,
  *                                                                          src/preprocess.py:37-82, gnomix.py:102-156
+ *   gnx_mode_filter       <- Smoother.predict's mode_filter               src/Smooth/utils.py:31-46, src/Smooth/smooth.py:63-64
+ *   gnx_label_runs        <- get_bed_data's walk over a haplotype column  src/postprocess.py:162-193
  *
  * Conventions
  *   - return 0 (GNX_OK) or a negative GNX_E* code; the message is kept per context (gnx_last_error).
@@ -774,6 +776,35 @@ int gnx_confusion_dev(gnx_ctx* ctx, const int32_t* d_y, const void* d_pred, int 
                       int64_t debug_flush_every, int64_t* debug_n_flushes);
 int gnx_confusion(gnx_ctx* ctx, const int32_t* y, const void* pred, int pred_kind, int64_t n, int32_t A, int64_t* cm,
                   int64_t debug_flush_every, int64_t* debug_n_flushes);
+
+/* ---- the window labels after the argmax (csrc/labels/k_labels.hip) ------------------------------------------------------------
+ * gnx_mode_filter: Smoother.predict's mode_filter (src/Smooth/smooth.py:63-64, src/Smooth/utils.py:31-46) with the meaning it has
+ *   under the scipy it was written for (< 1.11: stats.mode(arr)[0][0] is the smallest most frequent value).  in / out (N, W) int32
+ *   labels in [0, A), A <= GNX_MODE_FILTER_MAX_A; the arrays must not overlap.  ends = size / 2 (an even size acts as size + 1).
+ *   Position i with ends <= i < W - ends becomes the most frequent label of in[i - ends .. i + ends] when the smallest and the
+ *   largest most frequent label agree, and stays in[i] otherwise; every other position (all of them for size <= 1 and for
+ *   2 * ends >= W) is copied.  Windows are read from `in`, so nothing cascades.
+ *   GNX_EINVAL before the launch: size < 0 (and bad sizes / pointers); GNX_EINVAL after the launch: a label outside [0, A) was met
+ *   (such a label equals no class and is handed on unchanged; labels are only compared, never used as an index).
+ *   A row of at most GNX_MODE_FILTER_LDS_ROW labels is staged in LDS; a longer one is read from global memory by the same kernel.
+ *   Both forms synchronise the context stream once (the verdict on the labels is read back).  The _dev form takes row strides in
+ *   elements (>= W). */
+#define GNX_MODE_FILTER_MAX_A 32
+#define GNX_MODE_FILTER_LDS_ROW 16384
+int gnx_mode_filter_dev(gnx_ctx* ctx, const int32_t* d_in, int64_t ld_in, int32_t* d_out, int64_t ld_out, int64_t N, int64_t W,
+                        int32_t A, int64_t size);
+int gnx_mode_filter(gnx_ctx* ctx, const int32_t* in, int32_t* out, int64_t N, int64_t W, int32_t A, int64_t size);
+/* gnx_label_runs: the run-length encoding get_bed_data walks out of one haplotype column (src/postprocess.py:162-193), for all
+ *   rows at once.  labels (N, W) int32, rows ldl >= W elements apart (any values).  A run is a maximal stretch of equal labels of
+ *   a row.  counts (N) int64 = runs per row; offsets (N + 1) int64 = their exclusive prefix, offsets[N] = *total; triples
+ *   (capacity, 3) int32 = (first_window, last_window, label) of every run, row after row: row n owns triples offsets[n] ..
+ *   offsets[n + 1] - 1.  Two passes (count, fill) with the prefix between them; *total (a host word) is always set.
+ *   GNX_EINVAL with counts, offsets and *total written and the triples untouched: capacity < *total.  W == 0: no runs.
+ *   Both forms synchronise the context stream once (the total is read back). */
+int gnx_label_runs_dev(gnx_ctx* ctx, const int32_t* d_labels, int64_t ldl, int64_t N, int64_t W, int64_t* d_counts, int64_t* d_offsets,
+                       int32_t* d_triples, int64_t capacity, int64_t* total);
+int gnx_label_runs(gnx_ctx* ctx, const int32_t* labels, int64_t ldl, int64_t N, int64_t W, int64_t* counts, int64_t* offsets,
+                   int32_t* triples, int64_t capacity, int64_t* total);
 
 /* per-kernel device time, measured with hipEvents on the context stream around every launch */
 int gnx_profile_enable(gnx_ctx* ctx, int on);

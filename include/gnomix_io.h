@@ -13,6 +13,8 @@
  *   gnx_x_to_gt2_dev        <- X_query_phased[:, fmt_idx] per variant                   gnomix.py:69, src/utils.py:299-308
  *   gnx_write_msp           <- write_msp                                                src/postprocess.py:84-98
  *   gnx_write_fb            <- write_fb (pandas to_csv of float columns)                src/postprocess.py:100-126
+ *   gnx_write_lai           <- msp_to_lai (a DataFrame of every SNP's labels, to_csv)   src/postprocess.py:128-160
+ *   gnx_write_bed           <- msp_to_bed / get_bed_data (one DataFrame per haplotype)  src/postprocess.py:162-210
  *   gnx_write_vcf_gt2       <- npy_to_vcf (pandas to_csv of "a|b" columns)              src/utils.py:247-329
  *   gnx_format_floats       <- numpy's shortest round-trip float text (what `.astype(str)` / to_csv print)
  *
@@ -130,6 +132,23 @@ int gnx_phase_gt2_range(gnx_model* model, const uint8_t* G, int64_t V, int64_t l
 /* .msp row w: prefix, then "\t<labels[n, w]>" for every haplotype n (labels (N, ldl) int32, src/postprocess.py:84-98) */
 int gnx_write_msp(const char* path, const char* head, int64_t head_len, const char* prefix_blob, const int64_t* prefix_off,
                   const int32_t* labels, int64_t N, int64_t ldl, int64_t W, int n_threads);
+/* .lai (SNP-level labels, msp_to_lai, src/postprocess.py:128-160): behind `head`, one line per query SNP q, in order:
+ * "<positions[q]>" then "\t<labels[n, w]>" for every haplotype n, where w is the window that holds SNP q — window w holds the next
+ * n_snps[w] positions (the .msp's "n snps" column).  A window's labels are formatted once and copied per SNP.
+ * GNX_EINVAL, nothing written: the counts do not add up to n_positions (the reference's assert) or one is negative. */
+int gnx_write_lai(const char* path, const char* head, int64_t head_len, const int64_t* positions, int64_t n_positions,
+                  const int64_t* n_snps, const int32_t* labels, int64_t N, int64_t ldl, int64_t W, int n_threads);
+/* .bed (msp_to_bed / get_bed_data, src/postprocess.py:162-210): one file per haplotype column n, `dir`/<file n> (file_blob /
+ * file_off, N names; the directory exists), = `head` + one line per run of equal labels of that column:
+ *   chm[first] \t spos[first] \t epos[last] \t ancestry \t sgpos[first] \t egpos[last] \n
+ * runs as gnx_label_runs returns them: column n owns triples run_off[n] .. run_off[n + 1] - 1 of (first_window, last_window, label).
+ * col_blob / col_off: the 5 W column strings of the .msp rows, entry 5 w + {0 chm, 1 spos, 2 epos, 3 sgpos, 4 egpos}.  ancestry =
+ * entry `label` of anc_blob / anc_off (n_anc population names), or the label's number when n_anc == 0.  The files are written by
+ * at most n_threads threads (<= 0: the writers' default); the first failed file ends the job and is reported (GNX_EINVAL, as is a
+ * run outside [0, W) or a label without a name). */
+int gnx_write_bed(const char* dir, const char* file_blob, const int64_t* file_off, const char* head, int64_t head_len,
+                  const char* col_blob, const int64_t* col_off, const char* anc_blob, const int64_t* anc_off, int64_t n_anc,
+                  const int64_t* run_off, const int32_t* triples, int64_t N, int64_t W, int n_threads);
 /* .fb row w: prefix, then "\t<proba[n, w, a]>" for n, then a (proba (N, W, A) float32 or float64); numbers are printed as
  * pandas' to_csv prints a float column: numpy's shortest round-trip text, empty for NaN (src/postprocess.py:100-126) */
 int gnx_write_fb(const char* path, const char* head, int64_t head_len, const char* prefix_blob, const int64_t* prefix_off,

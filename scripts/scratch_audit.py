@@ -37,6 +37,7 @@ MUST_BE_CLEAN = [
     r"k_lda_",
     r"k_rf_",
     r"k_confusion<",
+    r"k_mode_filter", r"k_label_runs_",
 ]
 
 
