@@ -180,6 +180,7 @@ SYMBOLS = {
     "gnx_model_export_prepared": (C.c_int, [_VP, _VP, _I64, C.POINTER(_I64)]),
     "gnx_base_predict": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _VP]),
     "gnx_base_predict_dev": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _VP]),
+    "gnx_base_predict_ranks_dev": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _VP]),
     "gnx_smooth_predict": (C.c_int, [_VP, _VP, _I, _I64, _VP, _VP, _VP]),
     "gnx_smooth_predict_dev": (C.c_int, [_VP, _VP, _I, _I64, _VP, _VP, _VP]),
     "gnx_infer": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _VP, _VP]),

@@ -131,6 +131,7 @@ static void read_tune(gnx_tune& t) {
   if (const char* e = std::getenv("GNX_GNOFIX_IMPL")) t.gnofix_impl = std::string(e) == "f32" ? 1 : 0;
   t.gnofix_threads = geti("GNX_GNOFIX_T", 0);
   t.gnofix_aux = geti("GNX_GNOFIX_AUX", 1);
+  t.fuse_ranks = geti("GNX_FUSE_RANKS", 1);
 }
 
 extern "C" {
@@ -444,11 +445,37 @@ int gnx_model_get_info(const gnx_model* m, gnx_model_info* out) {
 }
 
 // ---- base ------------------------------------------------------------------------------------------
+// the logistic pass can rank its probabilities for k_smooth_xgb_h32 while it still holds them (BaseLRLaunch::rk16): the int8 kernel
+// of one column tile, with the smoother's rank table
+static bool base_can_rank(const gnx_model* m) {
+  const gnx_tune& t = m->ctx->tune;
+  if (m->info.base_kind != GNX_BASE_LOGISTIC || !m->lr_i8 || !m->xgb.rk_thr || !m->xgb.rk_lut) return false;
+#ifdef GNX_EXPERIMENTS
+  if (t.lr_ws || t.lr_w512 || (t.lr_flat > 0 && m->lr.V8F)) return false;
+#endif
+  const bool dl = t.lr_dl < 0 ? m->lr.NT >= 2 : t.lr_dl != 0;
+  return !dl && gnx_base_logistic_i8_ranks(m->lr, t);
+}
+
+static int base_predict_dev(gnx_model* m, const int8_t* dX, int64_t N, int64_t ldx, float* d_b32, double* d_b64, uint16_t* d_rk16);
+
 int gnx_base_predict_dev(gnx_model* m, const int8_t* dX, int64_t N, int64_t ldx, float* d_b32, double* d_b64) {
+  return base_predict_dev(m, dX, N, ldx, d_b32, d_b64, nullptr);
+}
+
+int gnx_base_predict_ranks_dev(gnx_model* m, const int8_t* dX, int64_t N, int64_t ldx, float* d_b32, uint16_t* d_rk16) {
+  if (!m) return GNX_EINVAL;
+  if (!d_rk16) return fail(m->ctx, GNX_EINVAL, "base_predict_ranks: no rank image");
+  if (!base_can_rank(m)) return fail(m->ctx, GNX_EUNSUPPORTED, "base_predict_ranks: this model's base pass does not write ranks");
+  return base_predict_dev(m, dX, N, ldx, d_b32, nullptr, d_rk16);
+}
+
+static int base_predict_dev(gnx_model* m, const int8_t* dX, int64_t N, int64_t ldx, float* d_b32, double* d_b64, uint16_t* d_rk16) {
   if (!m) return GNX_EINVAL;
   gnx_ctx* ctx = m->ctx;
   if (N < 0 || ldx < m->info.C || (N > 0 && !dX)) return fail(ctx, GNX_EINVAL, "base_predict: bad X / N / ldx");
-  if (N == 0 || (!d_b32 && !d_b64)) return GNX_OK;
+  if (N == 0 || (!d_b32 && !d_b64 && !d_rk16)) return GNX_OK;
+  if (d_rk16 && !base_can_rank(m)) return fail(ctx, GNX_ESTATE, "base_predict: a rank image from a base pass that writes none");
   GNX_BIND_DEVICE(ctx);
   if (m->info.base_kind == GNX_BASE_KNN) return gnx_base_predict_knn(m, dX, N, ldx, d_b32, d_b64);
   if (m->info.base_kind == GNX_BASE_NB) return gnx_base_predict_nb(m, dX, N, ldx, d_b32, d_b64);
@@ -529,6 +556,11 @@ int gnx_base_predict_dev(gnx_model* m, const int8_t* dX, int64_t N, int64_t ldx,
   L.h_win_chunk0 = m->lr_h_win_chunk0.data(); L.h_win_chunk1 = m->lr_h_win_chunk1.data();
   L.W = (int32_t)m->info.W; L.A = m->info.A;
   L.b32 = d_b32; L.b64 = d_b64;
+  if (d_rk16) {
+    L.rk16 = d_rk16;
+    L.rk_thr = m->xgb.rk_thr; L.rk_lut = m->xgb.rk_lut;
+    L.rk_K = m->xgb.rk_K; L.rk_bits = m->xgb.rk_bits; L.rk_steps = m->xgb.rk_steps;
+  }
   ProfScope ps(ctx, GNX_K_BASE_LOGISTIC);
   if (m->lr_i8) {
     const bool dl = ctx->tune.lr_dl < 0 ? m->lr.NT >= 2 : ctx->tune.lr_dl != 0;
@@ -547,22 +579,38 @@ int gnx_base_predict_dev(gnx_model* m, const int8_t* dX, int64_t N, int64_t ldx,
 }
 
 // ---- smoother ------------------------------------------------------------------------------------
-static int smooth_raw_dev(gnx_model* m, const void* dB, int b_is_f64, int64_t N, float* d_p32, double* d_p64, int32_t* d_lab);
+// d_rk16: the base pass's rank image in place of B (infer_any_dev, k_smooth_xgb_h32 only)
+static int smooth_raw_dev(gnx_model* m, const void* dB, int b_is_f64, int64_t N, float* d_p32, double* d_p64, int32_t* d_lab,
+                          const uint16_t* d_rk16 = nullptr);
+static int smooth_predict_dev(gnx_model* m, const void* dB, int b_is_f64, int64_t N, float* d_p32, double* d_p64, int32_t* d_lab,
+                              const uint16_t* d_rk16);
 
 int gnx_smooth_predict_dev(gnx_model* m, const void* dB, int b_is_f64, int64_t N, float* d_p32, double* d_p64,
                            int32_t* d_lab) {
+  return smooth_predict_dev(m, dB, b_is_f64, N, d_p32, d_p64, d_lab, nullptr);
+}
+
+// the tree smoother takes k_smooth_xgb_h32 for a batch of N haplotypes (smooth_raw_dev's choice)
+static bool smooth_takes_h32(const gnx_model* m, int64_t N) {
+  if (m->info.smooth_kind != GNX_SMOOTH_XGB || !m->xgb.rk_packed) return false;
+  const int64_t blocks = (N + 31) / 32 * ((m->info.W + GNX_H32_WPB - 1) / GNX_H32_WPB);
+  return (m->xgb.impl == 5 || (m->xgb.impl == 6 && blocks >= m->ctx->n_cu)) && gnx_smooth_h32_fits(m->xgb, m->info.A, m->info.S);
+}
+
+static int smooth_predict_dev(gnx_model* m, const void* dB, int b_is_f64, int64_t N, float* d_p32, double* d_p64, int32_t* d_lab,
+                              const uint16_t* d_rk16) {
   if (!m) return GNX_EINVAL;
   gnx_ctx* ctx = m->ctx;
   GNX_BIND_DEVICE(ctx);
-  if (!(m->calibrate_on && m->calib_off)) return smooth_raw_dev(m, dB, b_is_f64, N, d_p32, d_p64, d_lab);
-  if (N < 0 || (N > 0 && !dB)) return fail(ctx, GNX_EINVAL, "smooth_predict: bad B / N");
+  if (!(m->calibrate_on && m->calib_off)) return smooth_raw_dev(m, dB, b_is_f64, N, d_p32, d_p64, d_lab, d_rk16);
+  if (N < 0 || (N > 0 && !dB && !d_rk16)) return fail(ctx, GNX_EINVAL, "smooth_predict: bad B / N");
   if (N == 0) return GNX_OK;
   // Smoother.predict_proba with a calibrator (smooth.py:46-52): raw smoother probabilities -> Calibrator.transform
   const size_t n = (size_t)N * m->info.W * m->info.A;
   const bool nat64 = m->info.smooth_kind == GNX_SMOOTH_CRF;
   int rc = ws_reserve(ctx, ctx->ws_cal, n * (nat64 ? 8 : 4));
   if (rc != GNX_OK) return rc;
-  rc = smooth_raw_dev(m, dB, b_is_f64, N, nat64 ? nullptr : (float*)ctx->ws_cal.p, nat64 ? (double*)ctx->ws_cal.p : nullptr, nullptr);
+  rc = smooth_raw_dev(m, dB, b_is_f64, N, nat64 ? nullptr : (float*)ctx->ws_cal.p, nat64 ? (double*)ctx->ws_cal.p : nullptr, nullptr, d_rk16);
   if (rc != GNX_OK) return rc;
   CalibLaunch L{};
   L.in = ctx->ws_cal.p; L.in_is_f64 = nat64; L.R = N * m->info.W; L.A = m->info.A;
@@ -573,10 +621,12 @@ int gnx_smooth_predict_dev(gnx_model* m, const void* dB, int b_is_f64, int64_t N
   return GNX_OK;
 }
 
-static int smooth_raw_dev(gnx_model* m, const void* dB, int b_is_f64, int64_t N, float* d_p32, double* d_p64, int32_t* d_lab) {
+static int smooth_raw_dev(gnx_model* m, const void* dB, int b_is_f64, int64_t N, float* d_p32, double* d_p64, int32_t* d_lab,
+                          const uint16_t* d_rk16) {
   gnx_ctx* ctx = m->ctx;
-  if (N < 0 || (N > 0 && !dB)) return fail(ctx, GNX_EINVAL, "smooth_predict: bad B / N");
+  if (N < 0 || (N > 0 && !dB && !d_rk16)) return fail(ctx, GNX_EINVAL, "smooth_predict: bad B / N");
   if (N == 0) return GNX_OK;
+  if (d_rk16 && !smooth_takes_h32(m, N)) return fail(ctx, GNX_ESTATE, "smooth_predict: a rank image for a smoother that reads none");
   if (m->info.smooth_kind == GNX_SMOOTH_XGB) {
     const size_t n = (size_t)N * m->info.W * m->info.A;
     if (!d_p32) {  // margins are parked in the f32 output: borrow a workspace
@@ -626,9 +676,8 @@ static int smooth_raw_dev(gnx_model* m, const void* dB, int b_is_f64, int64_t N,
       // other shape silently takes the rank kernel with pointer nodes.  GNX_SMOOTH_IMPL=h32 forces it for any batch.
       // By default only for batches of at least one 32-haplotype block per CU: below that the rank kernel's 8-haplotype blocks
       // spread over more CUs.
-      const bool h32 = (m->xgb.impl == 5 || (m->xgb.impl == 6 && (N + 31) / 32 * ((L.W + GNX_H32_WPB - 1) / GNX_H32_WPB) >= ctx->n_cu)) &&
-                       gnx_smooth_h32_fits(m->xgb, L.A, L.S);
-      if (h32) {
+      if (smooth_takes_h32(m, N)) {
+        L.rk16 = d_rk16;
         HIPCHK(ctx, gnx_launch_smooth_xgb_h32(L, ctx->stream));
         return GNX_OK;
       }
@@ -724,7 +773,25 @@ static int infer_any_dev(gnx_model* m, const void* dIn, bool packed, int64_t N, 
   GNX_BIND_DEVICE(ctx);
   const size_t n = (size_t)N * m->info.W * m->info.A;
   const bool f64 = (m->info.smooth_kind == GNX_SMOOTH_CRF);  // CRF consumes float64 base probabilities
-  int rc = ws_reserve(ctx, f64 ? ctx->ws_b64 : ctx->ws_b32, n * (f64 ? 8 : 4));
+  int rc;
+  // Logistic base into the h32 tree smoother: the smoother never uses the float, only its 16-bit rank, so the base pass ranks every
+  // probability while it holds it and B is not written at all (GNX_FUSE_RANKS=0: the float route; the outputs are bit-identical)
+  if (!packed && ctx->tune.fuse_ranks != 0 && base_can_rank(m) && smooth_takes_h32(m, N)) {
+    if ((rc = ws_reserve(ctx, ctx->ws_rank, gnx_rank_image_bytes(N, (int)m->info.W, m->info.A))) != GNX_OK) return rc;
+    uint16_t* rk16 = (uint16_t*)ctx->ws_rank.p;
+#ifdef GNX_FUSE_ABLATE
+    // development only (scripts/dev/fuse_ablate.sh), never in the default library: each half of the fused route against the float
+    // route, timing only.  1: the smoother copies its strip from an image nobody wrote (WRONG outputs) while the base pass writes
+    // B as before; 2: the base pass writes the image beside B and the smoother ranks B as before (right outputs)
+    if ((rc = ws_reserve(ctx, ctx->ws_b32, n * 4)) != GNX_OK) return rc;
+    if ((rc = base_predict_dev(m, (const int8_t*)dIn, N, ld, (float*)ctx->ws_b32.p, nullptr, GNX_FUSE_ABLATE == 2 ? rk16 : nullptr)) != GNX_OK) return rc;
+    return smooth_predict_dev(m, ctx->ws_b32.p, 0, N, d_p32, d_p64, d_lab, GNX_FUSE_ABLATE == 1 ? rk16 : nullptr);
+#else
+    if ((rc = base_predict_dev(m, (const int8_t*)dIn, N, ld, nullptr, nullptr, rk16)) != GNX_OK) return rc;
+    return smooth_predict_dev(m, nullptr, 0, N, d_p32, d_p64, d_lab, rk16);
+#endif
+  }
+  rc = ws_reserve(ctx, f64 ? ctx->ws_b64 : ctx->ws_b32, n * (f64 ? 8 : 4));
   if (rc != GNX_OK) return rc;
   float* b32 = f64 ? nullptr : (float*)ctx->ws_b32.p;
   double* b64 = f64 ? (double*)ctx->ws_b64.p : nullptr;
@@ -845,6 +912,9 @@ static int infer_host(gnx_model* m, const void* src, bool packed, int64_t N, int
   {
     const bool f64 = (m->info.smooth_kind == GNX_SMOOTH_CRF);
     if ((rc = ws_reserve(ctx, f64 ? ctx->ws_b64 : ctx->ws_b32, nb * WA * (f64 ? 8 : 4))) != GNX_OK) return rc;
+    // a batch may also go through the rank image instead of B (infer_any_dev; the last, shorter batch may not)
+    if (!packed && ctx->tune.fuse_ranks != 0 && base_can_rank(m) && m->info.smooth_kind == GNX_SMOOTH_XGB &&
+        (rc = ws_reserve(ctx, ctx->ws_rank, gnx_rank_image_bytes(nb, (int)m->info.W, m->info.A))) != GNX_OK) return rc;
   }
   hipStream_t sc = ctx->stream, si = nbuf == 2 ? ctx->s_in : ctx->stream, so = nbuf == 2 ? ctx->s_out : ctx->stream;
   const uint8_t* hsrc = (const uint8_t*)src;

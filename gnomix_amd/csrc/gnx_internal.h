@@ -58,6 +58,8 @@ struct gnx_tune {
   int gnofix_impl = 0;                  // GNX_GNOFIX_IMPL=f32: the float32-strip kernel (k_gnofix_f32) even where the rank kernel runs
   int gnofix_aux = 1;                   // GNX_GNOFIX_AUX=0: the input-only pre-passes of k_gnofix on the context stream instead of beside the smoother
   int gnofix_threads = 0;               // GNX_GNOFIX_T: threads per individual of k_gnofix (192, 256, 384, 512)
+  int fuse_ranks = 1;                   // GNX_FUSE_RANKS=0: gnx_infer_dev keeps float32 B between k_base_logistic_i8 and k_smooth_xgb_h32 instead of
+                                        // the rank image the base pass's flush writes (A/B runs and tests; the outputs are bit-identical)
   int debug = 0;                        // GNX_DEBUG
 };
 
@@ -154,7 +156,16 @@ struct BaseLRLaunch {
   float* b32;
   double* b64;
   unsigned long long* dbg = nullptr;  // development (GNX_DEBUG & 2, k_base_logistic_p2f): per block 16 cycle counters (where the waves' time goes)
+  // optional rank image for k_smooth_xgb_h32 (k_base_logistic_i8, one column tile only): rk16[n / 32][w][a][n % 32] = the 16-bit rank
+  // (gnx_rank.h, the smoother's table) of the float32 probability b32 would hold; one 64-byte row per (haplotype block, window,
+  // class), ceil(N / 32) blocks; positions of haplotypes >= N are never written
+  uint16_t* rk16 = nullptr;
+  const float* rk_thr = nullptr;
+  const GnxRankEntry* rk_lut = nullptr;
+  int32_t rk_K = 0, rk_bits = 0, rk_steps = 0;
 };
+// bytes of BaseLRLaunch::rk16
+inline size_t gnx_rank_image_bytes(int64_t N, int W, int A) { return (size_t)((N + 31) / 32) * 32 * (size_t)W * (size_t)A * sizeof(uint16_t); }
 
 // ---- xgb smoother (k_smooth_xgb.hip) ----------------------------------------------------------------
 // Trees are re-ordered class-major and every tree is expanded to a complete binary tree of depth D >= 1,
@@ -285,6 +296,7 @@ struct SmoothXGBLaunch {
   float* marg;       // (A, N*W) class-major margin scratch of the rank kernel (coalesced parking)
   double* proba64;   // optional widened copy
   int32_t* labels;   // optional
+  const uint16_t* rk16 = nullptr;  // k_smooth_xgb_h32 only: the ranks of B in blocks of 32 haplotypes (BaseLRLaunch::rk16); B is then not read
 };
 
 
@@ -561,6 +573,8 @@ hipError_t gnx_launch_x_to_gt2(const int8_t* X, int64_t N, int64_t ldx, int64_t 
                                int64_t ldg, hipStream_t s);
 hipError_t gnx_launch_base_logistic(const BaseLRLaunch& L, int n_cu, hipStream_t s);
 hipError_t gnx_launch_base_logistic_i8(const BaseLRLaunch& L, int n_cu, const gnx_tune& tune, hipStream_t s);
+// BaseLRLaunch::rk16 is served by the default shapes of one column tile only (no GNX_LR_TUNE); otherwise the launcher refuses it
+bool gnx_base_logistic_i8_ranks(const BaseLRDev& d, const gnx_tune& tune);
 hipError_t gnx_launch_base_logistic_i8_dl(const BaseLRLaunch& L, int n_cu, const gnx_tune& tune, hipStream_t s);
 // 2-bit rows: L.X = packed matrix (gnx_pack_x layout), L.ldx = its row stride in bytes, L.last_row = zero-padded copy of packed row
 // N-1, L.h_win_chunk0/1 = HOST copies of d.win_run0/1; hipErrorNotSupported when no instantiation fits

@@ -25,6 +25,7 @@
 
 #include "gnx_internal.h"
 #include "gnx_exp.h"
+#include "gnx_rank.h"
 
 namespace {
 
@@ -91,7 +92,8 @@ __device__ __forceinline__ double combine(const v4i (&acc)[LIMBS], int reg, doub
     }                                                                                                 \
   }
 
-template <int MT, int NT, int WAVES, int CPS>
+// RK: the flush also writes BaseLRLaunch::rk16, the rank of every float32 probability in the smoother's table
+template <int MT, int NT, int WAVES, int CPS, bool RK = false>
 __global__ __launch_bounds__(WAVES * 64) void k_base_logistic_i8(BaseLRLaunch L) {
   static_assert(CPS == 2, "a step is 2 chunks = 8 pieces of 16 SNPs");
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -239,6 +241,23 @@ __global__ __launch_bounds__(WAVES * 64) void k_base_logistic_i8(BaseLRLaunch L)
                 if (L.b64) L.b64[o + a] = v;
                 if (L.b32) L.b32[o + a] = (float)v;
               }
+              if constexpr (RK) {
+                // the lanes of a wave are consecutive haplotypes of one 32-block: per class they fill one row of the image.  Four
+                // classes at a time, so that their table gathers are in flight together (measured on the bench's shape: eight at a
+                // time, one round for A = 7, cost 0.07 ms more per launch — 198 VGPRs against 181 and twice the gathers queued at once)
+                constexpr int RNV = 4;
+                uint16_t* rrow = L.rk16 + (((size_t)(n >> 5) * W + w) * A) * 32 + (n & 31);
+                for (int a0 = 0; a0 < A; a0 += RNV) {
+                  float pf[RNV];
+                  uint32_t rr[RNV];
+#pragma unroll
+                  for (int i = 0; i < RNV; ++i) pf[i] = (float)(z[min(a0 + i, A - 1)] * rs);
+                  ranks<RNV>(L.rk_thr, L.rk_lut, L.rk_K, L.rk_bits, L.rk_steps, pf, rr);
+#pragma unroll
+                  for (int i = 0; i < RNV; ++i)
+                    if (a0 + i < A) rrow[(size_t)(a0 + i) * 32] = (uint16_t)rr[i];
+                }
+              }
             }
           }
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -273,7 +292,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_base_logistic_i8(BaseLRLaunch L)
 #undef GNX_STAGE_LOAD
 #undef GNX_STAGE_STORE
 
-template <int MT, int NT, int WAVES, int CPS>
+template <int MT, int NT, int WAVES, int CPS, bool RK = false>
 hipError_t launch(const BaseLRLaunch& L, int n_cu, const gnx_tune& tune, hipStream_t s) {
   BaseLRLaunch P = L;
   const int haps_per_block = WAVES * MT * 16;
@@ -311,8 +330,8 @@ hipError_t launch(const BaseLRLaunch& L, int n_cu, const gnx_tune& tune, hipStre
   const int n_ranges8 = ((n_ranges + 7) / 8) * 8;
   P.wch = wch;
   P.n_htiles = (int)gx;
-  GNX_LDS_OPTIN(lds, k_base_logistic_i8<MT, NT, WAVES, CPS>);
-  hipLaunchKernelGGL((k_base_logistic_i8<MT, NT, WAVES, CPS>), dim3((unsigned)(gx * n_ranges8)), dim3(WAVES * 64), lds, s, P);
+  GNX_LDS_OPTIN(lds, k_base_logistic_i8<MT, NT, WAVES, CPS, RK>);
+  hipLaunchKernelGGL((k_base_logistic_i8<MT, NT, WAVES, CPS, RK>), dim3((unsigned)(gx * n_ranges8)), dim3(WAVES * 64), lds, s, P);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess && tune.debug) std::fprintf(stderr, "k_base_logistic_i8<%d,%d,%d>: lds=%zu grid=%lld wch=%d max_chunks=%d max_wins=%d\n", MT, NT, WAVES, lds, (long long)(gx * n_ranges8), wch, P.max_chunks, P.max_wins);
   return e;
@@ -320,10 +339,17 @@ hipError_t launch(const BaseLRLaunch& L, int n_cu, const gnx_tune& tune, hipStre
 
 }  // namespace
 
+bool gnx_base_logistic_i8_ranks(const BaseLRDev& d, const gnx_tune& tune) { return d.NT == 1 && tune.lr_mt == 0; }
+
 hipError_t gnx_launch_base_logistic_i8(const BaseLRLaunch& L0, int n_cu, const gnx_tune& tune, hipStream_t s) {
   if (L0.N <= 0) return hipSuccess;
   BaseLRLaunch L = L0;
   const bool small = L.N <= 64 * 8;
+  if (L.rk16) {  // the rank image: the two default shapes of one column tile
+    if (!gnx_base_logistic_i8_ranks(L.d, tune) || !L.rk_thr || !L.rk_lut) return hipErrorInvalidValue;
+    L.flags = tune.lr_flags;
+    return small ? launch<1, 1, 4, 2, true>(L, n_cu, tune, s) : launch<2, 1, 8, 2, true>(L, n_cu, tune, s);
+  }
   // tuning / ablation knobs (development only): GNX_LR_TUNE="mt,waves,cps", GNX_LR_FLAGS=bitmask
   const int tm = tune.lr_mt, tw = tune.lr_waves;
   L.flags = tune.lr_flags;

@@ -111,6 +111,8 @@ __device__ __forceinline__ void walk_h32(uint32_t tb, const uint32_t* rb, float*
 }
 
 // gw = waves whose probabilities the LDS holds at once in the output transpose (a power of two, the launcher's choice)
+// IMG: the strip is copied from the rank image the base pass wrote (SmoothXGBLaunch::rk16) instead of ranked from B
+template <bool IMG>
 __global__ __launch_bounds__(THREADS, 8) void k_smooth_xgb_h32(SmoothXGBLaunch L, int gw) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   const int A = L.A, W = L.W, S = L.S, pad = (S + 1) / 2;
@@ -130,7 +132,43 @@ __global__ __launch_bounds__(THREADS, 8) void k_smooth_xgb_h32(SmoothXGBLaunch L
   // Only a haplotype's first and last window block touch the reflection; a block whose slots all lie inside the chromosome reads
   // its strip as ONE run of P * A elements per haplotype (element rr of the strip is element rr of the run): no slide_src, no
   // clamps of the slot, no index arithmetic per element.  blockIdx.x decides, so the branch is uniform.
-  {
+  if constexpr (IMG) {
+    // The image holds the ranks already, one 64-byte row of the block's 32 haplotypes per (window, class): row (q, a) of the strip
+    // is the rows of its two source windows interleaved.  Four threads per strip row, 8 haplotypes each: two 16-byte loads, two
+    // 16-byte LDS writes (64 lanes = 2 KB in a run: no conflicts).  The source windows are uniform over a row, so the reflection
+    // costs nothing per element; a thread's rows are THREADS / 4 apart, so (q, a) advance by a fixed step.
+    constexpr int RPI = THREADS / 4;                // strip rows per iteration of the block
+    const int n_rows = ((P + 1) / 2) * A;
+    const uint16_t* img = L.rk16 + (size_t)hb * W * A * HB + (tid & 3) * 8;
+    const int dq = RPI / A, da = RPI - dq * A;
+    int row = tid >> 2;
+    int q = row / A, a = row - q * A;
+    for (int it = 0; it < (n_rows + RPI - 1) / RPI; ++it, row += RPI) {
+      const bool ok = row < n_rows;
+      const int qc = ok ? q : 0, ac = ok ? a : 0;  // clamped: loads stay unconditional
+      const int s0 = slide_src(min(w0 + 2 * qc, W + 2 * pad - 1), W, pad);
+      const int s1 = slide_src(min(w0 + 2 * qc + 1, W + 2 * pad - 1), W, pad);
+      const u32x4 x = *reinterpret_cast<const u32x4*>(img + ((size_t)s0 * A + ac) * HB);
+      const u32x4 y = *reinterpret_cast<const u32x4*>(img + ((size_t)s1 * A + ac) * HB);
+      u32x4 lo4, hi4;  // haplotypes 0-3 and 4-7 of the thread's eight: rank(2q) | rank(2q + 1) << 16
+      lo4.x = (x.x & 0xffffu) | (y.x << 16);
+      lo4.y = (x.x >> 16) | (y.x & 0xffff0000u);
+      lo4.z = (x.y & 0xffffu) | (y.y << 16);
+      lo4.w = (x.y >> 16) | (y.y & 0xffff0000u);
+      hi4.x = (x.z & 0xffffu) | (y.z << 16);
+      hi4.y = (x.z >> 16) | (y.z & 0xffff0000u);
+      hi4.z = (x.w & 0xffffu) | (y.w << 16);
+      hi4.w = (x.w >> 16) | (y.w & 0xffff0000u);
+      if (ok) {
+        u32x4* dst = reinterpret_cast<u32x4*>(strip + (size_t)row * 128 + (tid & 3) * 32);
+        dst[0] = lo4;
+        dst[1] = hi4;
+      }
+      a += da;
+      q += dq;
+      if (a >= A) { a -= A; ++q; }
+    }
+  } else {
     constexpr int NV = 4;
     const int per_h = P * A;
     const int hl = (wave & 1) * 16 + (lane >> 2);
@@ -321,7 +359,12 @@ hipError_t gnx_launch_smooth_xgb_h32(const SmoothXGBLaunch& L, hipStream_t s) {
   while (gw > 1 && (size_t)HB * ((size_t)(gw * WPW * L.A) | 1) * 4 > lds) gw >>= 1;
   if ((size_t)HB * ((size_t)(gw * WPW * L.A) | 1) * 4 > lds) return hipErrorInvalidValue;
   const dim3 grid((unsigned)((L.W + WPB - 1) / WPB), (unsigned)((L.N + HB - 1) / HB));
-  GNX_LDS_OPTIN(lds, k_smooth_xgb_h32);
-  hipLaunchKernelGGL(k_smooth_xgb_h32, grid, dim3(THREADS), lds, s, L, gw);
+  if (L.rk16) {
+    GNX_LDS_OPTIN(lds, k_smooth_xgb_h32<true>);
+    hipLaunchKernelGGL(k_smooth_xgb_h32<true>, grid, dim3(THREADS), lds, s, L, gw);
+  } else {
+    GNX_LDS_OPTIN(lds, k_smooth_xgb_h32<false>);
+    hipLaunchKernelGGL(k_smooth_xgb_h32<false>, grid, dim3(THREADS), lds, s, L, gw);
+  }
   return hipGetLastError();
 }

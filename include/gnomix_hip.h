@@ -367,6 +367,11 @@ int gnx_model_export_prepared(gnx_model* model, void* buf, int64_t cap, int64_t*
  * b_f32 is what the XGB smoother consumes (src/Smooth/utils.py:20), b_f64 what the reference returns. */
 int gnx_base_predict(gnx_model* model, const int8_t* X, int64_t N, int64_t ldx, float* b_f32, double* b_f64);
 int gnx_base_predict_dev(gnx_model* model, const int8_t* dX, int64_t N, int64_t ldx, float* d_b_f32, double* d_b_f64);
+/* The logistic pass with the rank image gnx_infer_dev hands the tree smoother in place of B (tests): d_rk16 holds
+ * ceil(N / 32) * 32 * W * A uint16, [n / 32][w][a][n % 32] = the rank of the float32 probability in the smoother's threshold
+ * table (NaN: 0xFFFF); positions of haplotypes >= N are not written.  d_b_f32 may be NULL.  GNX_EUNSUPPORTED for models whose
+ * base pass writes no ranks (any base but the int8 logistic pass of one column tile, any smoother without a rank table). */
+int gnx_base_predict_ranks_dev(gnx_model* model, const int8_t* dX, int64_t N, int64_t ldx, float* d_b_f32, uint16_t* d_rk16);
 
 /* Smoother.predict_proba / predict: B (N, W, A) (float64 if b_is_f64 else float32) ->
  * proba (N, W, A) and labels (N, W) (argmax, first max wins).  Any output may be NULL.
