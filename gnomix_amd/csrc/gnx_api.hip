@@ -106,10 +106,6 @@ static void read_tune(gnx_tune& t) {
   if (const char* e = std::getenv("GNX_LR_TUNE")) std::sscanf(e, "%d,%d", &t.lr_mt, &t.lr_waves);
   t.lr_flags = geti("GNX_LR_FLAGS", 0);
   t.lr_dl = geti("GNX_LR_DL", -1);
-  t.lr_flat = geti("GNX_LR_FLAT", -1);
-  t.lr_ws = geti("GNX_LR_WS", 0);
-  t.lr_w512 = geti("GNX_LR_W512", 0);
-  t.lr_ws_pw = geti("GNX_LR_WS_PW", 2);
   t.lr_nbuf = geti("GNX_LR_NBUF", 0);
   t.lr_p2 = geti("GNX_LR_P2", 1);
   t.p2_decline = geti("GNX_P2_DECLINE", 0);
@@ -119,7 +115,7 @@ static void read_tune(gnx_tune& t) {
   if (const char* e = std::getenv("GNX_SM_TUNE")) std::sscanf(e, "%d,%d", &t.smf_rpl, &t.smf_nw);
   if (const char* e = std::getenv("GNX_CRF_FLAGS")) t.crf_flags = atoi(e);
   if (const char* e = std::getenv("GNX_LDS_PAD")) std::sscanf(e, "%d,%d", &t.lr_lds_pad, &t.sm_lds_pad);
-  if (const char* e = std::getenv("GNX_CRF_IMPL")) t.crf_impl = !std::strcmp(e, "scan") ? 1 : !std::strcmp(e, "row") ? 2 : !std::strcmp(e, "lanes") ? 3 : !std::strcmp(e, "quad") ? 4 : !std::strcmp(e, "mm") ? 5 : 0;
+  if (const char* e = std::getenv("GNX_CRF_IMPL")) t.crf_impl = !std::strcmp(e, "scan") ? 1 : !std::strcmp(e, "row") ? 2 : !std::strcmp(e, "lanes") ? 3 : 0;
   t.forest_threads = geti("GNX_FOREST_T", 0);
   t.forest_wrun = geti("GNX_FOREST_WRUN", 0);
   t.forest_halves = geti("GNX_FOREST_H", 0);
@@ -138,13 +134,7 @@ extern "C" {
 
 int gnx_abi_version(void) { return GNX_ABI_VERSION; }
 
-int gnx_build_flags(void) {
-#ifdef GNX_EXPERIMENTS
-  return GNX_BUILD_EXPERIMENTS;
-#else
-  return 0;
-#endif
-}
+int gnx_build_flags(void) { return 0; }
 
 // HIP maps streams onto 4 hardware queues by default and two streams on one queue serialise; a context uses up to five (see
 // gnomix_amd/_lib.py: load).  Effective when the runtime has not been initialised yet; an embedding application that has already
@@ -447,14 +437,23 @@ int gnx_model_get_info(const gnx_model* m, gnx_model_info* out) {
 // ---- base ------------------------------------------------------------------------------------------
 // the logistic pass can rank its probabilities for k_smooth_xgb_h32 while it still holds them (BaseLRLaunch::rk16): the int8 kernel
 // of one column tile, with the smoother's rank table
+// the int8 logistic pass takes the LDS-direct kernel (k_base_logistic_i8_dl) for >= 2 column tiles unless GNX_LR_DL says otherwise
+static bool base_takes_dl(const gnx_model* m) {
+  const int dl = m->ctx->tune.lr_dl;
+  return dl < 0 ? m->lr.NT >= 2 : dl != 0;
+}
+
 static bool base_can_rank(const gnx_model* m) {
-  const gnx_tune& t = m->ctx->tune;
   if (m->info.base_kind != GNX_BASE_LOGISTIC || !m->lr_i8 || !m->xgb.rk_thr || !m->xgb.rk_lut) return false;
-#ifdef GNX_EXPERIMENTS
-  if (t.lr_ws || t.lr_w512 || (t.lr_flat > 0 && m->lr.V8F)) return false;
-#endif
-  const bool dl = t.lr_dl < 0 ? m->lr.NT >= 2 : t.lr_dl != 0;
-  return !dl && gnx_base_logistic_i8_ranks(m->lr, t);
+  return !base_takes_dl(m) && gnx_base_logistic_i8_ranks(m->lr, m->ctx->tune);
+}
+
+// the context's side stream and its fork / join events, created on first use
+static int aux_stream(gnx_ctx* ctx) {
+  if (ctx->s_aux) return GNX_OK;
+  HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->s_aux, hipStreamNonBlocking));
+  for (int b = 0; b < 2; ++b) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_aux[b], hipEventDisableTiming));
+  return GNX_OK;
 }
 
 static int base_predict_dev(gnx_model* m, const int8_t* dX, int64_t N, int64_t ldx, float* d_b32, double* d_b64, uint16_t* d_rk16);
@@ -505,10 +504,7 @@ static int base_predict_dev(gnx_model* m, const int8_t* dX, int64_t N, int64_t l
       L.rpair = (double*)ctx->ws_rpair.p;
       L.rpair_haps = haps;
     }
-    if (!ctx->s_aux) {
-      HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->s_aux, hipStreamNonBlocking));
-      for (int b = 0; b < 2; ++b) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_aux[b], hipEventDisableTiming));
-    }
+    if ((rc = aux_stream(ctx)) != GNX_OK) return rc;
     L.aux = ctx->s_aux; L.ev_fork = ctx->ev_aux[0]; L.ev_join = ctx->ev_aux[1]; L.n_cu = ctx->n_cu;
     HIPCHK(ctx, gnx_launch_covrsk(L, ctx->stream));
     return GNX_OK;
@@ -529,10 +525,9 @@ static int base_predict_dev(gnx_model* m, const int8_t* dX, int64_t N, int64_t l
     const bool v2 = m->forest.nodes2 && ctx->tune.forest_impl != 1 && (!L.rf_leafval || L.A <= 32) &&
                     gnx_forest2_lds_bytes(L.A, gnx_forest_ring_words(L.width_last), L.max_trees, L.D, L.rf_leafval != nullptr) <= (size_t)160 * 1024;
     if (v2) {
-      if (!ctx->s_aux) {  // the one wider last window (a grid of N / 128 blocks) runs beside the main grid on a side stream
-        HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->s_aux, hipStreamNonBlocking));
-        for (int b = 0; b < 2; ++b) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_aux[b], hipEventDisableTiming));
-      }
+      // the one wider last window (a grid of N / 128 blocks) runs beside the main grid on a side stream
+      const int rc = aux_stream(ctx);
+      if (rc != GNX_OK) return rc;
       HIPCHK(ctx, gnx_launch_base_forest2(L, m->forest.nodes2, ctx->n_cu, ctx->tune, ctx->stream, ctx->s_aux, ctx->ev_aux[0], ctx->ev_aux[1]));
     }
     else HIPCHK(ctx, gnx_launch_base_forest(L, ctx->n_cu, ctx->tune, ctx->stream));
@@ -563,14 +558,8 @@ static int base_predict_dev(gnx_model* m, const int8_t* dX, int64_t N, int64_t l
   }
   ProfScope ps(ctx, GNX_K_BASE_LOGISTIC);
   if (m->lr_i8) {
-    const bool dl = ctx->tune.lr_dl < 0 ? m->lr.NT >= 2 : ctx->tune.lr_dl != 0;
     hipError_t e = hipErrorNotSupported;
-#ifdef GNX_EXPERIMENTS  // make EXPERIMENTS=1: the measured-slower structures of DESIGN.md 5.2 (scripts/dev/rejected/)
-    if (ctx->tune.lr_ws) e = gnx_launch_base_logistic_i8_ws(L, ctx->n_cu, ctx->tune, ctx->stream);
-    if (e == hipErrorNotSupported && ctx->tune.lr_w512) e = gnx_launch_base_logistic_i8_w512(L, ctx->n_cu, ctx->tune, ctx->stream);
-    if (e == hipErrorNotSupported && ctx->tune.lr_flat > 0 && m->lr.V8F) e = gnx_launch_base_logistic_i8_fl(L, ctx->n_cu, ctx->tune, ctx->stream);
-#endif
-    if (e == hipErrorNotSupported && dl) e = gnx_launch_base_logistic_i8_dl(L, ctx->n_cu, ctx->tune, ctx->stream);
+    if (base_takes_dl(m)) e = gnx_launch_base_logistic_i8_dl(L, ctx->n_cu, ctx->tune, ctx->stream);
     if (e == hipErrorNotSupported) e = gnx_launch_base_logistic_i8(L, ctx->n_cu, ctx->tune, ctx->stream);  // > 2 column tiles
     HIPCHK(ctx, e);
   }
@@ -594,7 +583,7 @@ int gnx_smooth_predict_dev(gnx_model* m, const void* dB, int b_is_f64, int64_t N
 static bool smooth_takes_h32(const gnx_model* m, int64_t N) {
   if (m->info.smooth_kind != GNX_SMOOTH_XGB || !m->xgb.rk_packed) return false;
   const int64_t blocks = (N + 31) / 32 * ((m->info.W + GNX_H32_WPB - 1) / GNX_H32_WPB);
-  return (m->xgb.impl == 5 || (m->xgb.impl == 6 && blocks >= m->ctx->n_cu)) && gnx_smooth_h32_fits(m->xgb, m->info.A, m->info.S);
+  return (m->xgb.impl == GNX_SM_H32 || (m->xgb.impl == GNX_SM_AUTO && blocks >= m->ctx->n_cu)) && gnx_smooth_h32_fits(m->xgb, m->info.A, m->info.S);
 }
 
 static int smooth_predict_dev(gnx_model* m, const void* dB, int b_is_f64, int64_t N, float* d_p32, double* d_p64, int32_t* d_lab,
@@ -638,39 +627,14 @@ static int smooth_raw_dev(gnx_model* m, const void* dB, int b_is_f64, int64_t N,
     L.B = dB; L.b_is_f64 = b_is_f64; L.N = N;
     L.W = (int32_t)m->info.W; L.A = m->info.A; L.S = m->info.S;
     L.d = m->xgb; L.proba = d_p32; L.proba64 = d_p64; L.labels = d_lab;
-#ifdef GNX_EXPERIMENTS
-    const bool h64 = m->xgb.rk_packed && m->xgb.impl == 2 && gnx_smooth_h64_waves(m->xgb, m->info.A, m->info.S) > 0;
-    if (m->xgb.impl == 2 && !h64) return fail(ctx, GNX_EUNSUPPORTED, "GNX_SMOOTH_IMPL=h64: the model's strip does not fit the LDS");
-#else
-    [[maybe_unused]] constexpr bool h64 = false;
-#endif
     if (m->xgb.rk_packed) {
-      const size_t n_pad = (size_t)((N + 63) / 64 * 64) * m->info.W * m->info.A;   // h64 parks whole 64-haplotype lines
+      // k_smooth_xgb_h32 parks margins in whole 32-haplotype blocks (class stride ceil(N / 32) * 32 * W floats): N is padded, here to 64
+      const size_t n_pad = (size_t)((N + 63) / 64 * 64) * m->info.W * m->info.A;
       int rc = ws_reserve(ctx, ctx->ws_marg, n_pad * sizeof(float));
       if (rc != GNX_OK) return rc;
       L.marg = (float*)ctx->ws_marg.p;
-#ifdef GNX_EXPERIMENTS
-      if (h64 && (rc = ws_reserve(ctx, ctx->ws_rank, gnx_smooth_h64_rank_bytes(N, L.W, L.A, L.S))) != GNX_OK) return rc;
-#endif
     }
-#ifdef GNX_EXPERIMENTS
-    const bool bs = m->xgb.impl == 4 && gnx_smooth_bs_fits(m->xgb, m->info.A, m->info.S);
-    if (bs) {  // the rank pre-pass parks one 16-bit counter index per probability
-      int rc = ws_reserve(ctx, ctx->ws_marg, gnx_smooth_bs_scratch_bytes(N, L.W, L.A));
-      if (rc != GNX_OK) return rc;
-    }
-#endif
     ProfScope ps(ctx, GNX_K_SMOOTH_XGB);
-#ifdef GNX_EXPERIMENTS
-    if (bs) {
-      HIPCHK(ctx, gnx_launch_smooth_xgb_bs(L, (uint16_t*)ctx->ws_marg.p, ctx->n_cu, ctx->tune, ctx->stream));
-      return GNX_OK;
-    }
-#endif
-#ifdef GNX_EXPERIMENTS
-    if (h64) HIPCHK(ctx, gnx_launch_smooth_xgb_h64(L, (uint16_t*)ctx->ws_rank.p, ctx->tune, ctx->stream));
-    else
-#endif
     if (m->xgb.rk_packed) {
       // lane = haplotype, 32 per half-wave (k_smooth_xgb_h32) where the model has its tables and two blocks fit a CU's LDS; every
       // other shape silently takes the rank kernel with pointer nodes.  GNX_SMOOTH_IMPL=h32 forces it for any batch.
@@ -681,7 +645,7 @@ static int smooth_raw_dev(gnx_model* m, const void* dB, int b_is_f64, int64_t N,
         HIPCHK(ctx, gnx_launch_smooth_xgb_h32(L, ctx->stream));
         return GNX_OK;
       }
-      if (L.d.impl == 5 || L.d.impl == 6) L.d.impl = 3;
+      if (L.d.impl == GNX_SM_H32 || L.d.impl == GNX_SM_AUTO) L.d.impl = GNX_SM_RK_PTR;
       HIPCHK(ctx, gnx_launch_smooth_xgb_rk(L, ctx->tune, ctx->stream));
     } else HIPCHK(ctx, gnx_launch_smooth_xgb(L, ctx->tune, ctx->stream));
     return GNX_OK;

@@ -38,13 +38,10 @@ struct gnx_tune {
   int p2_decline = 0;                   // GNX_P2_DECLINE=1 (tests): the 2-bit launcher reports "no instantiation fits" -> the widening fallback runs
   int lr_p2 = 1;                        // GNX_LR_P2=0: packed (2-bit) input is widened to int8 in HBM and run through the int8 kernels
                                         // instead of k_base_logistic_p2 (A/B runs; the outputs are bit-identical)
-  int lr_flat = -1;                     // GNX_LR_FLAT: 1 = flat column tiles (k_base_logistic_i8_fl) wherever built, 0 = never
-  int lr_w512 = 0;                      // GNX_LR_W512=1: 512 rows per block, 64-SNP steps (k_base_logistic_i8_w512)
-  int lr_ws = 0, lr_ws_pw = 2;          // GNX_LR_WS=1: wave-specialised kernel (k_base_logistic_i8_ws); GNX_LR_WS_PW: producer waves (2, 4)
   int sm_nw = 0;                        // GNX_SM_NW: waves per block of the rank smoother
   int sm_pair = 1;                      // GNX_SM_PAIR=0: one tree at a time per lane in the rank smoother (default: two)
   int smf_rpl = 0, smf_nw = 0;          // GNX_SM_TUNE="rpl,nw": float smoother
-  int crf_impl = 0;                     // GNX_CRF_IMPL=scan|row|lanes (default: row for up to 16 labels, lanes above); quad in the EXPERIMENTS build
+  int crf_impl = 0;                     // GNX_CRF_IMPL=scan|row|lanes (default: row for up to 16 labels, lanes above)
   int crf_flags = 0;                    // GNX_CRF_FLAGS bit 0: row kernel computes psi itself instead of reading the pre-pass's (slower)
   int forest_threads = 0;               // GNX_FOREST_T
   int forest_wrun = 0;                  // GNX_FOREST_WRUN: windows per block of the forest bases
@@ -90,7 +87,7 @@ struct gnx_ctx {
   hipStream_t s_in = nullptr, s_out = nullptr;
   hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
   gnx_devbuf ws_pk, ws_xu, ws_xu2, ws_psi;  // ws_xu2: int8 rows widened from packed rows that themselves live in ws_xu
-  gnx_devbuf ws_rank;  // k_smooth_ranks -> k_smooth_xgb_h64
+  gnx_devbuf ws_rank;  // the rank image between the logistic pass and k_smooth_xgb_h32 (BaseLRLaunch::rk16)
   gnx_devbuf ws_fb, ws_fb_body;  // gnx_write_fb_dev: probabilities / lengths / tables, and the file's body as text
   gnx_devbuf ws_gt2, ws_src, ws_gt2o;  // file path (gnx_api_vcf.hip): variant-major 2-bit genotypes, column map, phased rows
   // profiling
@@ -107,7 +104,6 @@ struct gnx_ctx {
 struct BaseLRDev {
   const double* V = nullptr;        // f64 path: [n_chunks][16 steps][NT][64 lanes]
   const int8_t* V8 = nullptr;       // i8 path: [n_chunks][NT][7 limbs][64 lanes][16 bytes] balanced base-256 digits
-  const int8_t* V8F = nullptr;      // i8 path, flat column tiles (k_base_logistic_i8_fl): [n_chunks][NF][64 lanes][16 bytes], column q = slot * 7 + limb
   const double* wscale = nullptr;   // i8 path: [W] 2^-f_w
   const double* icpt = nullptr;     // [W][A]
   const int32_t* chunk_j0 = nullptr;     // [n_chunks] first real SNP of the chunk
@@ -118,7 +114,6 @@ struct BaseLRDev {
   int32_t n_chunks = 0;
   int32_t R = 0;   // windows simultaneously active = column slots
   int32_t NT = 0;  // 16-column tiles
-  int32_t NF = 0;  // flat column tiles of V8F (0: not built)
   int32_t max_piece_chunks = 0;  // longest piece, in chunks
   // 2-bit-native pass (k_base_logistic_p2.hip): the same pieces walked in RUNS of 256 SNPs (64 packed bytes per haplotype row,
   // dword-aligned: a piece starts at SNP b0 & ~15, the up to 15 SNPs before b0 meet zero weights); one run = 4 MFMA entries
@@ -192,12 +187,6 @@ struct SmoothXGBDev {
   int32_t rk_K = 0, rk_steps = 0, rk_stride = 0, rk_tree_bytes = 0, rk_n_groups = 0, rk_max_group = 0;
   int32_t rk_bits = 0;                   // log2 of rk_lut's bucket count; rk_steps = bisections behind an entry (0: none needed)
   int32_t rk_rpl = 0;                    // 64-window segments per strip the node offsets were laid out for
-  // lane = haplotype copy for k_smooth_xgb_h64 (same ranks, rk_thr / rk_lut): per tree 2^D nodes of 8 bytes {byte offset of the
-  // feature's slot = (s * A + a) * 128, rank field} (heap slot 0 unused) followed by 2^D float leaves, padded to 16 bytes
-  const uint8_t* h8_packed = nullptr;
-  const int32_t* h8_group_tree0 = nullptr;
-  const int32_t* h8_group_class = nullptr;
-  int32_t h8_tree_bytes = 0, h8_n_groups = 0, h8_max_group = 0;
   // pointer-node copy for k_smooth_xgb_rk<.., PTR> (same strip, ranks and offsets as rk_*): per tree 2^D slots of 8 bytes
   // {w0 = rank field << 16 | strip offset, w1 = address of the left child | address of the right child << 16} (addresses relative
   // to the staging group's first byte; children of the last level = the leaves) followed by 2^D float leaves; slot 0 carries
@@ -206,7 +195,7 @@ struct SmoothXGBDev {
   const int32_t* rp_group_tree0 = nullptr;
   const int32_t* rp_group_class = nullptr;
   int32_t rp_tree_bytes = 0, rp_n_groups = 0, rp_max_group = 0;
-  int32_t impl = 0;                      // 1 rk, 2 h64, 3 rk with pointer nodes, 5 h32, 6 unset: h32 for batches that fill the chip, else 3 (GNX_SMOOTH_IMPL at model load)
+  int32_t impl = 0;                      // a GnxSmoothImpl (below), from GNX_SMOOTH_IMPL at model load
   // pointer-node copy for k_smooth_xgb_h32 (depth 4 only; lane = haplotype, 32 per half-wave; same ranks, rk_thr / rk_lut).  The
   // strip is [slot pair][class][32 haplotypes] dwords, slot 2q in the low half and 2q + 1 in the high half.  Per tree 320 bytes:
   // 16 node slots of 8 bytes for windows at an EVEN strip position (w0 = rank field << 16 | byte offset of slot s of class a,
@@ -221,31 +210,14 @@ struct SmoothXGBDev {
   // s * A + a in the [class][gf_pitch] u16 tile) followed by 2^D float leaves; class-major tree order (class_tree0)
   const uint32_t* gf_packed = nullptr;
   int32_t gf_pitch = 0, gf_max_class = 0;
-  // bit-sliced copy for k_smooth_xgb_bs (ensembles of depth <= 4; NULL otherwise), trees in the same class-major order, every tree
-  // a complete depth-4 heap.  The kernel never walks: per chunk of bs_wc windows it sorts each class's base probabilities once
-  // (per-class ranks -> counting sort), keeps for every prefix length n of that order the bitmap "window is NOT among the n
-  // smallest" (rows of the table G), and a node (class a, threshold k, window offset s) is the row n = #{p < threshold} shifted by
-  // s: 32 windows per 32-bit operation.  Node j (heap 1..15) of a tree = words 2j, 2j+1 of its 32-word block:
-  //   w0 = (s & 31) | (LDS byte address of the node's counter) << 16   (byte 1: zero)
-  //   w1 = LDS byte address of word s >> 5 of class a's row 0 (rows are GnxBsLayout::rb bytes apart)
-  const uint32_t* bs_nodes = nullptr;    // [n_trees][32]
-  const float* bs_leaves = nullptr;      // [n_trees][16]
-  const float* bs_thr = nullptr;         // per-class sorted distinct finite thresholds: class c = [bs_uoff[c], bs_uoff[c+1])
-  const uint32_t* bs_lut = nullptr;      // [A][1024] first | (last << 16) candidate per 1/1024-wide bucket, relative to the class
-  const int32_t* bs_uoff = nullptr;      // [A+1]
-  const int32_t* bs_binoff = nullptr;    // [A+1] first counter of class c (ranks 0..K_c, then the NaN / outside-the-chromosome bin)
-  const int32_t* bs_class_tree0 = nullptr;  // [A+1]
-  int32_t bs_steps = 0, bs_nbins = 0, bs_wc = 0, bs_nthr = 0, bs_maxbins = 0;
 };
-
-// LDS map of k_smooth_xgb_bs (bytes from the block's first LDS byte, which the kernel checks to be address 0: the node words carry
-// absolute addresses).  wp = padded windows per chunk (<= 255: counters are bytes), nr = wp + 1 rows per class, rw words per row
-// (one beyond the last real one: a shifted read takes two), nseg segments of sl prefix lengths the rows are built in.
-struct GnxBsLayout {
-  int32_t wp, nr, rw, rb, nbins, hist_bytes, off_cnt, off_hist, off_P, off_bin, off_pi, off_seg, off_wtot, nseg, sl, total;
-  uint32_t inv_sl;  // ceil(2^32 / sl): n / sl = umulhi(n, inv_sl) for n < 256
+// SmoothXGBDev::impl: the kernel that serves a model with rank tables
+enum GnxSmoothImpl : int32_t {
+  GNX_SM_RK_HEAP = 1,  // "rk": k_smooth_xgb_rk, heap-index nodes
+  GNX_SM_RK_PTR = 3,   // "rp" or any other name: k_smooth_xgb_rk with pointer nodes where the shape allows
+  GNX_SM_H32 = 5,      // "h32": k_smooth_xgb_h32 for any batch
+  GNX_SM_AUTO = 6,     // unset: h32 for batches that fill the chip, else GNX_SM_RK_PTR
 };
-GnxBsLayout gnx_bs_layout(int A, int S, int wc, int nbins);  // k_smooth_xgb_bs.hip
 
 // 32-bit words per tree of SmoothXGBDev::gf_packed (2^D node words in heap order, slot 0 unused, then 2^D float leaves: the leaf of
 // heap index j is word j) and the zero trees that follow the last one (k_gnofix walks past a lane's range without clamping)
@@ -316,11 +288,6 @@ struct SmoothCRFLaunch {
   int32_t* labels;        // optional
   int32_t norm_mask;      // k_smooth_crf_ck takes the forward scale at windows t with (t & norm_mask) == norm_mask (0, 1, 3 or 7: gnx_build_crf)
 };
-
-#ifdef GNX_EXPERIMENTS
-hipError_t gnx_launch_smooth_crf_mm(const SmoothCRFLaunch& L, hipStream_t s);   // scripts/dev/rejected/k_smooth_crf_mm.hip: products on the float64 MFMA, 16 haplotypes per wave, A <= 16
-hipError_t gnx_launch_smooth_crf_quad(const SmoothCRFLaunch& L, hipStream_t s);  // scripts/dev/rejected/k_smooth_crf_quad.hip: four lanes per haplotype, A <= 12
-#endif
 
 // ---- cnn smoother (k_smooth_cnn.hip) -----------------------------------------------------------------
 struct SmoothCNNLaunch {
@@ -579,14 +546,6 @@ hipError_t gnx_launch_base_logistic_i8_dl(const BaseLRLaunch& L, int n_cu, const
 // 2-bit rows: L.X = packed matrix (gnx_pack_x layout), L.ldx = its row stride in bytes, L.last_row = zero-padded copy of packed row
 // N-1, L.h_win_chunk0/1 = HOST copies of d.win_run0/1; hipErrorNotSupported when no instantiation fits
 hipError_t gnx_launch_base_logistic_p2(const BaseLRLaunch& L, int n_cu, const gnx_tune& tune, hipStream_t s);
-#ifdef GNX_EXPERIMENTS  // scripts/dev/rejected/ (make EXPERIMENTS=1)
-hipError_t gnx_launch_base_logistic_i8_w512(const BaseLRLaunch& L, int n_cu, const gnx_tune& tune, hipStream_t s);
-hipError_t gnx_launch_base_logistic_i8_ws(const BaseLRLaunch& L, int n_cu, const gnx_tune& tune, hipStream_t s);
-hipError_t gnx_launch_base_logistic_i8_fl(const BaseLRLaunch& L, int n_cu, const gnx_tune& tune, hipStream_t s);
-hipError_t gnx_launch_smooth_xgb_h64(const SmoothXGBLaunch& L, uint16_t* Rk, const gnx_tune& tune, hipStream_t s);
-int gnx_smooth_h64_waves(const SmoothXGBDev& d, int A, int S);            // 0: the strip does not fit the LDS
-size_t gnx_smooth_h64_rank_bytes(int64_t N, int W, int A, int S);
-#endif
 hipError_t gnx_launch_fb_len(const float* d_proba, int64_t N, int64_t W, int A, uint8_t* d_len, unsigned long long* d_line_len, hipStream_t s);
 hipError_t gnx_launch_fb_emit(const float* d_proba, int64_t N, int64_t W, int A, const uint8_t* d_len, const char* d_pb, const int64_t* d_po,
                               const int64_t* d_line_off, char* d_body, hipStream_t s);
@@ -597,13 +556,6 @@ hipError_t gnx_launch_smooth_xgb_rk(const SmoothXGBLaunch& L, const gnx_tune& tu
 // hipErrorInvalidValue before it launches anything)
 bool gnx_smooth_h32_fits(const SmoothXGBDev& d, int A, int S);
 hipError_t gnx_launch_smooth_xgb_h32(const SmoothXGBLaunch& L, hipStream_t s);
-#ifdef GNX_EXPERIMENTS
-// bit-sliced tree smoother (scripts/dev/rejected/k_smooth_xgb_bs.hip, GNX_SMOOTH_IMPL=bs); bins = gnx_smooth_bs_scratch_bytes() of
-// device scratch (the rank pre-pass's output)
-hipError_t gnx_launch_smooth_xgb_bs(const SmoothXGBLaunch& L, uint16_t* bins, int n_cu, const gnx_tune& tune, hipStream_t s);
-size_t gnx_smooth_bs_scratch_bytes(int64_t N, int W, int A);
-bool gnx_smooth_bs_fits(const SmoothXGBDev& d, int A, int S);
-#endif
 hipError_t gnx_launch_smooth_rows(const SmoothXGBDev& d, const float* rows, int64_t R, int32_t F, int32_t A,
                                   float* proba, hipStream_t s);
 hipError_t gnx_launch_pack_bits(const int8_t* X, int64_t N, int64_t ldx, int64_t C, int64_t ctx, int64_t nwp,

@@ -289,25 +289,6 @@ int gnx_build_lr(gnx_model* m, const gnx_model_desc* d) {
     if (ph) rc = dev_upload_raw(m, blob_v8, (size_t)ph->v8_bytes, &m->lr.V8, 64);
     else rc = gnx_dev_upload(m, V8, &m->lr.V8, 64);
     if (rc != GNX_OK) return rc;
-#ifdef GNX_EXPERIMENTS
-    // flat column tiles for k_base_logistic_i8_fl: column q = slot * 7 + limb, ceil(NC * 7 / 16) tiles instead of NT * 7
-    // (A = 12 at the default context: 11 instead of 14); an experiment that measured slower (see the kernel's header): built only
-    // when GNX_LR_FLAT=1 asks for it at model load
-    const int NF = (int)((NC * 7 + 15) / 16);
-    if (!ph && NF < NT * 7 && NF >= 8 && NF <= 11 && A <= 16 && std::getenv("GNX_LR_FLAT") && std::atoi(std::getenv("GNX_LR_FLAT")) > 0) {
-      std::vector<int8_t> V8F(n_chunks * (size_t)NF * 64 * 16, 0);
-      for (size_t c = 0; c < n_chunks; ++c)
-        for (int ft = 0; ft < NF; ++ft)
-          for (int ln = 0; ln < 64; ++ln) {
-            const int q = ft * 16 + (ln & 15), slot = q / 7, l = q - 7 * slot;
-            if (slot >= NC) continue;
-            const int8_t* src = &V8[(((c * NT + (size_t)(slot / 16)) * 7 + (size_t)l) * 64 + (size_t)((ln & ~15) + slot % 16)) * 16];
-            std::copy(src, src + 16, &V8F[((c * NF + (size_t)ft) * 64 + (size_t)ln) * 16]);
-          }
-      if ((rc = gnx_dev_upload(m, V8F, &m->lr.V8F, 64)) != GNX_OK) return rc;
-      m->lr.NF = NF;
-    }
-#endif
     if ((rc = gnx_dev_upload(m, wscale, &m->lr.wscale)) != GNX_OK) return rc;
     // ---- the same weights for the 2-bit-native pass (k_base_logistic_p2.hip): the pieces walked in dword-aligned runs of 256 SNPs
     // (a piece [b0, b1) starts at SNP b0 & ~15: the up to 15 SNPs before b0 and everything from b1 on meet zero weights).
@@ -543,8 +524,21 @@ static void tree_fill_rk(const gnx_model_desc* d, int32_t o, int32_t nid, uint32
   tree_fill_rk(d, o, leaf ? nid : d->right[o + nid], 2 * j + 1, depth + 1, D, U, stride, nodes, leaves);
 }
 
+// staging groups of the trees in `order` (class-major): a new group when the class changes or the group holds G trees;
+// tree0[g] = first tree of group g (one entry beyond the last group: order.size()), cls[g] = its class
+static void staging_groups(const std::vector<int32_t>& order, const int32_t* tree_class, int G, std::vector<int32_t>& tree0,
+                           std::vector<int32_t>& cls) {
+  int in_group = 0, cur = -1;
+  for (size_t k = 0; k < order.size(); ++k) {
+    const int c = tree_class[order[k]];
+    if (c != cur || in_group == G) { tree0.push_back((int32_t)k); cls.push_back(c); in_group = 0; cur = c; }
+    ++in_group;
+  }
+  tree0.push_back((int32_t)order.size());
+}
+
 static int build_xgb_rk(gnx_model* m, const gnx_model_desc* d, const std::vector<int32_t>& order, int D) {
-  const char* impl = std::getenv("GNX_SMOOTH_IMPL");  // default: 16-bit ranks with pointer nodes; "rk" heap-index nodes, "h64" lane = haplotype, "f32" float features
+  const char* impl = std::getenv("GNX_SMOOTH_IMPL");  // default: 16-bit ranks with pointer nodes; "rk" heap-index nodes, "h32" lane = haplotype, "f32" float features; any other name = the default's rank kernel
   if (impl && std::string(impl) == "f32") return GNX_OK;
   const int A = d->A, S = d->S;
   std::vector<float> U;
@@ -581,15 +575,7 @@ static int build_xgb_rk(gnx_model* m, const gnx_model_desc* d, const std::vector
   if (const char* e = std::getenv("GNX_RK_GROUP_BYTES")) group_bytes = std::max(tree_bytes, std::min(8192, std::atoi(e)));
   const int G = std::max(1, group_bytes / tree_bytes);
   std::vector<int32_t> group_tree0, group_class;
-  {
-    int in_group = 0, cur = -1;
-    for (size_t k = 0; k < order.size(); ++k) {
-      const int c = d->tree_class[order[k]];
-      if (c != cur || in_group == G) { group_tree0.push_back((int32_t)k); group_class.push_back(c); in_group = 0; cur = c; }
-      ++in_group;
-    }
-    group_tree0.push_back((int32_t)order.size());
-  }
+  staging_groups(order, d->tree_class, G, group_tree0, group_class);
   std::vector<uint8_t> packed(order.size() * (size_t)tree_bytes, 0);
   for (size_t k = 0; k < order.size(); ++k) {
     uint8_t* tb = packed.data() + k * tree_bytes;
@@ -605,13 +591,9 @@ static int build_xgb_rk(gnx_model* m, const gnx_model_desc* d, const std::vector
   m->xgb.rk_K = K; m->xgb.rk_bits = rt.bits; m->xgb.rk_steps = steps; m->xgb.rk_stride = stride; m->xgb.rk_tree_bytes = tree_bytes;
   m->xgb.rk_n_groups = (int32_t)group_class.size(); m->xgb.rk_max_group = G; m->xgb.rk_rpl = rpl;
   // measured (chr22, 10 000 haplotypes, MI355X): rk 1.83 ms; h64 2.22 ms + 0.23 ms of rank pre-pass — conflict-free, and slower
-  // (DESIGN.md 4.2b): the rank kernel stays the default, h64 is what GNX_SMOOTH_IMPL=h64 selects
+  // (DESIGN.md 4.2b): the rank kernel stayed, h64 was removed from the tree
   // (round 3, same inputs: rk 1.83 ms, pointer nodes 1.78 ms, bit-identical: default where the shape allows, "rk" = heap-index nodes)
-#ifdef GNX_EXPERIMENTS
-  m->xgb.impl = (impl && std::string(impl) == "h64") ? 2 : (impl && std::string(impl) == "rk") ? 1 : 3;
-#else
-  m->xgb.impl = (impl && std::string(impl) == "rk") ? 1 : 3;
-#endif
+  m->xgb.impl = (impl && std::string(impl) == "rk") ? GNX_SM_RK_HEAP : GNX_SM_RK_PTR;
   // ---- the same trees for k_gnofix: heap-index nodes whose offsets address a [class][pitch] tile of 2S+2 window positions ----
   if ((size_t)A * (2 * S + 2) * 2 <= 65535) {
     const int pitch = 2 * S + 2;
@@ -632,15 +614,7 @@ static int build_xgb_rk(gnx_model* m, const gnx_model_desc* d, const std::vector
     const int tbp = 12 << D;
     const int Gp = std::max(2, (4096 / tbp) & ~1);  // even: trees are walked in pairs
     std::vector<int32_t> gp_tree0, gp_class;
-    {
-      int in_group = 0, cur = -1;
-      for (size_t k = 0; k < order.size(); ++k) {
-        const int c = d->tree_class[order[k]];
-        if (c != cur || in_group == Gp) { gp_tree0.push_back((int32_t)k); gp_class.push_back(c); in_group = 0; cur = c; }
-        ++in_group;
-      }
-      gp_tree0.push_back((int32_t)order.size());
-    }
+    staging_groups(order, d->tree_class, Gp, gp_tree0, gp_class);
     std::vector<uint8_t> pp(order.size() * (size_t)tbp, 0);
     std::vector<uint32_t> nodes((size_t)1 << D);
     std::vector<float> leaves((size_t)1 << D);
@@ -676,15 +650,7 @@ static int build_xgb_rk(gnx_model* m, const gnx_model_desc* d, const std::vector
       if (strip + 4 * (size_t)tb3 <= (size_t)80 * 1024) G3 = std::min(GNX_H32_MAX_GROUP, (int)((((size_t)80 * 1024 - strip) / 2) / tb3) & ~1);
     }
     std::vector<int32_t> g3_tree0, g3_class;
-    {
-      int in_group = 0, cur = -1;
-      for (size_t k = 0; k < order.size(); ++k) {
-        const int c = d->tree_class[order[k]];
-        if (c != cur || in_group == G3) { g3_tree0.push_back((int32_t)k); g3_class.push_back(c); in_group = 0; cur = c; }
-        ++in_group;
-      }
-      g3_tree0.push_back((int32_t)order.size());
-    }
+    staging_groups(order, d->tree_class, G3, g3_tree0, g3_class);
     std::vector<uint8_t> p3(order.size() * (size_t)tb3, 0);
     std::vector<uint32_t> nodes(16);
     std::vector<float> leaves(16);
@@ -718,161 +684,11 @@ static int build_xgb_rk(gnx_model* m, const gnx_model_desc* d, const std::vector
     m->xgb.h3_n_groups = (int32_t)g3_class.size(); m->xgb.h3_max_group = G3;
     // measured (chr22, A = 7, 10 000 haplotypes, MI355X): faster than the rank kernel -> what an unset GNX_SMOOTH_IMPL
     // runs for batches that fill the chip (gnx_api.hip); "h32" forces it, "rp" / "rk" keep the rank kernel
-    if (!impl || !*impl) m->xgb.impl = 6;
-    else if (std::string(impl) == "h32") m->xgb.impl = 5;
+    if (!impl || !*impl) m->xgb.impl = GNX_SM_AUTO;
+    else if (std::string(impl) == "h32") m->xgb.impl = GNX_SM_H32;
   }
-#ifdef GNX_EXPERIMENTS
-  // ---- the same trees for k_smooth_xgb_h64 (lane = haplotype): pointer nodes whose w0 carries the feature's SLOT s * A + a --------
-  if (D >= 2 && D <= 6 && (size_t)S * A < 65536) {
-    const int tb8 = 12 << D;
-    // a staging group = as many trees of one class as the LDS holds beside the 16-wave strip (two buffers): one block per CU means
-    // nothing covers a block barrier, so there should be few of them (chr22 / A = 7: a class = 100 trees = one group, 7 barriers
-    // instead of 35); a multiple of the trees walked side by side, at most 32 KB (staging registers)
-    int G8 = std::max(4, (4096 / tb8) & ~3);
-    {
-      const size_t strip16 = (size_t)(16 * 3 + S - 1) * A * 128;
-      if (strip16 + 2 * (size_t)G8 * tb8 <= (size_t)160 * 1024) {
-        int per_class = 0;
-        std::vector<int> cnt(A, 0);
-        for (size_t k = 0; k < order.size(); ++k) per_class = std::max(per_class, ++cnt[d->tree_class[order[k]]]);
-        const int fit = (int)((((size_t)160 * 1024 - strip16) / 2) / tb8) & ~3;
-        G8 = std::max(G8, std::min({fit, (32768 / tb8) & ~3, (per_class + 3) & ~3}));
-      }
-    }
-    std::vector<int32_t> g8_tree0, g8_class;
-    {
-      int in_group = 0, cur = -1;
-      for (size_t k = 0; k < order.size(); ++k) {
-        const int c = d->tree_class[order[k]];
-        if (c != cur || in_group == G8) { g8_tree0.push_back((int32_t)k); g8_class.push_back(c); in_group = 0; cur = c; }
-        ++in_group;
-      }
-      g8_tree0.push_back((int32_t)order.size());
-    }
-    std::vector<uint8_t> p8(order.size() * (size_t)tb8, 0);
-    std::vector<uint32_t> nodes((size_t)1 << D);
-    std::vector<float> leaves((size_t)1 << D);
-    size_t g = 0;
-    for (size_t k = 0; k < order.size(); ++k) {
-      while ((size_t)g8_tree0[g + 1] <= k) ++g;
-      const uint32_t base = (uint32_t)(k - (size_t)g8_tree0[g]) * (uint32_t)tb8;
-      std::fill(nodes.begin(), nodes.end(), 0u);
-      tree_fill_rk(d, d->tree_off[order[k]], 0, 1, 0, D, U, stride, nodes.data(), leaves.data());  // (field << 16) | strip offset
-      for (uint32_t j = 1; j < (1u << D); ++j) {
-        // the rank layout's byte offset (a * stride + s) * 2 back to (s, a); an early leaf's word (offset 0) reads slot 0
-        const uint32_t h = (nodes[j] & 0xffffu) / 2, a = h / (uint32_t)stride, sidx = h - a * (uint32_t)stride;
-        nodes[j] = (nodes[j] & 0xffff0000u) | (sidx * (uint32_t)A + a);
-      }
-      uint32_t* o = reinterpret_cast<uint32_t*>(p8.data() + k * tb8);
-      auto kids = [&](uint32_t j) {
-        const uint32_t l = 2 * j < (1u << D) ? base + 8u * (2 * j) : base + (8u << D) + 4u * (2 * j - (1u << D));
-        const uint32_t step = 2 * j < (1u << D) ? 8u : 4u;
-        return l | ((l + step) << 16);
-      };
-      for (uint32_t j = 2; j < (1u << D); ++j) { o[2 * j] = nodes[j]; o[2 * j + 1] = kids(j); }
-      o[0] = nodes[2]; o[1] = nodes[3]; o[2] = nodes[1]; o[3] = kids(2);
-      memcpy(p8.data() + k * tb8 + ((size_t)8 << D), leaves.data(), sizeof(float) << D);
-    }
-    if ((rc = gnx_dev_upload(m, p8, &m->xgb.h8_packed, 64)) != GNX_OK) return rc;
-    if ((rc = gnx_dev_upload(m, g8_tree0, &m->xgb.h8_group_tree0)) != GNX_OK) return rc;
-    if ((rc = gnx_dev_upload(m, g8_class, &m->xgb.h8_group_class)) != GNX_OK) return rc;
-    m->xgb.h8_tree_bytes = tb8; m->xgb.h8_n_groups = (int32_t)g8_class.size(); m->xgb.h8_max_group = G8;
-  }
-#endif
   return GNX_OK;
 }
-
-#ifdef GNX_EXPERIMENTS  // the bit-sliced smoother is parked (scripts/dev/rejected/k_smooth_xgb_bs.hip): its tables are built in that build only
-// bit-sliced trees (layout in gnx_internal.h: SmoothXGBDev::bs_nodes); Uc = per-class sorted thresholds, Y = the kernel's LDS map
-static void tree_fill_bs(const gnx_model_desc* d, int32_t o, int32_t nid, uint32_t j, int depth, const std::vector<std::vector<float>>& Uc,
-                         const std::vector<int32_t>& binoff, const GnxBsLayout& Y, uint32_t* words, float* leaves) {
-  const bool leaf = d->left[o + nid] == -1;
-  if (depth == 4) {
-    leaves[j - 16u] = d->cond[o + nid];
-    return;
-  }
-  // early leaf: both subtrees replicate the leaf, any node will do (class 0, rank field 0: row 0 = "every window goes right")
-  uint32_t a = 0, kf = 0, sw = 0;
-  if (!leaf) {
-    const float thr = d->cond[o + nid];
-    const int f = d->feat[o + nid], A = d->A;
-    a = (uint32_t)(f % A);
-    sw = (uint32_t)(f / A);
-    const std::vector<float>& U = Uc[a];
-    if (thr != thr || thr == -std::numeric_limits<float>::infinity()) kf = 0;                       // p < thr never holds
-    else if (thr == std::numeric_limits<float>::infinity()) kf = (uint32_t)U.size() + 1u;          // holds unless p is NaN
-    else kf = (uint32_t)(std::lower_bound(U.begin(), U.end(), thr) - U.begin()) + 1u;              // p < U[k] <=> rank(p) < k+1
-  }
-  const uint32_t cnt_addr = (uint32_t)Y.off_cnt + (uint32_t)binoff[a] + kf;
-  words[2 * j] = (sw & 31u) | (cnt_addr << 16);
-  words[2 * j + 1] = (uint32_t)Y.off_P + a * (uint32_t)(Y.nr * Y.rb) + (sw >> 5) * 4u;
-  tree_fill_bs(d, o, leaf ? nid : d->left[o + nid], 2 * j, depth + 1, Uc, binoff, Y, words, leaves);
-  tree_fill_bs(d, o, leaf ? nid : d->right[o + nid], 2 * j + 1, depth + 1, Uc, binoff, Y, words, leaves);
-}
-
-// k_smooth_xgb_bs: ensembles of depth <= 4 whose padded chunk fits byte counters and whose tables fit the LDS
-static int build_xgb_bs(gnx_model* m, const gnx_model_desc* d, const std::vector<int32_t>& order, int D) {
-  const char* impl = std::getenv("GNX_SMOOTH_IMPL");
-  if (impl && std::string(impl) == "f32") return GNX_OK;
-  const int A = d->A, S = d->S;
-  if (D > 4 || A > 16) return GNX_OK;
-  std::vector<std::vector<float>> Uc((size_t)A);
-  for (int t = 0; t < d->n_trees; ++t)
-    for (int32_t k = d->tree_off[t]; k < d->tree_off[t + 1]; ++k)
-      if (d->left[k] != -1 && std::isfinite(d->cond[k])) Uc[(size_t)(d->feat[k] % A)].push_back(d->cond[k]);
-  std::vector<int32_t> uoff((size_t)A + 1, 0), binoff((size_t)A + 1, 0);
-  std::vector<float> U;
-  for (int c = 0; c < A; ++c) {
-    std::vector<float>& u = Uc[(size_t)c];
-    std::sort(u.begin(), u.end());
-    u.erase(std::unique(u.begin(), u.end()), u.end());
-    if (u.empty()) u.push_back(0.5f);
-    if (u.size() > 60000) return GNX_OK;
-    U.insert(U.end(), u.begin(), u.end());
-    uoff[(size_t)c + 1] = (int32_t)U.size();
-    // ranks 0..K_c and the NaN bin (the class's LAST counter), padded to 16 bytes: a wave scans its class's counters as words
-    binoff[(size_t)c + 1] = binoff[(size_t)c] + (((int32_t)u.size() + 2 + 15) & ~15);
-  }
-  const int nbins = binoff[(size_t)A];
-  if (nbins > 65000) return GNX_OK;
-  int wc = 128;  // windows per chunk; counters are bytes: the padded chunk must stay below 256 windows
-  if (wc + S - 1 > 255 || gnx_bs_layout(A, S, wc, nbins).total > 160 * 1024) return GNX_OK;
-  const GnxBsLayout Y = gnx_bs_layout(A, S, wc, nbins);
-  std::vector<uint32_t> lut((size_t)A * 1024);
-  int steps = 0;
-  for (int c = 0; c < A; ++c) {
-    const std::vector<float>& u = Uc[(size_t)c];
-    const int K = (int)u.size();
-    for (int b = 0; b < 1024; ++b) {
-      const int lo = b == 0 ? 0 : (int)(std::lower_bound(u.begin(), u.end(), (float)b / 1024.0f) - u.begin());
-      const int hi = b == 1023 ? K : (int)(std::lower_bound(u.begin(), u.end(), (float)(b + 1) / 1024.0f) - u.begin());
-      lut[(size_t)c * 1024 + (size_t)b] = (uint32_t)lo | ((uint32_t)hi << 16);
-      int st = 0;
-      while ((1 << st) < hi - lo + 1) ++st;
-      steps = std::max(steps, st);
-    }
-  }
-  std::vector<uint32_t> nodes(order.size() * 32, 0u);
-  std::vector<float> leaves(order.size() * 16, 0.f);
-  for (size_t k = 0; k < order.size(); ++k)
-    tree_fill_bs(d, d->tree_off[order[k]], 0, 1, 0, Uc, binoff, Y, nodes.data() + k * 32, leaves.data() + k * 16);
-  std::vector<int32_t> ct0((size_t)A + 1, 0);
-  for (int t = 0; t < d->n_trees; ++t) ct0[(size_t)d->tree_class[t] + 1] += 1;
-  for (int c = 0; c < A; ++c) ct0[(size_t)c + 1] += ct0[(size_t)c];
-  int rc;
-  if ((rc = gnx_dev_upload(m, nodes, &m->xgb.bs_nodes, 128)) != GNX_OK) return rc;
-  if ((rc = gnx_dev_upload(m, leaves, &m->xgb.bs_leaves, 64)) != GNX_OK) return rc;
-  if ((rc = gnx_dev_upload(m, U, &m->xgb.bs_thr, 64)) != GNX_OK) return rc;
-  if ((rc = gnx_dev_upload(m, lut, &m->xgb.bs_lut)) != GNX_OK) return rc;
-  if ((rc = gnx_dev_upload(m, uoff, &m->xgb.bs_uoff)) != GNX_OK) return rc;
-  if ((rc = gnx_dev_upload(m, binoff, &m->xgb.bs_binoff)) != GNX_OK) return rc;
-  if ((rc = gnx_dev_upload(m, ct0, &m->xgb.bs_class_tree0)) != GNX_OK) return rc;
-  m->xgb.bs_steps = steps; m->xgb.bs_nbins = nbins; m->xgb.bs_wc = wc; m->xgb.bs_nthr = (int32_t)U.size();
-  for (int c = 0; c < A; ++c) m->xgb.bs_maxbins = std::max(m->xgb.bs_maxbins, binoff[(size_t)c + 1] - binoff[(size_t)c]);
-  if (impl && std::string(impl) == "bs") m->xgb.impl = 4;
-  return GNX_OK;
-}
-#endif  // GNX_EXPERIMENTS
 
 int gnx_build_xgb(gnx_model* m, const gnx_model_desc* d) {
   gnx_ctx* ctx = m->ctx;
@@ -933,9 +749,6 @@ int gnx_build_xgb(gnx_model* m, const gnx_model_desc* d) {
   m->info.n_trees = d->n_trees;
   m->info.tree_depth = D;
   if ((rc = build_xgb_rk(m, d, order, D)) != GNX_OK) return rc;
-#ifdef GNX_EXPERIMENTS
-  if ((rc = build_xgb_bs(m, d, order, D)) != GNX_OK) return rc;
-#endif
   return GNX_OK;
 }
 

@@ -6,7 +6,7 @@
 // shares an LDS bank.
 //
 // k_smooth_xgb_rk puts 64 consecutive WINDOWS of one haplotype on a wave, so lanes that took different branches gather their ranks
-// from unrelated addresses (a fifth of its LDS cycles are bank conflicts).  scripts/dev/rejected/k_smooth_xgb_h64.hip put 64
+// from unrelated addresses (a fifth of its LDS cycles are bank conflicts).  k_smooth_xgb_h64 (removed; sources at commit 8235b46) put 64
 // HAPLOTYPES on a wave: conflict-free, but its 109 KB strip left one 16-wave block per CU and the two pipes no longer overlapped.
 // `ds_read_u16` is banked per group of 32 lanes, so 32 haplotypes are enough: here lanes 0-31 and lanes 32-63 are the SAME 32
 // haplotypes at two neighbouring windows, and a dword of the strip holds two neighbouring strip slots of one haplotype:

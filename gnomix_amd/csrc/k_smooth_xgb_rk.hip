@@ -527,7 +527,7 @@ template <int RPL, int NWAVE>
 hipError_t launch(const SmoothXGBLaunch& L, bool pair, int lds_pad, hipStream_t s) {
   const dim3 grid((unsigned)((L.W + RPL * WS - 1) / (RPL * WS)), (unsigned)((L.N + NWAVE - 1) / NWAVE));
   // pointer nodes: depth 4, pair walks, and every node address must fit 16 bits
-  const bool ptr = L.d.impl == 3 && L.d.rp_packed && L.d.D == 4 && pair && RPL <= 3 && lds_bytes<NWAVE>(L.d, L.A, true) <= 65536;
+  const bool ptr = L.d.impl == GNX_SM_RK_PTR && L.d.rp_packed && L.d.D == 4 && pair && RPL <= 3 && lds_bytes<NWAVE>(L.d, L.A, true) <= 65536;
   size_t lds = lds_bytes<NWAVE>(L.d, L.A, ptr);
   if (lds > (size_t)160 * 1024) return hipErrorInvalidValue;
   lds = std::min(lds + (size_t)std::max(lds_pad, 0), (size_t)160 * 1024);

@@ -16,7 +16,7 @@ if [ "$1" = "build" ]; then
   HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}   # as gnomix_amd/csrc/Makefile
   TMPD=$(mktemp -d)
   FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -fno-fast-math -ffp-contract=off"
-  OBJS=$(ls *.o */*.o | grep -v -e '^gnx_api.o$' -e '^x_')   # the default build's objects (x_*: the EXPERIMENTS build's)
+  OBJS=$(ls *.o */*.o | grep -v -e '^gnx_api.o$')
   for v in 1 2; do
     $HIPCC $FLAGS -DGNX_FUSE_ABLATE=$v -c gnx_api.hip -o $TMPD/gnx_api_$v.obj || exit 1
     if [ $v = 1 ]; then OUT=$LIBA; else OUT=$LIBB; fi

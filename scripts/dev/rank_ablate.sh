@@ -12,7 +12,7 @@ if [ "$1" = "build" ]; then
   TMPO=$(mktemp -d)/k_smooth_xgb_h32_ablate.obj
   FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -fno-fast-math -ffp-contract=off"
   $HIPCC $FLAGS -DGNX_RANK_ABLATE -c k_smooth_xgb_h32.hip -o $TMPO || exit 1
-  OBJS=$(ls *.o */*.o | grep -v -e '^k_smooth_xgb_h32.o$' -e '^x_')   # the default build's objects (x_*: the EXPERIMENTS build's)
+  OBJS=$(ls *.o */*.o | grep -v -e '^k_smooth_xgb_h32.o$')
   $HIPCC --offload-arch=gfx950 -shared -o $ABL $OBJS $TMPO -Wl,-rpath,/opt/rocm/lib -Wl,--no-undefined -lpthread -lz
   exit $?
 fi

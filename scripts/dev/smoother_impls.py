@@ -1,4 +1,4 @@
-# the tree smoother of config 2 through its three kernels (GNX_SMOOTH_IMPL at model load): float, ranks (lane = window), h64 (lane = haplotype)
+# the tree smoother of config 2 through its kernels (GNX_SMOOTH_IMPL at model load): ranks (lane = window; heap-index and pointer nodes), h32 (lane = haplotype), float
 import os, sys, numpy as np, torch
 sys.path.insert(0, os.getcwd())
 import gnomix_amd
@@ -9,7 +9,7 @@ rng = np.random.RandomState(1)
 B = rng.dirichlet(np.ones(A) * 0.5, size=(N, W)).astype(np.float32)
 Bd = torch.from_numpy(B).cuda()
 ref = None
-for impl in os.environ.get("IMPLS", "rk,rp,h64,f32").split(","):
+for impl in os.environ.get("IMPLS", "rk,rp,h32,f32").split(","):
     os.environ["GNX_SMOOTH_IMPL"] = impl
     m = gnomix_amd.DeviceModel(d)
     p, l = m.smooth_predict_device(Bd); torch.cuda.synchronize()

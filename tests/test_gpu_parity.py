@@ -44,8 +44,8 @@ def _lr_data(ga, C, M, A, ctx, seed):
 def lr_impl(request, monkeypatch):
     """every shipped variant of the logistic pass on every geometry: exact int8-limb fixed point with register-staged loads
     (k_base_logistic_i8), the same arithmetic with LDS-direct loads (k_base_logistic_i8_dl), and f64 MFMA.  Launch knobs are read
-    once per context, so each variant gets a context of its own.  (The measured-slower structures of DESIGN.md 5.2 live under
-    scripts/dev/rejected/ and are built by `make EXPERIMENTS=1` only.)"""
+    once per context, so each variant gets a context of its own.  (The measured-slower structures of DESIGN.md 5.2 were removed from the
+    tree; their sources are at commit 8235b46.)"""
     from gnomix_amd import _lib
     monkeypatch.setenv("GNX_BASE_LR_IMPL", "f64" if request.param == "f64" else "i8")
     monkeypatch.setenv("GNX_LR_DL", "1" if request.param == "i8dl" else "0")
@@ -748,12 +748,6 @@ def test_smooth_rank_kernel_equals_float_kernel(ga, oracle, monkeypatch, W, A, S
         assert np.array_equal(pf, pr, equal_nan=True), rpl
         assert np.array_equal(lf, lr), rpl
     monkeypatch.delenv("GNX_RK_RPL")
-    # the bit-sliced kernel (k_smooth_xgb_bs: no walks; depth <= 4, other ensembles keep the rank kernel) — parked: `make EXPERIMENTS=1`
-    if ga.load_library().gnx_build_flags() & 1:
-        monkeypatch.setenv("GNX_SMOOTH_IMPL", "bs")
-        pr, lr = ga.DeviceModel(d).smooth_predict(B)
-        assert np.array_equal(pf, pr, equal_nan=True)
-        assert np.array_equal(lf, lr)
     finite = np.isfinite(B).all(axis=(1, 2))                                  # oracle as the third opinion
     T = _oracle_trees(oracle, d)
     p_ref, l_ref = oracle.smooth_xgb(T, B[finite], S)
@@ -761,53 +755,33 @@ def test_smooth_rank_kernel_equals_float_kernel(ga, oracle, monkeypatch, W, A, S
     _close_f32(pf[finite], p_ref)
 
 
-@pytest.mark.parametrize("W,A,S,rounds,depth,drop", [
-    (370, 7, 75, 37, 4, 0),      # chr22 shape: three chunks of 128 windows, the last one ragged; an odd tree-group tail
-    (127, 7, 31, 9, 4, 5),       # one chunk, shorter than 128 windows; classes with different numbers of trees
-    (129, 2, 5, 40, 3, 1),       # two classes, a second chunk of one window, shallow trees padded to depth 4
-    (1431, 12, 75, 3, 4, 7),     # chr1 / 12 ancestries: the 16-wave block
-    (300, 16, 129, 2, 2, 0),     # the widest smoother a 128-window chunk takes (padded chunk = 256 windows -> falls back), 16 classes
-    (260, 8, 127, 5, 4, 0),      # padded chunk = 254 windows: the widest smoother the byte counters take
-    (200, 16, 31, 2, 4, 3),      # 16 classes
-])
-def test_smooth_bitsliced_kernel_equals_rank_kernel(ga, monkeypatch, W, A, S, rounds, depth, drop):
-    """k_smooth_xgb_bs (sorted prefixes + bit-sliced node evaluation, gnomix_amd/csrc/k_smooth_xgb_bs.hip) never walks a tree; its
-    float32 margins are the same sums in the same order, so probabilities and labels must be BIT-identical to the rank kernel's,
-    whatever the chunking, the number of classes and trees per class, on thresholds hit exactly, NaN and infinities.
-    The kernel is parked (1.73 ms against the walk's 1.60 ms) under scripts/dev/rejected/ and linked by
-    `make -C gnomix_amd/csrc EXPERIMENTS=1` only: in the default build this test is skipped (GNX_SMOOTH_IMPL=bs does nothing there)."""
+def test_smooth_retired_impl_names_take_the_rank_kernel(ga, monkeypatch):
+    """GNX_SMOOTH_IMPL=bs and =h64 named kernels that are no longer in the tree: like any unrecognised name they select the rank
+    kernel with pointer nodes, so probabilities and labels are BIT-identical to GNX_SMOOTH_IMPL=rp, values exactly on a threshold,
+    one ulp off it, outside [0, 1], infinities and NaN included."""
     from gnomix_amd import synth
-    if not ga.load_library().gnx_build_flags() & 1:
-        pytest.skip("k_smooth_xgb_bs is linked by `make EXPERIMENTS=1` only")
-    rng = np.random.RandomState(W * 3 + A)
+    N, W, A, S = 5, 40, 3, 9
+    rng = np.random.RandomState(W + A)
     d = ga.GnxModelData(C=W * 10 + 3, M=10, A=A, S=S, context=5, smooth_kind="xgb")
-    T = synth.synthetic_trees(rounds, A, S * A, depth=depth, seed=W + 1, thr_lo=0.0, thr_hi=1.0, p_early_leaf=0.15)
-    if drop:                                                                  # the last classes get one tree less
-        n = len(T["tree_class"]) - drop
-        nn = int(T["tree_off"][n])
-        T = dict(tree_off=T["tree_off"][:n + 1], tree_class=T["tree_class"][:n],
-                 **{k: T[k][:nn] for k in ("left", "right", "feat", "cond")})
-    for k, v in T.items():
+    for k, v in synth.synthetic_trees(3, A, S * A, depth=4, seed=W, thr_lo=0.0, thr_hi=1.0, p_early_leaf=0.15).items():
         setattr(d, k, v)
-    N = 13
     B = rng.dirichlet(np.ones(A) * 0.4, size=(N, W)).astype(np.float32)
     thr = d.cond[d.left != -1]
     pick = rng.choice(thr, size=B.shape)
     m = rng.random_sample(B.shape)
-    B = np.where(m < 0.3, pick, B)
-    B = np.where((m >= 0.3) & (m < 0.4), np.nextafter(pick, np.float32(-1)), B)
-    special = np.array([0.0, 1.0, -0.25, 1.75, np.inf, -np.inf, np.nan, -0.0], np.float32)
+    B = np.where(m < 0.25, pick, B)                                            # exactly on a threshold
+    B = np.where((m >= 0.25) & (m < 0.35), np.nextafter(pick, np.float32(-1)), B)   # one ulp below
+    B = np.where((m >= 0.35) & (m < 0.45), np.nextafter(pick, np.float32(2)), B)    # one ulp above
+    special = np.array([0.0, 1.0, -0.25, 1.75, np.inf, -np.inf, np.nan, 1e-30, -0.0], np.float32)
     B = np.where(m > 0.97, rng.choice(special, size=B.shape), B).astype(np.float32)
-    B[:, : W // 3] = B[:, :1]                                                 # a tract: every window of it ties with every other
-    monkeypatch.setenv("GNX_SMOOTH_IMPL", "rk")
+    assert np.count_nonzero(np.isin(B, thr)) > 0
+    monkeypatch.setenv("GNX_SMOOTH_IMPL", "rp")
     pr, lr = ga.DeviceModel(d).smooth_predict(B)
-    monkeypatch.setenv("GNX_SMOOTH_IMPL", "bs")
-    dev = ga.DeviceModel(d)
-    pb, lb = dev.smooth_predict(B)
-    assert np.array_equal(pr, pb, equal_nan=True)
-    assert np.array_equal(lr, lb)
-    p64 = dev.smooth_predict(B.astype(np.float64))[0]                         # float64 B is narrowed exactly as the rank kernel does
-    assert np.array_equal(pr, p64, equal_nan=True)
+    for name in ("bs", "h64"):
+        monkeypatch.setenv("GNX_SMOOTH_IMPL", name)
+        p, lab = ga.DeviceModel(d).smooth_predict(B)
+        assert np.array_equal(pr, p, equal_nan=True), name
+        assert np.array_equal(lr, lab), name
 
 
 def test_forest_kernels_on_lgbm_and_catboost_models(ga, oracle, forest_ctx):
