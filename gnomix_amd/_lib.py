@@ -234,6 +234,8 @@ SYMBOLS = {
     "gnx_mode_filter": (C.c_int, [_VP, _VP, _VP, _I64, _I64, C.c_int32, _I64]),
     "gnx_label_runs_dev": (C.c_int, [_VP, _VP, _I64, _I64, _I64, _VP, _VP, _VP, _I64, C.POINTER(_I64)]),
     "gnx_label_runs": (C.c_int, [_VP, _VP, _I64, _I64, _I64, _VP, _VP, _VP, _I64, C.POINTER(_I64)]),
+    "gnx_ancestry_summary_dev": (C.c_int, [_VP, _VP, _I64, _VP, _I, _VP, _I64, _I64, C.c_int32, _VP, _VP, _VP, _VP, _VP]),
+    "gnx_ancestry_summary": (C.c_int, [_VP, _VP, _I64, _VP, _I, _VP, _I64, _I64, C.c_int32, _VP, _VP, _VP, _VP, _VP]),
     # include/gnomix_io.h: the file side
     "gnx_io_last_error": (C.c_char_p, []),
     "gnx_vcf_read": (C.c_int, [_VP, C.c_char_p, C.c_char_p, _I, C.POINTER(_VP)]),

@@ -132,14 +132,18 @@ class _Prefetch:
         return self._out
 
 
-def run_inference(base_args, model, snp_level=False, bed_file_output=False, verbose=False, timings=None, query=None, devices=None):
+def run_inference(base_args, model, snp_level=False, bed_file_output=False, verbose=False, timings=None, query=None, devices=None,
+                  global_ancestry_output=False):
     """gnomix.py:37-100 with the HIP model behind the same steps.  The query never becomes an (N, C) host matrix: the library
     parses the text into 2-bit rows (gnx_vcf_read), `column_map` keeps vcf_to_npy's bookkeeping (SNP intersection, REF flips,
     absent SNPs) as one int32 per model SNP, the GPU builds X and runs base + smoother (or Gnofix) on it, and the library
     formats .msp / .fb / the phased VCF.  `timings` (a dict) receives the seconds of each stage; `query` = a _Prefetch of
     vcfio.read_vcf started earlier (the command line parses the query while the GPU runtime starts and the model loads).
     `devices` = GPU ordinals (several: the individuals are cut over them, one context and one host thread each, the query parsed
-    once and the outputs written once: gnomix_amd/multi.py) or an existing multi.DeviceGroup; None = the model's own device."""
+    once and the outputs written once: gnomix_amd/multi.py) or an existing multi.DeviceGroup; None = the model's own device.
+    `global_ancestry_output` (config key inference.global_ancestry_output, off unless set): query_results.Q (global ancestry per
+    individual, hard calls) and query_results.tracts.tsv (tract statistics per haplotype and ancestry) as well, both with cM weights,
+    from the labels the .msp gets (Gnofix's when phasing), summarised on the device (gnx_ancestry_summary)."""
     from time import perf_counter as clock
     from . import postprocess as pp
     from . import vcfio
@@ -172,13 +176,15 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
         T["replicate_model"] = clock() - t0
         t0 = clock()
     try:
-        return _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out, T, t0, snp_level, bed_file_output, verbose)
+        return _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out, T, t0, snp_level, bed_file_output, verbose,
+                              global_ancestry_output)
     finally:
         if own_group is not None:
             own_group.close()
 
 
-def _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out, T, t0, snp_level, bed_file_output, verbose):
+def _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out, T, t0, snp_level, bed_file_output, verbose,
+                   global_ancestry_output=False):
     from time import perf_counter as clock
     from . import postprocess as pp
     from . import vcfio
@@ -224,6 +230,12 @@ def _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out,
         t0 = clock()
         pp.write_bed(output_path + "/" + "query_results_bed", meta, labels, samples, pop_order=model.population_order, ctx=model.dev.ctx)
         T["write_bed"] = clock() - t0
+    if global_ancestry_output:
+        t0 = clock()
+        summary = runner.ancestry_summary(labels, pp.window_weights(meta, "cM"))
+        pp.write_q(out_prefix, summary.hard, model.population_order, samples)
+        pp.write_tracts(out_prefix, summary, model.population_order, samples)
+        T["write_global_ancestry"] = clock() - t0
     return out_prefix
 
 
@@ -288,7 +300,8 @@ def main(argv=None):
             T = {"interpreter_and_imports": t_startup, "load_model": t_load}
         T.update(T_load)
         run_inference(base_args, model, snp_level=bool(inf.get("snp_level_inference")),
-                      bed_file_output=bool(inf.get("bed_file_output")), verbose=True, timings=T, query=query, devices=devices)
+                      bed_file_output=bool(inf.get("bed_file_output")), verbose=True, timings=T, query=query, devices=devices,
+                      global_ancestry_output=bool(inf.get("global_ancestry_output")))
         if os.environ.get("GNX_CLI_TIMING"):
             T["since_process_start"] = _since_process_start()
             sys.stderr.write("gnomix_amd timings (s): " + ", ".join("%s %.3f" % kv for kv in T.items()) + "\n")
@@ -448,7 +461,7 @@ def train_main(argv):
         print("Launching inference...")
         inf = config.get("inference") or {}
         run_inference(base_args, model, snp_level=bool(inf.get("snp_level_inference")), bed_file_output=bool(inf.get("bed_file_output")),
-                      verbose=True)
+                      verbose=True, global_ancestry_output=bool(inf.get("global_ancestry_output")))
     return 0
 
 

@@ -207,6 +207,32 @@ class HipGnomix:
         p, _ = self.dev.infer(X, want_proba=True, want_labels=False)
         return p
 
+    def global_ancestry(self, X, weights=None, soft=False):
+        """global ancestry proportions per individual, (N / 2, A) float64: the mean of the two haplotype rows of the weighted share
+        of each ancestry (weights (W,), e.g. postprocess.window_weights(meta, "cM"); None = every window counts the same).  Hard
+        calls come from the labels predict returns (mode_filter applied when set), soft=True from the probabilities predict_proba
+        returns; with a CUDA tensor neither leaves HBM and a CUDA tensor comes back."""
+        if X.shape[0] % 2:
+            raise ValueError(f"global_ancestry: X holds {X.shape[0]} haplotype rows, an individual has two")
+        mf = self.smooth.mode_filter
+        if resident.is_cuda(X):
+            import torch
+            pd = torch.float64 if self.dev.proba_dtype() == np.float64 else torch.float32
+            with resident.torch_stream(self.dev.ctx):
+                p, lab = self.dev.infer_device(resident.check_x(X, self.C, self.dev.ctx.device), want_proba=bool(soft), want_labels=True,
+                                               proba_dtype=pd)
+                if mf:
+                    lab = self.dev.mode_filter_device(lab, mf)
+                s = self.dev.ancestry_summary_device(lab, weights, p)
+                rows = s.soft if soft else s.hard
+                return (rows[0::2] + rows[1::2]) / 2
+        p, lab = self.dev.infer(X, want_proba=bool(soft), want_labels=True)
+        if mf:
+            lab = self.dev.mode_filter(lab, mf)
+        s = self.dev.ancestry_summary(lab, weights, p)
+        rows = s.soft if soft else s.hard
+        return (rows[0::2] + rows[1::2]) / 2
+
     def phase(self, X, B=None, verbose=False, **gnofix_kw):
         """Gnofix re-phasing (model.py:188-214): -> X_phased (N, C) int, Y_phased (N, W) int.  `gnofix_kw`: gnofix()'s search
         options (check_criterion, max_center_offset, non_lin_s, prob_comp, prior_switch_prob, padding, max_it); the reference's

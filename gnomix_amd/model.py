@@ -472,6 +472,34 @@ class DeviceModel:
                                                     self.A, int(size)))
         return out
 
+    def ancestry_summary(self, lab, weights=None, proba=None):
+        """global ancestry and tract statistics of (N, W) labels (and (N, W, A) probabilities) on the device (gnx_ancestry_summary;
+        gnomix_amd.postprocess.ancestry_summary) -> AncestrySummary of numpy arrays"""
+        from .postprocess import ancestry_summary
+        return ancestry_summary(self.ctx, lab, self.A, weights, proba)
+
+    def ancestry_summary_device(self, lab_t, weights=None, proba_t=None):
+        """the same on an (N, W) int32 CUDA tensor with contiguous rows (any row stride) and, optionally, a contiguous (N, W, A)
+        float32 / float64 CUDA tensor (gnx_ancestry_summary_dev) -> AncestrySummary of CUDA tensors; the weights are a host array"""
+        import torch
+        from .postprocess import AncestrySummary, _summary_weights
+        assert lab_t.is_cuda and lab_t.dtype == torch.int32 and lab_t.dim() == 2 and (lab_t.shape[1] == 0 or lab_t.stride(1) == 1)
+        N, W = lab_t.shape
+        if proba_t is not None:
+            assert proba_t.is_cuda and proba_t.dtype in (torch.float32, torch.float64) and proba_t.is_contiguous()
+            if tuple(proba_t.shape) != (N, W, self.A):
+                raise ValueError(f"proba must be (N={N}, W={W}, A={self.A}), got {tuple(proba_t.shape)}")
+        w = _summary_weights(weights, W)
+        self._bind_torch_stream()
+        new = lambda dt: torch.zeros((N, self.A), dtype=dt, device=lab_t.device)
+        hard, total, longest, count = new(torch.float64), new(torch.float64), new(torch.float64), new(torch.int32)
+        soft = new(torch.float64) if proba_t is not None else None
+        self.ctx.check(self.lib.gnx_ancestry_summary_dev(
+            self.ctx.h, lab_t.data_ptr(), lab_t.stride(0) if N > 1 else W, proba_t.data_ptr() if proba_t is not None else None,
+            int(proba_t is not None and proba_t.dtype == torch.float64), w.ctypes.data, N, W, self.A, hard.data_ptr(),
+            soft.data_ptr() if soft is not None else None, count.data_ptr(), total.data_ptr(), longest.data_ptr()))
+        return AncestrySummary(hard, soft, count, total, longest, w)
+
     def proba_dtype(self):
         """dtype of the probabilities this model's smoother returns: float64 for CRF and for calibrated output, else float32"""
         native64 = self.data.smooth_kind == "crf" or getattr(self, "calibrated", False)

@@ -198,6 +198,40 @@ class DeviceGroup:
         self._run(jobs)
         return p, lab
 
+    def ancestry_summary(self, lab, weights=None, proba=None):
+        """DeviceModel.ancestry_summary with the individuals cut over the group's devices: every device summarises its rows of the
+        host labels (and probabilities) into its rows of the shared result arrays -> AncestrySummary"""
+        from .postprocess import AncestrySummary, _summary_weights
+        lab = np.ascontiguousarray(lab, dtype=np.int32)
+        if lab.ndim != 2 or lab.shape[0] % 2:
+            raise ValueError(f"labels must be (N = 2 * individuals, W), got {lab.shape}")
+        N, W = lab.shape
+        A = self.A
+        w = _summary_weights(weights, W)
+        if proba is not None:
+            proba = np.asarray(proba)
+            if proba.dtype not in (np.float32, np.float64):
+                proba = proba.astype(np.float64)
+            proba = np.ascontiguousarray(proba)
+            if proba.shape != (N, W, A):
+                raise ValueError(f"proba must be (N={N}, W={W}, A={A}), got {proba.shape}")
+        hard, total, longest = (np.zeros((N, A), np.float64) for _ in range(3))
+        soft = np.zeros((N, A), np.float64) if proba is not None else None
+        count = np.zeros((N, A), np.int32)
+        jobs = []
+        for m, (i0, n) in zip(self.models, shard_individuals(N // 2, len(self.models))):
+            h0, nh = 2 * i0, 2 * n
+
+            def fn(m=m, h0=h0, nh=nh):
+                m.ctx.check(m.lib.gnx_ancestry_summary(
+                    m.ctx.h, lab[h0:].ctypes.data, W, proba[h0:].ctypes.data if proba is not None else None,
+                    int(proba is not None and proba.dtype == np.float64), w.ctypes.data, nh, W, A, hard[h0:].ctypes.data,
+                    soft[h0:].ctypes.data if soft is not None else None, count[h0:].ctypes.data, total[h0:].ctypes.data,
+                    longest[h0:].ctypes.data))
+            jobs.append((m, fn))
+        self._run(jobs)
+        return AncestrySummary(hard, soft, count, total, longest, w)
+
     def phase_gt2(self, G, N, src, out_cols=None, max_it=50, proba_dtype=None, out=None):
         """DeviceModel.phase_gt2 cut the same way -> (G_phased or None, proba, labels, n_switches)"""
         m0 = self.models[0]

@@ -158,6 +158,101 @@ def label_runs(ctx, labels):
     return counts, offsets, triples[:total.value]
 
 
+WEIGHT_KINDS = ("cM", "bp", "snps")
+
+
+def window_weights(meta, kind="cM"):
+    """(W,) float64 weights of the windows from the table write_msp prints (get_meta_data): "cM" = egpos - sgpos, "bp" = epos - spos,
+    "snps" = n snps"""
+    if kind == "cM":
+        return np.asarray(meta["egpos"], dtype=np.float64) - np.asarray(meta["sgpos"], dtype=np.float64)
+    if kind == "bp":
+        return (np.asarray(meta["epos"]).astype(np.int64) - np.asarray(meta["spos"]).astype(np.int64)).astype(np.float64)
+    if kind == "snps":
+        return np.asarray(meta["n snps"]).astype(np.float64)
+    raise ValueError(f"window_weights: kind must be one of {WEIGHT_KINDS}, got {kind!r}")
+
+
+class AncestrySummary:
+    """what ancestry_summary returns: (N, A) arrays hard, soft (None without probabilities), tract_total, tract_longest (float64)
+    and tract_count (int32), numpy arrays or CUDA tensors as the labels were; `weights` the (W,) float64 weights used"""
+    __slots__ = ("hard", "soft", "tract_count", "tract_total", "tract_longest", "weights")
+
+    def __init__(self, hard, soft, tract_count, tract_total, tract_longest, weights):
+        self.hard, self.soft, self.tract_count = hard, soft, tract_count
+        self.tract_total, self.tract_longest, self.weights = tract_total, tract_longest, weights
+
+
+def _summary_weights(weights, W):
+    if weights is None:
+        return np.ones(W, np.float64)
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.shape != (W,):
+        raise ValueError(f"weights must be (W={W},), got {w.shape}")
+    return w
+
+
+def ancestry_summary(ctx, labels, A, weights=None, proba=None):
+    """global ancestry proportions and tract statistics of (N, W) labels in [0, A) on the device (gnx_ancestry_summary):
+    hard[n, a] = share of the weights of row n's windows labelled a; soft[n, a] = the weighted mean of proba[n, :, a] (proba (N, W, A)
+    float32 / float64, optional); per ancestry the number of tracts, their total weight and the longest one -> AncestrySummary"""
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    if lab.ndim != 2:
+        raise ValueError(f"labels must be (N, W), got {lab.shape}")
+    N, W = lab.shape
+    w = _summary_weights(weights, W)
+    p = None
+    if proba is not None:
+        p = np.asarray(proba)
+        if p.dtype not in (np.float32, np.float64):
+            p = p.astype(np.float64)
+        p = np.ascontiguousarray(p)
+        if p.shape != (N, W, int(A)):
+            raise ValueError(f"proba must be (N={N}, W={W}, A={A}), got {p.shape}")
+    hard, total, longest = (np.zeros((N, int(A)), np.float64) for _ in range(3))
+    soft = np.zeros((N, int(A)), np.float64) if p is not None else None
+    count = np.zeros((N, int(A)), np.int32)
+    ctx.check(ctx.lib.gnx_ancestry_summary(ctx.h, lab.ctypes.data, W, p.ctypes.data if p is not None else None,
+                                           int(p is not None and p.dtype == np.float64), w.ctypes.data, N, W, int(A), hard.ctypes.data,
+                                           soft.ctypes.data if soft is not None else None, count.ctypes.data, total.ctypes.data,
+                                           longest.ctypes.data))
+    return AncestrySummary(hard, soft, count, total, longest, w)
+
+
+def _individuals(rows):
+    """(N, A) haplotype rows -> (N / 2, A): the mean of each individual's two rows"""
+    return (rows[0::2] + rows[1::2]) / 2
+
+
+def write_q(prefix, proportions, populations, samples, kind="hard calls", weights="cM"):
+    """<prefix>.Q: global ancestry per individual.  proportions (2 * len(samples), A) haplotype rows (AncestrySummary.hard or
+    .soft); an individual's value is the mean of its two rows, printed with five decimals"""
+    q = np.asarray(proportions, dtype=np.float64)
+    if q.ndim != 2 or q.shape != (2 * len(samples), len(populations)):
+        raise ValueError(f"proportions must be (2 * {len(samples)} haplotypes, {len(populations)} populations), got {q.shape}")
+    q = _individuals(q)
+    with open(prefix + ".Q", "w") as f:
+        f.write("#global ancestry, %s, weights: %s\n" % (kind, weights))
+        f.write("#sample\t" + "\t".join(str(p) for p in populations) + "\n")
+        for s, row in zip(samples, q):
+            f.write(str(s) + "\t" + "\t".join("%.5f" % v for v in row) + "\n")
+
+
+def write_tracts(prefix, summary, populations, samples):
+    """<prefix>.tracts.tsv: one line per haplotype (0, then 1) and ancestry (population order): number of tracts, their total
+    weight, the longest and the mean one (0 without tracts), lengths with five decimals"""
+    cnt, tot, lng = np.asarray(summary.tract_count), np.asarray(summary.tract_total), np.asarray(summary.tract_longest)
+    if cnt.shape != (2 * len(samples), len(populations)):
+        raise ValueError(f"the summary must hold (2 * {len(samples)} haplotypes, {len(populations)} populations), got {cnt.shape}")
+    with open(prefix + ".tracts.tsv", "w") as f:
+        f.write("sample\thaplotype\tancestry\tn_tracts\ttotal_cM\tlongest_cM\tmean_cM\n")
+        for i, s in enumerate(samples):
+            for h in (0, 1):
+                for a, pop in enumerate(populations):
+                    n, t = int(cnt[2 * i + h, a]), float(tot[2 * i + h, a])
+                    f.write("%s\t%d\t%s\t%d\t%.5f\t%.5f\t%.5f\n" % (s, h, pop, n, t, float(lng[2 * i + h, a]), t / n if n else 0.0))
+
+
 def write_lai(prefix, meta, labels, positions, samples, populations=None, n_threads=0, first_line=None):
     """<prefix>.lai — the bytes msp_to_lai writes from <prefix>.msp, from the labels themselves (gnx_write_lai): the .msp's first
     header line (built from `populations`, or given as `first_line`), "position" and the haplotype columns, then one line per query

@@ -37,6 +37,7 @@
  *                                                                          src/preprocess.py:37-82, gnomix.py:102-156
  *   gnx_mode_filter       <- Smoother.predict's mode_filter               src/Smooth/utils.py:31-46, src/Smooth/smooth.py:63-64
  *   gnx_label_runs        <- get_bed_data's walk over a haplotype column  src/postprocess.py:162-193
+ *   gnx_ancestry_summary  <- (no counterpart: the .Q table and the tract statistics users compute from an .msp)
  *
  * Conventions
  *   - return 0 (GNX_OK) or a negative GNX_E* code; the message is kept per context (gnx_last_error).
@@ -808,6 +809,34 @@ int gnx_label_runs_dev(gnx_ctx* ctx, const int32_t* d_labels, int64_t ldl, int64
                        int32_t* d_triples, int64_t capacity, int64_t* total);
 int gnx_label_runs(gnx_ctx* ctx, const int32_t* labels, int64_t ldl, int64_t N, int64_t W, int64_t* counts, int64_t* offsets,
                    int32_t* triples, int64_t capacity, int64_t* total);
+
+/* ---- global ancestry and tract summaries of the window labels (csrc/summary/k_ancestry_summary.hip) -----------------------------
+ * gnx_ancestry_summary: what an .msp is collapsed to first.  labels (N, W) int32 in [0, A), rows ld_labels >= W elements apart;
+ *   proba NULL or the smoother's (N, W, A) probabilities, float32 or float64 (proba_is_f64); weights a HOST array of W float64
+ *   window weights (NULL = all ones), e.g. the windows' lengths in cM.  Per row n and ancestry a, each an (N, A) array:
+ *     hard          float64  (sum of w[k] over the windows with labels[n, k] == a) / (sum of all w[k])
+ *     soft          float64  (sum of w[k] * proba[n, k, a]) / (sum of all w[k]); float32 values are widened before the multiply.
+ *                            NULL exactly when proba is NULL
+ *     tract_count   int32    number of maximal runs of label a in the row
+ *     tract_total   float64  the unnormalised numerator of hard
+ *     tract_longest float64  the largest sum of w over one such run (0 when there is none)
+ *   Any output but soft may be NULL (not wanted).  The float64 sums are taken in one fixed order that depends on W alone (stated in
+ *   the kernel file's header, restated in tests/summary_exact.py): two calls on the same input give the same bits.
+ *   GNX_EINVAL before the launch, nothing written: N < 0, W < 1, A < 1, ld_labels < W, a weight that is negative or not finite,
+ *     weights that sum to zero, soft and proba not both NULL or both given.
+ *   GNX_EUNSUPPORTED: A > GNX_SUMMARY_MAX_A or W > GNX_SUMMARY_MAX_W (a wave stages its row in LDS, one byte per label, four rows per
+ *     workgroup: 32 KB).
+ *   GNX_EINVAL after the launch: a label outside [0, A) was met.  Labels are only compared, never used as an index: such a label
+ *     counts for no ancestry (and ends a tract); everything else in the outputs is as stated.
+ *   N == 0: nothing launched.  Both forms synchronise the context stream once (the verdict on the labels is read back). */
+#define GNX_SUMMARY_MAX_A 32
+#define GNX_SUMMARY_MAX_W 8192
+int gnx_ancestry_summary_dev(gnx_ctx* ctx, const int32_t* d_labels, int64_t ld_labels, const void* d_proba, int proba_is_f64,
+                             const double* weights, int64_t N, int64_t W, int32_t A, double* d_hard, double* d_soft,
+                             int32_t* d_tract_count, double* d_tract_total, double* d_tract_longest);
+int gnx_ancestry_summary(gnx_ctx* ctx, const int32_t* labels, int64_t ld_labels, const void* proba, int proba_is_f64,
+                         const double* weights, int64_t N, int64_t W, int32_t A, double* hard, double* soft, int32_t* tract_count,
+                         double* tract_total, double* tract_longest);
 
 /* per-kernel device time, measured with hipEvents on the context stream around every launch */
 int gnx_profile_enable(gnx_ctx* ctx, int on);

@@ -38,6 +38,7 @@ MUST_BE_CLEAN = [
     r"k_rf_",
     r"k_confusion<",
     r"k_mode_filter", r"k_label_runs_",
+    r"k_ancestry_summary<",
 ]
 
 
