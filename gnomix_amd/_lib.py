@@ -16,6 +16,8 @@ SO_PATH = os.environ.get("GNX_LIBRARY") or os.path.join(_HERE, "libgnomix_hip.so
 
 GNX_ABI_VERSION = 16
 GNX_OK, GNX_EINVAL, GNX_ENOMEM, GNX_EHIP, GNX_EUNSUPPORTED, GNX_ESTATE, GNX_ESTALE = 0, -1, -2, -3, -4, -5, -6
+GNX_ROWS_INT8, GNX_ROWS_PACKED2 = 0, 1   # row_kind of gnx_ancestry_allele_counts / gnx_ancestry_dosage
+GNX_ALLELE_MAX_A = 32
 BASE_NONE, BASE_LOGISTIC, BASE_COVRSK_SVC, BASE_FOREST, BASE_RFOREST, BASE_KNN, BASE_NB, BASE_LDA = 0, 1, 2, 3, 4, 5, 6, 7
 SVC_KERNEL_SUBSTRINGS, SVC_KERNEL_POLY, SVC_KERNEL_ALL_LENGTHS, SVC_KERNEL_RBF = 0, 1, 2, 3
 SMOOTH_NONE, SMOOTH_XGB, SMOOTH_CRF, SMOOTH_CNN = 0, 1, 2, 3
@@ -236,6 +238,11 @@ SYMBOLS = {
     "gnx_label_runs": (C.c_int, [_VP, _VP, _I64, _I64, _I64, _VP, _VP, _VP, _I64, C.POINTER(_I64)]),
     "gnx_ancestry_summary_dev": (C.c_int, [_VP, _VP, _I64, _VP, _I, _VP, _I64, _I64, C.c_int32, _VP, _VP, _VP, _VP, _VP]),
     "gnx_ancestry_summary": (C.c_int, [_VP, _VP, _I64, _VP, _I, _VP, _I64, _I64, C.c_int32, _VP, _VP, _VP, _VP, _VP]),
+    "gnx_ancestry_allele_counts_dev": (C.c_int, [_VP, _VP, _I, _I64, _VP, _I64, _I64, _I64, _I64, _I64, C.c_int32, _VP, _VP, _VP, _I64, _I64]),
+    "gnx_ancestry_allele_counts": (C.c_int, [_VP, _VP, _I, _I64, _VP, _I64, _I64, _I64, _I64, _I64, C.c_int32, _VP, _VP, _VP, _I64, _I64]),
+    "gnx_ancestry_dosage_dev": (C.c_int, [_VP, _VP, _I, _I64, _VP, _I64, _I64, _I64, _I64, _I64, C.c_int32, C.c_int32, _VP, _I64, _VP, _I64]),
+    "gnx_ancestry_dosage": (C.c_int, [_VP, _VP, _I, _I64, _VP, _I64, _I64, _I64, _I64, _I64, C.c_int32, C.c_int32, _VP, _I64, _VP, _I64]),
+    "gnx_ancestry_allele_counts_gt2": (C.c_int, [_VP, _VP, _I64, _I64, _I64, _VP, _VP, _VP, _VP, _VP]),
     # include/gnomix_io.h: the file side
     "gnx_io_last_error": (C.c_char_p, []),
     "gnx_vcf_read": (C.c_int, [_VP, C.c_char_p, C.c_char_p, _I, C.POINTER(_VP)]),

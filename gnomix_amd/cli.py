@@ -133,7 +133,7 @@ class _Prefetch:
 
 
 def run_inference(base_args, model, snp_level=False, bed_file_output=False, verbose=False, timings=None, query=None, devices=None,
-                  global_ancestry_output=False):
+                  global_ancestry_output=False, ancestry_allele_freq_output=False):
     """gnomix.py:37-100 with the HIP model behind the same steps.  The query never becomes an (N, C) host matrix: the library
     parses the text into 2-bit rows (gnx_vcf_read), `column_map` keeps vcf_to_npy's bookkeeping (SNP intersection, REF flips,
     absent SNPs) as one int32 per model SNP, the GPU builds X and runs base + smoother (or Gnofix) on it, and the library
@@ -143,10 +143,17 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
     once and the outputs written once: gnomix_amd/multi.py) or an existing multi.DeviceGroup; None = the model's own device.
     `global_ancestry_output` (config key inference.global_ancestry_output, off unless set): query_results.Q (global ancestry per
     individual, hard calls) and query_results.tracts.tsv (tract statistics per haplotype and ancestry) as well, both with cM weights,
-    from the labels the .msp gets (Gnofix's when phasing), summarised on the device (gnx_ancestry_summary)."""
+    from the labels the .msp gets (Gnofix's when phasing), summarised on the device (gnx_ancestry_summary).
+    `ancestry_allele_freq_output` (config key inference.ancestry_allele_freq_output, off unless set): query_results.afreq.tsv as well,
+    the ancestry-specific allele counts and frequencies of every model SNP, counted on the device from the query's 2-bit rows and the
+    labels the .msp gets (gnx_ancestry_allele_counts_gt2).  Not with phase=True (ValueError before any work): the phased matrix is not
+    kept on that path; HipGnomix.phase followed by HipGnomix.allele_frequencies covers that use."""
     from time import perf_counter as clock
     from . import postprocess as pp
     from . import vcfio
+    if ancestry_allele_freq_output and base_args["phase"]:
+        raise ValueError("inference.ancestry_allele_freq_output with phase=True: the phased haplotypes are not kept on this path; "
+                         "use HipGnomix.phase followed by HipGnomix.allele_frequencies")
     query_file, chm, output_path = base_args["query_file"], base_args["chm"], base_args["output_basename"]
     T = timings if timings is not None else {}
     if verbose:
@@ -177,14 +184,14 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
         t0 = clock()
     try:
         return _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out, T, t0, snp_level, bed_file_output, verbose,
-                              global_ancestry_output)
+                              global_ancestry_output, ancestry_allele_freq_output)
     finally:
         if own_group is not None:
             own_group.close()
 
 
 def _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out, T, t0, snp_level, bed_file_output, verbose,
-                   global_ancestry_output=False):
+                   global_ancestry_output=False, ancestry_allele_freq_output=False):
     from time import perf_counter as clock
     from . import postprocess as pp
     from . import vcfio
@@ -236,6 +243,11 @@ def _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out,
         pp.write_q(out_prefix, summary.hard, model.population_order, samples)
         pp.write_tracts(out_prefix, summary, model.population_order, samples)
         T["write_global_ancestry"] = clock() - t0
+    if ancestry_allele_freq_output:
+        t0 = clock()
+        counts = runner.allele_counts_gt2(vcf.gt2, N, src, labels)
+        pp.write_afreq(out_prefix, chm, model.snp_pos, model.M, model.W, counts, model.population_order)
+        T["write_afreq"] = clock() - t0
     return out_prefix
 
 
@@ -301,7 +313,8 @@ def main(argv=None):
         T.update(T_load)
         run_inference(base_args, model, snp_level=bool(inf.get("snp_level_inference")),
                       bed_file_output=bool(inf.get("bed_file_output")), verbose=True, timings=T, query=query, devices=devices,
-                      global_ancestry_output=bool(inf.get("global_ancestry_output")))
+                      global_ancestry_output=bool(inf.get("global_ancestry_output")),
+                      ancestry_allele_freq_output=bool(inf.get("ancestry_allele_freq_output")))
         if os.environ.get("GNX_CLI_TIMING"):
             T["since_process_start"] = _since_process_start()
             sys.stderr.write("gnomix_amd timings (s): " + ", ".join("%s %.3f" % kv for kv in T.items()) + "\n")
@@ -461,7 +474,8 @@ def train_main(argv):
         print("Launching inference...")
         inf = config.get("inference") or {}
         run_inference(base_args, model, snp_level=bool(inf.get("snp_level_inference")), bed_file_output=bool(inf.get("bed_file_output")),
-                      verbose=True, global_ancestry_output=bool(inf.get("global_ancestry_output")))
+                      verbose=True, global_ancestry_output=bool(inf.get("global_ancestry_output")),
+                      ancestry_allele_freq_output=bool(inf.get("ancestry_allele_freq_output")))
     return 0
 
 

@@ -233,6 +233,24 @@ class HipGnomix:
         rows = s.soft if soft else s.hard
         return (rows[0::2] + rows[1::2]) / 2
 
+    def allele_frequencies(self, X):
+        """ancestry-specific allele counts of X under the labels predict returns (mode_filter applied when set) -> AlleleCounts of (A, C)
+        int32 tables n_obs / n_alt / n_miss (postprocess.AlleleCounts; .freq() = n_alt / n_obs, NaN where nothing was observed), counted
+        on the device (k_ancestry_allele_counts); with a CUDA tensor neither X nor the labels leave HBM and CUDA tensors come back.
+        For re-phased haplotypes: X_phased, _ = model.phase(X); model.allele_frequencies(X_phased)"""
+        mf = self.smooth.mode_filter
+        if resident.is_cuda(X):
+            with resident.torch_stream(self.dev.ctx):
+                X = resident.check_x(X, self.C, self.dev.ctx.device)
+                _, lab = self.dev.infer_device(X, want_proba=False, want_labels=True)
+                if mf:
+                    lab = self.dev.mode_filter_device(lab, mf)
+                return self.dev.ancestry_allele_counts_device(X, lab)
+        _, lab = self.dev.infer(X, want_proba=False, want_labels=True)
+        if mf:
+            lab = self.dev.mode_filter(lab, mf)
+        return self.dev.ancestry_allele_counts(self.dev._x(X), lab)
+
     def phase(self, X, B=None, verbose=False, **gnofix_kw):
         """Gnofix re-phasing (model.py:188-214): -> X_phased (N, C) int, Y_phased (N, W) int.  `gnofix_kw`: gnofix()'s search
         options (check_criterion, max_center_offset, non_lin_s, prob_comp, prior_switch_prob, padding, max_it); the reference's

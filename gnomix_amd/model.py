@@ -500,6 +500,72 @@ class DeviceModel:
             soft.data_ptr() if soft is not None else None, count.data_ptr(), total.data_ptr(), longest.data_ptr()))
         return AncestrySummary(hard, soft, count, total, longest, w)
 
+    def ancestry_allele_counts(self, X, labels, packed=False):
+        """ancestry-specific allele counts of X (N, C) int8 (packed=True: the 2-bit rows pack_x returns) under (N, W) labels, on the
+        device (gnx_ancestry_allele_counts; gnomix_amd.postprocess.allele_counts) -> AlleleCounts of (A, C) int32 arrays"""
+        from .postprocess import allele_counts
+        return allele_counts(self.ctx, X, labels, self.M, self.A, packed=packed, C=self.C)
+
+    def ancestry_dosage(self, X, labels, ancestry, packed=False):
+        """(dosage, hapcount) of one ancestry, (N / 2, C) uint8 each (gnx_ancestry_dosage; gnomix_amd.postprocess.ancestry_dosage)"""
+        from .postprocess import ancestry_dosage
+        return ancestry_dosage(self.ctx, X, labels, self.M, self.A, ancestry, packed=packed, C=self.C)
+
+    def _allele_device_args(self, X_t, lab_t):
+        import torch
+        assert X_t.is_cuda and X_t.dim() == 2 and (X_t.shape[1] == 0 or X_t.stride(1) == 1)
+        assert lab_t.is_cuda and lab_t.dtype == torch.int32 and lab_t.dim() == 2 and (lab_t.shape[1] == 0 or lab_t.stride(1) == 1)
+        N = X_t.shape[0]
+        if X_t.dtype == torch.int8:
+            kind, need = _lib.GNX_ROWS_INT8, self.C
+            if X_t.shape[1] != self.C:
+                raise ValueError(f"X must be (N, C={self.C}) int8, got {tuple(X_t.shape)}")
+        elif X_t.dtype == torch.uint8:
+            kind, need = _lib.GNX_ROWS_PACKED2, (self.C + 3) // 4
+            if X_t.shape[1] < need:
+                raise ValueError(f"packed X must be (N, >= {need}) uint8, got {tuple(X_t.shape)}")
+        else:
+            raise ValueError("X must be an int8 (N, C) tensor or the uint8 tensor pack_device returns")
+        if tuple(lab_t.shape) != (N, self.W):
+            raise ValueError(f"labels must be (N={N}, W={self.W}) int32, got {tuple(lab_t.shape)}")
+        ld = X_t.stride(0) if N > 1 else max(X_t.shape[1], need)
+        return kind, ld, (lab_t.stride(0) if N > 1 else self.W), N
+
+    def ancestry_allele_counts_device(self, X_t, lab_t):
+        """the same on CUDA tensors: X_t int8 (N, C) or the uint8 tensor pack_device returns, lab_t (N, W) int32 with any row stride
+        (gnx_ancestry_allele_counts_dev) -> AlleleCounts of (A, C) int32 CUDA tensors"""
+        import torch
+        from .postprocess import AlleleCounts
+        kind, ld, ldl, N = self._allele_device_args(X_t, lab_t)
+        self._bind_torch_stream()
+        obs, alt, miss = (torch.zeros((self.A, self.C), dtype=torch.int32, device=X_t.device) for _ in range(3))
+        self.ctx.check(self.lib.gnx_ancestry_allele_counts_dev(self.ctx.h, X_t.data_ptr(), kind, ld, lab_t.data_ptr(), ldl, N, self.C, self.M,
+                                                               self.W, self.A, obs.data_ptr(), alt.data_ptr(), miss.data_ptr(), 0, 0))
+        return AlleleCounts(obs, alt, miss)
+
+    def ancestry_dosage_device(self, X_t, lab_t, ancestry):
+        """(dosage, hapcount) uint8 (N / 2, C) CUDA tensors of one ancestry (gnx_ancestry_dosage_dev)"""
+        import torch
+        kind, ld, ldl, N = self._allele_device_args(X_t, lab_t)
+        self._bind_torch_stream()
+        dos, hap = (torch.zeros((N // 2, self.C), dtype=torch.uint8, device=X_t.device) for _ in range(2))
+        self.ctx.check(self.lib.gnx_ancestry_dosage_dev(self.ctx.h, X_t.data_ptr(), kind, ld, lab_t.data_ptr(), ldl, N, self.C, self.M, self.W,
+                                                        self.A, int(ancestry), dos.data_ptr(), self.C, hap.data_ptr(), self.C))
+        return dos, hap
+
+    def allele_counts_gt2(self, G, N, src, labels):
+        """ancestry-specific allele counts of the parsed query (G, N, src as infer_gt2 takes them) under host labels (N, W): the
+        packed rows are built and counted in HBM, batch by batch (gnx_ancestry_allele_counts_gt2) -> AlleleCounts"""
+        from .postprocess import AlleleCounts
+        G, N, src = self._gt2_args(G, N, src)
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.shape != (N, self.W):
+            raise ValueError(f"labels must be (N={N}, W={self.W}), got {lab.shape}")
+        obs, alt, miss = (np.zeros((self.A, self.C), np.int32) for _ in range(3))
+        self.ctx.check(self.lib.gnx_ancestry_allele_counts_gt2(self.h, G.ctypes.data, G.shape[0], G.shape[1], N, src.ctypes.data, lab.ctypes.data,
+                                                               obs.ctypes.data, alt.ctypes.data, miss.ctypes.data))
+        return AlleleCounts(obs, alt, miss)
+
     def proba_dtype(self):
         """dtype of the probabilities this model's smoother returns: float64 for CRF and for calibrated output, else float32"""
         native64 = self.data.smooth_kind == "crf" or getattr(self, "calibrated", False)

@@ -232,6 +232,36 @@ class DeviceGroup:
         self._run(jobs)
         return AncestrySummary(hard, soft, count, total, longest, w)
 
+    def allele_counts_gt2(self, G, N, src, labels):
+        """DeviceModel.allele_counts_gt2 with the individuals cut over the group's devices: every device counts its own haplotypes
+        (its bytes of G's rows, its rows of the labels) into tables of its own; counts are additive, the tables are added on the host
+        -> AlleleCounts"""
+        from .postprocess import AlleleCounts
+        m0 = self.models[0]
+        G, N, src = m0._gt2_args(G, N, src)
+        if N % 2:
+            raise ValueError("N = 2 * samples")
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.shape != (N, self.W):
+            raise ValueError(f"labels must be (N={N}, W={self.W}), got {lab.shape}")
+        C = m0.C
+        parts, jobs = [], []
+        for m, (i0, n) in zip(self.models, shard_individuals(N // 2, len(self.models))):
+            h0, nh = 2 * i0, 2 * n   # (h0 is a multiple of 4: whole bytes of every variant row)
+            t = np.zeros((3, self.A, C), np.int32)
+            parts.append(t)
+
+            def fn(m=m, h0=h0, nh=nh, t=t):
+                m.ctx.check(m.lib.gnx_ancestry_allele_counts_gt2(m.h, G.ctypes.data + h0 // 4, G.shape[0], G.shape[1], nh, src.ctypes.data,
+                                                                 lab.ctypes.data + h0 * self.W * 4, t[0].ctypes.data, t[1].ctypes.data,
+                                                                 t[2].ctypes.data))
+            jobs.append((m, fn))
+        self._run(jobs)
+        total = parts[0]
+        for t in parts[1:]:
+            total = total + t
+        return AlleleCounts(total[0], total[1], total[2])
+
     def phase_gt2(self, G, N, src, out_cols=None, max_it=50, proba_dtype=None, out=None):
         """DeviceModel.phase_gt2 cut the same way -> (G_phased or None, proba, labels, n_switches)"""
         m0 = self.models[0]

@@ -6,6 +6,7 @@ formatted and written by the library (include/gnomix_io.h: gnx_write_msp / gnx_w
 metadata (W rows) is plain numpy.  No pandas needed."""
 from __future__ import annotations
 
+import collections
 import os
 
 import numpy as np
@@ -251,6 +252,97 @@ def write_tracts(prefix, summary, populations, samples):
                 for a, pop in enumerate(populations):
                     n, t = int(cnt[2 * i + h, a]), float(tot[2 * i + h, a])
                     f.write("%s\t%d\t%s\t%d\t%.5f\t%.5f\t%.5f\n" % (s, h, pop, n, t, float(lng[2 * i + h, a]), t / n if n else 0.0))
+
+
+class AlleleCounts(collections.namedtuple("AlleleCounts", "n_obs n_alt n_miss")):
+    """what allele_counts returns: three (A, C) int32 tables (numpy arrays or CUDA tensors as the rows were).  Per ancestry a and
+    SNP c, over the haplotypes whose label at c's window is a: n_obs = called (0 or 1), n_alt = ALT (1), n_miss = missing"""
+    __slots__ = ()
+
+    def freq(self):
+        """n_alt / n_obs as float64 (A, C) numpy array, NaN where n_obs == 0"""
+        obs = np.asarray(_to_host(self.n_obs), dtype=np.float64)
+        alt = np.asarray(_to_host(self.n_alt), dtype=np.float64)
+        out = np.full(obs.shape, np.nan, dtype=np.float64)
+        np.divide(alt, obs, out=out, where=obs > 0)
+        return out
+
+
+def _to_host(a):
+    return a.cpu().numpy() if hasattr(a, "is_cuda") else a
+
+
+def _allele_rows(X_or_packed, packed, C):
+    """-> (C-contiguous rows, row_kind, C).  int8 rows keep their bytes (anything but 0 / 1 is a missing call); other integer dtypes
+    are re-coded to 0 / 1 / 2 first; packed rows (gnx_pack_x layout) need C"""
+    if packed:
+        rows = np.ascontiguousarray(X_or_packed, dtype=np.uint8)
+        if C is None:
+            raise ValueError("packed rows: pass C, the number of SNPs a row holds")
+        if rows.ndim != 2 or rows.shape[1] < (int(C) + 3) // 4:
+            raise ValueError(f"packed X must be (N, >= ceil(C / 4) = {(int(C) + 3) // 4}) uint8, got {rows.shape}")
+        return rows, _lib.GNX_ROWS_PACKED2, int(C)
+    X = np.asarray(X_or_packed)
+    if X.ndim != 2:
+        raise ValueError(f"X must be (N, C), got {X.shape}")
+    if C is not None and int(C) != X.shape[1]:
+        raise ValueError(f"X has {X.shape[1]} columns, C = {C}")
+    if X.dtype != np.int8:
+        X = np.where((X == 0) | (X == 1), X, 2).astype(np.int8)
+    return np.ascontiguousarray(X), _lib.GNX_ROWS_INT8, X.shape[1]
+
+
+def _allele_labels(labels, N):
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    if lab.ndim != 2 or lab.shape[0] != N:
+        raise ValueError(f"labels must be (N={N}, W), got {lab.shape}")
+    return lab
+
+
+def allele_counts(ctx, X_or_packed, labels, M, A, packed=False, C=None, debug_rows_per_chunk=0, debug_flush_every=0):
+    """ancestry-specific allele counts on the device (gnx_ancestry_allele_counts): X (N, C) int8 in the model's coding (0 REF, 1 ALT,
+    anything else missing), or with packed=True the 2-bit rows of DeviceModel.pack_x and C; labels (N, W) in [0, A); the window of SNP c
+    is min(c // M, W - 1) -> AlleleCounts of (A, C) int32 arrays"""
+    rows, kind, C = _allele_rows(X_or_packed, packed, C)
+    N = rows.shape[0]
+    lab = _allele_labels(labels, N)
+    W = lab.shape[1]
+    obs, alt, miss = (np.zeros((int(A), C), np.int32) for _ in range(3))
+    ctx.check(ctx.lib.gnx_ancestry_allele_counts(ctx.h, rows.ctypes.data, kind, rows.shape[1], lab.ctypes.data, W, N, C, int(M), W, int(A),
+                                                 obs.ctypes.data, alt.ctypes.data, miss.ctypes.data, int(debug_rows_per_chunk),
+                                                 int(debug_flush_every)))
+    return AlleleCounts(obs, alt, miss)
+
+
+def ancestry_dosage(ctx, X, labels, M, A, ancestry, packed=False, C=None):
+    """per-individual dosage of one ancestry on the device (gnx_ancestry_dosage): for individual i = rows 2 i, 2 i + 1 and SNP c,
+    hapcount = how many of the two haplotypes carry label `ancestry` at c's window, dosage = how many of those are ALT (a missing call
+    counts in hapcount only) -> (dosage, hapcount), (N / 2, C) uint8 arrays"""
+    rows, kind, C = _allele_rows(X, packed, C)
+    N = rows.shape[0]
+    lab = _allele_labels(labels, N)
+    W = lab.shape[1]
+    dos, hap = (np.zeros((N // 2, C), np.uint8) for _ in range(2))
+    ctx.check(ctx.lib.gnx_ancestry_dosage(ctx.h, rows.ctypes.data, kind, rows.shape[1], lab.ctypes.data, W, N, C, int(M), W, int(A),
+                                          int(ancestry), dos.ctypes.data, C, hap.ctypes.data, C))
+    return dos, hap
+
+
+def write_afreq(prefix, chm, snp_pos, M, W, counts, populations):
+    """<prefix>.afreq.tsv: one header line, then one line per model SNP in model order: chm, pos, window (min(c // M, W - 1)), then per
+    population <pop>.n_obs, <pop>.n_alt, <pop>.freq (n_alt / n_obs with six decimals, nan when n_obs == 0), tab-separated"""
+    obs, alt = np.asarray(_to_host(counts.n_obs)), np.asarray(_to_host(counts.n_alt))
+    pos = np.asarray(snp_pos)
+    if obs.ndim != 2 or obs.shape != alt.shape or obs.shape != (len(populations), len(pos)):
+        raise ValueError(f"counts must be ({len(populations)} populations, {len(pos)} SNPs), got {obs.shape}")
+    freq = counts.freq()
+    with open(prefix + ".afreq.tsv", "w") as f:
+        f.write("chm\tpos\twindow\t" + "\t".join("%s.n_obs\t%s.n_alt\t%s.freq" % (p, p, p) for p in populations) + "\n")
+        for c in range(len(pos)):
+            cells = [str(chm), str(int(pos[c])), str(min(c // int(M), int(W) - 1))]
+            for a in range(len(populations)):
+                cells += [str(int(obs[a, c])), str(int(alt[a, c])), format(float(freq[a, c]), ".6f") if obs[a, c] > 0 else "nan"]
+            f.write("\t".join(cells) + "\n")
 
 
 def write_lai(prefix, meta, labels, positions, samples, populations=None, n_threads=0, first_line=None):

@@ -38,6 +38,7 @@
  *   gnx_mode_filter       <- Smoother.predict's mode_filter               src/Smooth/utils.py:31-46, src/Smooth/smooth.py:63-64
  *   gnx_label_runs        <- get_bed_data's walk over a haplotype column  src/postprocess.py:162-193
  *   gnx_ancestry_summary  <- (no counterpart: the .Q table and the tract statistics users compute from an .msp)
+ *   gnx_ancestry_allele_counts <- (no counterpart: the join of the labels with the genotypes: ancestry-specific allele counts and dosages)
  *
  * Conventions
  *   - return 0 (GNX_OK) or a negative GNX_E* code; the message is kept per context (gnx_last_error).
@@ -837,6 +838,54 @@ int gnx_ancestry_summary_dev(gnx_ctx* ctx, const int32_t* d_labels, int64_t ld_l
 int gnx_ancestry_summary(gnx_ctx* ctx, const int32_t* labels, int64_t ld_labels, const void* proba, int proba_is_f64,
                          const double* weights, int64_t N, int64_t W, int32_t A, double* hard, double* soft, int32_t* tract_count,
                          double* tract_total, double* tract_longest);
+
+/* ---- ancestry-specific allele counts and per-ancestry dosage (csrc/summary/k_allele_counts.hip) ----------------------------------
+ * The join of a local-ancestry call with the genotypes.  rows: X (N, C) in the model's coding, row_kind GNX_ROWS_INT8 (one byte per
+ *   SNP: 0 = REF, 1 = ALT, ANY other byte, negatives included, = a missing call) or GNX_ROWS_PACKED2 (the gnx_pack_x layout: SNP j =
+ *   bits 2 (j % 4).. of byte j / 4; codes 2 and 3 = missing), rows ld_rows BYTES apart (>= C, or >= ceil(C / 4) packed).  labels (N, W)
+ *   int32, rows ld_labels >= W elements apart.  The window of SNP c is win(c) = min(c / M, W - 1): the last window takes the remainder
+ *   C - M W.  Required: M >= 1, W >= 1, M W <= C.
+ * gnx_ancestry_allele_counts: three int32 tables laid out (A, C), OVERWRITTEN (zeroed, then counted; any may be NULL):
+ *     n_obs[a, c]  = #{h : labels[h, win(c)] == a and X[h, c] in {0, 1}}
+ *     n_alt[a, c]  = #{h : labels[h, win(c)] == a and X[h, c] == 1}
+ *     n_miss[a, c] = #{h : labels[h, win(c)] == a and X[h, c] not in {0, 1}}
+ *   The frequency n_alt / n_obs is the caller's (float64, on the host).  All device arithmetic is integer: the tables are exact and do
+ *   not depend on the launch geometry.  Columns past C of a packed row's last byte are not counted.
+ *   debug_rows_per_chunk / debug_flush_every: 0 in production.  > 0 (tests): the rows one workgroup reduces per column tile (several
+ *   workgroups then add to one tile of the tables), and the rows after which the workgroup's 8-bit counters are added to the int32
+ *   tables (at most, and by default, 255).
+ * gnx_ancestry_dosage: for ONE ancestry and individual i = haplotype rows 2 i, 2 i + 1, two uint8 matrices (N / 2, C), rows ld_dosage /
+ *   ld_hapcount >= C bytes apart (either may be NULL):
+ *     hapcount[i, c] = how many of the two haplotypes carry label `ancestry` at win(c) (0..2)
+ *     dosage[i, c]   = how many of those have code 1
+ *   A missing call on such a haplotype counts in hapcount and not in dosage: sum_i dosage = n_alt[ancestry], sum_i hapcount =
+ *   n_obs[ancestry] + n_miss[ancestry].
+ * gnx_ancestry_allele_counts_gt2: the file path's form.  G, n_variants, ldg, src as gnx_infer_gt2 takes them; the packed rows are built in
+ *   HBM batch by batch as there (column map, REF flip, missing rule) and counted against the HOST labels (N, W) (contiguous rows) with
+ *   the model's C, M, W and A; the (N, C) matrix never exists on the host.  A model SNP the query lacks is missing in every row.
+ * GNX_EINVAL before the launch, nothing written: N < 0 or N >= 2^31, C < 1, A < 1, M < 1, W < 1, M W > C, a row stride too small, an
+ *   unknown row_kind, a negative debug argument; for the dosage also odd N and ancestry outside [0, A).
+ * GNX_EUNSUPPORTED: A > GNX_ALLELE_MAX_A (labels are staged as bytes and one workgroup holds 3 A KiB of counters), A C >= 2^31.  There
+ *   is no limit on M or W: a tile of 1024 columns that spans many windows (small M) only stages fewer rows per batch.
+ * GNX_EINVAL after the launch: labels outside [0, A) were met (the message says how many).  Labels are only compared, never used as an
+ *   index: such a label counts for no ancestry; everything else in the outputs is as stated.
+ * N == 0: the tables are zeroed, nothing is launched.  Every form synchronises the context stream once (the verdict on the labels). */
+enum { GNX_ROWS_INT8 = 0, GNX_ROWS_PACKED2 = 1 };
+#define GNX_ALLELE_MAX_A 32
+int gnx_ancestry_allele_counts_dev(gnx_ctx* ctx, const void* d_rows, int row_kind, int64_t ld_rows, const int32_t* d_labels,
+                                   int64_t ld_labels, int64_t N, int64_t C, int64_t M, int64_t W, int32_t A, int32_t* d_n_obs,
+                                   int32_t* d_n_alt, int32_t* d_n_miss, int64_t debug_rows_per_chunk, int64_t debug_flush_every);
+int gnx_ancestry_allele_counts(gnx_ctx* ctx, const void* rows, int row_kind, int64_t ld_rows, const int32_t* labels, int64_t ld_labels,
+                               int64_t N, int64_t C, int64_t M, int64_t W, int32_t A, int32_t* n_obs, int32_t* n_alt, int32_t* n_miss,
+                               int64_t debug_rows_per_chunk, int64_t debug_flush_every);
+int gnx_ancestry_dosage_dev(gnx_ctx* ctx, const void* d_rows, int row_kind, int64_t ld_rows, const int32_t* d_labels, int64_t ld_labels,
+                            int64_t N, int64_t C, int64_t M, int64_t W, int32_t A, int32_t ancestry, uint8_t* d_dosage, int64_t ld_dosage,
+                            uint8_t* d_hapcount, int64_t ld_hapcount);
+int gnx_ancestry_dosage(gnx_ctx* ctx, const void* rows, int row_kind, int64_t ld_rows, const int32_t* labels, int64_t ld_labels, int64_t N,
+                        int64_t C, int64_t M, int64_t W, int32_t A, int32_t ancestry, uint8_t* dosage, int64_t ld_dosage, uint8_t* hapcount,
+                        int64_t ld_hapcount);
+int gnx_ancestry_allele_counts_gt2(gnx_model* m, const uint8_t* G, int64_t n_variants, int64_t ldg, int64_t N, const int32_t* src,
+                                   const int32_t* labels, int32_t* n_obs, int32_t* n_alt, int32_t* n_miss);
 
 /* per-kernel device time, measured with hipEvents on the context stream around every launch */
 int gnx_profile_enable(gnx_ctx* ctx, int on);
