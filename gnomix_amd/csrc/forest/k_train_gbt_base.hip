@@ -14,7 +14,8 @@
 //   objective A >= 3: multi:softprob, K = A trees per round, tree k of a round adds to class k; margins start at base_score.
 //             A == 2: binary:logistic, K = 1 tree per round on the label y == 1; the margin starts at float(log(bs / (1 - bs))) (= 0).
 //             Margins are float32 and take each round's leaf with one float32 addition.
-//   gradients multi:  m = max_c F_c (float32), e_c = det_exp(double(F_c - m)), s = sum e_c in class order, p_c = e_c / s,
+//   gradients det_exp is gnx_det_exp.h's: the fixed-order float64 exp this trainer shares with the smoother's.
+//             multi:  m = max_c F_c (float32), e_c = det_exp(double(F_c - m)), s = sum e_c in class order, p_c = e_c / s,
 //                     g = p_c - [y == c], h = max(2 p_c (1 - p_c), 1e-16)              (k_train_gbt.hip's pair)
 //             binary: z = double(F), e = det_exp(-|z|), p = z >= 0 ? 1 / (1 + e) : e / (1 + e), g = p - [y == 1],
 //                     h = max(p (1 - p), 1e-16)
@@ -50,6 +51,8 @@
 #include <vector>
 
 #include "../gnx_internal.h"
+#include "../gnx_window.h"
+#include "gnx_det_exp.h"
 
 namespace {
 
@@ -63,35 +66,7 @@ struct FGeom {
   int32_t W, rem, A, K, maxw, R;  // K trees per round, R rounds
 };
 
-// column of X behind padded position p (base.py's reflect padding)
-__device__ __forceinline__ int64_t fbt_src(int64_t p, int64_t C, int64_t ctx) {
-  if (p < ctx) return ctx - 1 - p;
-  if (p < ctx + C) return p - ctx;
-  return C - 1 - (p - ctx - C);
-}
 __device__ __forceinline__ int fbt_width(int w, const FGeom& G) { return (int)(G.M + 2 * G.ctx) + (w == G.W - 1 ? G.rem : 0); }
-
-__device__ __forceinline__ double det_exp(double x) {  // x <= 0; the same operations, in the same order, as k_train_gbt.hip's
-  if (!(x > -745.0)) return 0.0;
-  const double LOG2E = 1.4426950408889634, LN2_HI = 6.93147180369123816490e-01, LN2_LO = 1.90821492927058770002e-10;
-  const double kf = rint(x * LOG2E);
-  const double r = (x - kf * LN2_HI) - kf * LN2_LO;
-  double p = 1.0 / 6227020800.0;
-  p = p * r + 1.0 / 479001600.0;
-  p = p * r + 1.0 / 39916800.0;
-  p = p * r + 1.0 / 3628800.0;
-  p = p * r + 1.0 / 362880.0;
-  p = p * r + 1.0 / 40320.0;
-  p = p * r + 1.0 / 5040.0;
-  p = p * r + 1.0 / 720.0;
-  p = p * r + 1.0 / 120.0;
-  p = p * r + 1.0 / 24.0;
-  p = p * r + 1.0 / 6.0;
-  p = p * r + 0.5;
-  p = p * r + 1.0;
-  p = p * r + 1.0;
-  return ldexp(p, (int)kf);
-}
 
 __global__ __launch_bounds__(256) void k_fbt_fill(float* p, float v, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -215,7 +190,7 @@ __global__ __launch_bounds__(FBT_CHUNK) void k_fbt_hist(const int8_t* __restrict
   const int rows = cnt;
   const int j = chunk * FBT_CHUNK + threadIdx.x;
   if (j >= width || (rows == 0 && n_slices > 1)) return;  // (a single slice stores: an empty node stores zeros)
-  const int8_t* xc = X + fbt_src((int64_t)w * G.M + j, G.C, G.ctx);
+  const int8_t* xc = X + gnx_pad_src((int64_t)w * G.M + j, G.C, G.ctx);
   long long G1 = 0, H1 = 0, Gm = 0, Hm = 0;
 #pragma unroll 4
   for (int i = 0; i < rows; ++i) {
@@ -305,7 +280,7 @@ __global__ __launch_bounds__(256) void k_fbt_partition(const int8_t* __restrict_
   const size_t o = fbt_tab(w, r, k, G), i = (size_t)wk * G.N + n;
   const int node = pos[i];
   if (node < (1 << d) - 1 || tS[o + node] != 2) return;
-  const int x = X[n * G.ldx + fbt_src((int64_t)w * G.M + tF[o + node], G.C, G.ctx)];
+  const int x = X[n * G.ldx + gnx_pad_src((int64_t)w * G.M + tF[o + node], G.C, G.ctx)];
   const int c = tC[o + node];
   // candidate 1: {0} | {1, m};  2: {0, m} | {1};  3: {0, 1} | {m}   (a code that is neither 1 nor 2 is a 0)
   const bool left = c == 1 ? (x != 1 && x != 2) : (c == 2 ? x != 1 : x != 2);
@@ -335,24 +310,11 @@ __global__ __launch_bounds__(256) void k_fbt_margin(float* Fm, const uint8_t* po
   Fm[e] += tV[fbt_tab((int)w, r, k, G) + pos[((size_t)w * G.K + k) * G.N + n]];
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-  template <typename T> T* as() { return reinterpret_cast<T*>(p); }
-};
-
 // per-phase wall times of the last run (gnx_train_gbt_base_phases): gradients + loss, table, split search, partition, leaves + margins
 bool g_phases_on = false;
 double g_phase_ms[5] = {0, 0, 0, 0, 0};
 
 }  // namespace
-
-#define FBT_HIP(x)                      \
-  do {                                  \
-    const hipError_t e_ = (x);          \
-    if (e_ != hipSuccess) return e_;    \
-  } while (0)
 
 // dX (N, ldx) int8 and dy (N, W) int32 on the device.  Host outputs as in gnx_train_gbt_base (include/gnomix_hip.h).
 static hipError_t gnx_train_gbt_base_run(const int8_t* dX, int64_t N, int64_t ldx, const int32_t* dy, int64_t C, int64_t M, int64_t ctx, int32_t A,
@@ -368,25 +330,25 @@ static hipError_t gnx_train_gbt_base_run(const int8_t* dX, int64_t N, int64_t ld
   const int nb = (int)((N + 255) / 256);
   const int n_chunks = (G.maxw + FBT_CHUNK - 1) / FBT_CHUNK, n_slices = (int)((N + FBT_SLICE - 1) / FBT_SLICE);
   const size_t hist_n = (size_t)WK * ((size_t)1 << (D - 1)) * G.maxw * 4;
-  DevBuf bFm, bG, bH, bPos, bTab, bHist, bPart, bLoss;
-  FBT_HIP(bFm.alloc((size_t)rows * 4));
-  FBT_HIP(bG.alloc((size_t)rows * 8));
-  FBT_HIP(bH.alloc((size_t)rows * 8));
-  FBT_HIP(bPos.alloc((size_t)rows));
-  FBT_HIP(bTab.alloc(tab_n * 32));
-  FBT_HIP(bHist.alloc(hist_n * 8));
-  FBT_HIP(bPart.alloc((size_t)W * nb * 8));
-  FBT_HIP(bLoss.alloc((size_t)(R + 1) * 8));
+  gnx_dev_tmp bFm, bG, bH, bPos, bTab, bHist, bPart, bLoss;
+  GNX_HIPRET(bFm.alloc((size_t)rows * 4));
+  GNX_HIPRET(bG.alloc((size_t)rows * 8));
+  GNX_HIPRET(bH.alloc((size_t)rows * 8));
+  GNX_HIPRET(bPos.alloc((size_t)rows));
+  GNX_HIPRET(bTab.alloc(tab_n * 32));
+  GNX_HIPRET(bHist.alloc(hist_n * 8));
+  GNX_HIPRET(bPart.alloc((size_t)W * nb * 8));
+  GNX_HIPRET(bLoss.alloc((size_t)(R + 1) * 8));
   long long* tG = bTab.as<long long>();
   long long* tH = tG + tab_n;
   int32_t* tF = reinterpret_cast<int32_t*>(tH + tab_n);
   int32_t* tC = tF + tab_n;
   int32_t* tS = tC + tab_n;
   float* tV = reinterpret_cast<float*>(tS + tab_n);
-  FBT_HIP(hipMemsetAsync(bTab.p, 0, tab_n * 32, s));
+  GNX_HIPRET(hipMemsetAsync(bTab.p, 0, tab_n * 32, s));
   const float m0 = K == 1 ? (float)std::log(P.base_score / (1.0 - P.base_score)) : (float)P.base_score;
   hipLaunchKernelGGL(k_fbt_fill, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, bFm.as<float>(), m0, rows);
-  FBT_HIP(hipGetLastError());
+  GNX_HIPRET(hipGetLastError());
 
   const bool prof = g_phases_on;
   double ms[5] = {0, 0, 0, 0, 0};
@@ -413,11 +375,11 @@ static hipError_t gnx_train_gbt_base_run(const int8_t* dX, int64_t N, int64_t ld
   phase(-1);
   for (int r = 0; r < R; ++r) {
     grad(r, 1);
-    FBT_HIP(hipGetLastError());
+    GNX_HIPRET(hipGetLastError());
     phase(0);
     for (int d = 0; d < D; ++d) {
       const int nl = 1 << d;
-      if (n_slices > 1) FBT_HIP(hipMemsetAsync(bHist.p, 0, (size_t)WK * nl * G.maxw * 32, s));
+      if (n_slices > 1) GNX_HIPRET(hipMemsetAsync(bHist.p, 0, (size_t)WK * nl * G.maxw * 32, s));
       hipLaunchKernelGGL(k_fbt_hist, dim3((unsigned)WK, (unsigned)(n_chunks * n_slices), (unsigned)nl), dim3(FBT_CHUNK), 0, s, dX, bG.as<long long>(),
                          bH.as<long long>(), bPos.as<uint8_t>(), tS, bHist.as<long long>(), r, d, n_chunks, n_slices, G);
       phase(1);
@@ -429,24 +391,24 @@ static hipError_t gnx_train_gbt_base_run(const int8_t* dX, int64_t N, int64_t ld
     }
     hipLaunchKernelGGL(k_fbt_close, dim3((unsigned)((WK * MAXN + 255) / 256)), dim3(256), 0, s, tG, tH, tS, tV, r, WK * MAXN, P.eta, P.lambda, G);
     hipLaunchKernelGGL(k_fbt_margin, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, bFm.as<float>(), bPos.as<uint8_t>(), tV, r, rows, G);
-    FBT_HIP(hipGetLastError());
+    GNX_HIPRET(hipGetLastError());
     phase(4);
   }
   grad(R, 0);
-  FBT_HIP(hipGetLastError());
+  GNX_HIPRET(hipGetLastError());
   phase(0);
-  FBT_HIP(perr);
+  GNX_HIPRET(perr);
 
   // ---- trees back to the host: window-major, round-major, nodes in heap order ----
   std::vector<int32_t> hF(tab_n), hC(tab_n), hS(tab_n);
   std::vector<float> hV(tab_n);
   std::vector<double> hL((size_t)R + 1);
-  FBT_HIP(hipMemcpyAsync(hF.data(), tF, tab_n * 4, hipMemcpyDeviceToHost, s));
-  FBT_HIP(hipMemcpyAsync(hC.data(), tC, tab_n * 4, hipMemcpyDeviceToHost, s));
-  FBT_HIP(hipMemcpyAsync(hS.data(), tS, tab_n * 4, hipMemcpyDeviceToHost, s));
-  FBT_HIP(hipMemcpyAsync(hV.data(), tV, tab_n * 4, hipMemcpyDeviceToHost, s));
-  FBT_HIP(hipMemcpyAsync(hL.data(), bLoss.p, hL.size() * 8, hipMemcpyDeviceToHost, s));
-  FBT_HIP(hipStreamSynchronize(s));
+  GNX_HIPRET(hipMemcpyAsync(hF.data(), tF, tab_n * 4, hipMemcpyDeviceToHost, s));
+  GNX_HIPRET(hipMemcpyAsync(hC.data(), tC, tab_n * 4, hipMemcpyDeviceToHost, s));
+  GNX_HIPRET(hipMemcpyAsync(hS.data(), tS, tab_n * 4, hipMemcpyDeviceToHost, s));
+  GNX_HIPRET(hipMemcpyAsync(hV.data(), tV, tab_n * 4, hipMemcpyDeviceToHost, s));
+  GNX_HIPRET(hipMemcpyAsync(hL.data(), bLoss.p, hL.size() * 8, hipMemcpyDeviceToHost, s));
+  GNX_HIPRET(hipStreamSynchronize(s));
   int64_t nn = 0;
   const int64_t T = WK * R;
   tree_off[0] = 0;
@@ -477,13 +439,6 @@ static hipError_t gnx_train_gbt_base_run(const int8_t* dX, int64_t N, int64_t ld
   if (prof) std::memcpy(g_phase_ms, ms, sizeof(ms));
   return hipSuccess;
 }
-
-#define HIPCHK(ctx, expr)                                                                          \
-  do {                                                                                             \
-    const hipError_t e__ = (expr);                                                                 \
-    if (e__ != hipSuccess)                                                                         \
-      return gnx_fail((ctx), GNX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));        \
-  } while (0)
 
 // ---- training the boosted-tree base (XGBBase) --------------------------------------------------------------------
 namespace {

@@ -39,19 +39,6 @@
 
 #pragma clang fp contract(off)
 
-#define HIPCHK(ctx, expr)                                                                          \
-  do {                                                                                             \
-    hipError_t e__ = (expr);                                                                       \
-    if (e__ != hipSuccess)                                                                         \
-      return gnx_fail((ctx), GNX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));        \
-  } while (0)
-
-#define RF_HIP(x)                       \
-  do {                                  \
-    const hipError_t e_ = (x);          \
-    if (e_ != hipSuccess) return e_;    \
-  } while (0)
-
 namespace {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -396,13 +383,6 @@ __global__ __launch_bounds__(256) void k_rf_partition(RfGeom G, int nb) {
   *hp = (uint8_t)(2 * h + ((double)G.X[n * G.ldx + src] <= tr->split_thr ? 0 : 1));
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-  template <typename T> T* as() { return reinterpret_cast<T*>(p); }
-};
-
 // per-phase wall times of the last timed run (gnx_train_rforest_phases): counts, draw, partition
 bool g_rf_phases_on = false;
 double g_rf_phase_ms[3] = {0, 0, 0};
@@ -435,19 +415,19 @@ hipError_t rforest_run(const int8_t* dX, int64_t N, int64_t ldx, const int32_t* 
   int64_t per = (int64_t)(RF_TAB_BYTES / tab_w);
   per = per < 1 ? 1 : per > W ? W : per > 65535 ? 65535 : per;
   const size_t TTm = (size_t)per * T;
-  DevBuf bHeap, bTab, bF, bCF, bTrees, bL, bR, bFe, bTh, bV, bFlag;
-  RF_HIP(bHeap.alloc(TTm * N));
-  RF_HIP(bTab.alloc((size_t)per * tab_w));
-  RF_HIP(bF.alloc(TTm * ldw * 2));
-  RF_HIP(bCF.alloc(TTm * ldw * 2));
-  RF_HIP(bTrees.alloc(TTm * sizeof(RfTree)));
-  RF_HIP(bL.alloc(TTm * cap * 4));
-  RF_HIP(bR.alloc(TTm * cap * 4));
-  RF_HIP(bFe.alloc(TTm * cap * 4));
-  RF_HIP(bTh.alloc(TTm * cap * 8));
-  RF_HIP(bV.alloc(TTm * cap * A * 8));
-  RF_HIP(bFlag.alloc(4));
-  RF_HIP(hipMemsetAsync(bFlag.p, 0, 4, s));
+  gnx_dev_tmp bHeap, bTab, bF, bCF, bTrees, bL, bR, bFe, bTh, bV, bFlag;
+  GNX_HIPRET(bHeap.alloc(TTm * N));
+  GNX_HIPRET(bTab.alloc((size_t)per * tab_w));
+  GNX_HIPRET(bF.alloc(TTm * ldw * 2));
+  GNX_HIPRET(bCF.alloc(TTm * ldw * 2));
+  GNX_HIPRET(bTrees.alloc(TTm * sizeof(RfTree)));
+  GNX_HIPRET(bL.alloc(TTm * cap * 4));
+  GNX_HIPRET(bR.alloc(TTm * cap * 4));
+  GNX_HIPRET(bFe.alloc(TTm * cap * 4));
+  GNX_HIPRET(bTh.alloc(TTm * cap * 8));
+  GNX_HIPRET(bV.alloc(TTm * cap * A * 8));
+  GNX_HIPRET(bFlag.alloc(4));
+  GNX_HIPRET(hipMemsetAsync(bFlag.p, 0, 4, s));
 
   const bool prof = g_rf_phases_on;
   double ms[3] = {0, 0, 0};
@@ -474,9 +454,9 @@ hipError_t rforest_run(const int8_t* dX, int64_t N, int64_t ldx, const int32_t* 
     RfGeom G{dX, dy, dwt, dstate, N, ldx, C, M, cx, (int32_t)W, A, T, D, (int32_t)w0, (int32_t)nw, (int32_t)ldw, RP, cap,
              bHeap.as<uint8_t>(), bTab.as<int32_t>(), bF.as<uint16_t>(), bCF.as<uint16_t>(), bTrees.as<RfTree>(), bL.as<int32_t>(),
              bR.as<int32_t>(), bFe.as<int32_t>(), bTh.as<double>(), bV.as<double>(), bFlag.as<int32_t>()};
-    RF_HIP(hipMemsetAsync(bHeap.p, 1, TT * N, s));
+    GNX_HIPRET(hipMemsetAsync(bHeap.p, 1, TT * N, s));
     hipLaunchKernelGGL(k_rf_init, dim3((unsigned)((TT + 63) / 64)), dim3(64), 0, s, G);
-    RF_HIP(hipGetLastError());
+    GNX_HIPRET(hipGetLastError());
     phase(-1);
     for (int r = 0; r < rounds; ++r) {
       hipLaunchKernelGGL(k_rf_counts, dim3((unsigned)((2 * ldw + RF_T - 1) / RF_T), (unsigned)nw, (unsigned)(RP / RF_T)), dim3(256), 0, s, G);
@@ -484,18 +464,18 @@ hipError_t rforest_run(const int8_t* dX, int64_t N, int64_t ldx, const int32_t* 
       hipLaunchKernelGGL(k_rf_draw, dim3((unsigned)((TT + 63) / 64)), dim3(64), 0, s, G);
       phase(1);
       if (r + 1 < rounds) hipLaunchKernelGGL(k_rf_partition, dim3((unsigned)(TT * nb)), dim3(256), 0, s, G, nb);
-      RF_HIP(hipGetLastError());
+      GNX_HIPRET(hipGetLastError());
       phase(2);
     }
     // ---- this range's trees back to the host, packed in window and tree order ----
     hTrees.resize(TT); hL.resize(TT * cap); hR.resize(TT * cap); hF.resize(TT * cap); hT.resize(TT * cap); hV.resize(TT * cap * A);
-    RF_HIP(hipMemcpyAsync(hTrees.data(), bTrees.p, TT * sizeof(RfTree), hipMemcpyDeviceToHost, s));
-    RF_HIP(hipMemcpyAsync(hL.data(), bL.p, TT * cap * 4, hipMemcpyDeviceToHost, s));
-    RF_HIP(hipMemcpyAsync(hR.data(), bR.p, TT * cap * 4, hipMemcpyDeviceToHost, s));
-    RF_HIP(hipMemcpyAsync(hF.data(), bFe.p, TT * cap * 4, hipMemcpyDeviceToHost, s));
-    RF_HIP(hipMemcpyAsync(hT.data(), bTh.p, TT * cap * 8, hipMemcpyDeviceToHost, s));
-    RF_HIP(hipMemcpyAsync(hV.data(), bV.p, TT * cap * A * 8, hipMemcpyDeviceToHost, s));
-    RF_HIP(hipStreamSynchronize(s));
+    GNX_HIPRET(hipMemcpyAsync(hTrees.data(), bTrees.p, TT * sizeof(RfTree), hipMemcpyDeviceToHost, s));
+    GNX_HIPRET(hipMemcpyAsync(hL.data(), bL.p, TT * cap * 4, hipMemcpyDeviceToHost, s));
+    GNX_HIPRET(hipMemcpyAsync(hR.data(), bR.p, TT * cap * 4, hipMemcpyDeviceToHost, s));
+    GNX_HIPRET(hipMemcpyAsync(hF.data(), bFe.p, TT * cap * 4, hipMemcpyDeviceToHost, s));
+    GNX_HIPRET(hipMemcpyAsync(hT.data(), bTh.p, TT * cap * 8, hipMemcpyDeviceToHost, s));
+    GNX_HIPRET(hipMemcpyAsync(hV.data(), bV.p, TT * cap * A * 8, hipMemcpyDeviceToHost, s));
+    GNX_HIPRET(hipStreamSynchronize(s));
     for (size_t t = 0; t < TT; ++t) {
       int32_t k = hTrees[t].n_nodes;
       if (k < 0 || k > cap || hTrees[t].active) return hipErrorUnknown;  // (cannot happen: a tree of depth D ends within 2^D - 1 searches)
@@ -508,10 +488,10 @@ hipError_t rforest_run(const int8_t* dX, int64_t N, int64_t ldx, const int32_t* 
       tree_off[++tglob] = (int32_t)nn;
     }
   }
-  RF_HIP(perr);
+  GNX_HIPRET(perr);
   int32_t flag = 0;
-  RF_HIP(hipMemcpyAsync(&flag, bFlag.p, 4, hipMemcpyDeviceToHost, s));
-  RF_HIP(hipStreamSynchronize(s));
+  GNX_HIPRET(hipMemcpyAsync(&flag, bFlag.p, 4, hipMemcpyDeviceToHost, s));
+  GNX_HIPRET(hipStreamSynchronize(s));
   *bad_weight = flag;
   for (int64_t w = 0; w <= W; ++w) win_tree0[w] = (int32_t)(w * T);
   *n_nodes_out = nn;

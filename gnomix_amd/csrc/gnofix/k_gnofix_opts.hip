@@ -350,7 +350,7 @@ __global__ __launch_bounds__(OT) void k_gnofix_opts(GnofixOptsK L) {
         for (int e = tid; e < 2 * nj * A; e += OT) {
           const int h = e >= nj * A ? 1 : 0, f = e - h * nj * A;
           const int q = (int)__umulhi((uint32_t)f, invA), a = f - q * A;
-          const int u = slide_src(gb + q, W, pad);
+          const int u = gnx_slide_src(gb + q, W, pad);
           seg[(h * A + a) * GP + q] = R0[(size_t)(h ^ pbit(u)) * WA + (size_t)u * A + a];
         }
         for (int r = tid; r < 2 * nwin; r += OT) {

@@ -21,13 +21,6 @@ int gnx_fail(gnx_ctx* ctx, int code, const std::string& msg) {
 }
 static inline int fail(gnx_ctx* ctx, int code, const std::string& msg) { return gnx_fail(ctx, code, msg); }
 
-#define HIPCHK(ctx, expr)                                                                      \
-  do {                                                                                         \
-    hipError_t e__ = (expr);                                                                   \
-    if (e__ != hipSuccess)                                                                     \
-      return fail((ctx), GNX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));        \
-  } while (0)
-
 static int ws_reserve(gnx_ctx* ctx, gnx_devbuf& b, size_t bytes);
 int gnx_ws_reserve(gnx_ctx* ctx, gnx_devbuf& b, size_t bytes) { return ws_reserve(ctx, b, bytes); }
 static int ws_reserve(gnx_ctx* ctx, gnx_devbuf& b, size_t bytes) {

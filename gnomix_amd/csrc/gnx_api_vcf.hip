@@ -7,13 +7,6 @@
 #include "gnx_internal.h"
 #include "gnx_io.h"
 
-#define HIPCHK(ctx, expr)                                                                          \
-  do {                                                                                             \
-    hipError_t e__ = (expr);                                                                       \
-    if (e__ != hipSuccess)                                                                         \
-      return gnx_fail((ctx), GNX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));        \
-  } while (0)
-
 // ---- reader ------------------------------------------------------------------------------------------------------------
 static void* alloc_plain(void*, size_t bytes) { return malloc(bytes); }
 static void free_plain(void*, void* p) { free(p); }

@@ -462,6 +462,31 @@ struct gnx_model {
 // shared with gnx_api_vcf.hip (defined in gnx_api.hip)
 int gnx_fail(gnx_ctx* ctx, int code, const std::string& msg);
 
+// ---- host helpers of every translation unit (the only definitions: tests/test_host_cpu.py counts them) ------------------
+// in a function that returns a GNX_* code: a failed HIP call is GNX_EHIP with "<the call's text>: <HIP's message>" in the context
+#define HIPCHK(ctx, expr)                                                                          \
+  do {                                                                                             \
+    const hipError_t e__ = (expr);                                                                 \
+    if (e__ != hipSuccess)                                                                         \
+      return gnx_fail((ctx), GNX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));        \
+  } while (0)
+// in a function that returns a hipError_t: a failed HIP call is handed up as it is
+#define GNX_HIPRET(expr)                \
+  do {                                  \
+    const hipError_t e_ = (expr);       \
+    if (e_ != hipSuccess) return e_;    \
+  } while (0)
+// device memory for the length of a scope: hipMalloc now (an empty request still gets an address), hipFree when the scope ends
+struct gnx_dev_tmp {
+  void* p = nullptr;
+  gnx_dev_tmp() = default;
+  ~gnx_dev_tmp() { if (p) (void)hipFree(p); }
+  gnx_dev_tmp(const gnx_dev_tmp&) = delete;
+  gnx_dev_tmp& operator=(const gnx_dev_tmp&) = delete;
+  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
+  template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
 // The HIP "current device" is per host THREAD (a new thread starts on device 0) and hipMalloc / kernel launches / event creation use
 // it, not the stream's device.  Every extern "C" entry that touches the GPU therefore binds its context's device for the duration of
 // the call and puts the caller's device back on return (one gnx_ctx per device, different contexts on different threads —

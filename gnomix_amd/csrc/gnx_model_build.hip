@@ -16,13 +16,6 @@
 
 static inline int fail(gnx_ctx* ctx, int code, const std::string& msg) { return gnx_fail(ctx, code, msg); }
 
-#define HIPCHK(ctx, expr)                                                                      \
-  do {                                                                                         \
-    hipError_t e__ = (expr);                                                                   \
-    if (e__ != hipSuccess)                                                                     \
-      return fail((ctx), GNX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));        \
-  } while (0)
-
 // [0, n) cut into contiguous ranges, one per host thread (at most 16, at least `grain` items each): fn(lo, hi, thread index).
 // Model preparation is host arithmetic over tens of millions of weights (a whole-genome set of logistic models: 2.5e8): single-threaded
 // it was most of gnx_model_load's time.  A thread that cannot be started (resource limits) is run inline: nothing is thrown.

@@ -10,15 +10,9 @@
 #include <stdint.h>
 
 #include "gnx_rank_table.h"
+#include "gnx_window.h"  // gnx_slide_src
 
 namespace {
-
-__device__ __forceinline__ int slide_src(int j, int W, int pad) {
-  // reflect padding of slide_window (src/Smooth/utils.py:14-17)
-  if (j < pad) return pad - 1 - j;
-  if (j < pad + W) return j - pad;
-  return W - 1 - (j - pad - W);
-}
 
 // NV independent rank computations side by side: r = #{U[k] <= p}; NaN -> 0xFFFF ("never less than a threshold").
 // One 16-byte gather from the model's table (gnx_rank_table.h) is the rank of nearly every probability; the bisection behind it

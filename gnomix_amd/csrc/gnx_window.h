@@ -1,5 +1,6 @@
-// gnx_window.h — the window geometry of Base.train_vectorized / predict_proba_vectorized (reference src/Base/base.py:41-44, 104-180), one
-// definition for the kernels that walk a window's slice of the reflect-padded row (nb/k_base_nb.hip, lda/k_train_lda.hip, lda/k_base_lda.hip).
+// gnx_window.h — the one home of window geometry: the base windows of Base.train_vectorized / predict_proba_vectorized (reference
+// src/Base/base.py:41-44, 104-180) over the reflect-padded row, and the smoother's reflect padding over windows.  Every kernel file
+// that walks either includes this header; none keeps a copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -15,4 +16,12 @@ __host__ __device__ __forceinline__ int64_t gnx_pad_src(int64_t p, int64_t C, in
 // padded row ends)
 __host__ __device__ __forceinline__ int64_t gnx_window_width(int64_t w, int64_t W, int64_t C, int64_t M, int64_t ctx) {
   return M + 2 * ctx + (w == W - 1 ? C - M * W : 0);
+}
+
+// window behind position j of the smoother's strip, padded by reflection with pad windows at both ends (j in [0, W + 2 pad)):
+// slide_window (reference src/Smooth/utils.py:14-17)
+__device__ __forceinline__ int gnx_slide_src(int j, int W, int pad) {
+  if (j < pad) return pad - 1 - j;
+  if (j < pad + W) return j - pad;
+  return W - 1 - (j - pad - W);
 }

@@ -18,14 +18,10 @@
 //    Platt sigmoids and the Wu-Lin-Weng coupling iteration run per lane on LDS-resident [index][lane] arrays.
 // Integer-ALU bound: W * n_sv * width symbol compares per haplotype.
 #include "gnx_internal.h"
+#include "gnx_window.h"
+#include "svm/gnx_svc_rbf.h"  // pair_index
 
 namespace {
-
-__device__ __forceinline__ int64_t pad_src(int64_t p, int64_t C, int64_t ctx) {
-  if (p < ctx) return ctx - 1 - p;
-  if (p < ctx + C) return p - ctx;
-  return C - 1 - (p - ctx - C);
-}
 
 // one thread = one 32-SNP word of the padded bit-planes
 __global__ __launch_bounds__(256) void k_pack_bits(const int8_t* X, int64_t N, int64_t ldx, int64_t C, int64_t ctx,
@@ -54,7 +50,7 @@ __global__ __launch_bounds__(256) void k_pack_bits(const int8_t* X, int64_t N, i
     for (int b = 0; b < 32; ++b) {
       const int64_t p = p0 + b;
       if (p < Cp) {
-        const uint32_t v = (uint32_t)(uint8_t)x[pad_src(p, C, ctx)];
+        const uint32_t v = (uint32_t)(uint8_t)x[gnx_pad_src(p, C, ctx)];
         lo |= (v & 1u) << b;
         hi |= ((v >> 1) & 1u) << b;
       }
@@ -63,8 +59,6 @@ __global__ __launch_bounds__(256) void k_pack_bits(const int8_t* X, int64_t N, i
   planes[(n * 2 + 0) * nwp + wd] = lo;
   planes[(n * 2 + 1) * nwp + wd] = hi;
 }
-
-__device__ __forceinline__ int pair_index(int i, int j, int A) { return i * (2 * A - i - 1) / 2 + (j - i - 1); }
 
 __device__ __forceinline__ double sigmoid_predict(double dec, double pa, double pb) {
   const double f = dec * pa + pb;

@@ -27,6 +27,7 @@
 //    (TP independent LDS chains), adds the leaves of each class in tree order (float32, as the restated predictor does),
 //    parks the margins in LDS and applies softmax / sigmoid in float32.
 #include "gnx_internal.h"
+#include "gnx_window.h"
 
 #include <cstdint>
 #include <cstdlib>
@@ -43,12 +44,6 @@ hipError_t gnx_forest_v1_part3(const ForestLaunch& L, int haps, size_t lds, bool
 namespace {
 
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int64_t pad_src(int64_t p, int64_t C, int64_t ctx) {
-  if (p < ctx) return ctx - 1 - p;
-  if (p < ctx + C) return p - ctx;
-  return C - 1 - (p - ctx - C);
-}
 
 // 4 SNP bytes (values 0..3) -> 8 bits
 __device__ __forceinline__ uint32_t squeeze4(uint32_t d) {
@@ -142,7 +137,7 @@ struct Stager {
       q = 0;
       for (int b = 0; b < 16; ++b) {
         const int64_t p = p0 + b;
-        if (p < C + 2 * ctx) q |= ((uint32_t)(uint8_t)r[pad_src(p, C, ctx)] & 3u) << (2 * b);
+        if (p < C + 2 * ctx) q |= ((uint32_t)(uint8_t)r[gnx_pad_src(p, C, ctx)] & 3u) << (2 * b);
       }
     }
     return q;

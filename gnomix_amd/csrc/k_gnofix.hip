@@ -607,7 +607,7 @@ __global__ __launch_bounds__(THREADS, (THREADS >= 512 ? 4 : 3)) void k_gnofix(Gn
         GNX_NOUNROLL for (int e = tz; e < 2 * nj * A; e += THREADS) {
           const int h = e >= nj * A ? 1 : 0, f = e - h * nj * A;
           const int q = (int)__umulhi((uint32_t)f, invA), a = f - q * A;
-          const int u = slide_src(gb + q, W, pad);
+          const int u = gnx_slide_src(gb + q, W, pad);
           seg[(h * A + a) * GP + q] = R0[(size_t)(h ^ parbit(u)) * WA + (size_t)u * A + a];
         }
         // lane = row (haplotype rh, window gb + rk) of row set `set`; set s walks class c0 + s.  The stage holds NSETMAX * cap trees:
@@ -859,7 +859,7 @@ __global__ __launch_bounds__(THREADS, (THREADS >= 512 ? 4 : 3)) void k_gnofix(Gn
       }
       if (tz == 0) { flags[2] = W; flags[3] = 0; }
       __syncthreads();
-      // Row w' sees unpadded windows {slide_src(w'+s)}: rows that only see windows >= w exchange their two labels, rows that see
+      // Row w' sees unpadded windows {gnx_slide_src(w'+s)}: rows that only see windows >= w exchange their two labels, rows that see
       // both sides are re-evaluated.  (The rows to re-evaluate form one contiguous range [r0, r1): re-evaluating a row of that range
       // that needed nothing, or one that was also swapped, just recomputes its label from the current strips.)
       GNX_NOUNROLL for (int wr = tz; wr < W; wr += THREADS) {

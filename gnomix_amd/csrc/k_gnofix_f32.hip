@@ -33,17 +33,12 @@
 // -DGNX_GNOFIX_CLOCKS turns n_switches into per-phase clock counts (scripts/dev/gnofix_phases.py).
 #include "gnx_internal.h"
 #include "gnx_exp.h"
+#include "gnx_window.h"
 
 namespace {
 
 constexpr int THREADS = 512;   // one workgroup per CU (the strips fill its LDS); 8 waves with up to 256 VGPRs each
 constexpr int NWAVES = THREADS / 64;
-
-__device__ __forceinline__ int slide_src(int j, int W, int pad) {
-  if (j < pad) return pad - 1 - j;
-  if (j < pad + W) return j - pad;
-  return W - 1 - (j - pad - W);
-}
 
 // NW independent walks side by side (generic pointers: trees in global memory, rows in LDS or global); same arithmetic as gnx_walk
 template <int NW>
@@ -137,7 +132,7 @@ __global__ __launch_bounds__(THREADS) void k_gnofix(GnofixLaunch L) {
   for (int e = tid; e < 2 * Wp * A; e += THREADS) {
     const int h = e / (Wp * A), r = e - h * Wp * A;
     const int j = r / A, a = r - j * A;
-    bp[e] = (float)L.B[(((size_t)(2 * ind + h)) * W + slide_src(j, W, pad)) * A + a];
+    bp[e] = (float)L.B[(((size_t)(2 * ind + h)) * W + gnx_slide_src(j, W, pad)) * A + a];
   }
   for (int e = tid; e < 2 * W; e += THREADS) Y[e] = (uint8_t)L.Y0[(size_t)2 * ind * W + e];
   for (int e = tid; e < NWD; e += THREADS) { par[e] = 0; dif[e] = 0; }
@@ -282,7 +277,7 @@ __global__ __launch_bounds__(THREADS) void k_gnofix(GnofixLaunch L) {
       ++n_switch;
       for (int e = tid; e < Wp * A; e += THREADS) {
         const int j = e / A;
-        if (slide_src(j, W, pad) >= w) {
+        if (gnx_slide_src(j, W, pad) >= w) {
           const float t0 = bp[e], t1 = bp[(size_t)Wp * A + e];
           bp[e] = t1;
           bp[(size_t)Wp * A + e] = t0;
@@ -298,7 +293,7 @@ __global__ __launch_bounds__(THREADS) void k_gnofix(GnofixLaunch L) {
       __syncthreads();
       // rows whose sliding window only sees windows >= w: the two haplotypes' rows are exchanged
       // rows that see windows on both sides of w: re-evaluate.  Row w' sees unpadded windows
-      // {slide_src(w'+s)} = [max(0,w'-pad) .. min(W-1,w'+S-1-pad)] plus reflections that stay inside it
+      // {gnx_slide_src(w'+s)} = [max(0,w'-pad) .. min(W-1,w'+S-1-pad)] plus reflections that stay inside it
       // except at the edges, where the reflected part can reach further: handled by the explicit min/max.
       // (The rows to re-evaluate form one contiguous range [r0, r1): re-evaluating a row of that range that needed nothing, or one
       // that was also swapped, just recomputes its label from the current strips.)

@@ -24,17 +24,11 @@
 
 #include "gnx_internal.h"
 #include "gnx_exp.h"
+#include "gnx_window.h"
 
 namespace {
 
 constexpr int WS = 64;  // windows per segment = one wave width
-
-__device__ __forceinline__ int slide_src(int j, int W, int pad) {
-  // reflect padding of slide_window (src/Smooth/utils.py:14-17)
-  if (j < pad) return pad - 1 - j;
-  if (j < pad + W) return j - pad;
-  return W - 1 - (j - pad - W);
-}
 
 template <int D>
 __device__ __forceinline__ float walk(const uint8_t* tb, const uint8_t* rowbase) {
@@ -81,7 +75,7 @@ __global__ __launch_bounds__(NWAVE * 64) void k_smooth_xgb(SmoothXGBLaunch L) {
       const int j = w0 + q;
       float v = 0.f;
       if (n < L.N && j < W + 2 * pad) {
-        const size_t idx = ((size_t)n * W + slide_src(j, W, pad)) * A + a;
+        const size_t idx = ((size_t)n * W + gnx_slide_src(j, W, pad)) * A + a;
         v = L.b_is_f64 ? (float)reinterpret_cast<const double*>(L.B)[idx] : reinterpret_cast<const float*>(L.B)[idx];
       }
       reinterpret_cast<float*>(strip)[e] = v;

@@ -146,8 +146,8 @@ __global__ __launch_bounds__(THREADS, 8) void k_smooth_xgb_h32(SmoothXGBLaunch L
     for (int it = 0; it < (n_rows + RPI - 1) / RPI; ++it, row += RPI) {
       const bool ok = row < n_rows;
       const int qc = ok ? q : 0, ac = ok ? a : 0;  // clamped: loads stay unconditional
-      const int s0 = slide_src(min(w0 + 2 * qc, W + 2 * pad - 1), W, pad);
-      const int s1 = slide_src(min(w0 + 2 * qc + 1, W + 2 * pad - 1), W, pad);
+      const int s0 = gnx_slide_src(min(w0 + 2 * qc, W + 2 * pad - 1), W, pad);
+      const int s1 = gnx_slide_src(min(w0 + 2 * qc + 1, W + 2 * pad - 1), W, pad);
       const u32x4 x = *reinterpret_cast<const u32x4*>(img + ((size_t)s0 * A + ac) * HB);
       const u32x4 y = *reinterpret_cast<const u32x4*>(img + ((size_t)s1 * A + ac) * HB);
       u32x4 lo4, hi4;  // haplotypes 0-3 and 4-7 of the thread's eight: rank(2q) | rank(2q + 1) << 16
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(THREADS, 8) void k_smooth_xgb_h32(SmoothXGBLaunch L
           ok[i] = rr + i * 32 < per_h;
           const int qc = ok[i] ? q : P - 1, ac = ok[i] ? a : A - 1;  // clamped: loads stay unconditional
           const int j = min(w0 + qc, W + 2 * pad - 1);
-          const size_t idx = (row + slide_src(j, W, pad)) * A + ac;
+          const size_t idx = (row + gnx_slide_src(j, W, pad)) * A + ac;
           p[i] = L.b_is_f64 ? (float)reinterpret_cast<const double*>(L.B)[idx] : reinterpret_cast<const float*>(L.B)[idx];
           dst[i] = ((qc >> 1) * A + ac) * 128 + hl * 4 + (qc & 1) * 2;
           a += da;

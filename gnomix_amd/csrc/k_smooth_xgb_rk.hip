@@ -386,7 +386,7 @@ __global__ __launch_bounds__(NWAVE * 64) void k_smooth_xgb_rk(SmoothXGBLaunch L)
         const int q = rr / A, a = rr - q * A;
         const int64_t n = min(h0 + hl, L.N - 1);
         const int j = min(w0 + q, W + 2 * pad - 1);
-        const size_t idx = ((size_t)n * W + slide_src(j, W, pad)) * A + a;
+        const size_t idx = ((size_t)n * W + gnx_slide_src(j, W, pad)) * A + a;
         p[i] = L.b_is_f64 ? (float)reinterpret_cast<const double*>(L.B)[idx] : reinterpret_cast<const float*>(L.B)[idx];
         dst[i] = (hl * A + a) * stride + q;
       }

@@ -14,7 +14,8 @@
 //     x a slice of the rows, its 128 KB of LDS holding [feature][node][bin] sums) that visits only the rows of the SMALLER child of
 //     every split (the sibling's histogram is parent - built, exact in int64), one split search (a wave per feature: prefix sums
 //     over the bins, gains in float64, ties to the lowest feature then the lowest bin), one partition pass;
-//   * the softmax goes through det_exp (plain IEEE operations in a fixed order) because the oracle must reproduce p exactly.
+//   * the softmax goes through det_exp (forest/gnx_det_exp.h: plain IEEE operations in a fixed order) because the oracle must
+//     reproduce p exactly.
 // The trees come back in the layout gnx_model_desc takes (tree_off / left / right / feat / cond / tree_class), thresholds on
 // the 1/65536 grid, so the trained smoother runs on k_smooth_xgb_rk like any other.
 #include <algorithm>
@@ -25,6 +26,8 @@
 #include <vector>
 
 #include "gnx_internal.h"
+#include "gnx_window.h"
+#include "forest/gnx_det_exp.h"
 
 namespace {
 
@@ -37,36 +40,9 @@ struct Geom {
   int32_t W, A, S, pad, Wp, F;
 };
 
-__device__ __forceinline__ int slide_src(int j, int W, int pad) {
-  if (j < pad) return pad - 1 - j;
-  if (j < pad + W) return j - pad;
-  return W - 1 - (j - pad - W);
-}
 __device__ __forceinline__ int bucket_of(float v) {
   int b = (v > 0.0f) ? (int)(v * 65536.0f) : 0;
   return (v >= 1.0f) ? 65535 : b;
-}
-
-__device__ __forceinline__ double det_exp(double x) {  // x <= 0; the same operations, in the same order, as the oracle's
-  if (!(x > -745.0)) return 0.0;
-  const double LOG2E = 1.4426950408889634, LN2_HI = 6.93147180369123816490e-01, LN2_LO = 1.90821492927058770002e-10;
-  const double kf = rint(x * LOG2E);
-  const double r = (x - kf * LN2_HI) - kf * LN2_LO;
-  double p = 1.0 / 6227020800.0;
-  p = p * r + 1.0 / 479001600.0;
-  p = p * r + 1.0 / 39916800.0;
-  p = p * r + 1.0 / 3628800.0;
-  p = p * r + 1.0 / 362880.0;
-  p = p * r + 1.0 / 40320.0;
-  p = p * r + 1.0 / 5040.0;
-  p = p * r + 1.0 / 720.0;
-  p = p * r + 1.0 / 120.0;
-  p = p * r + 1.0 / 24.0;
-  p = p * r + 1.0 / 6.0;
-  p = p * r + 0.5;
-  p = p * r + 1.0;
-  p = p * r + 1.0;
-  return ldexp(p, (int)kf);
 }
 
 template <bool IS64>
@@ -85,7 +61,7 @@ __global__ __launch_bounds__(256) void k_gbt_quantise(const float* Bf, const uin
   const int64_t nj = e / G.A;
   const int j = (int)(nj % G.Wp);
   const int64_t n = nj / G.Wp;
-  const float v = Bf[(n * G.W + slide_src(j, G.W, G.pad)) * G.A + a];
+  const float v = Bf[(n * G.W + gnx_slide_src(j, G.W, G.pad)) * G.A + a];
   Bq[e] = lut[(size_t)a * 65536 + bucket_of(v)];
 }
 
@@ -508,25 +484,12 @@ __global__ __launch_bounds__(256) void k_gbt_exact_partition(const float* Bf, ui
     const int64_t n = i / G.W;
     const int w = (int)(i - n * G.W);
     const int f = nF[c * MAXN + node], sft = f / G.A, a = f - sft * G.A;
-    const float v = Bf[(n * G.W + slide_src(w + sft, G.W, G.pad)) * G.A + a];
+    const float v = Bf[(n * G.W + gnx_slide_src(w + sft, G.W, G.pad)) * G.A + a];
     pos[(size_t)c * G.R + i] = (uint8_t)(v < __int_as_float(nB[c * MAXN + node]) ? 2 * node + 1 : 2 * node + 2);
   }
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-  template <typename T> T* as() { return reinterpret_cast<T*>(p); }
-};
-
 }  // namespace
-
-#define GBT_HIP(x)                      \
-  do {                                  \
-    const hipError_t e_ = (x);          \
-    if (e_ != hipSuccess) return e_;    \
-  } while (0)
 
 // dB (N, W, A) float32 / float64 and dy (N, W) int32 on the device.  Host outputs as in gnx_train_gbt (include/gnomix_hip.h).
 hipError_t gnx_train_gbt_run(const void* dB, int b_is_f64, const int32_t* dy, int64_t N, int32_t W, int32_t A, int32_t S,
@@ -536,39 +499,39 @@ hipError_t gnx_train_gbt_run(const void* dB, int b_is_f64, const int32_t* dy, in
   G.N = N; G.W = W; G.A = A; G.S = S; G.pad = (S + 1) / 2; G.Wp = W + 2 * G.pad; G.F = S * A; G.R = N * (int64_t)W;
   const int D = P.max_depth, T = P.n_rounds * A;
   const int64_t RA = G.R * A;
-  DevBuf bBf, bCnt, bLut, bBq, bFm, bG, bH, bPos, bPart, bTab, bNcut, bLoss, bCand, bRows, bLev;
-  GBT_HIP(bBf.alloc((size_t)RA * 4));
-  GBT_HIP(bCnt.alloc((size_t)A * 65536 * 4));
-  GBT_HIP(bLut.alloc((size_t)A * 65536));
-  GBT_HIP(bBq.alloc((size_t)N * G.Wp * A + 64));
-  GBT_HIP(bFm.alloc((size_t)RA * 4));
-  GBT_HIP(bG.alloc((size_t)RA * 8));
-  GBT_HIP(bH.alloc((size_t)RA * 8));
-  GBT_HIP(bPos.alloc((size_t)RA));
-  GBT_HIP(bNcut.alloc((size_t)A * 4));
-  GBT_HIP(bLoss.alloc((size_t)(P.n_rounds + 1) * 8));
-  GBT_HIP(bCand.alloc((size_t)A * 32 * SPLIT_CHUNKS * sizeof(Best)));
+  gnx_dev_tmp bBf, bCnt, bLut, bBq, bFm, bG, bH, bPos, bPart, bTab, bNcut, bLoss, bCand, bRows, bLev;
+  GNX_HIPRET(bBf.alloc((size_t)RA * 4));
+  GNX_HIPRET(bCnt.alloc((size_t)A * 65536 * 4));
+  GNX_HIPRET(bLut.alloc((size_t)A * 65536));
+  GNX_HIPRET(bBq.alloc((size_t)N * G.Wp * A + 64));
+  GNX_HIPRET(bFm.alloc((size_t)RA * 4));
+  GNX_HIPRET(bG.alloc((size_t)RA * 8));
+  GNX_HIPRET(bH.alloc((size_t)RA * 8));
+  GNX_HIPRET(bPos.alloc((size_t)RA));
+  GNX_HIPRET(bNcut.alloc((size_t)A * 4));
+  GNX_HIPRET(bLoss.alloc((size_t)(P.n_rounds + 1) * 8));
+  GNX_HIPRET(bCand.alloc((size_t)A * 32 * SPLIT_CHUNKS * sizeof(Best)));
   // node tables of every tree: [T][63] x {G, H (int64), F, B, st (int32), V (float)}
   const size_t tab_n = (size_t)T * MAXN;
-  GBT_HIP(bTab.alloc(tab_n * (8 + 8 + 4 + 4 + 4 + 4)));
+  GNX_HIPRET(bTab.alloc(tab_n * (8 + 8 + 4 + 4 + 4 + 4)));
   long long* tG = bTab.as<long long>();
   long long* tH = tG + tab_n;
   int32_t* tF = reinterpret_cast<int32_t*>(tH + tab_n);
   int32_t* tB = tF + tab_n;
   int32_t* tS = tB + tab_n;
   float* tV = reinterpret_cast<float*>(tS + tab_n);
-  GBT_HIP(hipMemsetAsync(bTab.p, 0, tab_n * 32, s));
-  GBT_HIP(hipMemsetAsync(bCnt.p, 0, (size_t)A * 65536 * 4, s));
-  GBT_HIP(hipMemsetAsync(bLoss.p, 0, (size_t)(P.n_rounds + 1) * 8, s));
+  GNX_HIPRET(hipMemsetAsync(bTab.p, 0, tab_n * 32, s));
+  GNX_HIPRET(hipMemsetAsync(bCnt.p, 0, (size_t)A * 65536 * 4, s));
+  GNX_HIPRET(hipMemsetAsync(bLoss.p, 0, (size_t)(P.n_rounds + 1) * 8, s));
 
   // ---- cuts ----
   const unsigned gRA = (unsigned)((RA + 255) / 256);
   if (b_is_f64) hipLaunchKernelGGL(k_gbt_cast_count<true>, dim3(gRA), dim3(256), 0, s, dB, bBf.as<float>(), bCnt.as<uint32_t>(), G);
   else hipLaunchKernelGGL(k_gbt_cast_count<false>, dim3(gRA), dim3(256), 0, s, dB, bBf.as<float>(), bCnt.as<uint32_t>(), G);
-  GBT_HIP(hipGetLastError());
+  GNX_HIPRET(hipGetLastError());
   std::vector<uint32_t> cnt((size_t)A * 65536);
-  GBT_HIP(hipMemcpyAsync(cnt.data(), bCnt.p, cnt.size() * 4, hipMemcpyDeviceToHost, s));
-  GBT_HIP(hipStreamSynchronize(s));
+  GNX_HIPRET(hipMemcpyAsync(cnt.data(), bCnt.p, cnt.size() * 4, hipMemcpyDeviceToHost, s));
+  GNX_HIPRET(hipStreamSynchronize(s));
   std::vector<float> cuts((size_t)A * 256, 0.f);
   std::vector<int32_t> ncut((size_t)A, 0);
   std::vector<uint8_t> lut((size_t)A * 65536);
@@ -588,21 +551,21 @@ hipError_t gnx_train_gbt_run(const void* dB, int b_is_f64, const int32_t* dy, in
       lut[(size_t)a * 65536 + u] = (uint8_t)c;
     }
   }
-  GBT_HIP(hipMemcpyAsync(bLut.p, lut.data(), lut.size(), hipMemcpyHostToDevice, s));
-  GBT_HIP(hipMemcpyAsync(bNcut.p, ncut.data(), (size_t)A * 4, hipMemcpyHostToDevice, s));
+  GNX_HIPRET(hipMemcpyAsync(bLut.p, lut.data(), lut.size(), hipMemcpyHostToDevice, s));
+  GNX_HIPRET(hipMemcpyAsync(bNcut.p, ncut.data(), (size_t)A * 4, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_gbt_quantise, dim3((unsigned)((N * G.Wp * A + 255) / 256)), dim3(256), 0, s, bBf.as<float>(), bLut.as<uint8_t>(),
                      bBq.as<uint8_t>(), G);
   hipLaunchKernelGGL(k_gbt_fill, dim3(gRA), dim3(256), 0, s, bFm.as<float>(), (float)P.base_score, RA);
-  GBT_HIP(hipGetLastError());
+  GNX_HIPRET(hipGetLastError());
 
   // ---- exact greedy: one sorted list of padded strip positions per class column (host sort, once per training) ----
   const bool exact = P.tree_method == 1;
-  DevBuf bOrdN, bOrdJ, bVal, bEx;
+  gnx_dev_tmp bOrdN, bOrdJ, bVal, bEx;
   if (exact) {
     const int64_t NP = N * G.Wp;
     std::vector<float> hB((size_t)RA);
-    GBT_HIP(hipMemcpyAsync(hB.data(), bBf.p, (size_t)RA * 4, hipMemcpyDeviceToHost, s));
-    GBT_HIP(hipStreamSynchronize(s));
+    GNX_HIPRET(hipMemcpyAsync(hB.data(), bBf.p, (size_t)RA * 4, hipMemcpyDeviceToHost, s));
+    GNX_HIPRET(hipStreamSynchronize(s));
     std::vector<int32_t> on((size_t)A * NP), oj((size_t)A * NP);
     std::vector<float> ov((size_t)A * NP);
     auto sort_col = [&](int a) {
@@ -630,14 +593,14 @@ hipError_t gnx_train_gbt_run(const void* dB, int b_is_f64, const int32_t* dy, in
       }
       for (auto& t : th) t.join();
     }
-    GBT_HIP(bOrdN.alloc((size_t)A * NP * 4));
-    GBT_HIP(bOrdJ.alloc((size_t)A * NP * 4));
-    GBT_HIP(bVal.alloc((size_t)A * NP * 4));
-    GBT_HIP(bEx.alloc((size_t)A * 16 * G.F * sizeof(ExBest)));
-    GBT_HIP(hipMemcpyAsync(bOrdN.p, on.data(), (size_t)A * NP * 4, hipMemcpyHostToDevice, s));
-    GBT_HIP(hipMemcpyAsync(bOrdJ.p, oj.data(), (size_t)A * NP * 4, hipMemcpyHostToDevice, s));
-    GBT_HIP(hipMemcpyAsync(bVal.p, ov.data(), (size_t)A * NP * 4, hipMemcpyHostToDevice, s));
-    GBT_HIP(hipStreamSynchronize(s));   // (the host vectors leave scope)
+    GNX_HIPRET(bOrdN.alloc((size_t)A * NP * 4));
+    GNX_HIPRET(bOrdJ.alloc((size_t)A * NP * 4));
+    GNX_HIPRET(bVal.alloc((size_t)A * NP * 4));
+    GNX_HIPRET(bEx.alloc((size_t)A * 16 * G.F * sizeof(ExBest)));
+    GNX_HIPRET(hipMemcpyAsync(bOrdN.p, on.data(), (size_t)A * NP * 4, hipMemcpyHostToDevice, s));
+    GNX_HIPRET(hipMemcpyAsync(bOrdJ.p, oj.data(), (size_t)A * NP * 4, hipMemcpyHostToDevice, s));
+    GNX_HIPRET(hipMemcpyAsync(bVal.p, ov.data(), (size_t)A * NP * 4, hipMemcpyHostToDevice, s));
+    GNX_HIPRET(hipStreamSynchronize(s));   // (the host vectors leave scope)
   }
 
   // ---- histogram geometry per level: features per block from the LDS budget, row slices to fill the chip ----
@@ -653,14 +616,14 @@ hipError_t gnx_train_gbt_run(const void* dB, int b_is_f64, const int32_t* dy, in
     nsl[d] = ns;
     part_entries = std::max(part_entries, (size_t)ns * A * nl * G.F * 512);
   }
-  GBT_HIP(bPart.alloc(part_entries * 8));
+  GNX_HIPRET(bPart.alloc(part_entries * 8));
   // rows per node and "build this node's histogram" flags of the round's trees; the level's summed histograms, this level's and the
   // previous one's (a derived node reads its parent's)
-  GBT_HIP(bRows.alloc((size_t)2 * A * MAXN * 4));
+  GNX_HIPRET(bRows.alloc((size_t)2 * A * MAXN * 4));
   int32_t* dCnt = bRows.as<int32_t>();
   int32_t* dBuild = dCnt + (size_t)A * MAXN;
   const size_t lev_entries = (size_t)A * ((size_t)1 << (D - 1)) * G.F * 512;
-  GBT_HIP(bLev.alloc(2 * lev_entries * 8));
+  GNX_HIPRET(bLev.alloc(2 * lev_entries * 8));
   GNX_LDS_OPTIN((size_t)HIST_ENTRIES * 16, k_gbt_hist);
 
   const unsigned gR = (unsigned)((G.R + 255) / 256);
@@ -673,22 +636,22 @@ hipError_t gnx_train_gbt_run(const void* dB, int b_is_f64, const int32_t* dy, in
     int32_t* rS = tS + o;
     float* rV = tV + o;
     if (r == P.n_rounds) {  // loss after the last round: gradients into scratch tables that are not read again
-      DevBuf scratch;
-      GBT_HIP(scratch.alloc((size_t)A * MAXN * 24));
-      GBT_HIP(hipMemsetAsync(scratch.p, 0, (size_t)A * MAXN * 24, s));
+      gnx_dev_tmp scratch;
+      GNX_HIPRET(scratch.alloc((size_t)A * MAXN * 24));
+      GNX_HIPRET(hipMemsetAsync(scratch.p, 0, (size_t)A * MAXN * 24, s));
       long long* sG = scratch.as<long long>();
       if (A <= 8) hipLaunchKernelGGL(k_gbt_grad<8>, dim3(gR), dim3(256), 0, s, bFm.as<float>(), dy, bG.as<long long>(), bH.as<long long>(), sG, sG + A * MAXN, bLoss.as<long long>() + r, bPos.as<uint8_t>(), reinterpret_cast<int32_t*>(sG + 2 * A * MAXN), G);
       else if (A <= 16) hipLaunchKernelGGL(k_gbt_grad<16>, dim3(gR), dim3(256), 0, s, bFm.as<float>(), dy, bG.as<long long>(), bH.as<long long>(), sG, sG + A * MAXN, bLoss.as<long long>() + r, bPos.as<uint8_t>(), reinterpret_cast<int32_t*>(sG + 2 * A * MAXN), G);
       else hipLaunchKernelGGL(k_gbt_grad<32>, dim3(gR), dim3(256), 0, s, bFm.as<float>(), dy, bG.as<long long>(), bH.as<long long>(), sG, sG + A * MAXN, bLoss.as<long long>() + r, bPos.as<uint8_t>(), reinterpret_cast<int32_t*>(sG + 2 * A * MAXN), G);
-      GBT_HIP(hipGetLastError());
-      GBT_HIP(hipStreamSynchronize(s));
+      GNX_HIPRET(hipGetLastError());
+      GNX_HIPRET(hipStreamSynchronize(s));
       break;
     }
     if (A <= 8) hipLaunchKernelGGL(k_gbt_grad<8>, dim3(gR), dim3(256), 0, s, bFm.as<float>(), dy, bG.as<long long>(), bH.as<long long>(), rG, rH, bLoss.as<long long>() + r, bPos.as<uint8_t>(), rS, G);
     else if (A <= 16) hipLaunchKernelGGL(k_gbt_grad<16>, dim3(gR), dim3(256), 0, s, bFm.as<float>(), dy, bG.as<long long>(), bH.as<long long>(), rG, rH, bLoss.as<long long>() + r, bPos.as<uint8_t>(), rS, G);
     else hipLaunchKernelGGL(k_gbt_grad<32>, dim3(gR), dim3(256), 0, s, bFm.as<float>(), dy, bG.as<long long>(), bH.as<long long>(), rG, rH, bLoss.as<long long>() + r, bPos.as<uint8_t>(), rS, G);
-    GBT_HIP(hipMemsetAsync(dCnt, 0, (size_t)A * MAXN * 4, s));
-    GBT_HIP(hipMemsetAsync(dBuild, 0xff, (size_t)A * MAXN * 4, s));  // (the roots are built; children are decided by k_gbt_choose)
+    GNX_HIPRET(hipMemsetAsync(dCnt, 0, (size_t)A * MAXN * 4, s));
+    GNX_HIPRET(hipMemsetAsync(dBuild, 0xff, (size_t)A * MAXN * 4, s));  // (the roots are built; children are decided by k_gbt_choose)
     for (int d = 0; exact && d < D; ++d) {
       const int nl = 1 << d;
       hipLaunchKernelGGL(k_gbt_exact_scan, dim3((unsigned)G.F, (unsigned)A), dim3(64), 0, s, bOrdN.as<int32_t>(), bOrdJ.as<int32_t>(), bVal.as<float>(),
@@ -710,19 +673,19 @@ hipError_t gnx_train_gbt_run(const void* dB, int b_is_f64, const int32_t* dy, in
     }
     hipLaunchKernelGGL(k_gbt_close, dim3((unsigned)((A * MAXN + 255) / 256)), dim3(256), 0, s, rG, rH, rS, rV, A, P.eta, P.lambda);
     hipLaunchKernelGGL(k_gbt_margin, dim3(gRA), dim3(256), 0, s, bFm.as<float>(), bPos.as<uint8_t>(), rV, G);
-    GBT_HIP(hipGetLastError());
+    GNX_HIPRET(hipGetLastError());
   }
 
   // ---- trees back to the host, nodes in heap order ----
   std::vector<int32_t> hF(tab_n), hB(tab_n), hS(tab_n);
   std::vector<float> hV(tab_n);
   std::vector<long long> hL((size_t)P.n_rounds + 1);
-  GBT_HIP(hipMemcpyAsync(hF.data(), tF, tab_n * 4, hipMemcpyDeviceToHost, s));
-  GBT_HIP(hipMemcpyAsync(hB.data(), tB, tab_n * 4, hipMemcpyDeviceToHost, s));
-  GBT_HIP(hipMemcpyAsync(hS.data(), tS, tab_n * 4, hipMemcpyDeviceToHost, s));
-  GBT_HIP(hipMemcpyAsync(hV.data(), tV, tab_n * 4, hipMemcpyDeviceToHost, s));
-  GBT_HIP(hipMemcpyAsync(hL.data(), bLoss.p, hL.size() * 8, hipMemcpyDeviceToHost, s));
-  GBT_HIP(hipStreamSynchronize(s));
+  GNX_HIPRET(hipMemcpyAsync(hF.data(), tF, tab_n * 4, hipMemcpyDeviceToHost, s));
+  GNX_HIPRET(hipMemcpyAsync(hB.data(), tB, tab_n * 4, hipMemcpyDeviceToHost, s));
+  GNX_HIPRET(hipMemcpyAsync(hS.data(), tS, tab_n * 4, hipMemcpyDeviceToHost, s));
+  GNX_HIPRET(hipMemcpyAsync(hV.data(), tV, tab_n * 4, hipMemcpyDeviceToHost, s));
+  GNX_HIPRET(hipMemcpyAsync(hL.data(), bLoss.p, hL.size() * 8, hipMemcpyDeviceToHost, s));
+  GNX_HIPRET(hipStreamSynchronize(s));
   int64_t nn = 0;
   tree_off[0] = 0;
   for (int t = 0; t < T; ++t) {

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "gnx_internal.h"
+#include "gnx_window.h"
 
 namespace {
 
@@ -34,12 +35,6 @@ struct Geom {
   int32_t W, A, npw;   // npw = problems per window: A (one-vs-rest) or 1 (A == 2)
   int32_t len, len_last, ldw;  // window widths (M + 2ctx, + C mod M for the last), row stride of the weight arrays (= len_last + 1)
 };
-
-__device__ __forceinline__ int64_t pad_src(int64_t p, int64_t C, int64_t ctx) {
-  if (p < ctx) return ctx - 1 - p;
-  if (p < ctx + C) return p - ctx;
-  return C - 1 - (p - ctx - C);
-}
 
 constexpr int AMAX = 32;
 constexpr int FH = 2;    // haplotypes per thread in the forward product
@@ -105,7 +100,7 @@ __global__ __launch_bounds__(128) void k_tr_forward(Geom g, const int8_t* __rest
       for (int k = 0; k < kc; ++k) {
         double x[FH];
 #pragma unroll
-        for (int h = 0; h < FH; ++h) x[h] = (double)row[h][pad_src(start + k0 + k, g.C, g.ctx)];
+        for (int h = 0; h < FH; ++h) x[h] = (double)row[h][gnx_pad_src(start + k0 + k, g.C, g.ctx)];
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
           const double v = vs[k * AMAX + p];
@@ -162,7 +157,7 @@ __global__ __launch_bounds__(BK) void k_tr_backward(Geom g, const int8_t* __rest
         const int r = e / BK, c = e - r * BK;
         const int64_t n = n0 + r, pp = start + k0 + c;
         uint8_t v = 0;
-        if (n < g.N && k0 + c < len) v = (uint8_t)X[n * g.ldx + pad_src(pp, g.C, g.ctx)];
+        if (n < g.N && k0 + c < len) v = (uint8_t)X[n * g.ldx + gnx_pad_src(pp, g.C, g.ctx)];
         else if (n < g.N && k0 + c == len) v = 1;  // the bias feature
         xt[r][c] = v;
       }
@@ -278,22 +273,6 @@ __global__ __launch_bounds__(256) void k_tr_vec(int ldw, double* __restrict__ a,
   }
 }
 
-struct DevArr {
-  double* p = nullptr;
-  hipError_t alloc(size_t n) {
-    hipError_t e = hipMalloc(&p, n * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(p, 0, n * sizeof(double));
-    return e;
-  }
-  ~DevArr() { if (p) (void)hipFree(p); }
-};
-
-#define TRCHK(expr)                                  \
-  do {                                               \
-    const hipError_t e_ = (expr);                    \
-    if (e_ != hipSuccess) return e_;                 \
-  } while (0)
-
 }  // namespace
 
 // Newton-CG for all P = W * npw problems in lockstep; per-problem step lengths, masks and stopping.
@@ -307,13 +286,20 @@ hipError_t gnx_train_lr_run(const int8_t* dX, int64_t N, int64_t ldx, const int3
   const int W = g.W, npw = g.npw, P = W * npw, ldw = g.ldw;
   const size_t PV = (size_t)P * ldw, NS = (size_t)N * W * npw;
 
-  DevArr w, grad, s, r, d, Hd, zv, pre, Z, Zs, R, D, sc1, sc2, sc3, loss, loss_try;
-  for (DevArr* a : {&w, &grad, &s, &r, &d, &Hd, &zv, &pre}) TRCHK(a->alloc(PV));
-  for (DevArr* a : {&Z, &Zs, &R, &D}) TRCHK(a->alloc(NS));
-  for (DevArr* a : {&sc1, &sc2, &sc3, &loss, &loss_try}) TRCHK(a->alloc((size_t)P));
-  int32_t* act = nullptr;
-  TRCHK(hipMalloc(&act, (size_t)P * sizeof(int32_t)));
-  struct ActFree { int32_t* p; ~ActFree() { (void)hipFree(p); } } act_free{act};
+  gnx_dev_tmp mem[18];  // the 17 float64 arrays below and act
+  int n_mem = 0;
+  auto zeros = [&](double*& out, size_t n) -> hipError_t {
+    gnx_dev_tmp& m = mem[n_mem++];
+    GNX_HIPRET(m.alloc(n * sizeof(double)));
+    out = m.as<double>();
+    return hipMemset(out, 0, n * sizeof(double));
+  };
+  double *w, *grad, *s, *r, *d, *Hd, *zv, *pre, *Z, *Zs, *R, *D, *sc1, *sc2, *sc3, *loss, *loss_try;
+  for (double** a : {&w, &grad, &s, &r, &d, &Hd, &zv, &pre}) GNX_HIPRET(zeros(*a, PV));
+  for (double** a : {&Z, &Zs, &R, &D}) GNX_HIPRET(zeros(*a, NS));
+  for (double** a : {&sc1, &sc2, &sc3, &loss, &loss_try}) GNX_HIPRET(zeros(*a, (size_t)P));
+  GNX_HIPRET(mem[n_mem].alloc((size_t)P * sizeof(int32_t)));
+  int32_t* const act = mem[n_mem].as<int32_t>();
 
   const dim3 fgrid((unsigned)((N + 128 * FH - 1) / (128 * FH)), (unsigned)W);
   const dim3 bgrid((unsigned)((g.len_last + 1 + BK - 1) / BK), (unsigned)W);
@@ -331,34 +317,34 @@ hipError_t gnx_train_lr_run(const int8_t* dX, int64_t N, int64_t ldx, const int3
   };
   std::vector<double> h1((size_t)P), h2((size_t)P), h3((size_t)P), hf((size_t)P), hfold((size_t)P), gnorm0((size_t)P), step((size_t)P);
   std::vector<int32_t> hact((size_t)P, 1), done((size_t)P, 0);
-  auto pull = [&](const DevArr& a, std::vector<double>& h) -> hipError_t {
-    TRCHK(hipMemcpyAsync(h.data(), a.p, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, st));
+  auto pull = [&](const double* a, std::vector<double>& h) -> hipError_t {
+    GNX_HIPRET(hipMemcpyAsync(h.data(), a, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, st));
     return hipStreamSynchronize(st);
   };
-  auto push = [&](const std::vector<double>& h, DevArr& a) -> hipError_t {
-    return hipMemcpyAsync(a.p, h.data(), (size_t)P * sizeof(double), hipMemcpyHostToDevice, st);
+  auto push = [&](const std::vector<double>& h, double* a) -> hipError_t {
+    return hipMemcpyAsync(a, h.data(), (size_t)P * sizeof(double), hipMemcpyHostToDevice, st);
   };
   auto push_act = [&](const std::vector<int32_t>& h) -> hipError_t {
-    TRCHK(hipMemcpyAsync(act, h.data(), (size_t)P * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    GNX_HIPRET(hipMemcpyAsync(act, h.data(), (size_t)P * sizeof(int32_t), hipMemcpyHostToDevice, st));
     return hipStreamSynchronize(st);  // the host vector is reused right away
   };
   // f, gradient and Hessian weights at the current w (Z = X w is kept up to date by the caller)
   auto eval_grad = [&]() -> hipError_t {
-    TRCHK(hipMemsetAsync(loss.p, 0, (size_t)P * sizeof(double), st));
-    hipLaunchKernelGGL(k_tr_sample<1>, sgrid, dim3(256), 0, st, g, Creg, dY, Z.p, nullptr, nullptr, R.p, D.p, loss.p);
-    backward(R.p, grad.p);
-    hipLaunchKernelGGL(k_tr_vec<V_ADD>, dim3(P), dim3(256), 0, st, ldw, grad.p, grad.p, w.p, nullptr, nullptr, nullptr, 1.0);  // + w
-    vdot(w.p, w.p, sc1.p);
-    vdot(grad.p, grad.p, sc2.p);
-    TRCHK(pull(loss, hf));
-    TRCHK(pull(sc1, h1));
-    TRCHK(pull(sc2, h2));
+    GNX_HIPRET(hipMemsetAsync(loss, 0, (size_t)P * sizeof(double), st));
+    hipLaunchKernelGGL(k_tr_sample<1>, sgrid, dim3(256), 0, st, g, Creg, dY, Z, nullptr, nullptr, R, D, loss);
+    backward(R, grad);
+    hipLaunchKernelGGL(k_tr_vec<V_ADD>, dim3(P), dim3(256), 0, st, ldw, grad, grad, w, nullptr, nullptr, nullptr, 1.0);  // + w
+    vdot(w, w, sc1);
+    vdot(grad, grad, sc2);
+    GNX_HIPRET(pull(loss, hf));
+    GNX_HIPRET(pull(sc1, h1));
+    GNX_HIPRET(pull(sc2, h2));
     for (int p = 0; p < P; ++p) hf[(size_t)p] += 0.5 * h1[(size_t)p];
     return hipGetLastError();
   };
 
   // w = 0: Z = 0 already
-  TRCHK(eval_grad());
+  GNX_HIPRET(eval_grad());
   for (int p = 0; p < P; ++p) gnorm0[(size_t)p] = std::sqrt(h2[(size_t)p]);
   int newton = 0, cg_total = 0;
   for (; newton < max_newton; ++newton) {
@@ -370,18 +356,18 @@ hipError_t gnx_train_lr_run(const int8_t* dX, int64_t N, int64_t ldx, const int3
       n_act += hact[(size_t)p];
     }
     if (n_act == 0) break;
-    TRCHK(push_act(hact));
+    GNX_HIPRET(push_act(hact));
     // ---- preconditioned CG on H s = -g, H v = v + X'(D .* X v) ----
-    backward_sq(D.p, pre.p);
-    hipLaunchKernelGGL(k_tr_vec<V_PRECOND>, dim3(P), dim3(256), 0, st, ldw, pre.p, pre.p, nullptr, nullptr, nullptr, nullptr, 1.0);
-    TRCHK(hipMemsetAsync(s.p, 0, PV * sizeof(double), st));
-    hipLaunchKernelGGL(k_tr_vec<V_COPY>, dim3(P), dim3(256), 0, st, ldw, r.p, grad.p, nullptr, nullptr, nullptr, nullptr, 1.0);
-    hipLaunchKernelGGL(k_tr_vec<V_AXPY>, dim3(P), dim3(256), 0, st, ldw, r.p, grad.p, nullptr, nullptr, nullptr, nullptr, -2.0);  // r = -g
-    hipLaunchKernelGGL(k_tr_vec<V_DIV>, dim3(P), dim3(256), 0, st, ldw, zv.p, r.p, pre.p, nullptr, nullptr, nullptr, 1.0);
-    hipLaunchKernelGGL(k_tr_vec<V_COPY>, dim3(P), dim3(256), 0, st, ldw, d.p, zv.p, nullptr, nullptr, nullptr, nullptr, 1.0);
-    vdot(zv.p, r.p, sc1.p);
+    backward_sq(D, pre);
+    hipLaunchKernelGGL(k_tr_vec<V_PRECOND>, dim3(P), dim3(256), 0, st, ldw, pre, pre, nullptr, nullptr, nullptr, nullptr, 1.0);
+    GNX_HIPRET(hipMemsetAsync(s, 0, PV * sizeof(double), st));
+    hipLaunchKernelGGL(k_tr_vec<V_COPY>, dim3(P), dim3(256), 0, st, ldw, r, grad, nullptr, nullptr, nullptr, nullptr, 1.0);
+    hipLaunchKernelGGL(k_tr_vec<V_AXPY>, dim3(P), dim3(256), 0, st, ldw, r, grad, nullptr, nullptr, nullptr, nullptr, -2.0);  // r = -g
+    hipLaunchKernelGGL(k_tr_vec<V_DIV>, dim3(P), dim3(256), 0, st, ldw, zv, r, pre, nullptr, nullptr, nullptr, 1.0);
+    hipLaunchKernelGGL(k_tr_vec<V_COPY>, dim3(P), dim3(256), 0, st, ldw, d, zv, nullptr, nullptr, nullptr, nullptr, 1.0);
+    vdot(zv, r, sc1);
     std::vector<double> ztr((size_t)P), ztr0((size_t)P);
-    TRCHK(pull(sc1, ztr));
+    GNX_HIPRET(pull(sc1, ztr));
     ztr0 = ztr;
     std::vector<int32_t> cact = hact;
     for (int it = 0; it < max_cg; ++it) {
@@ -393,42 +379,42 @@ hipError_t gnx_train_lr_run(const int8_t* dX, int64_t N, int64_t ldx, const int3
         nc += cact[(size_t)p];
       }
       if (nc == 0) break;
-      TRCHK(push_act(cact));
-      forward(d.p, Zs.p);
-      hipLaunchKernelGGL(k_tr_sample<2>, sgrid, dim3(256), 0, st, g, Creg, dY, Z.p, Zs.p, nullptr, R.p, D.p, nullptr);
-      backward(R.p, Hd.p);
-      hipLaunchKernelGGL(k_tr_vec<V_ADD>, dim3(P), dim3(256), 0, st, ldw, Hd.p, Hd.p, d.p, nullptr, nullptr, nullptr, 1.0);
-      vdot(d.p, Hd.p, sc2.p);
-      TRCHK(pull(sc2, h3));
+      GNX_HIPRET(push_act(cact));
+      forward(d, Zs);
+      hipLaunchKernelGGL(k_tr_sample<2>, sgrid, dim3(256), 0, st, g, Creg, dY, Z, Zs, nullptr, R, D, nullptr);
+      backward(R, Hd);
+      hipLaunchKernelGGL(k_tr_vec<V_ADD>, dim3(P), dim3(256), 0, st, ldw, Hd, Hd, d, nullptr, nullptr, nullptr, 1.0);
+      vdot(d, Hd, sc2);
+      GNX_HIPRET(pull(sc2, h3));
       std::vector<double> al((size_t)P, 0.0);
       for (int p = 0; p < P; ++p)
         if (cact[(size_t)p]) al[(size_t)p] = h3[(size_t)p] > 0 ? ztr[(size_t)p] / h3[(size_t)p] : 0.0;
-      TRCHK(push(al, sc3));
-      hipLaunchKernelGGL(k_tr_vec<V_AXPY>, dim3(P), dim3(256), 0, st, ldw, s.p, d.p, nullptr, sc3.p, act, nullptr, 1.0);
-      hipLaunchKernelGGL(k_tr_vec<V_AXPY>, dim3(P), dim3(256), 0, st, ldw, r.p, Hd.p, nullptr, sc3.p, act, nullptr, -1.0);
-      hipLaunchKernelGGL(k_tr_vec<V_DIV>, dim3(P), dim3(256), 0, st, ldw, zv.p, r.p, pre.p, nullptr, act, nullptr, 1.0);
-      vdot(zv.p, r.p, sc1.p);
+      GNX_HIPRET(push(al, sc3));
+      hipLaunchKernelGGL(k_tr_vec<V_AXPY>, dim3(P), dim3(256), 0, st, ldw, s, d, nullptr, sc3, act, nullptr, 1.0);
+      hipLaunchKernelGGL(k_tr_vec<V_AXPY>, dim3(P), dim3(256), 0, st, ldw, r, Hd, nullptr, sc3, act, nullptr, -1.0);
+      hipLaunchKernelGGL(k_tr_vec<V_DIV>, dim3(P), dim3(256), 0, st, ldw, zv, r, pre, nullptr, act, nullptr, 1.0);
+      vdot(zv, r, sc1);
       std::vector<double> znew((size_t)P);
-      TRCHK(pull(sc1, znew));
+      GNX_HIPRET(pull(sc1, znew));
       std::vector<double> beta((size_t)P, 0.0);
       for (int p = 0; p < P; ++p)
         if (cact[(size_t)p]) { beta[(size_t)p] = ztr[(size_t)p] > 0 ? znew[(size_t)p] / ztr[(size_t)p] : 0.0; ztr[(size_t)p] = znew[(size_t)p]; }
-      TRCHK(push(beta, sc3));
-      hipLaunchKernelGGL(k_tr_vec<V_XPBY>, dim3(P), dim3(256), 0, st, ldw, d.p, zv.p, nullptr, sc3.p, act, nullptr, 1.0);  // d = z + beta d
+      GNX_HIPRET(push(beta, sc3));
+      hipLaunchKernelGGL(k_tr_vec<V_XPBY>, dim3(P), dim3(256), 0, st, ldw, d, zv, nullptr, sc3, act, nullptr, 1.0);  // d = z + beta d
       ++cg_total;
     }
     // ---- Armijo backtracking along s: f(w + a s) <= f(w) + eta a g's ----
-    TRCHK(push_act(hact));
-    forward(s.p, Zs.p);
-    vdot(grad.p, s.p, sc1.p);
-    vdot(s.p, s.p, sc2.p);
-    vdot(w.p, s.p, sc3.p);
+    GNX_HIPRET(push_act(hact));
+    forward(s, Zs);
+    vdot(grad, s, sc1);
+    vdot(s, s, sc2);
+    vdot(w, s, sc3);
     std::vector<double> gs((size_t)P), ss((size_t)P), ws((size_t)P), ww((size_t)P);
-    TRCHK(pull(sc1, gs));
-    TRCHK(pull(sc2, ss));
-    TRCHK(pull(sc3, ws));
-    vdot(w.p, w.p, sc1.p);
-    TRCHK(pull(sc1, ww));
+    GNX_HIPRET(pull(sc1, gs));
+    GNX_HIPRET(pull(sc2, ss));
+    GNX_HIPRET(pull(sc3, ws));
+    vdot(w, w, sc1);
+    GNX_HIPRET(pull(sc1, ww));
     hfold = hf;
     std::vector<int32_t> ls = hact;
     for (int p = 0; p < P; ++p) step[(size_t)p] = hact[(size_t)p] ? 1.0 : 0.0;
@@ -436,10 +422,10 @@ hipError_t gnx_train_lr_run(const int8_t* dX, int64_t N, int64_t ldx, const int3
       int nl = 0;
       for (int p = 0; p < P; ++p) nl += ls[(size_t)p];
       if (nl == 0) break;
-      TRCHK(push(step, sc3));
-      TRCHK(hipMemsetAsync(loss_try.p, 0, (size_t)P * sizeof(double), st));
-      hipLaunchKernelGGL(k_tr_sample<0>, sgrid, dim3(256), 0, st, g, Creg, dY, Z.p, Zs.p, sc3.p, nullptr, nullptr, loss_try.p);
-      TRCHK(pull(loss_try, h3));
+      GNX_HIPRET(push(step, sc3));
+      GNX_HIPRET(hipMemsetAsync(loss_try, 0, (size_t)P * sizeof(double), st));
+      hipLaunchKernelGGL(k_tr_sample<0>, sgrid, dim3(256), 0, st, g, Creg, dY, Z, Zs, sc3, nullptr, nullptr, loss_try);
+      GNX_HIPRET(pull(loss_try, h3));
       for (int p = 0; p < P; ++p) {
         if (!ls[(size_t)p]) continue;
         const double a = step[(size_t)p];
@@ -450,17 +436,17 @@ hipError_t gnx_train_lr_run(const int8_t* dX, int64_t N, int64_t ldx, const int3
     }
     for (int p = 0; p < P; ++p)
       if (ls[(size_t)p]) { step[(size_t)p] = 0.0; done[(size_t)p] = 1; }  // no descent within 30 halvings: numerically at the optimum
-    TRCHK(push(step, sc3));
-    hipLaunchKernelGGL(k_tr_vec<V_AXPY>, dim3(P), dim3(256), 0, st, ldw, w.p, s.p, nullptr, sc3.p, nullptr, nullptr, 1.0);
-    forward(w.p, Z.p);  // exact Z for the new w (no drift from accumulating alpha * Zs)
-    TRCHK(eval_grad());
+    GNX_HIPRET(push(step, sc3));
+    hipLaunchKernelGGL(k_tr_vec<V_AXPY>, dim3(P), dim3(256), 0, st, ldw, w, s, nullptr, sc3, nullptr, nullptr, 1.0);
+    forward(w, Z);  // exact Z for the new w (no drift from accumulating alpha * Zs)
+    GNX_HIPRET(eval_grad());
     for (int p = 0; p < P; ++p)
       if (hact[(size_t)p] && std::fabs(hfold[(size_t)p] - hf[(size_t)p]) <= 1e-15 * std::fabs(hf[(size_t)p])) done[(size_t)p] = 1;
   }
   // ---- results ----
   std::vector<double> hw(PV);
-  TRCHK(hipMemcpyAsync(hw.data(), w.p, PV * sizeof(double), hipMemcpyDeviceToHost, st));
-  TRCHK(hipStreamSynchronize(st));
+  GNX_HIPRET(hipMemcpyAsync(hw.data(), w, PV * sizeof(double), hipMemcpyDeviceToHost, st));
+  GNX_HIPRET(hipStreamSynchronize(st));
   double worst = 0.0;
   for (int p = 0; p < P; ++p)
     if (gnorm0[(size_t)p] > 0) worst = std::max(worst, std::sqrt(h2[(size_t)p]) / gnorm0[(size_t)p]);

@@ -38,15 +38,9 @@
 // No float64, no table, no distance ever leaves the registers, no scratch, no runtime-indexed array, plain vector stores.
 // There is no training kernel: fitting a 1-NN classifier is storing the rows (gnomix_amd.train.train_knn_base).
 #include "../gnx_internal.h"
+#include "../gnx_window.h"
 
 #include <cstring>
-
-#define HIPCHK(ctx, expr)                                                                          \
-  do {                                                                                             \
-    hipError_t e__ = (expr);                                                                       \
-    if (e__ != hipSuccess)                                                                         \
-      return gnx_fail((ctx), GNX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));        \
-  } while (0)
 
 struct KnnWinDev {
   int32_t width, kp, n_fit, n_pad;  // SNPs; row pitch in bytes (width rounded up to 64); fit rows; rows rounded up to 128
@@ -82,12 +76,6 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 constexpr int32_t KNN_PAD_NORM = 1 << 30;
 constexpr int KNN_STEP = 128;  // fit rows per step: 4 waves x 2 column tiles of 16
 
-__device__ __forceinline__ int64_t pad_src(int64_t p, int64_t C, int64_t ctx) {
-  if (p < ctx) return ctx - 1 - p;
-  if (p < ctx + C) return p - ctx;
-  return C - 1 - (p - ctx - C);
-}
-
 // red [QB][4] int64 | cls [QB] int32 | xq [QB][kp + 16] int8   (QB * 36 is a multiple of 16)
 size_t knn_lds_bytes(int QB, int kp) { return (size_t)QB * 36 + (size_t)QB * (kp + 16); }
 
@@ -119,7 +107,7 @@ __global__ __launch_bounds__(256) void k_knn_argmin(KnnLaunch L) {
       uint32_t v = 0;
 #pragma unroll
       for (int b = 0; b < 4; ++b)
-        if (k4 + b < width) v |= (uint32_t)(uint8_t)row[pad_src(s + k4 + b, L.C, L.ctx)] << (8 * b);
+        if (k4 + b < width) v |= (uint32_t)(uint8_t)row[gnx_pad_src(s + k4 + b, L.C, L.ctx)] << (8 * b);
       *reinterpret_cast<uint32_t*>(xq + q * xs + k4) = v;
     }
   }

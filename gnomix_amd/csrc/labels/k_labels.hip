@@ -22,13 +22,6 @@
 // word is written by exactly one lane: no atomics.
 #include "../gnx_internal.h"
 
-#define HIPCHK(ctx, expr)                                                                          \
-  do {                                                                                             \
-    hipError_t e__ = (expr);                                                                       \
-    if (e__ != hipSuccess)                                                                         \
-      return gnx_fail((ctx), GNX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));        \
-  } while (0)
-
 namespace {
 
 constexpr int MF_THREADS = 256;

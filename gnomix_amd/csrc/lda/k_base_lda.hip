@@ -35,13 +35,6 @@
 
 #include <cmath>
 
-#define HIPCHK(ctx, expr)                                                                          \
-  do {                                                                                             \
-    hipError_t e__ = (expr);                                                                       \
-    if (e__ != hipSuccess)                                                                         \
-      return gnx_fail((ctx), GNX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));        \
-  } while (0)
-
 struct LdaWinDev {
   int64_t tab_off;  // positions: this window's coefficient rows start at tab[tab_off * 16]
   int32_t width;    // SNPs

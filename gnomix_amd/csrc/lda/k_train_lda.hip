@@ -29,13 +29,6 @@
 #include "../gnx_internal.h"
 #include "../gnx_window.h"
 
-#define HIPCHK(ctx, expr)                                                                          \
-  do {                                                                                             \
-    hipError_t e__ = (expr);                                                                       \
-    if (e__ != hipSuccess)                                                                         \
-      return gnx_fail((ctx), GNX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));        \
-  } while (0)
-
 namespace {
 
 typedef int v4i __attribute__((ext_vector_type(4)));

@@ -56,13 +56,6 @@
 #include <cmath>
 #include <cstring>
 
-#define HIPCHK(ctx, expr)                                                                          \
-  do {                                                                                             \
-    hipError_t e__ = (expr);                                                                       \
-    if (e__ != hipSuccess)                                                                         \
-      return gnx_fail((ctx), GNX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));        \
-  } while (0)
-
 struct NbWinDev {
   int64_t tab_off;   // positions: this window's table rows start at tab[tab_off * 64]
   int32_t width;     // SNPs
@@ -96,8 +89,6 @@ constexpr int NB_WAVES = 4;
 constexpr int NB_ROWS = NB_WAVES * NB_MT * 16;  // query rows per block
 constexpr int NB_PC = 16;                 // positions per X chunk (one 16-byte load per lane)
 
-__device__ __forceinline__ int64_t pad_src(int64_t p, int64_t C, int64_t ctx) { return gnx_pad_src(p, C, ctx); }
-
 __device__ __forceinline__ xbytes16 load_x16(const int8_t* p) {  // unaligned global_load_dwordx4
   xbytes16 r;
   __builtin_memcpy(&r, p, 16);
@@ -112,7 +103,7 @@ __device__ __forceinline__ xbytes16 gather_x16(const int8_t* row, int64_t s, int
     uint32_t v = 0;
 #pragma unroll
     for (int b = 0; b < 4; ++b)
-      if (p0 + 4 * q + b < width) v |= (uint32_t)(uint8_t)row[pad_src(s + p0 + 4 * q + b, C, ctx)] << (8 * b);
+      if (p0 + 4 * q + b < width) v |= (uint32_t)(uint8_t)row[gnx_pad_src(s + p0 + 4 * q + b, C, ctx)] << (8 * b);
     r.v[q] = v;
   }
   return r;
@@ -229,7 +220,7 @@ __global__ __launch_bounds__(NBC_BLOCK) void k_nb_count(const int8_t* __restrict
   const int width = (int)(M + 2 * ctx + (w == W - 1 ? C - M * W : 0));
   for (int c = 0; c < 2 * A; ++c) cnt[c * NBC_BLOCK + t] = 0;
   if (p < width) {
-    const int8_t* col = X + pad_src((int64_t)w * M + p, C, ctx);
+    const int8_t* col = X + gnx_pad_src((int64_t)w * M + p, C, ctx);
     for (int64_t n = 0; n < N; ++n) {
       const int32_t y = Y[n * W + w];  // the same address for the whole block
       const int x = col[n * ldx];

@@ -13,13 +13,6 @@
 // A true label or a predicted label outside [0, A) never indexes anything: it is counted in one extra cell.
 #include "../gnx_internal.h"
 
-#define HIPCHK(ctx, expr)                                                                          \
-  do {                                                                                             \
-    hipError_t e__ = (expr);                                                                       \
-    if (e__ != hipSuccess)                                                                         \
-      return gnx_fail((ctx), GNX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));        \
-  } while (0)
-
 namespace {
 
 constexpr int CM_THREADS = 256;

@@ -16,13 +16,6 @@
 // k_sim_check_tables / k_sim_check_founders: validation before anything is written; the first offence is kept with atomicMin.
 #include "../gnx_internal.h"
 
-#define HIPCHK(ctx, expr)                                                                          \
-  do {                                                                                             \
-    hipError_t e__ = (expr);                                                                       \
-    if (e__ != hipSuccess)                                                                         \
-      return gnx_fail((ctx), GNX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));        \
-  } while (0)
-
 namespace {
 
 constexpr int SIM_THREADS = 256;
@@ -271,12 +264,6 @@ extern "C" int gnx_simulate_admix_dev(gnx_ctx* ctx, const int8_t* dF, int64_t n_
 }
 
 namespace {
-struct DevBlock {  // the host entry's staging buffers, freed on every return
-  void* p = nullptr;
-  ~DevBlock() {
-    if (p) (void)hipFree(p);
-  }
-};
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 }  // namespace
 
@@ -300,8 +287,8 @@ extern "C" int gnx_simulate_admix(gnx_ctx* ctx, const int8_t* F, int64_t n_found
                bA = anc ? up256((size_t)N * C) : 0, bOff = up256((size_t)(N + 1) * 8), bSeg = up256((size_t)S * 4),
                bAnc = up256((size_t)n_founder_haps);
   GNX_BIND_DEVICE(ctx);
-  DevBlock blk;
-  hipError_t e = hipMalloc(&blk.p, bF + bX + bY + bA + bOff + 2 * bSeg + bAnc);
+  gnx_dev_tmp blk;  // the staging buffers, freed on every return
+  hipError_t e = blk.alloc(bF + bX + bY + bA + bOff + 2 * bSeg + bAnc);
   if (e != hipSuccess) {
     blk.p = nullptr;
     return gnx_fail(ctx, GNX_ENOMEM, std::string("simulate_admix: hipMalloc: ") + hipGetErrorString(e));

@@ -26,13 +26,6 @@
 // Neither kernel has a per-thread array that is indexed at run time; no scratch.
 #include "../gnx_internal.h"
 
-#define HIPCHK(ctx, expr)                                                                          \
-  do {                                                                                             \
-    hipError_t e__ = (expr);                                                                       \
-    if (e__ != hipSuccess)                                                                         \
-      return gnx_fail((ctx), GNX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));        \
-  } while (0)
-
 namespace {
 
 constexpr int AC_THREADS = 64;
@@ -361,6 +354,34 @@ extern "C" int gnx_ancestry_allele_counts_dev(gnx_ctx* ctx, const void* d_rows, 
   return verdict(ctx, "ancestry_allele_counts", d_bad, A, s);
 }
 
+namespace {
+// the (A, C) int32 tables of a host-pointer entry: three slabs of tb bytes in ws_b32, NULL for a table the caller did not ask for
+int table_slab(gnx_ctx* ctx, size_t tb, const int32_t* n_obs, const int32_t* n_alt, const int32_t* n_miss, int32_t** d_obs, int32_t** d_alt,
+               int32_t** d_miss) {
+  const int rc = gnx_ws_reserve(ctx, ctx->ws_b32, 3 * tb);
+  if (rc != GNX_OK) return rc;
+  char* o = (char*)ctx->ws_b32.p;
+  *d_obs = n_obs ? (int32_t*)o : nullptr;
+  *d_alt = n_alt ? (int32_t*)(o + tb) : nullptr;
+  *d_miss = n_miss ? (int32_t*)(o + 2 * tb) : nullptr;
+  return GNX_OK;
+}
+
+// the N > 0 host rows and labels of a host-pointer entry -> ws_xu and ws_lab
+int stage_rows_labels(gnx_ctx* ctx, const void* rows, int row_kind, int64_t ld_rows, const int32_t* labels, int64_t ld_labels, int64_t N, int64_t C,
+                      int64_t W, hipStream_t s) {
+  // the last row ends after its own bytes / labels, not after a whole stride
+  const size_t br = (size_t)(N - 1) * (size_t)ld_rows + (size_t)min_row_bytes(row_kind, C);
+  const size_t bl = ((size_t)(N - 1) * (size_t)ld_labels + (size_t)W) * sizeof(int32_t);
+  int rc;
+  if ((rc = gnx_ws_reserve(ctx, ctx->ws_xu, br + 64)) != GNX_OK) return rc;
+  if ((rc = gnx_ws_reserve(ctx, ctx->ws_lab, bl + 64)) != GNX_OK) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->ws_xu.p, rows, br, hipMemcpyHostToDevice, s));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->ws_lab.p, labels, bl, hipMemcpyHostToDevice, s));
+  return GNX_OK;
+}
+}  // namespace
+
 extern "C" int gnx_ancestry_allele_counts(gnx_ctx* ctx, const void* rows, int row_kind, int64_t ld_rows, const int32_t* labels, int64_t ld_labels,
                                           int64_t N, int64_t C, int64_t M, int64_t W, int32_t A, int32_t* n_obs, int32_t* n_alt, int32_t* n_miss,
                                           int64_t debug_rows_per_chunk, int64_t debug_flush_every) {
@@ -370,21 +391,10 @@ extern "C" int gnx_ancestry_allele_counts(gnx_ctx* ctx, const void* rows, int ro
   GNX_BIND_DEVICE(ctx);
   hipStream_t s = ctx->stream;
   const size_t tb = ((size_t)A * (size_t)C * sizeof(int32_t) + 255) & ~(size_t)255;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_b32, 3 * tb)) != GNX_OK) return rc;
-  char* o = (char*)ctx->ws_b32.p;
-  int32_t* d_obs = n_obs ? (int32_t*)o : nullptr;
-  int32_t* d_alt = n_alt ? (int32_t*)(o + tb) : nullptr;
-  int32_t* d_miss = n_miss ? (int32_t*)(o + 2 * tb) : nullptr;
+  int32_t *d_obs, *d_alt, *d_miss;
+  if ((rc = table_slab(ctx, tb, n_obs, n_alt, n_miss, &d_obs, &d_alt, &d_miss)) != GNX_OK) return rc;
   std::string msg;
-  if (N > 0) {
-    // the last row ends after its own bytes / labels, not after a whole stride
-    const size_t br = (size_t)(N - 1) * (size_t)ld_rows + (size_t)min_row_bytes(row_kind, C);
-    const size_t bl = ((size_t)(N - 1) * (size_t)ld_labels + (size_t)W) * sizeof(int32_t);
-    if ((rc = gnx_ws_reserve(ctx, ctx->ws_xu, br + 64)) != GNX_OK) return rc;
-    if ((rc = gnx_ws_reserve(ctx, ctx->ws_lab, bl + 64)) != GNX_OK) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ws_xu.p, rows, br, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ws_lab.p, labels, bl, hipMemcpyHostToDevice, s));
-  }
+  if (N > 0 && (rc = stage_rows_labels(ctx, rows, row_kind, ld_rows, labels, ld_labels, N, C, W, s)) != GNX_OK) return rc;
   rc = gnx_ancestry_allele_counts_dev(ctx, ctx->ws_xu.p, row_kind, ld_rows, (const int32_t*)ctx->ws_lab.p, ld_labels, N, C, M, W, A, d_obs, d_alt,
                                       d_miss, debug_rows_per_chunk, debug_flush_every);
   if (rc != GNX_OK && rc != GNX_EINVAL) return rc;
@@ -449,16 +459,11 @@ extern "C" int gnx_ancestry_dosage(gnx_ctx* ctx, const void* rows, int row_kind,
   GNX_BIND_DEVICE(ctx);
   hipStream_t s = ctx->stream;
   const int64_t n_ind = N / 2, ldo = (C + 15) / 16 * 16;
-  const size_t br = (size_t)(N - 1) * (size_t)ld_rows + (size_t)min_row_bytes(row_kind, C);
-  const size_t bl = ((size_t)(N - 1) * (size_t)ld_labels + (size_t)W) * sizeof(int32_t);
   const size_t bo = ((size_t)n_ind * (size_t)ldo + 255) & ~(size_t)255;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_xu, br + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_lab, bl + 64)) != GNX_OK) return rc;
   if ((rc = gnx_ws_reserve(ctx, ctx->ws_b32, 2 * bo)) != GNX_OK) return rc;
   uint8_t* d_d = dosage ? (uint8_t*)ctx->ws_b32.p : nullptr;
   uint8_t* d_h = hapcount ? (uint8_t*)ctx->ws_b32.p + bo : nullptr;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->ws_xu.p, rows, br, hipMemcpyHostToDevice, s));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->ws_lab.p, labels, bl, hipMemcpyHostToDevice, s));
+  if ((rc = stage_rows_labels(ctx, rows, row_kind, ld_rows, labels, ld_labels, N, C, W, s)) != GNX_OK) return rc;
   rc = gnx_ancestry_dosage_dev(ctx, ctx->ws_xu.p, row_kind, ld_rows, (const int32_t*)ctx->ws_lab.p, ld_labels, N, C, M, W, A, ancestry, d_d, ldo, d_h,
                                ldo);
   if (rc != GNX_OK && rc != GNX_EINVAL) return rc;
@@ -495,12 +500,9 @@ extern "C" int gnx_ancestry_allele_counts_gt2(gnx_model* m, const uint8_t* G, in
   hipStream_t s = ctx->stream;
   int rc;
   const size_t tbytes = (size_t)A * (size_t)C * sizeof(int32_t), tb = (tbytes + 255) & ~(size_t)255;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_b32, 3 * tb)) != GNX_OK) return rc;
-  char* o = (char*)ctx->ws_b32.p;
-  int32_t* d_obs = n_obs ? (int32_t*)o : nullptr;
-  int32_t* d_alt = n_alt ? (int32_t*)(o + tb) : nullptr;
-  int32_t* d_miss = n_miss ? (int32_t*)(o + 2 * tb) : nullptr;
-  HIPCHK(ctx, hipMemsetAsync(o, 0, 3 * tb, s));
+  int32_t *d_obs, *d_alt, *d_miss;
+  if ((rc = table_slab(ctx, tb, n_obs, n_alt, n_miss, &d_obs, &d_alt, &d_miss)) != GNX_OK) return rc;
+  HIPCHK(ctx, hipMemsetAsync(ctx->ws_b32.p, 0, 3 * tb, s));
   unsigned long long h_bad = 0;
   if (N > 0) {
     const int64_t ldp = (C + 255) / 256 * 64;  // 64-byte aligned packed rows

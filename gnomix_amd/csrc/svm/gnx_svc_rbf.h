@@ -1,6 +1,12 @@
-// gnx_svc_rbf.h — what the RBF SVC base (k_base_rbf.hip) shares with the SVC trainer (k_train_svc.hip)
+// gnx_svc_rbf.h — what the RBF SVC base (k_base_rbf.hip) shares with the SVC trainer (k_train_svc.hip) and the CovRSK base
+// (k_base_covrsk.hip)
 #pragma once
 #include "../gnx_internal.h"
+
+#if defined(__HIPCC__)
+// position of the class pair (i, j), i < j, in libsvm's order of the A (A - 1) / 2 pairwise problems
+__device__ __forceinline__ int pair_index(int i, int j, int A) { return i * (2 * A - i - 1) / 2 + (j - i - 1); }
+#endif
 
 // T[k] = exp(-gamma * k), k = 0 .. n-1, with the HOST C library's exp: libsvm's kernel value for the integer squared distance k,
 // as the same host's scikit-learn computes it

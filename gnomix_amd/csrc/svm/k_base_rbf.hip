@@ -25,17 +25,11 @@
 // covers 9 * width.  Any other int8 value is outside the contract: the distance is clamped to the table's end, never out of bounds.
 // The Gram pass of the trainer (k_rbf_stage / k_rbf_gram, used by k_train_svc.hip) is the same arithmetic on N x N rows.
 #include "gnx_svc_rbf.h"
+#include "../gnx_window.h"
 
 #include <cmath>
 #include <cstring>
 #include <map>
-
-#define HIPCHK(ctx, expr)                                                                          \
-  do {                                                                                             \
-    hipError_t e__ = (expr);                                                                       \
-    if (e__ != hipSuccess)                                                                         \
-      return gnx_fail((ctx), GNX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));        \
-  } while (0)
 
 struct RbfWinDev {
   int32_t width, kp, n_sv, tmax;  // SNPs; row pitch in bytes (width rounded up to 64); support vectors; last table index
@@ -72,14 +66,6 @@ struct RbfLaunch {
 namespace {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int64_t pad_src(int64_t p, int64_t C, int64_t ctx) {
-  if (p < ctx) return ctx - 1 - p;
-  if (p < ctx + C) return p - ctx;
-  return C - 1 - (p - ctx - C);
-}
-
-__device__ __forceinline__ int pair_index(int i, int j, int A) { return i * (2 * A - i - 1) / 2 + (j - i - 1); }
 
 __device__ __forceinline__ double sigmoid_predict(double dec, double pa, double pb) {
   const double f = dec * pa + pb;
@@ -119,7 +105,7 @@ __global__ __launch_bounds__(256) void k_rbf_dec(RbfLaunch L) {
       const int q = idx / kp, k = idx - q * kp;
       const int64_t n = (n0 + q < n_end) ? n0 + q : n_end - 1;
       int8_t v = 0;
-      if (k < width) v = L.X[n * L.ldx + pad_src(s + k, L.C, L.ctx)];
+      if (k < width) v = L.X[n * L.ldx + gnx_pad_src(s + k, L.C, L.ctx)];
       xq[q * xs + k] = v;
     }
     for (int i = t; i < P * QB; i += 256) dec[i] = 0.0;
@@ -220,7 +206,7 @@ __global__ __launch_bounds__(256) void k_rbf_stage(const int8_t* X, int64_t N, i
   if (n < N)
     for (int b = 0; b < 4; ++b) {
       const int k = k4 * 4 + b;
-      if (k < width) v |= (uint32_t)(uint8_t)X[n * ldx + pad_src((int64_t)w * M + k, C, ctx)] << (8 * b);
+      if (k < width) v |= (uint32_t)(uint8_t)X[n * ldx + gnx_pad_src((int64_t)w * M + k, C, ctx)] << (8 * b);
     }
   reinterpret_cast<uint32_t*>(xw)[idx] = v;
 }

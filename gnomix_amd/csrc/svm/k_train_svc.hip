@@ -46,17 +46,11 @@
 //   OF THE POSSIBILITY OF SUCH DAMAGE.
 #include "../gnx_internal.h"
 #include "gnx_svc_rbf.h"
+#include "../gnx_window.h"
 #include "gnx_np_pairwise.h"
 
 #include <cmath>
 #include <random>
-
-#define HIPCHK(ctx, expr)                                                                          \
-  do {                                                                                             \
-    hipError_t e__ = (expr);                                                                       \
-    if (e__ != hipSuccess)                                                                         \
-      return gnx_fail((ctx), GNX_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));        \
-  } while (0)
 
 namespace {
 
@@ -73,12 +67,6 @@ constexpr double SVC_TAU = 1e-12;             // libsvm TAU
 constexpr int64_t SVC_ITER_GUARD = 50000000;  // a hang guard, not libsvm's max_iter (sklearn passes -1): counted in the info
 constexpr int8_t ST_LOWER = 0, ST_UPPER = 1, ST_FREE = 2;
 
-__device__ __forceinline__ int64_t pad_src(int64_t p, int64_t C, int64_t ctx) {
-  if (p < ctx) return ctx - 1 - p;
-  if (p < ctx + C) return p - ctx;
-  return C - 1 - (p - ctx - C);
-}
-
 // one thread = one 32-SNP word of one (window, row): planes[((wl * N + n) * 2 + plane) * nwm + word]
 __global__ __launch_bounds__(256) void k_svc_pack(const int8_t* X, int64_t N, int64_t ldx, int64_t C, int64_t M, int64_t ctx,
                                                    int w_first, int wb, int W, int rem, int nwm, uint32_t* planes) {
@@ -94,7 +82,7 @@ __global__ __launch_bounds__(256) void k_svc_pack(const int8_t* X, int64_t N, in
   for (int b = 0; b < 32; ++b) {
     const int t = wd * 32 + b;
     if (t < width) {
-      const uint32_t v = (uint32_t)(uint8_t)x[pad_src((int64_t)w * M + t, C, ctx)];
+      const uint32_t v = (uint32_t)(uint8_t)x[gnx_pad_src((int64_t)w * M + t, C, ctx)];
       lo |= (v & 1u) << b;
       hi |= ((v >> 1) & 1u) << b;
     }
@@ -699,12 +687,6 @@ void fold_permutation(uint32_t seed, int l, int32_t* perm) {
   }
 }
 
-struct DevBlock {
-  void* p = nullptr;
-  ~DevBlock() {
-    if (p) (void)hipFree(p);
-  }
-};
 struct DevEvents {
   hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
   ~DevEvents() {
@@ -752,8 +734,8 @@ int train_svc_impl(gnx_ctx* ctx, const int8_t* dX, int64_t N, int64_t ldx, const
   const size_t bS8 = up256(max_solves * 8), bS4 = up256(max_solves * 4);
   const size_t bT4 = up256(max_rows * 4), bT8 = up256(max_rows * 8), bP8 = up256(max_pairs * 8), bP4 = up256(max_pairs * 4);
   const size_t total = bPl + bGram + bG + bSol + 4 * bE8 + 2 * bE4 + 3 * bE1 + bS8 + 2 * bS4 + 2 * bT4 + 2 * bT8 + 3 * bP8 + 2 * bP4 + bXw + bNrm + bD2 + bTab + bRv;
-  DevBlock blk;
-  hipError_t e = hipMalloc(&blk.p, total);
+  gnx_dev_tmp blk;
+  hipError_t e = blk.alloc(total);
   if (e != hipSuccess) {
     blk.p = nullptr;
     return gnx_fail(ctx, GNX_ENOMEM, std::string("train_svc: hipMalloc of ") + std::to_string(total >> 20) + " MiB: " + hipGetErrorString(e));
@@ -1081,8 +1063,8 @@ int train_svc_host_any(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t ldx, co
   if (rc != GNX_OK) return rc;
   if ((rc = train_svc_labels(ctx, y, N, (int)(C / M), A)) != GNX_OK) return rc;
   GNX_BIND_DEVICE(ctx);
-  DevBlock xb;
-  hipError_t e = hipMalloc(&xb.p, (size_t)N * C + 64);
+  gnx_dev_tmp xb;
+  hipError_t e = xb.alloc((size_t)N * C + 64);
   if (e != hipSuccess) {
     xb.p = nullptr;
     return gnx_fail(ctx, GNX_ENOMEM, std::string("train_svc: hipMalloc: ") + hipGetErrorString(e));
@@ -1154,8 +1136,8 @@ extern "C" int gnx_svc_gram(gnx_ctx* ctx, const int8_t* X, int64_t N, int64_t ld
   const std::vector<uint32_t> g = is_poly ? std::vector<uint32_t>(width_last + 1, 0) : run_table(kernel_kind, width_last);
   const size_t bX = up256((size_t)N * C + 64), bPl = up256((size_t)wb * N * 2 * nwm * 4), bGram = up256((size_t)wb * gram_w);
   const size_t bG = up256((size_t)(width_last + 1) * 4), bRv = is_poly ? up256((size_t)(width_last + 1) * 8) : 0;
-  DevBlock blk;
-  hipError_t e = hipMalloc(&blk.p, bX + bPl + bGram + bG + bRv);
+  gnx_dev_tmp blk;
+  hipError_t e = blk.alloc(bX + bPl + bGram + bG + bRv);
   if (e != hipSuccess) {
     blk.p = nullptr;
     return gnx_fail(ctx, GNX_ENOMEM, std::string("svc_gram: hipMalloc: ") + hipGetErrorString(e));

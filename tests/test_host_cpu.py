@@ -544,3 +544,37 @@ def test_committed_counter_files_are_stamped_with_the_kernel_sources():
         with open(os.path.join(here, "profiles", name)) as f:
             d = json.load(f)
         assert d.get("kernel_src_sha16") == sha, f"profiles/{name} was collected at other kernel sources ({d.get('kernel_src_sha16')} != {sha}): re-collect it"
+
+
+def test_shared_helpers_have_one_definition():
+    """The helpers every HIP source shares are defined once under gnomix_amd/csrc (DESIGN.md names the owning header of each): a
+    pasted copy drifts silently — det_exp is held bit-exact to two CPU restatements, the error strings of HIPCHK reach callers."""
+    csrc = os.path.join(ROOT, "gnomix_amd", "csrc")
+    text = {}
+    for d, _, files in os.walk(csrc):
+        for f in files:
+            if f.endswith((".hip", ".h", ".cpp")):
+                src = open(os.path.join(d, f)).read()
+                text[os.path.relpath(os.path.join(d, f), csrc)] = re.sub(r"//[^\n]*", "", src)   # prose may name them
+    assert len(text) > 40
+
+    def homes(pattern):
+        return sorted((name, m.group(0).strip()) for name, src in text.items() for m in re.finditer(pattern, src, flags=re.M))
+
+    qual = r"^(?:__host__ |__device__ |__forceinline__ |static |inline |constexpr )*"
+    once = {
+        "HIPCHK": (r"#define HIPCHK\(", "gnx_internal.h"),
+        "pad_src": (qual + r"\w+\s+\w*pad_src\([^()]*\)\s*\{", "gnx_window.h"),
+        "slide_src": (qual + r"\w+\s+\w*slide_src\([^()]*\)\s*\{", "gnx_window.h"),
+        "det_exp": (r"\bdouble det_exp\(", os.path.join("forest", "gnx_det_exp.h")),
+        "pair_index": (r"\bint pair_index\(", os.path.join("svm", "gnx_svc_rbf.h")),
+        "hipFree in a destructor": (r"~\w+\(\)\s*\{[^}]*hipFree\(", "gnx_internal.h"),
+    }
+    for what, (pattern, home) in once.items():
+        found = homes(pattern)
+        assert [name for name, _ in found] == [home], f"{what}: expected one definition, in {home}; found {found}"
+    for retired in ("GBT_HIP", "FBT_HIP", "RF_HIP", "TRCHK"):
+        found = homes(r"#\s*define\s+%s\b" % retired)
+        assert not found, f"{retired} is retired (GNX_HIPRET in gnx_internal.h): {found}"
+    # the shared names are called under the names they are defined with
+    assert homes(r"(?<![\w])(?:pad_src|slide_src|fbt_src)\(") == []
