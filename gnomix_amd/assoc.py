@@ -1,0 +1,234 @@
+"""Ancestry-specific association (the Tractor model) from the device's sufficient statistics (gnx_ancestry_assoc_stats,
+include/gnomix_hip.h states the model and the blocks).  The device reduces X and the labels to per-SNP and
+per-window blocks; this module assembles the normal equations of the kept columns, factors them (a batched Cholesky, numpy float64)
+and returns beta, se, t and p per (SNP, ancestry).  scipy is imported here only, and only for the p-values."""
+import collections
+
+import numpy as np
+
+from . import _lib
+
+STATS_CHUNK_BYTES = 64 << 20      # the statistics of one chunk of SNPs (the blocks that leave the device per call) stay below this
+FINISH_CHUNK_BYTES = 64 << 20     # ... and so do the assembled normal matrices of one batched factorisation
+PIVOT_MIN = 2.0 ** -40            # a pivot of the unit-diagonal normal matrix at or below this: not positive definite (status 1)
+
+AncestryAssoc = collections.namedtuple("AncestryAssoc", "beta se t p n_alt n_hap n df n_miss status")
+AncestryAssoc.__doc__ = """what ancestry_assoc returns.  beta, se, t, p: (C, A) float64, NaN for a dropped dosage term and for a SNP with status != 0;
+n_alt = sum d, n_hap = sum h: (C, A) int32; n, df, n_miss, status: (C,) int32 (status 0 fitted, 1 not positive definite, 2 df < 1)"""
+
+AssocStats = collections.namedtuple("AssocStats", "dtz dty dtd dth sum_d n_miss gram n sum_h window n_bad")
+AssocStats.__doc__ = """the raw blocks of SNPs [c0, c1): dtz (nc, A, K), dty (nc, A) float64; dtd (nc, A (A + 1) / 2), dth (nc, A, A - 1), sum_d (nc, A),
+n_miss (nc,) int32; per window of the range: gram (nw, K + A, K + A) float64 of [Z, h_0 .. h_{A-2}, y], n (nw,), sum_h (nw, A) int32;
+window (nc,): the row of the window blocks a SNP uses; n_bad: labels outside [0, A)"""
+
+
+def layout(A, K):
+    """sizes of the blocks: NF float64 and NI int32 per SNP, NWF float64 and NWI int32 per window"""
+    return A * (K + 1), A * (A + 1) // 2 + A * (A - 1) + A + 1, (K + A) ** 2, 1 + A
+
+
+def snps_per_chunk(A, K, max_bytes=STATS_CHUNK_BYTES):
+    NF, NI, _, _ = layout(A, K)
+    return max(1, max_bytes // (NF * 8 + NI * 4))
+
+
+def split_blocks(snp_f, snp_i, win_f, win_i, A, K, c0, c1, M, W, n_bad=0):
+    """the four arrays of the C ABI -> AssocStats (views)"""
+    nc = c1 - c0
+    nDD, nDH = A * (A + 1) // 2, A * (A - 1)
+    snp_f = snp_f.reshape(nc, A, K + 1)
+    snp_i = snp_i.reshape(nc, -1)
+    w = np.minimum(np.arange(c0, c1) // M, W - 1)
+    nw = int(w[-1] - w[0] + 1)
+    win_i = win_i.reshape(nw, 1 + A)
+    return AssocStats(snp_f[:, :, :K], snp_f[:, :, K], snp_i[:, :nDD], snp_i[:, nDD:nDD + nDH].reshape(nc, A, A - 1), snp_i[:, nDD + nDH:nDD + nDH + A],
+                      snp_i[:, nDD + nDH + A], win_f.reshape(nw, K + A, K + A), win_i[:, 0], win_i[:, 1:], w - w[0], int(n_bad))
+
+
+def _cholesky_batched(G):
+    """G (B, Q, Q) symmetric with unit diagonal -> L (lower, B, Q, Q), bad (B,): a pivot <= PIVOT_MIN (or not finite) was met"""
+    B, Q, _ = G.shape
+    L = np.zeros_like(G)
+    bad = np.zeros(B, bool)
+    for j in range(Q):
+        piv = G[:, j, j] - np.einsum("bk,bk->b", L[:, j, :j], L[:, j, :j])
+        bad |= ~(piv > PIVOT_MIN)
+        piv = np.where(piv > PIVOT_MIN, piv, 1.0)
+        d = np.sqrt(piv)
+        L[:, j, j] = d
+        if j + 1 < Q:
+            L[:, j + 1:, j] = (G[:, j + 1:, j] - np.einsum("bik,bk->bi", L[:, j + 1:, :j], L[:, j, :j])) / d[:, None]
+    return L, bad
+
+
+def _lower_inverse_batched(L):
+    B, Q, _ = L.shape
+    Li = np.zeros_like(L)
+    for j in range(Q):       # row j of L^-1: (e_j - L[j, :j] Li[:j]) / L[j, j]
+        Li[:, j, :] = -np.einsum("bk,bkq->bq", L[:, j, :j], Li[:, :j, :])
+        Li[:, j, j] += 1.0
+        Li[:, j, :] /= L[:, j, j][:, None]
+    return Li
+
+
+def _finish_chunk(st, sl, A, K, min_ac):
+    P, Q = K + A - 1, K + 2 * A - 1
+    w = st.window[sl]
+    nc = len(w)
+    gram = st.gram[w]                                  # (nc, P + 1, P + 1)
+    G = np.zeros((nc, Q, Q))
+    b = np.zeros((nc, Q))
+    G[:, :P, :P] = gram[:, :P, :P]
+    b[:, :P] = gram[:, :P, P]
+    yty = gram[:, P, P]
+    G[:, P:, :K] = st.dtz[sl]
+    G[:, P:, K:P] = st.dth[sl]
+    G[:, :P, P:] = np.transpose(G[:, P:, :P], (0, 2, 1))
+    iu = np.triu_indices(A)
+    DD = np.zeros((nc, A, A))
+    DD[:, iu[0], iu[1]] = st.dtd[sl]
+    DD[:, iu[1], iu[0]] = st.dtd[sl]
+    G[:, P:, P:] = DD
+    b[:, P:] = st.dty[sl]
+    keep = np.ones((nc, Q), bool)
+    keep[:, K:P] = st.sum_h[w][:, :A - 1] > 0
+    keep[:, P:] = st.sum_d[sl] >= min_ac
+    n = st.n[w].astype(np.int64)
+    df = n - keep.sum(1)
+    # a dropped column becomes a unit row / column with a zero right-hand side: one batch shape for every SNP
+    kk = keep[:, :, None] & keep[:, None, :]
+    G = np.where(kk, G, 0.0)
+    b = np.where(keep, b, 0.0)
+    diag = np.einsum("bqq->bq", G)
+    s = np.sqrt(np.where(keep & (diag > 0), diag, 1.0))
+    zero_col = keep & ~(diag > 0)                       # a kept column of zeros (a covariate): never positive definite
+    Gs = G / (s[:, :, None] * s[:, None, :])
+    Gs[:, np.arange(Q), np.arange(Q)] = np.where(keep & (diag > 0), 1.0, np.where(keep, 0.0, 1.0))
+    L, bad = _cholesky_batched(Gs)
+    bad |= zero_col.any(1)
+    Li = _lower_inverse_batched(L)
+    inv = np.einsum("bkq,bkr->bqr", Li, Li)
+    beta_s = np.einsum("bqr,br->bq", inv, b / s)
+    beta = beta_s / s
+    rss = np.maximum(yty - np.einsum("bq,bq->b", b, beta), 0.0)
+    status = np.where(df < 1, 2, np.where(bad, 1, 0)).astype(np.int32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        s2 = rss / df
+        se = np.sqrt(s2[:, None] * np.einsum("bqq->bq", inv)) / s
+        tt = beta / se
+    dead = (status != 0)[:, None] | ~keep
+    beta, se, tt = (np.where(dead, np.nan, v)[:, P:] for v in (beta, se, tt))
+    return beta, se, tt, n.astype(np.int32), df.astype(np.int32), status
+
+
+def finish(st, A, K, min_ac=1, max_bytes=FINISH_CHUNK_BYTES):
+    """AssocStats of a range of SNPs -> (beta, se, t, n_alt, n_hap, n, df, n_miss, status) of that range"""
+    if min_ac < 1:
+        raise ValueError("min_ac must be >= 1")
+    nc = len(st.window)
+    Q = K + 2 * A - 1
+    step = max(1, max_bytes // (Q * Q * 8 * 6))
+    parts = [_finish_chunk(st, slice(i, min(i + step, nc)), A, K, min_ac) for i in range(0, nc, step)]
+    beta, se, tt, n, df, status = (np.concatenate([p[i] for p in parts]) for i in range(6))
+    return beta, se, tt, np.asarray(st.sum_d, np.int32).copy(), np.asarray(st.sum_h[st.window], np.int32), n, df, np.asarray(st.n_miss, np.int32).copy(), status
+
+
+def p_values(t, df):
+    """two-sided p of t with df degrees of freedom ((C, A) and (C,)); NaN where t is"""
+    from scipy import stats
+    with np.errstate(invalid="ignore"):
+        return 2.0 * stats.t.sf(np.abs(t), np.maximum(df, 1)[:, None].astype(np.float64))
+
+
+def assoc_from_stats(stats_fn, C, A, K, min_ac=1):
+    """stats_fn(c0, c1) -> AssocStats; walks the SNPs in chunks of snps_per_chunk(A, K) and finishes each -> AncestryAssoc.  A
+    GNX_EINVAL for labels out of range is stats_fn's to raise."""
+    step = snps_per_chunk(A, K)
+    parts = [finish(stats_fn(c0, min(c0 + step, C)), A, K, min_ac) for c0 in range(0, C, step)]
+    beta, se, tt, n_alt, n_hap, n, df, n_miss, status = (np.concatenate([p[i] for p in parts]) for i in range(9))
+    return AncestryAssoc(beta, se, tt, p_values(tt, df), n_alt, n_hap, n, df, n_miss, status)
+
+
+def covariates(n_ind, y, Z=None, use=None):
+    """y (n_ind,), Z (n_ind, K) or None (the intercept only), use (n_ind,) or None -> contiguous float64 / float64 / uint8 arrays"""
+    y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+    if y.shape[0] != n_ind:
+        raise ValueError(f"y must have one value per individual ({n_ind}), got {y.shape[0]}")
+    Z = np.ones((n_ind, 1)) if Z is None else np.ascontiguousarray(Z, dtype=np.float64)
+    if Z.ndim != 2 or Z.shape[0] != n_ind or Z.shape[1] < 1:
+        raise ValueError(f"Z must be (n_ind={n_ind}, K >= 1), got {Z.shape}")
+    use = np.ones(n_ind, np.uint8) if use is None else np.ascontiguousarray(np.asarray(use) != 0, dtype=np.uint8)
+    if use.shape != (n_ind,):
+        raise ValueError(f"use must have one byte per individual ({n_ind}), got {use.shape}")
+    return y, Z, use
+
+
+def read_phenotypes(path, samples):
+    """the phenotype file: a TSV with a header `sample  pheno  [covariate ...]`, matched to `samples` by name -> (y, Z, use, names).
+    Z gets an intercept column in front of the file's covariates.  A query sample the file lacks, or whose phenotype is empty / NA, has
+    use = 0 (y = NaN); a covariate that is empty, NA or not finite stays non-finite in Z, which the model's participation rule drops.
+    File samples the query lacks are ignored.  A sample listed twice is an error."""
+    with open(path) as f:
+        lines = [ln.rstrip("\n").rstrip("\r") for ln in f if ln.strip()]
+    if not lines:
+        raise ValueError(f"{path}: empty phenotype file")
+    head = lines[0].split("\t")
+    if len(head) < 2 or head[0] != "sample" or head[1] != "pheno":
+        raise ValueError(f"{path}: the header must start with 'sample<TAB>pheno', got {head[:2]}")
+    cov_names = head[2:]
+
+    def num(cell):
+        cell = cell.strip()
+        if cell == "" or cell.upper() in ("NA", "NAN", "."):
+            return np.nan
+        try:
+            return float(cell)
+        except ValueError:
+            raise ValueError(f"{path}: '{cell}' is not a number") from None
+
+    rows = {}
+    for ln in lines[1:]:
+        cells = ln.split("\t")
+        if len(cells) != len(head):
+            raise ValueError(f"{path}: a line has {len(cells)} cells, the header {len(head)}")
+        if cells[0] in rows:
+            raise ValueError(f"{path}: sample '{cells[0]}' is listed twice")
+        rows[cells[0]] = [num(c) for c in cells[1:]]
+    n = len(samples)
+    y = np.full(n, np.nan)
+    Z = np.ones((n, 1 + len(cov_names)))
+    use = np.zeros(n, np.uint8)
+    for i, name in enumerate(samples):
+        r = rows.get(str(name))
+        if r is None:
+            Z[i, 1:] = np.nan
+            continue
+        y[i] = r[0]
+        Z[i, 1:] = r[1:]
+        use[i] = 1 if np.isfinite(r[0]) else 0
+    return y, Z, use, ["intercept"] + cov_names
+
+
+def stats_host(ctx, X, labels, M, A, y, Z, use, c0, c1, min_ac=1, check=True):
+    """gnx_ancestry_assoc_stats on host arrays: X (N, C) int8, labels (N, W) int32 -> AssocStats of [c0, c1)"""
+    import ctypes
+    X = np.asarray(X)
+    if X.dtype != np.int8 or X.ndim != 2 or X.strides[1] != 1:
+        X = np.ascontiguousarray(X, dtype=np.int8)
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    N, C = X.shape
+    W = lab.shape[1]
+    y, Z, use = covariates(N // 2, y, Z, use)
+    K = Z.shape[1]
+    NF, NI, NWF, NWI = layout(A, K)
+    nc = c1 - c0
+    nw = int(min((c1 - 1) // M, W - 1) - min(c0 // M, W - 1) + 1) if 0 <= c0 < c1 and M >= 1 else 1
+    sf, si = np.zeros((max(nc, 0), NF)), np.zeros((max(nc, 0), NI), np.int32)
+    wf, wi = np.zeros((nw, NWF)), np.zeros((nw, NWI), np.int32)
+    n_bad = ctypes.c_int64(0)
+    rc = ctx.lib.gnx_ancestry_assoc_stats(ctx.h, X.ctypes.data, X.strides[0] if N > 1 else C, lab.ctypes.data, W, N, C, int(M), W, int(A), y.ctypes.data,
+                                          Z.ctypes.data, K, use.ctypes.data, int(min_ac), c0, c1, sf.ctypes.data, si.ctypes.data, wf.ctypes.data,
+                                          wi.ctypes.data, ctypes.byref(n_bad))
+    if check or (rc != _lib.GNX_OK and not n_bad.value):
+        ctx.check(rc)
+    return split_blocks(sf, si, wf, wi, A, K, c0, c1, M, W, n_bad.value)

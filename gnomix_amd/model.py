@@ -553,6 +553,89 @@ class DeviceModel:
                                                         self.A, int(ancestry), dos.data_ptr(), self.C, hap.data_ptr(), self.C))
         return dos, hap
 
+    def ancestry_assoc_stats(self, X, labels, y, Z=None, use=None, c0=0, c1=None, min_ac=1, check=True):
+        """the sufficient statistics of the ancestry-specific association model for the SNPs [c0, c1) (gnx_ancestry_assoc_stats[_dev];
+        include/gnomix_hip.h states the blocks) -> gnomix_amd.assoc.AssocStats of numpy arrays.  X (N, C) int8 and labels (N, W) int32 as
+        numpy arrays, or as CUDA tensors (X int8 or the uint8 tensor pack_device returns, labels with any row stride): those never leave
+        HBM.  check=False: labels out of range do not raise, their count is AssocStats.n_bad."""
+        from . import assoc
+        c1 = self.C if c1 is None else int(c1)
+        c0 = int(c0)
+        if not hasattr(X, "is_cuda"):
+            X = self._x(X)
+            lab = np.ascontiguousarray(labels, dtype=np.int32)
+            if lab.shape != (X.shape[0], self.W):
+                raise ValueError(f"labels must be (N={X.shape[0]}, W={self.W}), got {lab.shape}")
+            return assoc.stats_host(self.ctx, X, lab, self.M, self.A, y, Z, use, c0, c1, min_ac=min_ac, check=check)
+        import ctypes
+        import torch
+        kind, ld, ldl, N = self._allele_device_args(X, labels)
+        yh, Zh, uh = assoc.covariates(N // 2, y, Z, use)
+        K = Zh.shape[1]
+        NF, NI, NWF, NWI = assoc.layout(self.A, K)
+        nc = max(c1 - c0, 0)
+        nw = int(min((c1 - 1) // self.M, self.W - 1) - min(c0 // self.M, self.W - 1) + 1) if 0 <= c0 < c1 else 1
+        dev = X.device
+        y_t, Z_t, u_t = (torch.from_numpy(v).to(dev) for v in (yh, Zh, uh))
+        sf, wf = torch.empty((nc, NF), dtype=torch.float64, device=dev), torch.empty((nw, NWF), dtype=torch.float64, device=dev)
+        si, wi = torch.empty((nc, NI), dtype=torch.int32, device=dev), torch.empty((nw, NWI), dtype=torch.int32, device=dev)
+        n_bad = ctypes.c_int64(0)
+        self._bind_torch_stream()
+        rc = self.lib.gnx_ancestry_assoc_stats_dev(self.ctx.h, X.data_ptr(), kind, ld, labels.data_ptr(), ldl, N, self.C, self.M, self.W, self.A,
+                                                   y_t.data_ptr(), Z_t.data_ptr(), K, u_t.data_ptr(), int(min_ac), c0, c1, sf.data_ptr(), si.data_ptr(),
+                                                   wf.data_ptr(), wi.data_ptr(), ctypes.byref(n_bad))
+        if check or (rc != _lib.GNX_OK and not n_bad.value):
+            self.ctx.check(rc)
+        return assoc.split_blocks(sf.cpu().numpy(), si.cpu().numpy(), wf.cpu().numpy(), wi.cpu().numpy(), self.A, K, c0, c1, self.M, self.W, n_bad.value)
+
+    def ancestry_assoc(self, X, labels, y, Z=None, use=None, min_ac=1):
+        """ancestry-specific association (the Tractor model: y = Z g + sum_{a < A-1} alpha_a hapcount_a + sum_a beta_a dosage_a, OLS per
+        SNP over the individuals that take part) -> gnomix_amd.assoc.AncestryAssoc.  y (N / 2,), Z (N / 2, K) float64 with the intercept
+        column (None = the intercept only), use (N / 2,) (0 = takes no part).  The device reduces X and the labels to per-SNP blocks, chunk
+        of SNPs by chunk (gnx_ancestry_assoc_stats); the host factors them (gnomix_amd/assoc.py).  X and labels: numpy arrays or CUDA
+        tensors, as ancestry_assoc_stats takes them."""
+        from . import assoc
+        if min_ac < 1:
+            raise ValueError("min_ac must be >= 1")
+        n_ind = X.shape[0] // 2
+        y, Z, use = assoc.covariates(n_ind, y, Z, use)
+        return assoc.assoc_from_stats(lambda c0, c1: self.ancestry_assoc_stats(X, labels, y, Z, use, c0, c1, min_ac), self.C, self.A, Z.shape[1], min_ac)
+
+    def ancestry_assoc_stats_gt2(self, G, N, src, labels, y, Z=None, use=None, c0=0, c1=None, min_ac=1, check=True):
+        """ancestry_assoc_stats of the parsed query (G, N, src as infer_gt2 takes them) under host labels (N, W): the packed rows are
+        built and reduced in HBM, batch of individuals by batch (gnx_ancestry_assoc_stats_gt2) -> assoc.AssocStats of [c0, c1)"""
+        import ctypes
+        from . import assoc
+        G, N, src = self._gt2_args(G, N, src)
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.shape != (N, self.W):
+            raise ValueError(f"labels must be (N={N}, W={self.W}), got {lab.shape}")
+        c1 = self.C if c1 is None else int(c1)
+        c0 = int(c0)
+        y, Z, use = assoc.covariates(N // 2, y, Z, use)
+        K = Z.shape[1]
+        NF, NI, NWF, NWI = assoc.layout(self.A, K)
+        nc = max(c1 - c0, 0)
+        nw = int(min((c1 - 1) // self.M, self.W - 1) - min(c0 // self.M, self.W - 1) + 1) if 0 <= c0 < c1 else 1
+        sf, si = np.zeros((nc, NF)), np.zeros((nc, NI), np.int32)
+        wf, wi = np.zeros((nw, NWF)), np.zeros((nw, NWI), np.int32)
+        n_bad = ctypes.c_int64(0)
+        rc = self.lib.gnx_ancestry_assoc_stats_gt2(self.h, G.ctypes.data, G.shape[0], G.shape[1], N, src.ctypes.data, lab.ctypes.data, y.ctypes.data,
+                                                   Z.ctypes.data, K, use.ctypes.data, int(min_ac), c0, c1, sf.ctypes.data, si.ctypes.data,
+                                                   wf.ctypes.data, wi.ctypes.data, ctypes.byref(n_bad))
+        if check or (rc != _lib.GNX_OK and not n_bad.value):
+            self.ctx.check(rc)
+        return assoc.split_blocks(sf, si, wf, wi, self.A, K, c0, c1, self.M, self.W, n_bad.value)
+
+    def ancestry_assoc_gt2(self, G, N, src, labels, y, Z=None, use=None, min_ac=1):
+        """ancestry_assoc of the parsed query under host labels (the command line's path) -> assoc.AncestryAssoc"""
+        from . import assoc
+        if min_ac < 1:
+            raise ValueError("min_ac must be >= 1")
+        y, Z, use = assoc.covariates(int(N) // 2, y, Z, use)
+        return assoc.assoc_from_stats(lambda c0, c1: self.ancestry_assoc_stats_gt2(G, N, src, labels, y, Z, use, c0, c1, min_ac), self.C, self.A,
+                                      Z.shape[1], min_ac)
+
     def allele_counts_gt2(self, G, N, src, labels):
         """ancestry-specific allele counts of the parsed query (G, N, src as infer_gt2 takes them) under host labels (N, W): the
         packed rows are built and counted in HBM, batch by batch (gnx_ancestry_allele_counts_gt2) -> AlleleCounts"""

@@ -887,6 +887,58 @@ int gnx_ancestry_dosage(gnx_ctx* ctx, const void* rows, int row_kind, int64_t ld
 int gnx_ancestry_allele_counts_gt2(gnx_model* m, const uint8_t* G, int64_t n_variants, int64_t ldg, int64_t N, const int32_t* src,
                                    const int32_t* labels, int32_t* n_obs, int32_t* n_alt, int32_t* n_miss);
 
+/* ---- ancestry-specific association: the sufficient statistics of the Tractor model (csrc/summary/k_ancestry_assoc.hip) -------------
+ * THE MODEL.  rows, labels, M, W, A, win(c) as above; gnx_ancestry_assoc_stats takes int8 rows X only, the _dev form either row_kind.
+ *   Per individual i (haplotype rows 2 i, 2 i + 1): a phenotype y[i] (float64), covariates Z[i, :K] (float64, row-major, contiguous; the
+ *   CALLER supplies the intercept column; 1 <= K <= GNX_ASSOC_MAX_K) and a byte use[i] (0 = takes no part; use == NULL = all ones).
+ *   Per SNP c and ancestry a, h[i, a] and d[i, a] are EXACTLY gnx_ancestry_dosage's hapcount and dosage of that ancestry: a missing
+ *   call carries its label in h and adds nothing to d.
+ *   Individual i takes part at window k when use[i] != 0, y[i] and Z[i, :] are finite and both its labels at k lie in [0, A).
+ *   At SNP c, over the n individuals that take part at win(c):   y = Z g + sum_{a < A-1} alpha_a h_a + sum_a beta_a d_a + e   (OLS).
+ *   Column rule (integers only, hence exact): a hapcount column with sum_i h[i, a] == 0 is dropped; a dosage column with
+ *   sum_i d[i, a] < min_ac is dropped (min_ac >= 1) and its term reports NaN.  If the normal matrix of the kept columns is not positive
+ *   definite in the host's Cholesky (gnomix_amd/assoc.py: a pivot of the unit-diagonal matrix <= 2^-40) the SNP has status 1 and NaN
+ *   results; with df = n - p_kept < 1 it has status 2 and NaN results; else status 0.  Per (c, a): beta, se = sqrt(s2 (X^T X)^-1_jj)
+ *   with s2 = RSS / df, t = beta / se, n_alt = sum d, n_hap = sum h (int32).  Per c: n, df, n_miss, status.
+ * THE STATISTICS these entries write, for the SNPs [c0, c1) and the windows w0 = win(c0) .. w1 = win(c1 - 1), all OVERWRITTEN, one
+ *   owner per value, plain stores; the finish is the host's (gnomix_amd/assoc.py).  With K1 = K + 1 and P1 = K + A:
+ *     snp_f64 (c1 - c0, A, K1)   [a, k < K] = sum_i d[i, a] Z[i, k]  (D^T Z),   [a, K] = sum_i d[i, a] y[i]  (D^T y)
+ *     snp_i32 (c1 - c0, NI), NI = A (A + 1) / 2 + A (A - 1) + A + 1:   D^T D (upper triangle, row-major: (0,0) .. (0,A-1), (1,1) ..),
+ *                                then D^T H ([a][b < A - 1] = sum_i d[i, a] h[i, b]), then sum_i d[i, a] [A], then n_miss: the missing
+ *                                calls at c on the haplotypes of the individuals that take part
+ *     win_f64 (w1 - w0 + 1, P1, P1)   the Gram matrix of U = [Z, h_0 .. h_{A-2}, y]: R^T R, R^T y and y^T y for R = [Z, h_0 .. h_{A-2}]
+ *     win_i32 (w1 - w0 + 1, 1 + A)    n, then sum_i h[i, a] for EVERY a < A
+ *   The integers are exact.  Every float64 sum runs over the individuals in ascending i, one product per individual rounded once, no
+ *   fused multiply-add: the values are a function of the inputs alone, not of the grid, of [c0, c1) or of the row form.
+ * GNX_EINVAL before the launch, nothing written: odd N, N < 0, K < 1, min_ac < 1 (min_ac is only validated here: the column rule is
+ *   the finish's), M < 1, W < 1, M W > C, not 0 <= c0 < c1 <= C, a stride too small, an unknown row_kind, a null pointer (use and
+ *   n_bad may be NULL).  GNX_EUNSUPPORTED: A > GNX_ALLELE_MAX_A, K > GNX_ASSOC_MAX_K, N > 2^28 (the integer blocks are int32).
+ * GNX_EINVAL after the launch: labels outside [0, A) were met among ALL rows at the windows w0 .. w1; *n_bad is their count (0
+ *   otherwise).  Labels are only compared: such an individual takes no part at that window and every value is as stated.
+ * Both forms synchronise the context stream once.  In the _dev form every pointer but n_bad is a device pointer.
+ * gnx_ancestry_assoc_stats_gt2: the file path's form.  G, n_variants, ldg, src as gnx_infer_gt2 takes them; the packed rows are built in
+ *   HBM batch by batch as there and reduced against the HOST labels (N, W) (contiguous rows), y, Z, use with the model's C, M, W and A;
+ *   a batch holds whole individuals in ascending order and goes on from the blocks of the batches before it, so every running sum is
+ *   the one a single launch makes: the blocks equal gnx_ancestry_assoc_stats' of the vcf_to_npy matrix bit for bit, whatever the batch
+ *   size.  A model SNP the query lacks is missing in every row.  Also GNX_EINVAL before the launch: a column map entry outside G.
+ * NOTE on status 1.  The hapcount columns h_0 .. h_{A-2} of the individuals that take part sum to 2 - h_{A-1}.  In a window where NO
+ *   participant carries ancestry A - 1 they sum to twice the intercept column, the kept design is rank-deficient and EVERY SNP of that
+ *   window has status 1 (the column rule only drops hapcount columns that are zero, and A - 1 has none to drop).  With many ancestries
+ *   and few individuals this is common; order the populations so that the last one is present everywhere, or expect those windows. */
+#define GNX_ASSOC_MAX_K 16
+int gnx_ancestry_assoc_stats_dev(gnx_ctx* ctx, const void* d_rows, int row_kind, int64_t ld_rows, const int32_t* d_labels, int64_t ld_labels,
+                                 int64_t N, int64_t C, int64_t M, int64_t W, int32_t A, const double* d_y, const double* d_Z, int32_t K,
+                                 const uint8_t* d_use, int32_t min_ac, int64_t c0, int64_t c1, double* d_snp_f64, int32_t* d_snp_i32,
+                                 double* d_win_f64, int32_t* d_win_i32, int64_t* n_bad);
+int gnx_ancestry_assoc_stats(gnx_ctx* ctx, const int8_t* X, int64_t ld_rows, const int32_t* labels, int64_t ld_labels, int64_t N, int64_t C,
+                             int64_t M, int64_t W, int32_t A, const double* y, const double* Z, int32_t K, const uint8_t* use,
+                             int32_t min_ac, int64_t c0, int64_t c1, double* snp_f64, int32_t* snp_i32, double* win_f64, int32_t* win_i32,
+                             int64_t* n_bad);
+int gnx_ancestry_assoc_stats_gt2(gnx_model* m, const uint8_t* G, int64_t n_variants, int64_t ldg, int64_t N, const int32_t* src,
+                                 const int32_t* labels, const double* y, const double* Z, int32_t K, const uint8_t* use, int32_t min_ac,
+                                 int64_t c0, int64_t c1, double* snp_f64, int32_t* snp_i32, double* win_f64, int32_t* win_i32,
+                                 int64_t* n_bad);
+
 /* per-kernel device time, measured with hipEvents on the context stream around every launch */
 int gnx_profile_enable(gnx_ctx* ctx, int on);
 int gnx_profile_reset(gnx_ctx* ctx);

@@ -40,6 +40,7 @@ MUST_BE_CLEAN = [
     r"k_mode_filter", r"k_label_runs_",
     r"k_ancestry_summary<",
     r"k_ancestry_allele_counts<", r"k_ancestry_dosage<",
+    r"k_ancestry_assoc_",
 ]
 
 
