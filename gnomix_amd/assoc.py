@@ -16,6 +16,20 @@ AncestryAssoc = collections.namedtuple("AncestryAssoc", "beta se t p n_alt n_hap
 AncestryAssoc.__doc__ = """what ancestry_assoc returns.  beta, se, t, p: (C, A) float64, NaN for a dropped dosage term and for a SNP with status != 0;
 n_alt = sum d, n_hap = sum h: (C, A) int32; n, df, n_miss, status: (C,) int32 (status 0 fitted, 1 not positive definite, 2 df < 1)"""
 
+AncestryAssocLogit = collections.namedtuple("AncestryAssocLogit", "beta se z p lrt lrt_df lrt_p n_alt n_alt_case n_hap n n_case df n_miss iters status")
+AncestryAssocLogit.__doc__ = """what ancestry_assoc_logit returns (the logistic Tractor model of gnx_ancestry_assoc_logit, fitted on the device).  beta, se,
+z = beta / se, p (two-sided normal): (C, A) float64, NaN for a dropped dosage term and for a SNP with status != 0; lrt = dev0[window] - dev
+(the null model is fitted on the same participants: the joint test of the SNP's kept dosage terms), lrt_df = the number of kept dosage
+terms, lrt_p = chi2.sf(lrt, lrt_df): (C,); n_alt, n_alt_case, n_hap: (C, A) int32; n, n_case, df, n_miss, iters, status: (C,) int32 (status
+0 fitted, 1 not positive definite, 2 df < 1, 3 no finite optimum, 4 the window's null model failed)"""
+
+LogitFit = collections.namedtuple("LogitFit", "beta se dev theta n_alt n_alt_case n_miss iters status theta0 dev0 n n_case sum_h iters0 status0 window n_bad")
+LogitFit.__doc__ = """the raw outputs of gnx_ancestry_assoc_logit for SNPs [c0, c1): beta, se (nc, A), dev (nc,), theta (nc, Q) or None; n_alt,
+n_alt_case (nc, A), n_miss, iters, status (nc,) int32; per window of the range theta0 (nw, P), dev0 (nw,), n, n_case (nw,), sum_h (nw, A), iters0,
+status0 (nw,); window (nc,): the row of the window arrays a SNP uses; n_bad: labels outside [0, A)"""
+
+LOGIT_TOL, LOGIT_MAX_ITER, LOGIT_MAX_Q = 1e-10, 25, 47     # GNX_ASSOC_LOGIT_TOL / _MAX_ITER / _MAX_Q of include/gnomix_hip.h
+
 AssocStats = collections.namedtuple("AssocStats", "dtz dty dtd dth sum_d n_miss gram n sum_h window n_bad")
 AssocStats.__doc__ = """the raw blocks of SNPs [c0, c1): dtz (nc, A, K), dty (nc, A) float64; dtd (nc, A (A + 1) / 2), dth (nc, A, A - 1), sum_d (nc, A),
 n_miss (nc,) int32; per window of the range: gram (nw, K + A, K + A) float64 of [Z, h_0 .. h_{A-2}, y], n (nw,), sum_h (nw, A) int32;
@@ -147,6 +161,103 @@ def assoc_from_stats(stats_fn, C, A, K, min_ac=1):
     parts = [finish(stats_fn(c0, min(c0 + step, C)), A, K, min_ac) for c0 in range(0, C, step)]
     beta, se, tt, n_alt, n_hap, n, df, n_miss, status = (np.concatenate([p[i] for p in parts]) for i in range(9))
     return AncestryAssoc(beta, se, tt, p_values(tt, df), n_alt, n_hap, n, df, n_miss, status)
+
+
+def logit_layout(A, K):
+    """columns of snp_f64, snp_i32, theta, win_f64, win_i32 of gnx_ancestry_assoc_logit"""
+    return 2 * A + 1, 2 * A + 3, K + 2 * A - 1, K + A, A + 4
+
+
+def logit_snps_per_chunk(A, K, max_bytes=STATS_CHUNK_BYTES):
+    SF, SI, Q, _, _ = logit_layout(A, K)
+    return max(1, max_bytes // ((SF + Q) * 8 + SI * 4))
+
+
+def logit_buffers(A, K, c0, c1, M, W, want_theta=True, empty=None):
+    """zeroed (or empty(shape, dtype)) arrays of one call, in the order of the C ABI: snp_f64, snp_i32, theta or None, win_f64, win_i32"""
+    SF, SI, Q, WF, WI = logit_layout(A, K)
+    nc = max(c1 - c0, 0)
+    nw = int(min((c1 - 1) // M, W - 1) - min(c0 // M, W - 1) + 1) if 0 <= c0 < c1 and M >= 1 else 1
+    new = empty or (lambda shape, dtype: np.zeros(shape, dtype))
+    return new((nc, SF), np.float64), new((nc, SI), np.int32), new((nc, Q), np.float64) if want_theta else None, new((nw, WF), np.float64), new((nw, WI), np.int32)
+
+
+def split_logit(sf, si, th, wf, wi, A, K, c0, c1, M, W, n_bad=0):
+    """the arrays of the C ABI -> LogitFit (views)"""
+    w = np.minimum(np.arange(c0, c1) // M, W - 1)
+    P = K + A - 1
+    return LogitFit(sf[:, :A], sf[:, A:2 * A], sf[:, 2 * A], th, si[:, :A], si[:, A:2 * A], si[:, 2 * A], si[:, 2 * A + 1], si[:, 2 * A + 2],
+                    wf[:, :P], wf[:, P], wi[:, 0], wi[:, 1], wi[:, 2:2 + A], wi[:, 2 + A], wi[:, 3 + A], w - w[0], int(n_bad))
+
+
+def logit_p_values(beta, se, lrt, lrt_df):
+    """-> z, p (two-sided normal), lrt_p (chi-square with lrt_df degrees of freedom; NaN where lrt is or lrt_df is 0)"""
+    from scipy import stats
+    with np.errstate(divide="ignore", invalid="ignore"):
+        z = beta / se
+        p = 2.0 * stats.norm.sf(np.abs(z))
+        lrt_p = np.where(lrt_df > 0, stats.chi2.sf(lrt, np.maximum(lrt_df, 1)), np.nan)
+    return z, p, lrt_p
+
+
+def finish_logit(fit, K):
+    """one LogitFit -> the columns of AncestryAssocLogit but z, p and lrt_p (added once over all chunks)"""
+    w = fit.window
+    A = fit.beta.shape[1]
+    kept_d = ~np.isnan(fit.beta) if len(fit.beta) else np.zeros((0, A), bool)
+    ok = fit.status == 0
+    lrt = np.where(ok, fit.dev0[w] - fit.dev, np.nan)
+    lrt_df = np.where(ok, kept_d.sum(1), 0).astype(np.int32)
+    n = fit.n[w].astype(np.int32)
+    # p_kept of the column rule: the covariates, the hapcount columns with a positive sum, the kept dosage columns (known where the SNP
+    # was fitted; elsewhere df counts the null model's columns)
+    p_kept = K + (fit.sum_h[w][:, :A - 1] > 0).sum(1) + lrt_df
+    return (np.array(fit.beta), np.array(fit.se), lrt, lrt_df, np.array(fit.n_alt, np.int32), np.array(fit.n_alt_case, np.int32),
+            np.array(fit.sum_h[w], np.int32), n, fit.n_case[w].astype(np.int32), (n - p_kept).astype(np.int32), np.array(fit.n_miss, np.int32),
+            np.array(fit.iters, np.int32), np.array(fit.status, np.int32))
+
+
+def logit_from_fits(fit_fn, C, A, K):
+    """fit_fn(c0, c1) -> LogitFit; walks the SNPs in chunks of logit_snps_per_chunk(A, K) -> AncestryAssocLogit.  A GNX_EINVAL (labels out of
+    range, a phenotype that is not 0 / 1) is fit_fn's to raise."""
+    step = logit_snps_per_chunk(A, K)
+    parts = [finish_logit(fit_fn(c0, min(c0 + step, C)), K) for c0 in range(0, C, step)]
+    beta, se, lrt, lrt_df, n_alt, n_alt_case, n_hap, n, n_case, df, n_miss, iters, status = (np.concatenate([p[i] for p in parts]) for i in range(13))
+    z, p, lrt_p = logit_p_values(beta, se, lrt, lrt_df)
+    return AncestryAssocLogit(beta, se, z, p, lrt, lrt_df, lrt_p, n_alt, n_alt_case, n_hap, n, n_case, df, n_miss, iters, status)
+
+
+def check_binary(y, use, names=None):
+    """ValueError when a used individual's finite phenotype is neither 0 nor 1 (names: the sample names for the message)"""
+    y = np.asarray(y, np.float64)
+    bad = np.isfinite(y) & (y != 0.0) & (y != 1.0)
+    if use is not None:
+        bad &= np.asarray(use) != 0
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        who = f"sample '{names[i]}'" if names is not None else f"individual {i}"
+        raise ValueError(f"a logistic association needs phenotypes coded 0 / 1: {who} has {y[i]:g} ({int(bad.sum())} such in all)")
+
+
+def logit_host(ctx, X, labels, M, A, y, Z, use, c0, c1, min_ac=1, tol=LOGIT_TOL, max_iter=LOGIT_MAX_ITER, check=True, want_theta=True):
+    """gnx_ancestry_assoc_logit on host arrays: X (N, C) int8, labels (N, W) int32 -> LogitFit of [c0, c1)"""
+    import ctypes
+    X = np.asarray(X)
+    if X.dtype != np.int8 or X.ndim != 2 or X.strides[1] != 1:
+        X = np.ascontiguousarray(X, dtype=np.int8)
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    N, C = X.shape
+    W = lab.shape[1]
+    y, Z, use = covariates(N // 2, y, Z, use)
+    K = Z.shape[1]
+    sf, si, th, wf, wi = logit_buffers(A, K, c0, c1, M, W, want_theta)
+    n_bad = ctypes.c_int64(0)
+    rc = ctx.lib.gnx_ancestry_assoc_logit(ctx.h, X.ctypes.data, X.strides[0] if N > 1 else C, lab.ctypes.data, W, N, C, int(M), W, int(A), y.ctypes.data,
+                                          Z.ctypes.data, K, use.ctypes.data, int(min_ac), c0, c1, float(tol), int(max_iter), sf.ctypes.data,
+                                          si.ctypes.data, th.ctypes.data if want_theta else None, wf.ctypes.data, wi.ctypes.data, ctypes.byref(n_bad))
+    if check or rc not in (_lib.GNX_OK, _lib.GNX_EINVAL) or (rc != _lib.GNX_OK and not n_bad.value):
+        ctx.check(rc)
+    return split_logit(sf, si, th, wf, wi, A, K, c0, c1, M, W, n_bad.value)
 
 
 def covariates(n_ind, y, Z=None, use=None):

@@ -133,7 +133,8 @@ class _Prefetch:
 
 
 def run_inference(base_args, model, snp_level=False, bed_file_output=False, verbose=False, timings=None, query=None, devices=None,
-                  global_ancestry_output=False, ancestry_allele_freq_output=False, ancestry_assoc_output=False, phenotype_file=None):
+                  global_ancestry_output=False, ancestry_allele_freq_output=False, ancestry_assoc_output=False, phenotype_file=None,
+                  ancestry_assoc_model="linear"):
     """gnomix.py:37-100 with the HIP model behind the same steps.  The query never becomes an (N, C) host matrix: the library
     parses the text into 2-bit rows (gnx_vcf_read), `column_map` keeps vcf_to_npy's bookkeeping (SNP intersection, REF flips,
     absent SNPs) as one int32 per model SNP, the GPU builds X and runs base + smoother (or Gnofix) on it, and the library
@@ -152,13 +153,18 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
     a TSV with the header `sample  pheno  [covariates]`, matched by sample name; query samples it lacks take no part; an intercept is
     added): query_results.assoc.tsv as well, the ancestry-specific association (Tractor model) of every model
     SNP, its statistics reduced on the model's own GPU from the query's 2-bit rows and the labels the .msp gets
-    (gnx_ancestry_assoc_stats_gt2).  Not with phase=True (ValueError before any work), for the same reason."""
+    (gnx_ancestry_assoc_stats_gt2).  Not with phase=True (ValueError before any work), for the same reason.
+    `ancestry_assoc_model` (config key inference.ancestry_assoc_model: linear | logistic; absent = linear): with logistic the
+    phenotype is a case / control trait coded 0 / 1 (another value on a used sample: ValueError naming the sample) and the file is
+    query_results.assoc.logistic.tsv instead, one logistic fit per SNP on the device (gnx_ancestry_assoc_logit_gt2)."""
     from time import perf_counter as clock
     from . import postprocess as pp
     from . import vcfio
     if ancestry_allele_freq_output and base_args["phase"]:
         raise ValueError("inference.ancestry_allele_freq_output with phase=True: the phased haplotypes are not kept on this path; "
                          "use HipGnomix.phase followed by HipGnomix.allele_frequencies")
+    if ancestry_assoc_model not in ("linear", "logistic"):
+        raise ValueError(f"inference.ancestry_assoc_model must be 'linear' or 'logistic', got {ancestry_assoc_model!r}")
     if ancestry_assoc_output and base_args["phase"]:
         raise ValueError("inference.ancestry_assoc_output with phase=True: the phased haplotypes are not kept on this path; "
                          "use HipGnomix.phase followed by HipGnomix.ancestry_association")
@@ -194,14 +200,15 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
         t0 = clock()
     try:
         return _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out, T, t0, snp_level, bed_file_output, verbose,
-                              global_ancestry_output, ancestry_allele_freq_output, ancestry_assoc_output, phenotype_file)
+                              global_ancestry_output, ancestry_allele_freq_output, ancestry_assoc_output, phenotype_file, ancestry_assoc_model)
     finally:
         if own_group is not None:
             own_group.close()
 
 
 def _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out, T, t0, snp_level, bed_file_output, verbose,
-                   global_ancestry_output=False, ancestry_allele_freq_output=False, ancestry_assoc_output=False, phenotype_file=None):
+                   global_ancestry_output=False, ancestry_allele_freq_output=False, ancestry_assoc_output=False, phenotype_file=None,
+                   ancestry_assoc_model="linear"):
     from time import perf_counter as clock
     from . import postprocess as pp
     from . import vcfio
@@ -261,9 +268,15 @@ def _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out,
     if ancestry_assoc_output:
         t0 = clock()
         from . import assoc
-        y, Z, use, _ = assoc.read_phenotypes(phenotype_file, [str(s) for s in samples])
-        result = model.dev.ancestry_assoc_gt2(vcf.gt2, N, src, labels, y, Z, use)     # one GPU: the model's own
-        pp.write_assoc(out_prefix, chm, model.snp_pos, model.M, model.W, result, model.population_order)
+        names = [str(s) for s in samples]
+        y, Z, use, _ = assoc.read_phenotypes(phenotype_file, names)
+        if ancestry_assoc_model == "logistic":
+            assoc.check_binary(y, use, names)
+            result = model.dev.ancestry_assoc_logit_gt2(vcf.gt2, N, src, labels, y, Z, use)
+            pp.write_assoc_logit(out_prefix, chm, model.snp_pos, model.M, model.W, result, model.population_order)
+        else:
+            result = model.dev.ancestry_assoc_gt2(vcf.gt2, N, src, labels, y, Z, use)     # one GPU: the model's own
+            pp.write_assoc(out_prefix, chm, model.snp_pos, model.M, model.W, result, model.population_order)
         T["write_assoc"] = clock() - t0
     return out_prefix
 
@@ -332,7 +345,8 @@ def main(argv=None):
                       bed_file_output=bool(inf.get("bed_file_output")), verbose=True, timings=T, query=query, devices=devices,
                       global_ancestry_output=bool(inf.get("global_ancestry_output")),
                       ancestry_allele_freq_output=bool(inf.get("ancestry_allele_freq_output")),
-                      ancestry_assoc_output=bool(inf.get("ancestry_assoc_output")), phenotype_file=inf.get("phenotype_file"))
+                      ancestry_assoc_output=bool(inf.get("ancestry_assoc_output")), phenotype_file=inf.get("phenotype_file"),
+                      ancestry_assoc_model=inf.get("ancestry_assoc_model") or "linear")
         if os.environ.get("GNX_CLI_TIMING"):
             T["since_process_start"] = _since_process_start()
             sys.stderr.write("gnomix_amd timings (s): " + ", ".join("%s %.3f" % kv for kv in T.items()) + "\n")
@@ -494,7 +508,8 @@ def train_main(argv):
         run_inference(base_args, model, snp_level=bool(inf.get("snp_level_inference")), bed_file_output=bool(inf.get("bed_file_output")),
                       verbose=True, global_ancestry_output=bool(inf.get("global_ancestry_output")),
                       ancestry_allele_freq_output=bool(inf.get("ancestry_allele_freq_output")),
-                      ancestry_assoc_output=bool(inf.get("ancestry_assoc_output")), phenotype_file=inf.get("phenotype_file"))
+                      ancestry_assoc_output=bool(inf.get("ancestry_assoc_output")), phenotype_file=inf.get("phenotype_file"),
+                      ancestry_assoc_model=inf.get("ancestry_assoc_model") or "linear")
     return 0
 
 

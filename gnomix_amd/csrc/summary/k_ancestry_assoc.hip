@@ -27,7 +27,7 @@
 // The VALU form was kept: a wave's work per (individual, SNP) is dominated by the LDS read-modify-write of the rows the individual's
 // two ancestries select, which the float64 matrix cores would not remove.
 // No per-thread array is indexed at run time; no scratch.
-#include "../gnx_internal.h"
+#include "gnx_assoc_rows.h"
 
 namespace {
 
@@ -105,14 +105,6 @@ __global__ __launch_bounds__(AS_WIN_THREADS) void k_ancestry_assoc_window(const 
       if (j == 0 && nbad) atomicAdd(bad, nbad);
     }
   }
-}
-
-// the field of column c of one row: 0 REF, 1 ALT, 2 / 3 missing (the coding of k_allele_counts.hip's load_fields)
-template <int KIND>
-__device__ __forceinline__ uint32_t as_code(const uint8_t* __restrict__ row, int64_t c) {
-  if (KIND == GNX_ROWS_PACKED2) return ((uint32_t)row[c >> 2] >> (2 * (int)(c & 3))) & 3u;
-  const uint32_t b = row[c];
-  return b <= 1u ? b : 2u;
 }
 
 template <int KIND>
@@ -201,10 +193,6 @@ __global__ __launch_bounds__(AS_THREADS) void k_ancestry_assoc_snp(const uint8_t
     oi[e] = accI[s * TC + col];
   }
 }
-
-int64_t as_min_row_bytes(int row_kind, int64_t C) { return row_kind == GNX_ROWS_PACKED2 ? (C + 3) / 4 : C; }
-
-int64_t as_win(int64_t c, int64_t M, int64_t W) { return std::min(c / M, W - 1); }
 
 // the largest power of two <= 64 whose tile of blocks fits AS_LDS_BYTES (>= 4 at A = 32, K = 16)
 int as_tile_cols(const AsLayout& L) {

@@ -251,12 +251,18 @@ class HipGnomix:
             lab = self.dev.mode_filter(lab, mf)
         return self.dev.ancestry_allele_counts(self.dev._x(X), lab)
 
-    def ancestry_association(self, X, y, Z=None, use=None, min_ac=1):
+    def ancestry_association(self, X, y, Z=None, use=None, min_ac=1, model="linear"):
         """ancestry-specific association (the Tractor model) of X under the labels predict returns (mode_filter applied when set):
         per SNP, y = Z g + sum_{a < A-1} alpha_a hapcount_a + sum_a beta_a dosage_a by OLS over the individuals (rows 2 i, 2 i + 1)
         -> assoc.AncestryAssoc(beta, se, t, p, n_alt, n_hap, n, df, n_miss, status).  y (N / 2,), Z (N / 2, K) with the intercept
         column (None = the intercept only), use (N / 2,) bytes.  The sufficient statistics are reduced on the device
-        (k_ancestry_assoc_snp); with a CUDA tensor neither X nor the labels leave HBM.  Results are numpy arrays."""
+        (k_ancestry_assoc_snp); with a CUDA tensor neither X nor the labels leave HBM.  Results are numpy arrays.
+        model="logistic": a case / control trait (y coded 0 / 1), the same terms with a logit link, fitted by maximum likelihood on the
+        device (k_ancestry_assoc_logit_snp) -> assoc.AncestryAssocLogit.  Any other value: ValueError."""
+        if model not in ("linear", "logistic"):
+            raise ValueError(f"model must be 'linear' or 'logistic', got {model!r}")
+        fit = (lambda X, lab: self.dev.ancestry_assoc(X, lab, y, Z, use, min_ac)) if model == "linear" else (
+            lambda X, lab: self.dev.ancestry_assoc_logit(X, lab, y, Z, use, min_ac))
         mf = self.smooth.mode_filter
         if resident.is_cuda(X):
             with resident.torch_stream(self.dev.ctx):
@@ -264,11 +270,11 @@ class HipGnomix:
                 _, lab = self.dev.infer_device(X, want_proba=False, want_labels=True)
                 if mf:
                     lab = self.dev.mode_filter_device(lab, mf)
-                return self.dev.ancestry_assoc(X, lab, y, Z, use, min_ac)
+                return fit(X, lab)
         _, lab = self.dev.infer(X, want_proba=False, want_labels=True)
         if mf:
             lab = self.dev.mode_filter(lab, mf)
-        return self.dev.ancestry_assoc(self.dev._x(X), lab, y, Z, use, min_ac)
+        return fit(self.dev._x(X), lab)
 
     def phase(self, X, B=None, verbose=False, **gnofix_kw):
         """Gnofix re-phasing (model.py:188-214): -> X_phased (N, C) int, Y_phased (N, W) int.  `gnofix_kw`: gnofix()'s search

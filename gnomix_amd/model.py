@@ -636,6 +636,89 @@ class DeviceModel:
         return assoc.assoc_from_stats(lambda c0, c1: self.ancestry_assoc_stats_gt2(G, N, src, labels, y, Z, use, c0, c1, min_ac), self.C, self.A,
                                       Z.shape[1], min_ac)
 
+    def ancestry_assoc_logit_fit(self, X, labels, y, Z=None, use=None, c0=0, c1=None, min_ac=1, tol=None, max_iter=None, check=True):
+        """the logistic fits of the SNPs [c0, c1) (gnx_ancestry_assoc_logit[_dev]; include/gnomix_hip.h states the model and the iteration)
+        -> gnomix_amd.assoc.LogitFit of numpy arrays.  X and labels as ancestry_assoc_stats takes them (numpy arrays, or CUDA tensors
+        that never leave HBM).  check=False: labels out of range do not raise, their count is LogitFit.n_bad."""
+        from . import assoc
+        c1 = self.C if c1 is None else int(c1)
+        c0 = int(c0)
+        tol = assoc.LOGIT_TOL if tol is None else float(tol)
+        max_iter = assoc.LOGIT_MAX_ITER if max_iter is None else int(max_iter)
+        if not hasattr(X, "is_cuda"):
+            X = self._x(X)
+            lab = np.ascontiguousarray(labels, dtype=np.int32)
+            if lab.shape != (X.shape[0], self.W):
+                raise ValueError(f"labels must be (N={X.shape[0]}, W={self.W}), got {lab.shape}")
+            return assoc.logit_host(self.ctx, X, lab, self.M, self.A, y, Z, use, c0, c1, min_ac=min_ac, tol=tol, max_iter=max_iter, check=check)
+        import ctypes
+        import torch
+        kind, ld, ldl, N = self._allele_device_args(X, labels)
+        yh, Zh, uh = assoc.covariates(N // 2, y, Z, use)
+        K = Zh.shape[1]
+        dev = X.device
+        y_t, Z_t, u_t = (torch.from_numpy(v).to(dev) for v in (yh, Zh, uh))
+        sf, si, th, wf, wi = assoc.logit_buffers(self.A, K, c0, c1, self.M, self.W, empty=lambda shape, dt: torch.zeros(
+            shape, dtype=torch.float64 if dt == np.float64 else torch.int32, device=dev))
+        n_bad = ctypes.c_int64(0)
+        self._bind_torch_stream()
+        rc = self.lib.gnx_ancestry_assoc_logit_dev(self.ctx.h, X.data_ptr(), kind, ld, labels.data_ptr(), ldl, N, self.C, self.M, self.W, self.A,
+                                                   y_t.data_ptr(), Z_t.data_ptr(), K, u_t.data_ptr(), int(min_ac), c0, c1, tol, max_iter,
+                                                   sf.data_ptr(), si.data_ptr(), th.data_ptr(), wf.data_ptr(), wi.data_ptr(), ctypes.byref(n_bad))
+        if check or rc not in (_lib.GNX_OK, _lib.GNX_EINVAL) or (rc != _lib.GNX_OK and not n_bad.value):
+            self.ctx.check(rc)
+        return assoc.split_logit(sf.cpu().numpy(), si.cpu().numpy(), th.cpu().numpy(), wf.cpu().numpy(), wi.cpu().numpy(), self.A, K, c0, c1, self.M,
+                                 self.W, n_bad.value)
+
+    def ancestry_assoc_logit(self, X, labels, y, Z=None, use=None, min_ac=1, tol=None, max_iter=None):
+        """ancestry-specific association of a case / control trait (the Tractor model with a logit link: logit P(y = 1) = Z g +
+        sum_{a < A-1} alpha_a hapcount_a + sum_a beta_a dosage_a, maximum likelihood per SNP over the individuals that take part, fitted
+        on the device: k_ancestry_assoc_logit_snp) -> gnomix_amd.assoc.AncestryAssocLogit.  y (N / 2,) coded 0 / 1, Z, use as
+        ancestry_assoc takes them; X and labels numpy arrays or CUDA tensors.  The SNPs are walked in chunks whose outputs stay below
+        assoc.STATS_CHUNK_BYTES."""
+        from . import assoc
+        if min_ac < 1:
+            raise ValueError("min_ac must be >= 1")
+        n_ind = X.shape[0] // 2
+        y, Z, use = assoc.covariates(n_ind, y, Z, use)
+        assoc.check_binary(y, use)
+        return assoc.logit_from_fits(lambda c0, c1: self.ancestry_assoc_logit_fit(X, labels, y, Z, use, c0, c1, min_ac, tol, max_iter), self.C, self.A,
+                                     Z.shape[1])
+
+    def ancestry_assoc_logit_fit_gt2(self, G, N, src, labels, y, Z=None, use=None, c0=0, c1=None, min_ac=1, tol=None, max_iter=None, check=True):
+        """ancestry_assoc_logit_fit of the parsed query (G, N, src as infer_gt2 takes them) under host labels (N, W): the packed rows of
+        all individuals are built in HBM and fitted there (gnx_ancestry_assoc_logit_gt2) -> assoc.LogitFit of [c0, c1)"""
+        import ctypes
+        from . import assoc
+        G, N, src = self._gt2_args(G, N, src)
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.shape != (N, self.W):
+            raise ValueError(f"labels must be (N={N}, W={self.W}), got {lab.shape}")
+        c1 = self.C if c1 is None else int(c1)
+        c0 = int(c0)
+        tol = assoc.LOGIT_TOL if tol is None else float(tol)
+        max_iter = assoc.LOGIT_MAX_ITER if max_iter is None else int(max_iter)
+        y, Z, use = assoc.covariates(N // 2, y, Z, use)
+        K = Z.shape[1]
+        sf, si, th, wf, wi = assoc.logit_buffers(self.A, K, c0, c1, self.M, self.W)
+        n_bad = ctypes.c_int64(0)
+        rc = self.lib.gnx_ancestry_assoc_logit_gt2(self.h, G.ctypes.data, G.shape[0], G.shape[1], N, src.ctypes.data, lab.ctypes.data, y.ctypes.data,
+                                                   Z.ctypes.data, K, use.ctypes.data, int(min_ac), c0, c1, tol, max_iter, sf.ctypes.data, si.ctypes.data,
+                                                   th.ctypes.data, wf.ctypes.data, wi.ctypes.data, ctypes.byref(n_bad))
+        if check or rc not in (_lib.GNX_OK, _lib.GNX_EINVAL) or (rc != _lib.GNX_OK and not n_bad.value):
+            self.ctx.check(rc)
+        return assoc.split_logit(sf, si, th, wf, wi, self.A, K, c0, c1, self.M, self.W, n_bad.value)
+
+    def ancestry_assoc_logit_gt2(self, G, N, src, labels, y, Z=None, use=None, min_ac=1, tol=None, max_iter=None):
+        """ancestry_assoc_logit of the parsed query under host labels (the command line's path) -> assoc.AncestryAssocLogit"""
+        from . import assoc
+        if min_ac < 1:
+            raise ValueError("min_ac must be >= 1")
+        y, Z, use = assoc.covariates(int(N) // 2, y, Z, use)
+        assoc.check_binary(y, use)
+        return assoc.logit_from_fits(lambda c0, c1: self.ancestry_assoc_logit_fit_gt2(G, N, src, labels, y, Z, use, c0, c1, min_ac, tol, max_iter),
+                                     self.C, self.A, Z.shape[1])
+
     def allele_counts_gt2(self, G, N, src, labels):
         """ancestry-specific allele counts of the parsed query (G, N, src as infer_gt2 takes them) under host labels (N, W): the
         packed rows are built and counted in HBM, batch by batch (gnx_ancestry_allele_counts_gt2) -> AlleleCounts"""

@@ -366,6 +366,28 @@ def write_assoc(prefix, chm, snp_pos, M, W, result, populations):
             f.write("\t".join(cells) + "\n")
 
 
+def write_assoc_logit(prefix, chm, snp_pos, M, W, result, populations):
+    """<prefix>.assoc.logistic.tsv from an assoc.AncestryAssocLogit: one header line, then one line per model SNP in model order: chm,
+    pos, window, n, n_case, df, status, iters, n_miss, lrt, lrt_df, lrt_p, then per population <pop>.n_hap, .n_alt, .n_alt_case, .beta,
+    .se, .z, .p (floats with six significant digits, nan for a dropped term or a SNP that was not fitted), tab-separated"""
+    pos = np.asarray(snp_pos)
+    A, C = len(populations), len(pos)
+    if np.asarray(result.beta).shape != (C, A):
+        raise ValueError(f"result must be ({C} SNPs, {A} populations), got {np.asarray(result.beta).shape}")
+    num = lambda v: format(float(v), ".6g") if np.isfinite(v) else "nan"
+    with open(prefix + ".assoc.logistic.tsv", "w") as f:
+        f.write("chm\tpos\twindow\tn\tn_case\tdf\tstatus\titers\tn_miss\tlrt\tlrt_df\tlrt_p\t" +
+                "\t".join("\t".join(p + s for s in (".n_hap", ".n_alt", ".n_alt_case", ".beta", ".se", ".z", ".p")) for p in populations) + "\n")
+        for c in range(C):
+            cells = [str(chm), str(int(pos[c])), str(min(c // int(M), int(W) - 1)), str(int(result.n[c])), str(int(result.n_case[c])),
+                     str(int(result.df[c])), str(int(result.status[c])), str(int(result.iters[c])), str(int(result.n_miss[c])), num(result.lrt[c]),
+                     str(int(result.lrt_df[c])), num(result.lrt_p[c])]
+            for a in range(A):
+                cells += [str(int(result.n_hap[c, a])), str(int(result.n_alt[c, a])), str(int(result.n_alt_case[c, a])), num(result.beta[c, a]),
+                          num(result.se[c, a]), num(result.z[c, a]), num(result.p[c, a])]
+            f.write("\t".join(cells) + "\n")
+
+
 def write_lai(prefix, meta, labels, positions, samples, populations=None, n_threads=0, first_line=None):
     """<prefix>.lai — the bytes msp_to_lai writes from <prefix>.msp, from the labels themselves (gnx_write_lai): the .msp's first
     header line (built from `populations`, or given as `first_line`), "position" and the haplotype columns, then one line per query

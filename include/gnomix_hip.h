@@ -939,6 +939,71 @@ int gnx_ancestry_assoc_stats_gt2(gnx_model* m, const uint8_t* G, int64_t n_varia
                                  int64_t c0, int64_t c1, double* snp_f64, int32_t* snp_i32, double* win_f64, int32_t* win_i32,
                                  int64_t* n_bad);
 
+/* ---- ancestry-specific association for case / control traits: one logistic fit per SNP, on the device ---------------------------------
+ * (csrc/summary/k_ancestry_assoc_logit.hip)
+ * Everything not stated here is EXACTLY as gnx_ancestry_assoc_stats has it: rows, labels, M, W, A, win(c), h[i, a], d[i, a], y, Z, K, use,
+ *   the handling of missing calls and of labels outside [0, A).
+ * PARTICIPATION.  Individual i takes part at window k as above.  A participant's y[i] must be exactly 0.0 (control) or 1.0 (case): if any
+ *   individual with use[i] != 0 and a finite y[i] has another value, the entry returns GNX_EINVAL BEFORE any fit, *n_bad is the count of
+ *   such individuals, the message says so and the outputs are untouched.
+ * THE MODEL.  At SNP c, over the n participants of win(c), by maximum likelihood:
+ *     logit P(y = 1) = Z g + sum_{a < A-1} alpha_a h_a + sum_a beta_a d_a
+ *   theta = (g [K], alpha [A - 1], beta [A]): Q = K + 2 A - 1 columns X; the first P = K + A - 1 are U = [Z, h_0 .. h_{A-2}].
+ * COLUMN RULE (integers only, hence exact).  A hapcount column with sum_i h[i, a] == 0 is dropped.  A dosage column is kept iff
+ *   sum_i d[i, a] >= min_ac AND 0 < sum_i d[i, a] y[i] < sum_i d[i, a] (at least one ALT copy among the cases and one among the
+ *   controls: a one-sided allele would separate the data and take the SNP's other ancestries with it); a dropped dosage term reports
+ *   NaN.  A dropped column's theta stays 0.
+ * THE WINDOW'S NULL MODEL.  U alone (kept columns) is fitted once per window from theta = 0; the SNP's fit starts from the null theta
+ *   with beta = 0.
+ * EVALUATION at a theta, per participant, in float64 without fused multiply-add: eta = sum_j x_j theta_j (ascending j, zero x_j
+ *   skipped); e = exp(-|eta|) (csrc/gnx_exp.h); q = 1 / (1 + e); mu = q or e q and 1 - mu = e q or q (eta >= 0 or < 0); w = (e q) q;
+ *   the deviance term is 2 (max(t, 0) + log1p(e)) with t = -eta for a case, eta for a control.  dev = sum of the terms (-2 loglik),
+ *   g = X^T (y - mu), H = X^T W X: every sum over the participants in ascending i, one term per individual ((w x_j) x_k for H, j >= k),
+ *   rounded once, added to the running sum.  The order depends on N alone.
+ * ITERATION (fixed, so that results are reproducible), at most max_iter steps:
+ *   1. g and H at the current theta.  2. H to unit diagonal (s_j = sqrt(H_jj); a dropped column is a unit row), Cholesky; a pivot
+ *   <= 2^-40 or not finite, or a kept column with H_jj <= 0: status 1.  3. delta = H^-1 g, lambda2 = g^T delta.  4. lambda2 <= tol: take
+ *   the full step and stop; H is evaluated once more at the returned theta for the standard errors, dev is the deviance there (no
+ *   deviance comparison on this step).  5. Otherwise the trial theta + t delta, t = 1, is halved at most 10 times while its deviance
+ *   is not below the current one, then taken.  iters counts the steps taken (the last one included).
+ * STATUS per SNP: 0 fitted; 1 Hessian not positive definite; 2 df = n - p_kept < 1; 3 no finite optimum (max_iter steps without
+ *   lambda2 <= tol, or some participant has w_i < 2^-40 at the returned theta: fitted probabilities numerically 0 or 1, separation);
+ *   4 the window's null model has status0 != 0 (status0 is 0, 1, 2 or 3 by the same rules; e.g. all participants are cases).  Status 4 is
+ *   tested before 2.  beta, se, dev and theta are NaN whenever status != 0; theta0 and dev0 whenever status0 != 0.  The NOTE on status 1
+ *   above applies: a window where no participant carries ancestry A - 1 has status0 1, its SNPs status 4.
+ * OUTPUTS for the SNPs [c0, c1) and the windows win(c0) .. win(c1 - 1), all OVERWRITTEN, one owner per value, plain stores:
+ *     snp_f64 (c1 - c0, 2 A + 1)   beta [A], se [A] (se_j = sqrt((X^T W X)^-1_jj)), dev
+ *     snp_i32 (c1 - c0, 2 A + 3)   n_alt [A] = sum_i d[i, a], n_alt_case [A] = sum_i d[i, a] y[i], n_miss, iters, status
+ *     theta   (c1 - c0, Q)         optional (NULL: not written): the fitted theta, 0 at a dropped column
+ *     win_f64 (nw, P + 1)          theta0 [P], dev0
+ *     win_i32 (nw, A + 4)          n, n_case, sum_h [A], iters0, status0
+ *   n_alt, n_miss, n and sum_h equal gnx_ancestry_assoc_stats' integers on the same inputs.  A SNP's results are a function of its
+ *   column, its window's labels, y, Z, use, N, A, K, min_ac, tol and max_iter alone: not of [c0, c1), the grid or the row form.
+ * GNX_EINVAL before the launch, nothing written: as gnx_ancestry_assoc_stats, and tol not finite or < 0, max_iter < 1 (callers use
+ *   GNX_ASSOC_LOGIT_TOL and GNX_ASSOC_LOGIT_MAX_ITER).  GNX_EUNSUPPORTED, nothing written: K > GNX_ASSOC_MAX_K or
+ *   Q > GNX_ASSOC_LOGIT_MAX_Q (the message names both numbers; A <= 16 with K <= 16 runs), N > 2^28.
+ * GNX_EINVAL after the launch: labels outside [0, A) among all rows at the range's windows; *n_bad is their count; every value is as
+ *   stated (such an individual takes no part at that window).
+ * gnx_ancestry_assoc_logit_gt2: the file path's form, arguments as gnx_ancestry_assoc_stats_gt2.  A Newton step needs every individual,
+ *   so the packed rows of ALL individuals are built in HBM (N ceil(C / 4) bytes, 64-byte aligned rows); GNX_HOST_BATCH only governs how
+ *   they are built: the results equal gnx_ancestry_assoc_logit's of the vcf_to_npy matrix bit for bit.
+ * OUT OF SCOPE: Firth or otherwise penalised fits, score tests, mixed models and relatedness, several devices. */
+#define GNX_ASSOC_LOGIT_MAX_Q 47
+#define GNX_ASSOC_LOGIT_TOL 1e-10
+#define GNX_ASSOC_LOGIT_MAX_ITER 25
+int gnx_ancestry_assoc_logit_dev(gnx_ctx* ctx, const void* d_rows, int row_kind, int64_t ld_rows, const int32_t* d_labels, int64_t ld_labels,
+                                 int64_t N, int64_t C, int64_t M, int64_t W, int32_t A, const double* d_y, const double* d_Z, int32_t K,
+                                 const uint8_t* d_use, int32_t min_ac, int64_t c0, int64_t c1, double tol, int32_t max_iter, double* d_snp_f64,
+                                 int32_t* d_snp_i32, double* d_theta, double* d_win_f64, int32_t* d_win_i32, int64_t* n_bad);
+int gnx_ancestry_assoc_logit(gnx_ctx* ctx, const int8_t* X, int64_t ld_rows, const int32_t* labels, int64_t ld_labels, int64_t N, int64_t C,
+                             int64_t M, int64_t W, int32_t A, const double* y, const double* Z, int32_t K, const uint8_t* use,
+                             int32_t min_ac, int64_t c0, int64_t c1, double tol, int32_t max_iter, double* snp_f64, int32_t* snp_i32,
+                             double* theta, double* win_f64, int32_t* win_i32, int64_t* n_bad);
+int gnx_ancestry_assoc_logit_gt2(gnx_model* m, const uint8_t* G, int64_t n_variants, int64_t ldg, int64_t N, const int32_t* src,
+                                 const int32_t* labels, const double* y, const double* Z, int32_t K, const uint8_t* use, int32_t min_ac,
+                                 int64_t c0, int64_t c1, double tol, int32_t max_iter, double* snp_f64, int32_t* snp_i32, double* theta,
+                                 double* win_f64, int32_t* win_i32, int64_t* n_bad);
+
 /* per-kernel device time, measured with hipEvents on the context stream around every launch */
 int gnx_profile_enable(gnx_ctx* ctx, int on);
 int gnx_profile_reset(gnx_ctx* ctx);
