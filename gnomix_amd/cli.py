@@ -134,7 +134,7 @@ class _Prefetch:
 
 def run_inference(base_args, model, snp_level=False, bed_file_output=False, verbose=False, timings=None, query=None, devices=None,
                   global_ancestry_output=False, ancestry_allele_freq_output=False, ancestry_assoc_output=False, phenotype_file=None,
-                  ancestry_assoc_model="linear"):
+                  ancestry_assoc_model="linear", ancestry_score_output=False, score_file=None):
     """gnomix.py:37-100 with the HIP model behind the same steps.  The query never becomes an (N, C) host matrix: the library
     parses the text into 2-bit rows (gnx_vcf_read), `column_map` keeps vcf_to_npy's bookkeeping (SNP intersection, REF flips,
     absent SNPs) as one int32 per model SNP, the GPU builds X and runs base + smoother (or Gnofix) on it, and the library
@@ -156,7 +156,12 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
     (gnx_ancestry_assoc_stats_gt2).  Not with phase=True (ValueError before any work), for the same reason.
     `ancestry_assoc_model` (config key inference.ancestry_assoc_model: linear | logistic; absent = linear): with logistic the
     phenotype is a case / control trait coded 0 / 1 (another value on a used sample: ValueError naming the sample) and the file is
-    query_results.assoc.logistic.tsv instead, one logistic fit per SNP on the device (gnx_ancestry_assoc_logit_gt2)."""
+    query_results.assoc.logistic.tsv instead, one logistic fit per SNP on the device (gnx_ancestry_assoc_logit_gt2).
+    `ancestry_score_output` (config key inference.ancestry_score_output, off unless set) with `score_file` (inference.score_file: a TSV
+    with the header `chm  pos  effect_allele` and weight columns NAME or NAME:POP, score.read_score_file): query_results.sscore.tsv as
+    well, the ancestry-partitioned polygenic scores of every individual, summed on the model's own GPU from the query's 2-bit rows
+    and the labels the .msp gets (gnx_ancestry_score_gt2).  Not with phase=True (ValueError before any work), for the
+    same reason."""
     from time import perf_counter as clock
     from . import postprocess as pp
     from . import vcfio
@@ -170,6 +175,11 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
                          "use HipGnomix.phase followed by HipGnomix.ancestry_association")
     if ancestry_assoc_output and not phenotype_file:
         raise ValueError("inference.ancestry_assoc_output needs inference.phenotype_file (a TSV: sample, pheno, then covariates)")
+    if ancestry_score_output and base_args["phase"]:
+        raise ValueError("inference.ancestry_score_output with phase=True: the phased haplotypes are not kept on this path; "
+                         "use HipGnomix.phase followed by HipGnomix.ancestry_scores")
+    if ancestry_score_output and not score_file:
+        raise ValueError("inference.ancestry_score_output needs inference.score_file (a TSV: chm, pos, effect_allele, then weight columns)")
     query_file, chm, output_path = base_args["query_file"], base_args["chm"], base_args["output_basename"]
     T = timings if timings is not None else {}
     if verbose:
@@ -200,7 +210,8 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
         t0 = clock()
     try:
         return _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out, T, t0, snp_level, bed_file_output, verbose,
-                              global_ancestry_output, ancestry_allele_freq_output, ancestry_assoc_output, phenotype_file, ancestry_assoc_model)
+                              global_ancestry_output, ancestry_allele_freq_output, ancestry_assoc_output, phenotype_file, ancestry_assoc_model,
+                              ancestry_score_output=ancestry_score_output, score_file=score_file)
     finally:
         if own_group is not None:
             own_group.close()
@@ -208,7 +219,7 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
 
 def _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out, T, t0, snp_level, bed_file_output, verbose,
                    global_ancestry_output=False, ancestry_allele_freq_output=False, ancestry_assoc_output=False, phenotype_file=None,
-                   ancestry_assoc_model="linear"):
+                   ancestry_assoc_model="linear", ancestry_score_output=False, score_file=None):
     from time import perf_counter as clock
     from . import postprocess as pp
     from . import vcfio
@@ -278,6 +289,13 @@ def _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out,
             result = model.dev.ancestry_assoc_gt2(vcf.gt2, N, src, labels, y, Z, use)     # one GPU: the model's own
             pp.write_assoc(out_prefix, chm, model.snp_pos, model.M, model.W, result, model.population_order)
         T["write_assoc"] = clock() - t0
+    if ancestry_score_output:
+        t0 = clock()
+        from . import score
+        weights, effect, names, _ = score.read_score_file(score_file, chm, model.snp_pos, model.snp_ref, model.snp_alt, model.population_order)
+        result = model.dev.ancestry_scores_gt2(vcf.gt2, N, src, labels, weights, effect)         # one GPU: the model's own
+        pp.write_sscore(out_prefix, result, names, model.population_order, [str(s) for s in samples])
+        T["write_sscore"] = clock() - t0
     return out_prefix
 
 
@@ -346,7 +364,8 @@ def main(argv=None):
                       global_ancestry_output=bool(inf.get("global_ancestry_output")),
                       ancestry_allele_freq_output=bool(inf.get("ancestry_allele_freq_output")),
                       ancestry_assoc_output=bool(inf.get("ancestry_assoc_output")), phenotype_file=inf.get("phenotype_file"),
-                      ancestry_assoc_model=inf.get("ancestry_assoc_model") or "linear")
+                      ancestry_assoc_model=inf.get("ancestry_assoc_model") or "linear",
+                      ancestry_score_output=bool(inf.get("ancestry_score_output")), score_file=inf.get("score_file"))
         if os.environ.get("GNX_CLI_TIMING"):
             T["since_process_start"] = _since_process_start()
             sys.stderr.write("gnomix_amd timings (s): " + ", ".join("%s %.3f" % kv for kv in T.items()) + "\n")
@@ -509,7 +528,8 @@ def train_main(argv):
                       verbose=True, global_ancestry_output=bool(inf.get("global_ancestry_output")),
                       ancestry_allele_freq_output=bool(inf.get("ancestry_allele_freq_output")),
                       ancestry_assoc_output=bool(inf.get("ancestry_assoc_output")), phenotype_file=inf.get("phenotype_file"),
-                      ancestry_assoc_model=inf.get("ancestry_assoc_model") or "linear")
+                      ancestry_assoc_model=inf.get("ancestry_assoc_model") or "linear",
+                      ancestry_score_output=bool(inf.get("ancestry_score_output")), score_file=inf.get("score_file"))
     return 0
 
 

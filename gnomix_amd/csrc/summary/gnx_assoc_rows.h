@@ -1,14 +1,52 @@
-// summary/gnx_assoc_rows.h — what the two ancestry-specific association files share about rows and windows (k_ancestry_assoc.hip, the
-// linear model's sufficient statistics; k_ancestry_assoc_logit.hip, the logistic fits): one definition of each.
+// summary/gnx_assoc_rows.h — what the files of this folder share about rows and windows (k_ancestry_assoc.hip, the linear model's
+// sufficient statistics; k_ancestry_assoc_logit.hip, the logistic fits; k_allele_counts.hip and k_ancestry_score.hip, which read a
+// row 16 columns at a time): one definition of each.
 #pragma once
 #include "../gnx_internal.h"
 
-// the field of column c of one row: 0 REF, 1 ALT, 2 / 3 missing (the coding of k_allele_counts.hip's load_fields)
+// the field of column c of one row: 0 REF, 1 ALT, 2 / 3 missing (the coding of as_fields16 below)
 template <int KIND>
 __device__ __forceinline__ uint32_t as_code(const uint8_t* __restrict__ row, int64_t c) {
   if (KIND == GNX_ROWS_PACKED2) return ((uint32_t)row[c >> 2] >> (2 * (int)(c & 3))) & 3u;
   const uint32_t b = row[c];
   return b <= 1u ? b : 2u;
+}
+
+// the 16 fields of the columns c0 .. c0 + 15 of one row (c0 a multiple of 16), field j at bits 2 j; fields of columns >= C are
+// unspecified.  aligned: the rows' base and stride are multiples of 4 (packed) or 16 (int8) bytes, so the group is one load.  Shared by
+// k_allele_counts.hip and k_ancestry_score.hip.
+template <int KIND>
+__device__ __forceinline__ uint32_t as_fields16(const uint8_t* __restrict__ row, int64_t c0, int64_t C, int aligned) {
+  if (KIND == GNX_ROWS_PACKED2) {
+    const int64_t b0 = c0 >> 2, nbytes = ((C + 3) >> 2) - b0;  // never read past the row's last packed byte
+    if (aligned && nbytes >= 4) return *reinterpret_cast<const uint32_t*>(row + b0);
+    uint32_t w = 0;
+    for (int b = 0; b < 4 && b < nbytes; ++b) w |= (uint32_t)row[b0 + b] << (8 * b);
+    return w;
+  } else {
+    uint32_t x0 = 0x02020202u, x1 = 0x02020202u, x2 = 0x02020202u, x3 = 0x02020202u;
+    if (aligned && c0 + 16 <= C) {
+      const uint4 q = *reinterpret_cast<const uint4*>(row + c0);
+      x0 = q.x; x1 = q.y; x2 = q.z; x3 = q.w;
+    } else {
+      const int n = (int)((C - c0 < 16) ? C - c0 : 16);
+      uint32_t y0 = 0, y1 = 0, y2 = 0, y3 = 0;
+      for (int j = 0; j < n; ++j) {
+        const uint32_t b = (uint32_t)row[c0 + j] << (8 * (j & 3));
+        if (j < 4) y0 |= b; else if (j < 8) y1 |= b; else if (j < 12) y2 |= b; else y3 |= b;
+      }
+      x0 = y0; x1 = y1; x2 = y2; x3 = y3;
+    }
+    // a byte -> its field: 0 -> 0, 1 -> 1, anything else -> 2
+    uint32_t w = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const uint32_t x = j < 4 ? x0 : j < 8 ? x1 : j < 12 ? x2 : x3;
+      const uint32_t b = (x >> (8 * (j & 3))) & 0xFFu;
+      w |= (b <= 1u ? b : 2u) << (2 * j);
+    }
+    return w;
+  }
 }
 
 inline int64_t as_min_row_bytes(int row_kind, int64_t C) { return row_kind == GNX_ROWS_PACKED2 ? (C + 3) / 4 : C; }

@@ -24,7 +24,7 @@
 // where the group spans a window border), two 16-byte stores.
 //
 // Neither kernel has a per-thread array that is indexed at run time; no scratch.
-#include "../gnx_internal.h"
+#include "gnx_assoc_rows.h"
 
 namespace {
 
@@ -39,41 +39,6 @@ constexpr uint32_t EVEN = 0x55555555u, ONES = 0x01010101u;
 // fields 4 q .. 4 q + 3 of x (one bit each, at the even positions) -> the four bytes of a word, 0 or 1 each: the bits 0, 2, 4, 6 of the
 // byte move up by 0, 6, 12, 18 (two partial products meet only at bits 6, 12 and 18, and their carry ends in an empty odd bit)
 __device__ __forceinline__ uint32_t spread(uint32_t x, int q) { return (((x >> (8 * q)) & 0x55u) * 0x00041041u) & ONES; }
-
-// the 16 fields of the columns c0 .. c0 + 15 of one row (c0 a multiple of 16); fields of columns >= C are unspecified
-template <int KIND>
-__device__ __forceinline__ uint32_t load_fields(const uint8_t* __restrict__ row, int64_t c0, int64_t C, int aligned) {
-  if (KIND == GNX_ROWS_PACKED2) {
-    const int64_t b0 = c0 >> 2, nbytes = ((C + 3) >> 2) - b0;  // never read past the row's last packed byte
-    if (aligned && nbytes >= 4) return *reinterpret_cast<const uint32_t*>(row + b0);
-    uint32_t w = 0;
-    for (int b = 0; b < 4 && b < nbytes; ++b) w |= (uint32_t)row[b0 + b] << (8 * b);
-    return w;
-  } else {
-    uint32_t x0 = 0x02020202u, x1 = 0x02020202u, x2 = 0x02020202u, x3 = 0x02020202u;
-    if (aligned && c0 + 16 <= C) {
-      const uint4 q = *reinterpret_cast<const uint4*>(row + c0);
-      x0 = q.x; x1 = q.y; x2 = q.z; x3 = q.w;
-    } else {
-      const int n = (int)((C - c0 < 16) ? C - c0 : 16);
-      uint32_t y0 = 0, y1 = 0, y2 = 0, y3 = 0;
-      for (int j = 0; j < n; ++j) {
-        const uint32_t b = (uint32_t)row[c0 + j] << (8 * (j & 3));
-        if (j < 4) y0 |= b; else if (j < 8) y1 |= b; else if (j < 12) y2 |= b; else y3 |= b;
-      }
-      x0 = y0; x1 = y1; x2 = y2; x3 = y3;
-    }
-    // a byte -> its field: 0 -> 0, 1 -> 1, anything else -> 2
-    uint32_t w = 0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const uint32_t x = j < 4 ? x0 : j < 8 ? x1 : j < 12 ? x2 : x3;
-      const uint32_t b = (x >> (8 * (j & 3))) & 0xFFu;
-      w |= (b <= 1u ? b : 2u) << (2 * j);
-    }
-    return w;
-  }
-}
 
 // 0x01 in the bytes of the valid ones of the columns 4 k .. 4 k + 3 of a group with nvalid valid columns
 __device__ __forceinline__ uint32_t valid_bytes(int nvalid, int k) {
@@ -127,10 +92,10 @@ __global__ __launch_bounds__(AC_THREADS) void k_ancestry_allele_counts(const uin
     if (nvalid > 0) {
       for (int rb = 0; rb < nb; rb += 4) {
         uint32_t f0 = 0, f1 = 0, f2 = 0, f3 = 0;   // four rows' loads in flight before the first is used
-        f0 = load_fields<KIND>(rows + (r0 + rb) * ld, c0, C, aligned);
-        if (rb + 1 < nb) f1 = load_fields<KIND>(rows + (r0 + rb + 1) * ld, c0, C, aligned);
-        if (rb + 2 < nb) f2 = load_fields<KIND>(rows + (r0 + rb + 2) * ld, c0, C, aligned);
-        if (rb + 3 < nb) f3 = load_fields<KIND>(rows + (r0 + rb + 3) * ld, c0, C, aligned);
+        f0 = as_fields16<KIND>(rows + (r0 + rb) * ld, c0, C, aligned);
+        if (rb + 1 < nb) f1 = as_fields16<KIND>(rows + (r0 + rb + 1) * ld, c0, C, aligned);
+        if (rb + 2 < nb) f2 = as_fields16<KIND>(rows + (r0 + rb + 2) * ld, c0, C, aligned);
+        if (rb + 3 < nb) f3 = as_fields16<KIND>(rows + (r0 + rb + 3) * ld, c0, C, aligned);
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           if (rb + u >= nb) break;
@@ -223,8 +188,8 @@ __global__ __launch_bounds__(256) void k_ancestry_dosage(const uint8_t* __restri
     const int64_t i = e / G, g = e - i * G;
     const int64_t c0 = g * AC_COLS;
     const int n = (int)((C - c0 < AC_COLS) ? C - c0 : AC_COLS);
-    const uint32_t fa = load_fields<KIND>(rows + (2 * i) * ld, c0, C, aligned_in);
-    const uint32_t fb = load_fields<KIND>(rows + (2 * i + 1) * ld, c0, C, aligned_in);
+    const uint32_t fa = as_fields16<KIND>(rows + (2 * i) * ld, c0, C, aligned_in);
+    const uint32_t fb = as_fields16<KIND>(rows + (2 * i + 1) * ld, c0, C, aligned_in);
     const uint32_t sa = select_fields(lab + (2 * i) * ldl, c0, n, M, W, A, anc, &my_bad);
     const uint32_t sb = select_fields(lab + (2 * i + 1) * ldl, c0, n, M, W, A, anc, &my_bad);
     const uint32_t alt_a = fa & EVEN & ~((fa >> 1) & EVEN) & sa, alt_b = fb & EVEN & ~((fb >> 1) & EVEN) & sb;

@@ -276,6 +276,26 @@ class HipGnomix:
             lab = self.dev.mode_filter(lab, mf)
         return fit(self.dev._x(X), lab)
 
+    def ancestry_scores(self, X, weights, effect=None):
+        """ancestry-partitioned polygenic scores ("partial PRS") of X under the labels predict returns (mode_filter applied when set):
+        per individual (rows 2 i, 2 i + 1), ancestry a and score s, the sum of weights[c, a, s] over the SNPs c and the individual's
+        haplotypes labelled a at c's window that carry the effect allele -> postprocess.AncestryScores(score (N / 2, A, S), n_effect,
+        n_scored, n_miss (N / 2, A); .avg() = score / n_scored).  weights (C,), (C, A) or (C, A, S) (score.weights_from_assoc,
+        score.read_score_file); effect None (ALT everywhere) or (C,) of 1 (ALT), 0 (REF), 255 (not scored).  One fused pass on the
+        device (k_ancestry_score_partial); with a CUDA tensor neither X nor the labels leave HBM and CUDA tensors come back."""
+        mf = self.smooth.mode_filter
+        if resident.is_cuda(X):
+            with resident.torch_stream(self.dev.ctx):
+                X = resident.check_x(X, self.C, self.dev.ctx.device)
+                _, lab = self.dev.infer_device(X, want_proba=False, want_labels=True)
+                if mf:
+                    lab = self.dev.mode_filter_device(lab, mf)
+                return self.dev.ancestry_scores_device(X, lab, weights, effect)
+        _, lab = self.dev.infer(X, want_proba=False, want_labels=True)
+        if mf:
+            lab = self.dev.mode_filter(lab, mf)
+        return self.dev.ancestry_scores(self.dev._x(X), lab, weights, effect)
+
     def phase(self, X, B=None, verbose=False, **gnofix_kw):
         """Gnofix re-phasing (model.py:188-214): -> X_phased (N, C) int, Y_phased (N, W) int.  `gnofix_kw`: gnofix()'s search
         options (check_criterion, max_center_offset, non_lin_s, prob_comp, prior_switch_prob, padding, max_it); the reference's

@@ -553,6 +553,83 @@ class DeviceModel:
                                                         self.A, int(ancestry), dos.data_ptr(), self.C, hap.data_ptr(), self.C))
         return dos, hap
 
+    def ancestry_scores(self, X, labels, weights, effect=None, packed=False):
+        """ancestry-partitioned polygenic scores of X (N, C) int8 (packed=True: the 2-bit rows pack_x returns) under (N, W) labels, on the
+        device (gnx_ancestry_score; gnomix_amd.postprocess.ancestry_scores) -> AncestryScores of numpy arrays.  weights (C,), (C, A) or
+        (C, A, S) float64; effect None (ALT everywhere) or (C,) of 1 (ALT), 0 (REF), 255 (not scored)"""
+        from .postprocess import ancestry_scores
+        return ancestry_scores(self.ctx, X, labels, self.M, self.A, weights, effect, packed=packed, C=self.C)
+
+    def ancestry_scores_device(self, X_t, lab_t, weights, effect=None):
+        """the same on CUDA tensors: X_t int8 (N, C) or the uint8 tensor pack_device returns, lab_t (N, W) int32 with any row stride;
+        weights and effect as numpy arrays or CUDA tensors (gnx_ancestry_score_dev) -> AncestryScores of CUDA tensors"""
+        import ctypes
+        import torch
+        from .postprocess import AncestryScores, score_tables, score_chunks
+        kind, ld, ldl, N = self._allele_device_args(X_t, lab_t)
+        if N % 2:
+            raise ValueError("N must be even (an individual has two haplotype rows)")
+        dev = X_t.device
+        if hasattr(weights, "is_cuda") and (effect is None or hasattr(effect, "is_cuda")):
+            w_t = weights.to(device=dev, dtype=torch.float64)
+            w_t = w_t[:, None].expand(-1, self.A)[:, :, None] if w_t.dim() == 1 else w_t[:, :, None] if w_t.dim() == 2 else w_t
+            if w_t.dim() != 3 or tuple(w_t.shape[:2]) != (self.C, self.A) or w_t.shape[2] < 1:
+                raise ValueError(f"weights must be (C={self.C},), (C, A={self.A}) or (C, A, S >= 1), got {tuple(weights.shape)}")
+            w_t = w_t.contiguous()
+            e_t = torch.ones(self.C, dtype=torch.uint8, device=dev) if effect is None else effect.to(device=dev, dtype=torch.uint8).contiguous()
+            if tuple(e_t.shape) != (self.C,):
+                raise ValueError(f"effect must be (C={self.C},), got {tuple(e_t.shape)}")
+        else:
+            to_host = lambda v: v.cpu().numpy() if hasattr(v, "is_cuda") else v
+            w, eff = score_tables(to_host(weights), None if effect is None else to_host(effect), self.C, self.A)
+            w_t, e_t = torch.from_numpy(w).to(dev), torch.from_numpy(eff).to(dev)
+        S = w_t.shape[2]
+        self._bind_torch_stream()
+        score = torch.zeros((N // 2, self.A, S), dtype=torch.float64, device=dev)
+        ne, ns, nm = (torch.zeros((N // 2, self.A), dtype=torch.int32, device=dev) for _ in range(3))
+        for s0, s1 in score_chunks(S):
+            whole = (s0, s1) == (0, S)
+            wc = w_t if whole else w_t[:, :, s0:s1].contiguous()
+            out = score if whole else torch.zeros((N // 2, self.A, s1 - s0), dtype=torch.float64, device=dev)
+            first = s0 == 0
+            n_bad = ctypes.c_int64(0)
+            self.ctx.check(self.lib.gnx_ancestry_score_dev(self.ctx.h, X_t.data_ptr(), kind, ld, lab_t.data_ptr(), ldl, N, self.C, self.M, self.W, self.A,
+                                                           wc.data_ptr(), s1 - s0, e_t.data_ptr(), out.data_ptr(), ne.data_ptr() if first else None,
+                                                           ns.data_ptr() if first else None, nm.data_ptr() if first else None, 0, 0,
+                                                           ctypes.byref(n_bad)))
+            if not whole:
+                score[:, :, s0:s1] = out
+        return AncestryScores(score, ne, ns, nm)
+
+    def ancestry_scores_gt2(self, G, N, src, labels, weights, effect=None):
+        """ancestry_scores of the parsed query (G, N, src as infer_gt2 takes them) under host labels (N, W): the packed rows are built and
+        scored in HBM, batch of individuals by batch (gnx_ancestry_score_gt2) -> AncestryScores of numpy arrays"""
+        import ctypes
+        from .postprocess import AncestryScores, score_tables, score_chunks
+        G, N, src = self._gt2_args(G, N, src)
+        if N % 2:
+            raise ValueError("N must be even (an individual has two haplotype rows)")
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.shape != (N, self.W):
+            raise ValueError(f"labels must be (N={N}, W={self.W}), got {lab.shape}")
+        w, eff = score_tables(weights, effect, self.C, self.A)
+        S = w.shape[2]
+        score = np.zeros((N // 2, self.A, S))
+        ne, ns, nm = (np.zeros((N // 2, self.A), np.int32) for _ in range(3))
+        for s0, s1 in score_chunks(S):
+            whole = (s0, s1) == (0, S)
+            wc = w if whole else np.ascontiguousarray(w[:, :, s0:s1])
+            out = score if whole else np.zeros((N // 2, self.A, s1 - s0))
+            first = s0 == 0
+            n_bad = ctypes.c_int64(0)
+            self.ctx.check(self.lib.gnx_ancestry_score_gt2(self.h, G.ctypes.data, G.shape[0], G.shape[1], N, src.ctypes.data, lab.ctypes.data,
+                                                           wc.ctypes.data, s1 - s0, eff.ctypes.data, out.ctypes.data,
+                                                           ne.ctypes.data if first else None, ns.ctypes.data if first else None,
+                                                           nm.ctypes.data if first else None, ctypes.byref(n_bad)))
+            if not whole:
+                score[:, :, s0:s1] = out
+        return AncestryScores(score, ne, ns, nm)
+
     def ancestry_assoc_stats(self, X, labels, y, Z=None, use=None, c0=0, c1=None, min_ac=1, check=True):
         """the sufficient statistics of the ancestry-specific association model for the SNPs [c0, c1) (gnx_ancestry_assoc_stats[_dev];
         include/gnomix_hip.h states the blocks) -> gnomix_amd.assoc.AssocStats of numpy arrays.  X (N, C) int8 and labels (N, W) int32 as

@@ -328,6 +328,107 @@ def ancestry_dosage(ctx, X, labels, M, A, ancestry, packed=False, C=None):
     return dos, hap
 
 
+class AncestryScores(collections.namedtuple("AncestryScores", "score n_effect n_scored n_miss")):
+    """what ancestry_scores returns (numpy arrays or CUDA tensors as the rows were).  Individual i is haplotype rows 2 i, 2 i + 1.
+    score (N / 2, A, S) float64: per ancestry a and score s, the sum of weights[c, a, s] over the scored SNPs c and the individual's
+    haplotypes labelled a at c's window that carry the effect allele; n_effect, n_scored, n_miss (N / 2, A) int32: the number of such
+    (haplotype, SNP) pairs, of the pairs with a called genotype (0 or 1) and of those with a missing call"""
+    __slots__ = ()
+
+    def avg(self):
+        """score / n_scored as a float64 (N / 2, A, S) numpy array, NaN where nothing was scored"""
+        score = np.asarray(_to_host(self.score), dtype=np.float64)
+        den = np.asarray(_to_host(self.n_scored), dtype=np.float64)[:, :, None]
+        out = np.full(score.shape, np.nan, dtype=np.float64)
+        np.divide(score, den, out=out, where=np.broadcast_to(den > 0, score.shape))
+        return out
+
+
+def score_tables(weights, effect, C, A):
+    """the weights and effect alleles of ancestry_scores as the device takes them -> (weights (C, A, S) float64 C-contiguous, effect (C,)
+    uint8).  weights: (C,) (one score, the same weight for every ancestry), (C, A) (one score) or (C, A, S); effect: None (ALT
+    everywhere) or (C,) of 1 (ALT), 0 (REF), 255 (not scored)"""
+    w = np.asarray(weights, dtype=np.float64)
+    C, A = int(C), int(A)
+    if w.ndim == 1 and w.shape == (C,):
+        w = np.repeat(w[:, None], A, axis=1)[:, :, None]
+    elif w.ndim == 2 and w.shape == (C, A):
+        w = w[:, :, None]
+    elif not (w.ndim == 3 and w.shape[:2] == (C, A) and w.shape[2] >= 1):
+        raise ValueError(f"weights must be (C={C},), (C, A={A}) or (C, A, S >= 1), got {w.shape}")
+    if effect is None:
+        eff = np.ones(C, np.uint8)
+    else:
+        e = np.asarray(effect)
+        if e.shape != (C,) or not np.all((e == 0) | (e == 1) | (e == 255)):
+            raise ValueError(f"effect must be (C={C},) of 1 (ALT), 0 (REF) or 255 (not scored)")
+        eff = e.astype(np.uint8)
+    return np.ascontiguousarray(w), eff
+
+
+def score_chunks(S):
+    """the column ranges [s0, s1) in which a table of S scores is served: at most GNX_SCORE_MAX_S per call of the library"""
+    step = _lib.GNX_SCORE_MAX_S
+    return [(s0, min(s0 + step, S)) for s0 in range(0, S, step)]
+
+
+def ancestry_scores(ctx, X_or_packed, labels, M, A, weights, effect=None, packed=False, C=None, debug_windows_per_block=0,
+                    debug_rows_per_pass=0):
+    """ancestry-partitioned polygenic scores on the device (gnx_ancestry_score; include/gnomix_hip.h states the contract and the
+    summation order): X (N, C) int8 in the model's coding, or with packed=True the 2-bit rows of DeviceModel.pack_x and C; labels (N, W)
+    in [0, A); weights and effect as score_tables takes them -> AncestryScores of numpy arrays.  More than GNX_SCORE_MAX_S scores are
+    served in chunks; every score's bits are those of a call with that score alone."""
+    import ctypes
+    rows, kind, C = _allele_rows(X_or_packed, packed, C)
+    N = rows.shape[0]
+    if N % 2:
+        raise ValueError("N must be even (an individual has two haplotype rows)")
+    lab = _allele_labels(labels, N)
+    W = lab.shape[1]
+    w, eff = score_tables(weights, effect, C, A)
+    S = w.shape[2]
+    score = np.zeros((N // 2, int(A), S))
+    ne, ns, nm = (np.zeros((N // 2, int(A)), np.int32) for _ in range(3))
+    for s0, s1 in score_chunks(S):
+        wc = w if (s0, s1) == (0, S) else np.ascontiguousarray(w[:, :, s0:s1])
+        out = score if (s0, s1) == (0, S) else np.zeros((N // 2, int(A), s1 - s0))
+        first = s0 == 0
+        n_bad = ctypes.c_int64(0)
+        ctx.check(ctx.lib.gnx_ancestry_score(ctx.h, rows.ctypes.data, kind, rows.shape[1], lab.ctypes.data, W, N, C, int(M), W, int(A),
+                                             wc.ctypes.data, s1 - s0, eff.ctypes.data, out.ctypes.data, ne.ctypes.data if first else None,
+                                             ns.ctypes.data if first else None, nm.ctypes.data if first else None,
+                                             int(debug_windows_per_block), int(debug_rows_per_pass), ctypes.byref(n_bad)))
+        if out is not score:
+            score[:, :, s0:s1] = out
+    return AncestryScores(score, ne, ns, nm)
+
+
+def write_sscore(prefix, scores, names, populations, samples):
+    """<prefix>.sscore.tsv from an AncestryScores: one header line, then one line per individual: sample, then per population
+    <pop>.n_scored, <pop>.n_effect, <pop>.n_miss, then per score <name>.<pop> for every population and <name>.total (their sum in
+    population order), tab-separated.  Floats are written with repr, the shortest text that reads back to the same float64."""
+    score = np.asarray(_to_host(scores.score), dtype=np.float64)
+    ne, ns, nm = (np.asarray(_to_host(v)) for v in (scores.n_effect, scores.n_scored, scores.n_miss))
+    n_ind, A, S = len(samples), len(populations), len(names)
+    if score.shape != (n_ind, A, S) or ne.shape != (n_ind, A):
+        raise ValueError(f"scores must be ({n_ind} individuals, {A} populations, {S} scores), got {score.shape}")
+    num = lambda v: repr(float(v))
+    with open(prefix + ".sscore.tsv", "w") as f:
+        f.write("sample\t" + "\t".join("%s.n_scored\t%s.n_effect\t%s.n_miss" % (p, p, p) for p in populations) + "\t" +
+                "\t".join("\t".join(["%s.%s" % (n, p) for p in populations] + ["%s.total" % n]) for n in names) + "\n")
+        for i in range(n_ind):
+            cells = [str(samples[i])]
+            for a in range(A):
+                cells += [str(int(ns[i, a])), str(int(ne[i, a])), str(int(nm[i, a]))]
+            for s in range(S):
+                total = 0.0
+                for a in range(A):
+                    total += float(score[i, a, s])
+                    cells.append(num(score[i, a, s]))
+                cells.append(num(total))
+            f.write("\t".join(cells) + "\n")
+
+
 def write_afreq(prefix, chm, snp_pos, M, W, counts, populations):
     """<prefix>.afreq.tsv: one header line, then one line per model SNP in model order: chm, pos, window (min(c // M, W - 1)), then per
     population <pop>.n_obs, <pop>.n_alt, <pop>.freq (n_alt / n_obs with six decimals, nan when n_obs == 0), tab-separated"""

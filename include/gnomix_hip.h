@@ -1004,6 +1004,55 @@ int gnx_ancestry_assoc_logit_gt2(gnx_model* m, const uint8_t* G, int64_t n_varia
                                  int64_t c0, int64_t c1, double tol, int32_t max_iter, double* snp_f64, int32_t* snp_i32, double* theta,
                                  double* win_f64, int32_t* win_i32, int64_t* n_bad);
 
+/* ---- ancestry-partitioned polygenic scores ("partial PRS"), fused on the device (csrc/summary/k_ancestry_score.hip) -----
+ * INPUTS.  rows, row_kind (GNX_ROWS_INT8 / GNX_ROWS_PACKED2), the codes (0 = REF, 1 = ALT, anything else = a missing call), labels (N, W)
+ *   int32, ld_rows, ld_labels, win(c) = min(c / M, W - 1) and the requirement M W <= C are EXACTLY gnx_ancestry_allele_counts'.  Also:
+ *     weights (C, A, S) float64, C-contiguous, 1 <= S <= GNX_SCORE_MAX_S (a caller with more scores calls in chunks of S);
+ *     effect (C,) uint8: 1 = the effect allele of SNP c is ALT (code 1), 0 = it is REF (code 0), 255 = the SNP is not scored.
+ * OUTPUTS.  Individual i is haplotype rows 2 i, 2 i + 1.  Every output is OVERWRITTEN (one owner per value, plain stores) and any may be
+ *   NULL.  With "h of i" = h in {2 i, 2 i + 1}:
+ *     score    (N / 2, A, S) float64   sum of weights[c, a, s] over the SNPs c with effect[c] != 255 and the h of i with
+ *                                      labels[h, win(c)] == a and X[h, c] == effect[c]
+ *     n_effect (N / 2, A) int32        the number of such (h, c) pairs
+ *     n_scored (N / 2, A) int32        the pairs with labels[h, win(c)] == a, effect[c] != 255 and X[h, c] in {0, 1}: the denominator
+ *                                      of an averaged score
+ *     n_miss   (N / 2, A) int32        the pairs with labels[h, win(c)] == a, effect[c] != 255 and a missing call
+ * SUMMATION ORDER.  The integers are exact.  The float64 sums are taken in ONE order, a function of (C, M, W) alone, in two levels:
+ *     1. per haplotype h and window k with a = labels[h, k] in [0, A): a partial p[h, k, s] starts at +0.0 and adds weights[c, a, s] over
+ *        the SNPs c of window k with effect[c] != 255 and X[h, c] == effect[c], in ASCENDING c;
+ *     2. per (i, a, s): the score starts at +0.0 and adds, in ASCENDING k, first p[2 i, k, s] if labels[2 i, k] == a, then
+ *        p[2 i + 1, k, s] if labels[2 i + 1, k] == a.
+ *   One rounding per add, no fused multiply-add, terms that do not apply are skipped.  The order, and so every bit of score, does not
+ *   depend on N (an individual's values are those of a call with that individual alone), on the grid or the tile sizes, on the row
+ *   form, on the file path's batches or on the debug arguments.
+ *   debug_windows_per_block / debug_rows_per_pass: 0 in production.  > 0 (tests): the windows one workgroup walks, and the rows whose
+ *   partials share the workspace at a time (rounded down to a multiple of 256, at least 256).
+ * GNX_EINVAL before the launch, nothing written: the conditions of gnx_ancestry_allele_counts (N < 0 or >= 2^31, C < 1, A < 1, M < 1,
+ *   W < 1, M W > C, a stride too small, an unknown row_kind, a negative debug argument), odd N, S < 1, a null weights or effect; an
+ *   effect byte outside {0, 1, 255}; a weight that is not finite at a SNP with effect[c] != 255 (a small checking pass over the device
+ *   copies counts both and the count is read back: the message names it).
+ * GNX_EUNSUPPORTED, nothing written: A > GNX_ALLELE_MAX_A, S > GNX_SCORE_MAX_S, C >= 2^30 (the counts are int32).
+ * GNX_EINVAL after the launch, *n_bad set (0 otherwise; n_bad may be NULL): labels outside [0, A) were met, *n_bad of them.  Labels are only
+ *   compared, never used as an index: such a haplotype counts for no ancestry at that window; every output is as stated.
+ * N == 0: nothing is launched, nothing is written.  Every form synchronises the context stream twice (the checking pass, the labels).
+ * In the _dev form every pointer but n_bad is a device pointer.
+ * gnx_ancestry_score_gt2: the file path's form.  G, n_variants, ldg, src as gnx_infer_gt2 takes them; the packed rows are built in HBM
+ *   batch by batch as gnx_ancestry_allele_counts_gt2 builds them and scored against the HOST labels (N, W) (contiguous rows) with the
+ *   model's C, M, W and A.  A batch holds whole individuals, so the outputs equal the matrix path's bit for bit whatever GNX_HOST_BATCH
+ *   is.  A model SNP the query lacks is missing in every row.  Also GNX_EINVAL before the launch: a column map entry outside G. */
+#define GNX_SCORE_MAX_S 16
+int gnx_ancestry_score_dev(gnx_ctx* ctx, const void* d_rows, int row_kind, int64_t ld_rows, const int32_t* d_labels, int64_t ld_labels,
+                           int64_t N, int64_t C, int64_t M, int64_t W, int32_t A, const double* d_weights, int32_t S, const uint8_t* d_effect,
+                           double* d_score, int32_t* d_n_effect, int32_t* d_n_scored, int32_t* d_n_miss, int64_t debug_windows_per_block,
+                           int64_t debug_rows_per_pass, int64_t* n_bad);
+int gnx_ancestry_score(gnx_ctx* ctx, const void* rows, int row_kind, int64_t ld_rows, const int32_t* labels, int64_t ld_labels, int64_t N,
+                       int64_t C, int64_t M, int64_t W, int32_t A, const double* weights, int32_t S, const uint8_t* effect, double* score,
+                       int32_t* n_effect, int32_t* n_scored, int32_t* n_miss, int64_t debug_windows_per_block, int64_t debug_rows_per_pass,
+                       int64_t* n_bad);
+int gnx_ancestry_score_gt2(gnx_model* m, const uint8_t* G, int64_t n_variants, int64_t ldg, int64_t N, const int32_t* src,
+                           const int32_t* labels, const double* weights, int32_t S, const uint8_t* effect, double* score, int32_t* n_effect,
+                           int32_t* n_scored, int32_t* n_miss, int64_t* n_bad);
+
 /* per-kernel device time, measured with hipEvents on the context stream around every launch */
 int gnx_profile_enable(gnx_ctx* ctx, int on);
 int gnx_profile_reset(gnx_ctx* ctx);
