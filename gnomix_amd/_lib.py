@@ -261,6 +261,11 @@ SYMBOLS = {
     "gnx_ancestry_score": (C.c_int, [_VP, _VP, _I, _I64, _VP, _I64, _I64, _I64, _I64, _I64, C.c_int32, _VP, C.c_int32, _VP, _VP, _VP, _VP, _VP,
                                      _I64, _I64, C.POINTER(_I64)]),
     "gnx_ancestry_score_gt2": (C.c_int, [_VP, _VP, _I64, _I64, _I64, _VP, _VP, _VP, C.c_int32, _VP, _VP, _VP, _VP, _VP, C.POINTER(_I64)]),
+    "gnx_ancestry_pair_counts_dev": (C.c_int, [_VP, _VP, _I, _I64, _VP, _I64, _I64, _I64, _I64, _I64, C.c_int32, C.c_int32, _I64, _I64, _VP, _VP, _VP,
+                                               _I64, _I64, C.POINTER(_I64)]),
+    "gnx_ancestry_pair_counts": (C.c_int, [_VP, _VP, _I, _I64, _VP, _I64, _I64, _I64, _I64, _I64, C.c_int32, C.c_int32, _I64, _I64, _VP, _VP, _VP,
+                                           _I64, _I64, C.POINTER(_I64)]),
+    "gnx_ancestry_pair_counts_gt2": (C.c_int, [_VP, _VP, _I64, _I64, _I64, _VP, _VP, C.c_int32, _I64, _I64, _VP, _VP, _VP, _I64, C.POINTER(_I64)]),
     # include/gnomix_io.h: the file side
     "gnx_io_last_error": (C.c_char_p, []),
     "gnx_vcf_read": (C.c_int, [_VP, C.c_char_p, C.c_char_p, _I, C.POINTER(_VP)]),

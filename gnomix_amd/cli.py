@@ -134,7 +134,8 @@ class _Prefetch:
 
 def run_inference(base_args, model, snp_level=False, bed_file_output=False, verbose=False, timings=None, query=None, devices=None,
                   global_ancestry_output=False, ancestry_allele_freq_output=False, ancestry_assoc_output=False, phenotype_file=None,
-                  ancestry_assoc_model="linear", ancestry_score_output=False, score_file=None):
+                  ancestry_assoc_model="linear", ancestry_score_output=False, score_file=None, ancestry_mds_output=False,
+                  ancestry_mds_components=None, ancestry_mds_min_sites=None):
     """gnomix.py:37-100 with the HIP model behind the same steps.  The query never becomes an (N, C) host matrix: the library
     parses the text into 2-bit rows (gnx_vcf_read), `column_map` keeps vcf_to_npy's bookkeeping (SNP intersection, REF flips,
     absent SNPs) as one int32 per model SNP, the GPU builds X and runs base + smoother (or Gnofix) on it, and the library
@@ -161,7 +162,13 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
     with the header `chm  pos  effect_allele` and weight columns NAME or NAME:POP, score.read_score_file): query_results.sscore.tsv as
     well, the ancestry-partitioned polygenic scores of every individual, summed on the model's own GPU from the query's 2-bit rows
     and the labels the .msp gets (gnx_ancestry_score_gt2).  Not with phase=True (ValueError before any work), for the
-    same reason."""
+    same reason.
+    `ancestry_mds_output` (config key inference.ancestry_mds_output, off unless set; inference.ancestry_mds_components, default 4, and
+    inference.ancestry_mds_min_sites, default 1000, optional): query_results.asmds.tsv as well, the ancestry-specific MDS of every
+    ancestry: the pair count tables from the model's own GPU, from the query's 2-bit rows and the labels the .msp gets
+    (gnx_ancestry_pair_counts_gt2), the embedding on the host (gnomix_amd.asmds).  An ancestry with fewer than
+    components + 1 individuals kept gets a header line and no rows.  Not with phase=True (ValueError before any work), for the same
+    reason."""
     from time import perf_counter as clock
     from . import postprocess as pp
     from . import vcfio
@@ -180,6 +187,13 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
                          "use HipGnomix.phase followed by HipGnomix.ancestry_scores")
     if ancestry_score_output and not score_file:
         raise ValueError("inference.ancestry_score_output needs inference.score_file (a TSV: chm, pos, effect_allele, then weight columns)")
+    if ancestry_mds_output and base_args["phase"]:
+        raise ValueError("inference.ancestry_mds_output with phase=True: the phased haplotypes are not kept on this path; "
+                         "use HipGnomix.phase followed by HipGnomix.ancestry_mds")
+    mds_k = 4 if ancestry_mds_components is None else int(ancestry_mds_components)
+    mds_sites = 1000 if ancestry_mds_min_sites is None else int(ancestry_mds_min_sites)
+    if ancestry_mds_output and (mds_k < 1 or mds_sites < 1):
+        raise ValueError("inference.ancestry_mds_components and inference.ancestry_mds_min_sites must be >= 1")
     query_file, chm, output_path = base_args["query_file"], base_args["chm"], base_args["output_basename"]
     T = timings if timings is not None else {}
     if verbose:
@@ -211,7 +225,8 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
     try:
         return _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out, T, t0, snp_level, bed_file_output, verbose,
                               global_ancestry_output, ancestry_allele_freq_output, ancestry_assoc_output, phenotype_file, ancestry_assoc_model,
-                              ancestry_score_output=ancestry_score_output, score_file=score_file)
+                              ancestry_score_output=ancestry_score_output, score_file=score_file,
+                              ancestry_mds=(mds_k, mds_sites) if ancestry_mds_output else None)
     finally:
         if own_group is not None:
             own_group.close()
@@ -219,7 +234,7 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
 
 def _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out, T, t0, snp_level, bed_file_output, verbose,
                    global_ancestry_output=False, ancestry_allele_freq_output=False, ancestry_assoc_output=False, phenotype_file=None,
-                   ancestry_assoc_model="linear", ancestry_score_output=False, score_file=None):
+                   ancestry_assoc_model="linear", ancestry_score_output=False, score_file=None, ancestry_mds=None):
     from time import perf_counter as clock
     from . import postprocess as pp
     from . import vcfio
@@ -296,6 +311,14 @@ def _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out,
         result = model.dev.ancestry_scores_gt2(vcf.gt2, N, src, labels, weights, effect)         # one GPU: the model's own
         pp.write_sscore(out_prefix, result, names, model.population_order, [str(s) for s in samples])
         T["write_sscore"] = clock() - t0
+    if ancestry_mds is not None:
+        t0 = clock()
+        from . import asmds
+        k, min_sites = ancestry_mds
+        results = [asmds.ancestry_mds(model.dev.ancestry_pair_counts_gt2(vcf.gt2, N, src, labels, a), k=k, min_sites=min_sites)
+                   for a in range(model.A)]                                                      # one GPU: the model's own
+        pp.write_asmds(out_prefix, results, model.population_order, [str(s) for s in samples])
+        T["write_asmds"] = clock() - t0
     return out_prefix
 
 
@@ -365,7 +388,9 @@ def main(argv=None):
                       ancestry_allele_freq_output=bool(inf.get("ancestry_allele_freq_output")),
                       ancestry_assoc_output=bool(inf.get("ancestry_assoc_output")), phenotype_file=inf.get("phenotype_file"),
                       ancestry_assoc_model=inf.get("ancestry_assoc_model") or "linear",
-                      ancestry_score_output=bool(inf.get("ancestry_score_output")), score_file=inf.get("score_file"))
+                      ancestry_score_output=bool(inf.get("ancestry_score_output")), score_file=inf.get("score_file"),
+                      ancestry_mds_output=bool(inf.get("ancestry_mds_output")), ancestry_mds_components=inf.get("ancestry_mds_components"),
+                      ancestry_mds_min_sites=inf.get("ancestry_mds_min_sites"))
         if os.environ.get("GNX_CLI_TIMING"):
             T["since_process_start"] = _since_process_start()
             sys.stderr.write("gnomix_amd timings (s): " + ", ".join("%s %.3f" % kv for kv in T.items()) + "\n")
@@ -529,7 +554,9 @@ def train_main(argv):
                       ancestry_allele_freq_output=bool(inf.get("ancestry_allele_freq_output")),
                       ancestry_assoc_output=bool(inf.get("ancestry_assoc_output")), phenotype_file=inf.get("phenotype_file"),
                       ancestry_assoc_model=inf.get("ancestry_assoc_model") or "linear",
-                      ancestry_score_output=bool(inf.get("ancestry_score_output")), score_file=inf.get("score_file"))
+                      ancestry_score_output=bool(inf.get("ancestry_score_output")), score_file=inf.get("score_file"),
+                      ancestry_mds_output=bool(inf.get("ancestry_mds_output")), ancestry_mds_components=inf.get("ancestry_mds_components"),
+                      ancestry_mds_min_sites=inf.get("ancestry_mds_min_sites"))
     return 0
 
 

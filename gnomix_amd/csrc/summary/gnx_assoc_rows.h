@@ -1,6 +1,6 @@
 // summary/gnx_assoc_rows.h — what the files of this folder share about rows and windows (k_ancestry_assoc.hip, the linear model's
-// sufficient statistics; k_ancestry_assoc_logit.hip, the logistic fits; k_allele_counts.hip and k_ancestry_score.hip, which read a
-// row 16 columns at a time): one definition of each.
+// sufficient statistics; k_ancestry_assoc_logit.hip, the logistic fits; k_allele_counts.hip, k_ancestry_score.hip and
+// k_ancestry_pairs.hip, which read a row 16 columns at a time): one definition of each.
 #pragma once
 #include "../gnx_internal.h"
 
@@ -47,6 +47,13 @@ __device__ __forceinline__ uint32_t as_fields16(const uint8_t* __restrict__ row,
     }
     return w;
   }
+}
+
+// the even bits of the fields lo .. hi - 1 of a group of 16 (0 <= lo < 16, lo < hi <= 16).  Shared by k_ancestry_score.hip and
+// k_ancestry_pairs.hip.
+__device__ __forceinline__ uint32_t as_range16(int lo, int hi) {
+  const uint32_t below_hi = hi >= 16 ? 0xFFFFFFFFu : ((1u << (2 * hi)) - 1u);
+  return below_hi & ~((1u << (2 * lo)) - 1u) & 0x55555555u;
 }
 
 inline int64_t as_min_row_bytes(int row_kind, int64_t C) { return row_kind == GNX_ROWS_PACKED2 ? (C + 3) / 4 : C; }

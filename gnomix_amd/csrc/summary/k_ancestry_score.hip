@@ -68,12 +68,6 @@ __global__ __launch_bounds__(256) void k_ancestry_score_check(const double* __re
   if (bad_w) atomicAdd(bad + 2, (unsigned long long)bad_w);
 }
 
-// the even bits of the fields lo .. hi - 1 of a group (0 <= lo < 16, lo < hi <= 16)
-__device__ __forceinline__ uint32_t sc_range(int lo, int hi) {
-  const uint32_t below_hi = hi >= 16 ? 0xFFFFFFFFu : ((1u << (2 * hi)) - 1u);
-  return below_hi & ~((1u << (2 * lo)) - 1u) & SC_EVEN;
-}
-
 // rows, lab: of the pass's first row; n rows in the pass.  Workspace of the pass: part [W][S][n] float64, cnt [W][3][n] int32 (effect,
 // scored, missing), lab8 [W][n] bytes.
 template <int KIND, int SB>
@@ -155,7 +149,7 @@ __global__ __launch_bounds__(SC_ROWS) void k_ancestry_score_partial(const uint8_
             const int gi = (int)((g0 - t0) >> 4);
             const uint32_t f = xt[tid * T::LD + gi];
             const int lo = (int)(c > g0 ? c - g0 : 0), hi = (int)(se - g0 < 16 ? se - g0 : 16);
-            const uint32_t sc = msc[gi] & sc_range(lo, hi);
+            const uint32_t sc = msc[gi] & as_range16(lo, hi);
             const uint32_t miss = (f >> 1) & SC_EVEN, alt = f & SC_EVEN & ~miss;
             const uint32_t mt = sc & ~miss & ~(alt ^ mef[gi]);
             nm += __popc(sc & miss);

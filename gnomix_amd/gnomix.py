@@ -296,6 +296,34 @@ class HipGnomix:
             lab = self.dev.mode_filter(lab, mf)
         return self.dev.ancestry_scores(self.dev._x(X), lab, weights, effect)
 
+    def ancestry_pair_counts(self, X, ancestry, snp_range=None):
+        """the pairwise count tables of one ancestry (index into population_order) of X under the labels predict returns (mode_filter
+        applied when set) -> asmds.PairCounts(DD, DO, OO), (N / 2, N / 2) int32 each: sums over the SNPs of d[i] d[j], d[i] o[j] and
+        o[i] o[j], o = an individual's haplotypes labelled `ancestry` with an observed call, d = those of them that are ALT.  One fused
+        pass on the int8 matrix cores (k_ancestry_pairs); with a CUDA tensor neither X nor the labels leave HBM and CUDA tensors come back."""
+        mf = self.smooth.mode_filter
+        if resident.is_cuda(X):
+            with resident.torch_stream(self.dev.ctx):
+                X = resident.check_x(X, self.C, self.dev.ctx.device)
+                _, lab = self.dev.infer_device(X, want_proba=False, want_labels=True)
+                if mf:
+                    lab = self.dev.mode_filter_device(lab, mf)
+                return self.dev.ancestry_pair_counts_device(X, lab, ancestry, snp_range)
+        _, lab = self.dev.infer(X, want_proba=False, want_labels=True)
+        if mf:
+            lab = self.dev.mode_filter(lab, mf)
+        return self.dev.ancestry_pair_counts(self.dev._x(X), lab, ancestry, snp_range)
+
+    def ancestry_mds(self, X, ancestry, k=4, min_sites=1000, min_pair_sites=None):
+        """ancestry-specific MDS: the structure inside one ancestry component.  ancestry_pair_counts, then on the host (gnomix_amd.asmds)
+        the individuals with at least min_sites compared sites of their own and min_pair_sites (default: min_sites) with every other
+        kept individual (asmds.select), their allele-sharing distances mism / comp and classical MDS with k components ->
+        asmds.AncestryMDS(coords (n_kept, k), eigenvalues, explained, kept, n_sites), or None when fewer than k + 1 individuals are kept"""
+        from . import asmds
+        counts = self.ancestry_pair_counts(X, ancestry)
+        counts = asmds.PairCounts(*(t.cpu().numpy() if hasattr(t, "is_cuda") else t for t in counts))
+        return asmds.ancestry_mds(counts, k=k, min_sites=min_sites, min_pair_sites=min_pair_sites)
+
     def phase(self, X, B=None, verbose=False, **gnofix_kw):
         """Gnofix re-phasing (model.py:188-214): -> X_phased (N, C) int, Y_phased (N, W) int.  `gnofix_kw`: gnofix()'s search
         options (check_criterion, max_center_offset, non_lin_s, prob_comp, prior_switch_prob, padding, max_it); the reference's

@@ -630,6 +630,52 @@ class DeviceModel:
                 score[:, :, s0:s1] = out
         return AncestryScores(score, ne, ns, nm)
 
+    def ancestry_pair_counts(self, X, labels, ancestry, snp_range=None, packed=False):
+        """the pairwise count tables DD, DO, OO of one ancestry over the SNPs snp_range = (c0, c1) (None: all), X (N, C) int8
+        (packed=True: the 2-bit rows pack_x returns) under (N, W) labels, on the int8 matrix cores (gnx_ancestry_pair_counts;
+        gnomix_amd.postprocess.pair_counts) -> asmds.PairCounts of (N / 2, N / 2) int32 arrays"""
+        from .postprocess import pair_counts
+        return pair_counts(self.ctx, X, labels, self.M, self.A, ancestry, snp_range, packed=packed, C=self.C)
+
+    def ancestry_pair_counts_device(self, X_t, lab_t, ancestry, snp_range=None, debug_snps_per_block=0):
+        """the same on CUDA tensors: X_t int8 (N, C) or the uint8 tensor pack_device returns, lab_t (N, W) int32 with any row stride
+        (gnx_ancestry_pair_counts_dev) -> asmds.PairCounts of (N / 2, N / 2) int32 CUDA tensors"""
+        import ctypes
+        import torch
+        from .asmds import PairCounts
+        kind, ld, ldl, N = self._allele_device_args(X_t, lab_t)
+        if N % 2:
+            raise ValueError("N must be even (an individual has two haplotype rows)")
+        c0, c1 = (0, self.C) if snp_range is None else (int(snp_range[0]), int(snp_range[1]))
+        n = N // 2
+        self._bind_torch_stream()
+        DD, DO, OO = (torch.zeros((n, n), dtype=torch.int32, device=X_t.device) for _ in range(3))
+        n_bad = ctypes.c_int64(0)
+        self.ctx.check(self.lib.gnx_ancestry_pair_counts_dev(self.ctx.h, X_t.data_ptr(), kind, ld, lab_t.data_ptr(), ldl, N, self.C, self.M, self.W,
+                                                             self.A, int(ancestry), c0, c1, DD.data_ptr(), DO.data_ptr(), OO.data_ptr(), n,
+                                                             int(debug_snps_per_block), ctypes.byref(n_bad)))
+        return PairCounts(DD, DO, OO)
+
+    def ancestry_pair_counts_gt2(self, G, N, src, labels, ancestry, snp_range=None):
+        """ancestry_pair_counts of the parsed query (G, N, src as infer_gt2 takes them) under host labels (N, W): the whole packed matrix is
+        built in HBM and the kernel runs once (gnx_ancestry_pair_counts_gt2) -> asmds.PairCounts of numpy arrays"""
+        import ctypes
+        from .asmds import PairCounts
+        G, N, src = self._gt2_args(G, N, src)
+        if N % 2:
+            raise ValueError("N must be even (an individual has two haplotype rows)")
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.shape != (N, self.W):
+            raise ValueError(f"labels must be (N={N}, W={self.W}), got {lab.shape}")
+        c0, c1 = (0, self.C) if snp_range is None else (int(snp_range[0]), int(snp_range[1]))
+        n = N // 2
+        DD, DO, OO = (np.zeros((n, n), np.int32) for _ in range(3))
+        n_bad = ctypes.c_int64(0)
+        self.ctx.check(self.lib.gnx_ancestry_pair_counts_gt2(self.h, G.ctypes.data, G.shape[0], G.shape[1], N, src.ctypes.data, lab.ctypes.data,
+                                                             int(ancestry), c0, c1, DD.ctypes.data, DO.ctypes.data, OO.ctypes.data, n,
+                                                             ctypes.byref(n_bad)))
+        return PairCounts(DD, DO, OO)
+
     def ancestry_assoc_stats(self, X, labels, y, Z=None, use=None, c0=0, c1=None, min_ac=1, check=True):
         """the sufficient statistics of the ancestry-specific association model for the SNPs [c0, c1) (gnx_ancestry_assoc_stats[_dev];
         include/gnomix_hip.h states the blocks) -> gnomix_amd.assoc.AssocStats of numpy arrays.  X (N, C) int8 and labels (N, W) int32 as

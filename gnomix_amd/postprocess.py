@@ -429,6 +429,61 @@ def write_sscore(prefix, scores, names, populations, samples):
             f.write("\t".join(cells) + "\n")
 
 
+def pair_counts(ctx, X_or_packed, labels, M, A, ancestry, snp_range=None, packed=False, C=None, debug_snps_per_block=0, check=True):
+    """ancestry-specific pairwise counts on the device (gnx_ancestry_pair_counts; include/gnomix_hip.h states the tables): X (N, C) int8
+    in the model's coding, or with packed=True the 2-bit rows of DeviceModel.pack_x and C; labels (N, W); snp_range (c0, c1), None = every
+    SNP -> asmds.PairCounts of (N / 2, N / 2) int32 arrays.  check=False: labels outside [0, A) do not raise (they count for no ancestry)"""
+    import ctypes
+    from .asmds import PairCounts
+    rows, kind, C = _allele_rows(X_or_packed, packed, C)
+    N = rows.shape[0]
+    if N % 2:
+        raise ValueError("N must be even (an individual has two haplotype rows)")
+    lab = _allele_labels(labels, N)
+    W = lab.shape[1]
+    c0, c1 = (0, C) if snp_range is None else (int(snp_range[0]), int(snp_range[1]))
+    n = N // 2
+    DD, DO, OO = (np.zeros((n, n), np.int32) for _ in range(3))
+    n_bad = ctypes.c_int64(0)
+    rc = ctx.lib.gnx_ancestry_pair_counts(ctx.h, rows.ctypes.data, kind, rows.shape[1], lab.ctypes.data, W, N, C, int(M), W, int(A), int(ancestry),
+                                          c0, c1, DD.ctypes.data, DO.ctypes.data, OO.ctypes.data, n, int(debug_snps_per_block), ctypes.byref(n_bad))
+    if check or not n_bad.value:
+        ctx.check(rc)
+    return PairCounts(DD, DO, OO)
+
+
+def write_asmds(prefix, results, population_order, samples):
+    """<prefix>.asmds.tsv from the ancestry-specific MDS of every ancestry: results[a] is an asmds.AncestryMDS over the len(samples)
+    individuals (kept = the indices embedded, n_sites = their OO[i, i]) or None (fewer than k + 1 individuals kept: the ancestry gets
+    its header line and no rows).  One block per ancestry in population order: a header line `sample  population  n_sites  kept  PC1..PCk`,
+    then one line per individual; a dropped individual has kept = 0, n_sites NA and NA coordinates.  Floats are written with repr, the
+    shortest text that reads back to the same float64."""
+    if len(results) != len(population_order):
+        raise ValueError(f"one result per population: {len(results)} results, {len(population_order)} populations")
+    ks = {np.asarray(r.coords).shape[1] for r in results if r is not None}
+    if len(ks) > 1:
+        raise ValueError(f"the embeddings have different numbers of components: {sorted(ks)}")
+    k = ks.pop() if ks else 0
+    head = "sample\tpopulation\tn_sites\tkept" + "".join("\tPC%d" % (q + 1) for q in range(k)) + "\n"
+    with open(prefix + ".asmds.tsv", "w") as f:
+        for pop, r in zip(population_order, results):
+            f.write(head)
+            if r is None:
+                continue
+            coords = np.asarray(r.coords, dtype=np.float64)
+            kept = np.arange(len(samples)) if r.kept is None else np.asarray(r.kept)
+            if coords.shape[0] != kept.shape[0] or (kept.size and kept.max() >= len(samples)):
+                raise ValueError(f"{pop}: {coords.shape[0]} embedded rows, {kept.shape[0]} kept indices, {len(samples)} samples")
+            row_of = {int(i): q for q, i in enumerate(kept)}
+            for i, smp in enumerate(samples):
+                q = row_of.get(i)
+                if q is None:
+                    f.write("%s\t%s\tNA\t0%s\n" % (smp, pop, "\tNA" * k))
+                else:
+                    sites = "NA" if r.n_sites is None else str(int(r.n_sites[q]))
+                    f.write("%s\t%s\t%s\t1\t%s\n" % (smp, pop, sites, "\t".join(repr(float(v)) for v in coords[q])))
+
+
 def write_afreq(prefix, chm, snp_pos, M, W, counts, populations):
     """<prefix>.afreq.tsv: one header line, then one line per model SNP in model order: chm, pos, window (min(c // M, W - 1)), then per
     population <pop>.n_obs, <pop>.n_alt, <pop>.freq (n_alt / n_obs with six decimals, nan when n_obs == 0), tab-separated"""

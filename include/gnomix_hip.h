@@ -1053,6 +1053,50 @@ int gnx_ancestry_score_gt2(gnx_model* m, const uint8_t* G, int64_t n_variants, i
                            const int32_t* labels, const double* weights, int32_t S, const uint8_t* effect, double* score, int32_t* n_effect,
                            int32_t* n_scored, int32_t* n_miss, int64_t* n_bad);
 
+/* ---- ancestry-specific pairwise counts on the int8 matrix cores (csrc/summary/k_ancestry_pairs.hip) ----------------------
+ * INPUTS.  rows, row_kind, the codes, labels (N, W) int32, ld_rows, ld_labels, M, W, A, win(c) = min(c / M, W - 1) and the requirement
+ *   M W <= C are EXACTLY gnx_ancestry_allele_counts'.  The n = N / 2 individuals are the haplotype rows 2 i, 2 i + 1.  For ONE ancestry
+ *   `ancestry`, individual i and SNP c:
+ *     o[i, c] = how many of the two haplotypes h have labels[h, win(c)] == ancestry AND an observed call (code 0 or 1)      0..2
+ *               (NOT gnx_ancestry_dosage's hapcount, which also counts the missing calls)
+ *     d[i, c] = how many of those haplotypes have code 1                                                                   0..o[i, c]
+ * OUTPUTS.  Over the SNP range [c0, c1) three (n, n) int32 tables, rows ld >= n ELEMENTS apart, OVERWRITTEN (the n columns of the n rows;
+ *   what lies between n and ld is not touched); any may be NULL:
+ *     DD[i, j] = sum_c d[i, c] d[j, c]   (symmetric)
+ *     DO[i, j] = sum_c d[i, c] o[j, c]   (NOT symmetric)
+ *     OO[i, j] = sum_c o[i, c] o[j, c]   (symmetric)
+ *   Every term lies in 0..4, so int32 is exact while 4 (c1 - c0) < 2^31.  All device arithmetic is integer: the tables do not depend on
+ *   the grid, the tile sizes, the row form or the debug argument, and the tables of a partition of a range add up to the range's.
+ *   For i != j the caller derives mism[i, j] = DO[i, j] + DO[j, i] - 2 DD[i, j], the mismatching pairs of ancestry-labelled haplotypes one
+ *   from i and one from j, comp[i, j] = OO[i, j], the pairs compared, and the allele-sharing distance mism / comp (gnomix_amd/asmds.py).
+ *   debug_snps_per_block: 0 in production (the split of the SNP range over workgroups is taken from n and c1 - c0).  > 0 (tests): the
+ *   SNPs one workgroup walks, rounded up to the kernel's chunk of 128.
+ * GNX_EINVAL before any launch, nothing written: the conditions of gnx_ancestry_allele_counts (N < 0 or >= 2^31, C < 1, A < 1, M < 1,
+ *   W < 1, M W > C, a stride too small, an unknown row_kind), odd N, ancestry outside [0, A), c0 < 0, c1 <= c0, c1 > C, ld < N / 2, a
+ *   negative debug argument.
+ * GNX_EUNSUPPORTED, nothing written: A > GNX_ALLELE_MAX_A, c1 - c0 >= 2^29, more than 2^31 - 1 workgroups (tile pairs x SNP segments).
+ *   The index arithmetic is 64-bit throughout: there is no limit on N / 2 other than the tables' size.
+ * GNX_EINVAL after the launch, *n_bad set (0 otherwise; n_bad may be NULL): labels outside [0, A) were met in the windows that meet
+ *   [c0, c1), *n_bad of them.  Labels are only compared, never used as an index: such a haplotype counts for no ancestry at that window;
+ *   the tables are as stated.
+ * N == 0: nothing is launched, nothing is written.  Every form synchronises the context stream ONCE (the verdict on the labels, with the
+ *   tables' copies of the host forms in front of it).  In the _dev form every pointer but n_bad is a device pointer.
+ * gnx_ancestry_pair_counts_gt2: the file path's form.  G, n_variants, ldg, src as gnx_infer_gt2 takes them; labels (N, W) on the HOST,
+ *   contiguous rows; the model's C, M, W and A.  A pair needs every row at once, so the WHOLE packed matrix is built in HBM, in device
+ *   memory the call allocates and frees, batch by batch as gnx_ancestry_score_gt2 builds its batches, and the kernel runs once: the
+ *   tables equal the matrix path's whatever GNX_HOST_BATCH is.  A model SNP the query lacks is missing in every row.  GNX_EUNSUPPORTED
+ *   with the byte count in the message if the rows plus the tables exceed the device's memory; GNX_EINVAL before the launch also for a
+ *   column map entry outside G. */
+int gnx_ancestry_pair_counts_dev(gnx_ctx* ctx, const void* d_rows, int row_kind, int64_t ld_rows, const int32_t* d_labels, int64_t ld_labels,
+                                 int64_t N, int64_t C, int64_t M, int64_t W, int32_t A, int32_t ancestry, int64_t c0, int64_t c1,
+                                 int32_t* d_DD, int32_t* d_DO, int32_t* d_OO, int64_t ld, int64_t debug_snps_per_block, int64_t* n_bad);
+int gnx_ancestry_pair_counts(gnx_ctx* ctx, const void* rows, int row_kind, int64_t ld_rows, const int32_t* labels, int64_t ld_labels, int64_t N,
+                             int64_t C, int64_t M, int64_t W, int32_t A, int32_t ancestry, int64_t c0, int64_t c1, int32_t* DD, int32_t* DO,
+                             int32_t* OO, int64_t ld, int64_t debug_snps_per_block, int64_t* n_bad);
+int gnx_ancestry_pair_counts_gt2(gnx_model* m, const uint8_t* G, int64_t n_variants, int64_t ldg, int64_t N, const int32_t* src,
+                                 const int32_t* labels, int32_t ancestry, int64_t c0, int64_t c1, int32_t* DD, int32_t* DO, int32_t* OO,
+                                 int64_t ld, int64_t* n_bad);
+
 /* per-kernel device time, measured with hipEvents on the context stream around every launch */
 int gnx_profile_enable(gnx_ctx* ctx, int on);
 int gnx_profile_reset(gnx_ctx* ctx);
