@@ -24,7 +24,7 @@
 // where the group spans a window border), two 16-byte stores.
 //
 // Neither kernel has a per-thread array that is indexed at run time; no scratch.
-#include "gnx_assoc_rows.h"
+#include "gnx_summary_host.h"
 
 namespace {
 
@@ -214,24 +214,14 @@ __global__ __launch_bounds__(256) void k_ancestry_dosage(const uint8_t* __restri
   if (my_bad) atomicAdd(bad, (unsigned long long)my_bad);
 }
 
-int64_t min_row_bytes(int row_kind, int64_t C) { return row_kind == GNX_ROWS_PACKED2 ? (C + 3) / 4 : C; }
-
-int in_aligned(const void* rows, int row_kind, int64_t ld) {
-  const uintptr_t a = row_kind == GNX_ROWS_PACKED2 ? 4 : 16;
-  return ((uintptr_t)rows % a == 0) && (ld % (int64_t)a == 0);
-}
+const char* const AC_TAIL = "such a label counts for no ancestry";
 
 // the checks the counts and the dosage share; GNX_OK or the refusal
 int geometry_check(gnx_ctx* ctx, const char* who, const void* rows, int row_kind, int64_t ld_rows, const void* labels, int64_t ld_labels, int64_t N,
                    int64_t C, int64_t M, int64_t W, int32_t A) {
   const std::string w(who);
-  if (!ctx->usable) return gnx_fail(ctx, GNX_ESTATE, "context has no device (gnx_init failed)");
-  if (row_kind != GNX_ROWS_INT8 && row_kind != GNX_ROWS_PACKED2) return gnx_fail(ctx, GNX_EINVAL, w + ": row_kind is GNX_ROWS_INT8 or GNX_ROWS_PACKED2");
-  if (N < 0 || C < 1 || A < 1) return gnx_fail(ctx, GNX_EINVAL, w + ": need N >= 0, C >= 1 and A >= 1");
-  if (M < 1 || W < 1 || M > C || W > C / M) return gnx_fail(ctx, GNX_EINVAL, w + ": need M >= 1, W >= 1 and M * W <= C");
-  if (ld_rows < min_row_bytes(row_kind, C)) return gnx_fail(ctx, GNX_EINVAL, w + ": the rows' stride is smaller than a row (C bytes, or ceil(C / 4) packed)");
-  if (ld_labels < W) return gnx_fail(ctx, GNX_EINVAL, w + ": the labels' row stride is smaller than W");
-  if (N > 0 && (!rows || !labels)) return gnx_fail(ctx, GNX_EINVAL, w + ": no rows or no labels");
+  const int rc = gnx_sum_geometry_check(ctx, who, 0, rows, row_kind, ld_rows, labels, ld_labels, N, C, M, W, A);
+  if (rc != GNX_OK) return rc;
   if (N >= ((int64_t)1 << 31)) return gnx_fail(ctx, GNX_EINVAL, w + ": N must be below 2^31");
   if (A > AC_MAX_A)
     return gnx_fail(ctx, GNX_EUNSUPPORTED, w + ": A = " + std::to_string(A) + " ancestries, a staged label is compared with at most " +
@@ -256,17 +246,6 @@ int zero_tables(gnx_ctx* ctx, int32_t A, int64_t C, int32_t* d_obs, int32_t* d_a
   return GNX_OK;
 }
 
-// reads the count of out-of-range labels back (one synchronisation of the stream)
-int verdict(gnx_ctx* ctx, const char* who, const unsigned long long* d_bad, int32_t A, hipStream_t s) {
-  unsigned long long h_bad = 0;
-  HIPCHK(ctx, hipMemcpyAsync(&h_bad, d_bad, sizeof h_bad, hipMemcpyDeviceToHost, s));
-  HIPCHK(ctx, hipStreamSynchronize(s));
-  if (h_bad)
-    return gnx_fail(ctx, GNX_EINVAL, std::string(who) + ": " + std::to_string(h_bad) + " labels lie outside [0, " + std::to_string(A) +
-                                         "); such a label counts for no ancestry");
-  return GNX_OK;
-}
-
 }  // namespace
 
 // adds the counts of N rows to the tables (which the caller has zeroed) and the number of out-of-range labels to *d_bad; arguments checked
@@ -286,7 +265,7 @@ static hipError_t gnx_launch_allele_counts(const void* d_rows, int row_kind, int
   if (n_chunks > ((int64_t)1 << 31) / n_ctiles - 1) return hipErrorInvalidConfiguration;
   const int fe = (int)(flush_every > 0 ? std::min<int64_t>(flush_every, AC_MAX_FLUSH) : AC_MAX_FLUSH);
   const size_t lds = (size_t)A * 3 * AC_TILE + AC_LAB_BYTES;
-  const int aligned = in_aligned(d_rows, row_kind, ld_rows);
+  const int aligned = gnx_sum_rows_aligned(d_rows, row_kind, ld_rows);
   const dim3 grid((unsigned)(n_ctiles * n_chunks));
   const uint8_t* rows = (const uint8_t*)d_rows;
   if (row_kind == GNX_ROWS_PACKED2) {
@@ -311,12 +290,11 @@ extern "C" int gnx_ancestry_allele_counts_dev(gnx_ctx* ctx, const void* d_rows, 
   hipStream_t s = ctx->stream;
   if ((rc = zero_tables(ctx, A, C, d_n_obs, d_n_alt, d_n_miss, s)) != GNX_OK) return rc;
   if (N == 0) return GNX_OK;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_misc, 256)) != GNX_OK) return rc;
-  unsigned long long* d_bad = (unsigned long long*)ctx->ws_misc.p;
-  HIPCHK(ctx, hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), s));
+  unsigned long long* d_bad;
+  if ((rc = gnx_sum_bad_counter(ctx, 1, &d_bad, s)) != GNX_OK) return rc;
   HIPCHK(ctx, gnx_launch_allele_counts(d_rows, row_kind, ld_rows, d_labels, ld_labels, N, C, M, W, A, d_n_obs, d_n_alt, d_n_miss,
                                        debug_rows_per_chunk, debug_flush_every, d_bad, ctx->n_cu, s));
-  return verdict(ctx, "ancestry_allele_counts", d_bad, A, s);
+  return gnx_sum_read_verdict(ctx, "ancestry_allele_counts", d_bad, A, AC_TAIL, nullptr, s);
 }
 
 namespace {
@@ -329,20 +307,6 @@ int table_slab(gnx_ctx* ctx, size_t tb, const int32_t* n_obs, const int32_t* n_a
   *d_obs = n_obs ? (int32_t*)o : nullptr;
   *d_alt = n_alt ? (int32_t*)(o + tb) : nullptr;
   *d_miss = n_miss ? (int32_t*)(o + 2 * tb) : nullptr;
-  return GNX_OK;
-}
-
-// the N > 0 host rows and labels of a host-pointer entry -> ws_xu and ws_lab
-int stage_rows_labels(gnx_ctx* ctx, const void* rows, int row_kind, int64_t ld_rows, const int32_t* labels, int64_t ld_labels, int64_t N, int64_t C,
-                      int64_t W, hipStream_t s) {
-  // the last row ends after its own bytes / labels, not after a whole stride
-  const size_t br = (size_t)(N - 1) * (size_t)ld_rows + (size_t)min_row_bytes(row_kind, C);
-  const size_t bl = ((size_t)(N - 1) * (size_t)ld_labels + (size_t)W) * sizeof(int32_t);
-  int rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_xu, br + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_lab, bl + 64)) != GNX_OK) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->ws_xu.p, rows, br, hipMemcpyHostToDevice, s));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->ws_lab.p, labels, bl, hipMemcpyHostToDevice, s));
   return GNX_OK;
 }
 }  // namespace
@@ -359,7 +323,7 @@ extern "C" int gnx_ancestry_allele_counts(gnx_ctx* ctx, const void* rows, int ro
   int32_t *d_obs, *d_alt, *d_miss;
   if ((rc = table_slab(ctx, tb, n_obs, n_alt, n_miss, &d_obs, &d_alt, &d_miss)) != GNX_OK) return rc;
   std::string msg;
-  if (N > 0 && (rc = stage_rows_labels(ctx, rows, row_kind, ld_rows, labels, ld_labels, N, C, W, s)) != GNX_OK) return rc;
+  if (N > 0 && (rc = gnx_sum_stage_rows_labels(ctx, rows, row_kind, ld_rows, labels, ld_labels, N, C, W, s)) != GNX_OK) return rc;
   rc = gnx_ancestry_allele_counts_dev(ctx, ctx->ws_xu.p, row_kind, ld_rows, (const int32_t*)ctx->ws_lab.p, ld_labels, N, C, M, W, A, d_obs, d_alt,
                                       d_miss, debug_rows_per_chunk, debug_flush_every);
   if (rc != GNX_OK && rc != GNX_EINVAL) return rc;
@@ -395,12 +359,11 @@ extern "C" int gnx_ancestry_dosage_dev(gnx_ctx* ctx, const void* d_rows, int row
   if (N == 0) return GNX_OK;
   GNX_BIND_DEVICE(ctx);
   hipStream_t s = ctx->stream;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_misc, 256)) != GNX_OK) return rc;
-  unsigned long long* d_bad = (unsigned long long*)ctx->ws_misc.p;
-  HIPCHK(ctx, hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), s));
+  unsigned long long* d_bad;
+  if ((rc = gnx_sum_bad_counter(ctx, 1, &d_bad, s)) != GNX_OK) return rc;
   const int64_t G = (C + AC_COLS - 1) / AC_COLS, total = (N / 2) * G;
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, (int64_t)ctx->n_cu * 32));
-  const int a_in = in_aligned(d_rows, row_kind, ld_rows);
+  const int a_in = gnx_sum_rows_aligned(d_rows, row_kind, ld_rows);
   const int a_out = (!d_dosage || ((uintptr_t)d_dosage % 16 == 0 && ld_dosage % 16 == 0)) &&
                     (!d_hapcount || ((uintptr_t)d_hapcount % 16 == 0 && ld_hapcount % 16 == 0));
   const uint8_t* rows = (const uint8_t*)d_rows;
@@ -411,7 +374,7 @@ extern "C" int gnx_ancestry_dosage_dev(gnx_ctx* ctx, const void* d_rows, int row
     hipLaunchKernelGGL(k_ancestry_dosage<GNX_ROWS_INT8>, dim3(grid), dim3(256), 0, s, rows, ld_rows, d_labels, ld_labels, N / 2, C, M, W, (int)A,
                        (int)ancestry, G, a_in, d_dosage, ld_dosage, d_hapcount, ld_hapcount, a_out, d_bad);
   HIPCHK(ctx, hipGetLastError());
-  return verdict(ctx, "ancestry_dosage", d_bad, A, s);
+  return gnx_sum_read_verdict(ctx, "ancestry_dosage", d_bad, A, AC_TAIL, nullptr, s);
 }
 
 extern "C" int gnx_ancestry_dosage(gnx_ctx* ctx, const void* rows, int row_kind, int64_t ld_rows, const int32_t* labels, int64_t ld_labels, int64_t N,
@@ -428,7 +391,7 @@ extern "C" int gnx_ancestry_dosage(gnx_ctx* ctx, const void* rows, int row_kind,
   if ((rc = gnx_ws_reserve(ctx, ctx->ws_b32, 2 * bo)) != GNX_OK) return rc;
   uint8_t* d_d = dosage ? (uint8_t*)ctx->ws_b32.p : nullptr;
   uint8_t* d_h = hapcount ? (uint8_t*)ctx->ws_b32.p + bo : nullptr;
-  if ((rc = stage_rows_labels(ctx, rows, row_kind, ld_rows, labels, ld_labels, N, C, W, s)) != GNX_OK) return rc;
+  if ((rc = gnx_sum_stage_rows_labels(ctx, rows, row_kind, ld_rows, labels, ld_labels, N, C, W, s)) != GNX_OK) return rc;
   rc = gnx_ancestry_dosage_dev(ctx, ctx->ws_xu.p, row_kind, ld_rows, (const int32_t*)ctx->ws_lab.p, ld_labels, N, C, M, W, A, ancestry, d_d, ldo, d_h,
                                ldo);
   if (rc != GNX_OK && rc != GNX_EINVAL) return rc;
@@ -456,43 +419,24 @@ extern "C" int gnx_ancestry_allele_counts_gt2(gnx_model* m, const uint8_t* G, in
     return gnx_fail(ctx, GNX_EUNSUPPORTED, "ancestry_allele_counts_gt2: A = " + std::to_string(A) + " ancestries, at most " + std::to_string(AC_MAX_A) +
                                                " are counted");
   if (A > ((int64_t)1 << 31) / C) return gnx_fail(ctx, GNX_EUNSUPPORTED, "ancestry_allele_counts_gt2: A * C must stay below 2^31");
-  for (int64_t c = 0; c < C; ++c) {
-    const int32_t sv = src[c];
-    if (sv != -1 && (sv < 0 || (int64_t)(sv & 0x3FFFFFFF) >= V))
-      return gnx_fail(ctx, GNX_EINVAL, "ancestry_allele_counts_gt2: column map entry outside the variant rows");
-  }
+  int rc = gnx_sum_check_src(ctx, "ancestry_allele_counts_gt2", src, C, V);
+  if (rc != GNX_OK) return rc;
   GNX_BIND_DEVICE(ctx);
   hipStream_t s = ctx->stream;
-  int rc;
   const size_t tbytes = (size_t)A * (size_t)C * sizeof(int32_t), tb = (tbytes + 255) & ~(size_t)255;
   int32_t *d_obs, *d_alt, *d_miss;
   if ((rc = table_slab(ctx, tb, n_obs, n_alt, n_miss, &d_obs, &d_alt, &d_miss)) != GNX_OK) return rc;
   HIPCHK(ctx, hipMemsetAsync(ctx->ws_b32.p, 0, 3 * tb, s));
   unsigned long long h_bad = 0;
   if (N > 0) {
-    const int64_t ldp = (C + 255) / 256 * 64;  // 64-byte aligned packed rows
-    int64_t nb = (((int64_t)1 << 30) / ldp) / 1024 * 1024;  // a batch: <= ~1 GiB of packed rows, whole 1024-haplotype tiles of the transpose
-    if (ctx->tune.host_batch > 0) nb = (ctx->tune.host_batch + 3) / 4 * 4;  // tests: several batches on small inputs
-    nb = std::min(std::max<int64_t>(4, nb), (N + 3) / 4 * 4);
-    const int64_t wbytes = (N + 3) / 4, ldg_d = wbytes == ldg ? ldg : (wbytes + 63) / 64 * 64;
-    if ((rc = gnx_ws_reserve(ctx, ctx->ws_gt2, (size_t)V * ldg_d + 64)) != GNX_OK) return rc;
-    if ((rc = gnx_ws_reserve(ctx, ctx->ws_src, (size_t)C * 4 + 64)) != GNX_OK) return rc;
-    if ((rc = gnx_ws_reserve(ctx, ctx->ws_xu, (size_t)nb * ldp + 256)) != GNX_OK) return rc;
-    if ((rc = gnx_ws_reserve(ctx, ctx->ws_lab, (size_t)N * (size_t)W * 4 + 64)) != GNX_OK) return rc;
-    if ((rc = gnx_ws_reserve(ctx, ctx->ws_misc, 256)) != GNX_OK) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ws_src.p, src, (size_t)C * 4, hipMemcpyHostToDevice, s));
-    if (V > 0) {
-      if (ldg_d == ldg) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_gt2.p, G, (size_t)V * ldg, hipMemcpyHostToDevice, s));
-      else HIPCHK(ctx, hipMemcpy2DAsync(ctx->ws_gt2.p, (size_t)ldg_d, G, (size_t)ldg, (size_t)wbytes, (size_t)V, hipMemcpyHostToDevice, s));
-    }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ws_lab.p, labels, (size_t)N * (size_t)W * 4, hipMemcpyHostToDevice, s));
-    const int32_t* d_lab = (const int32_t*)ctx->ws_lab.p;
-    unsigned long long* d_bad = (unsigned long long*)ctx->ws_misc.p;
-    HIPCHK(ctx, hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), s));
-    for (int64_t n0 = 0; n0 < N; n0 += nb) {
-      const int64_t n = std::min(nb, N - n0);
-      HIPCHK(ctx, gnx_launch_gt2_to_p2((const uint8_t*)ctx->ws_gt2.p, V, ldg_d, n0, n, (const int32_t*)ctx->ws_src.p, C, (uint8_t*)ctx->ws_xu.p, ldp, s));
-      HIPCHK(ctx, gnx_launch_allele_counts(ctx->ws_xu.p, GNX_ROWS_PACKED2, ldp, d_lab + n0 * W, W, n, C, M, W, A, d_obs, d_alt, d_miss, 0, 0, d_bad,
+    gnx_sum_gt2 st;
+    unsigned long long* d_bad;
+    if ((rc = gnx_sum_gt2_stage(ctx, G, V, ldg, N, src, labels, C, W, true, &st, s)) != GNX_OK) return rc;
+    if ((rc = gnx_sum_bad_counter(ctx, 1, &d_bad, s)) != GNX_OK) return rc;
+    for (int64_t n0 = 0; n0 < N; n0 += st.nb) {
+      const int64_t n = std::min(st.nb, N - n0);
+      HIPCHK(ctx, gnx_sum_gt2_batch(st, n0, n, C, ctx->ws_xu.p, s));
+      HIPCHK(ctx, gnx_launch_allele_counts(ctx->ws_xu.p, GNX_ROWS_PACKED2, st.ldp, st.d_lab + n0 * W, W, n, C, M, W, A, d_obs, d_alt, d_miss, 0, 0, d_bad,
                                            ctx->n_cu, s));
     }
     HIPCHK(ctx, hipMemcpyAsync(&h_bad, d_bad, sizeof h_bad, hipMemcpyDeviceToHost, s));
@@ -501,8 +445,5 @@ extern "C" int gnx_ancestry_allele_counts_gt2(gnx_model* m, const uint8_t* G, in
   if (n_alt) HIPCHK(ctx, hipMemcpyAsync(n_alt, d_alt, tbytes, hipMemcpyDeviceToHost, s));
   if (n_miss) HIPCHK(ctx, hipMemcpyAsync(n_miss, d_miss, tbytes, hipMemcpyDeviceToHost, s));
   HIPCHK(ctx, hipStreamSynchronize(s));
-  if (h_bad)
-    return gnx_fail(ctx, GNX_EINVAL, "ancestry_allele_counts_gt2: " + std::to_string(h_bad) + " labels lie outside [0, " + std::to_string(A) +
-                                         "); such a label counts for no ancestry");
-  return GNX_OK;
+  return gnx_sum_label_verdict(ctx, "ancestry_allele_counts_gt2", h_bad, A, AC_TAIL, nullptr);
 }

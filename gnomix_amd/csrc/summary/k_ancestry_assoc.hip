@@ -27,7 +27,7 @@
 // The VALU form was kept: a wave's work per (individual, SNP) is dominated by the LDS read-modify-write of the rows the individual's
 // two ancestries select, which the float64 matrix cores would not remove.
 // No per-thread array is indexed at run time; no scratch.
-#include "gnx_assoc_rows.h"
+#include "gnx_summary_host.h"
 
 namespace {
 
@@ -202,22 +202,21 @@ int as_tile_cols(const AsLayout& L) {
   return tc;
 }
 
-// every refusal before the launch; GNX_OK or the code
-int assoc_check(gnx_ctx* ctx, const void* rows, int row_kind, int64_t ld_rows, const void* labels, int64_t ld_labels, int64_t N, int64_t C, int64_t M,
-                int64_t W, int32_t A, const void* y, const void* Z, int32_t K, int32_t min_ac, int64_t c0, int64_t c1, const void* snp_f64,
+const char* const AS_TAIL = "an individual with such a label takes no part at that window";
+
+// every refusal before the launch; GNX_OK or the code.  built: the rows are built by this call (the file path's form)
+int assoc_check(gnx_ctx* ctx, bool built, const void* rows, int row_kind, int64_t ld_rows, const void* labels, int64_t ld_labels, int64_t N, int64_t C,
+                int64_t M, int64_t W, int32_t A, const void* y, const void* Z, int32_t K, int32_t min_ac, int64_t c0, int64_t c1, const void* snp_f64,
                 const void* snp_i32, const void* win_f64, const void* win_i32) {
   const std::string w("ancestry_assoc_stats");
-  if (!ctx->usable) return gnx_fail(ctx, GNX_ESTATE, "context has no device (gnx_init failed)");
-  if (row_kind != GNX_ROWS_INT8 && row_kind != GNX_ROWS_PACKED2) return gnx_fail(ctx, GNX_EINVAL, w + ": row_kind is GNX_ROWS_INT8 or GNX_ROWS_PACKED2");
-  if (N < 0 || C < 1 || A < 1) return gnx_fail(ctx, GNX_EINVAL, w + ": need N >= 0, C >= 1 and A >= 1");
-  if (N & 1) return gnx_fail(ctx, GNX_EINVAL, w + ": N must be even (an individual has two haplotype rows)");
-  if (M < 1 || W < 1 || M > C || W > C / M) return gnx_fail(ctx, GNX_EINVAL, w + ": need M >= 1, W >= 1 and M * W <= C");
+  const int rc = gnx_sum_geometry_check(ctx, "ancestry_assoc_stats", GNX_SUM_N_EVEN | GNX_SUM_OWN_NULLS, rows, row_kind, ld_rows, labels, ld_labels, N, C,
+                                        M, W, A);
+  if (rc != GNX_OK) return rc;
   if (K < 1) return gnx_fail(ctx, GNX_EINVAL, w + ": need K >= 1 covariates (the caller supplies the intercept column)");
   if (min_ac < 1) return gnx_fail(ctx, GNX_EINVAL, w + ": need min_ac >= 1");
   if (c0 < 0 || c1 > C || c0 >= c1) return gnx_fail(ctx, GNX_EINVAL, w + ": need 0 <= c0 < c1 <= C");
-  if (ld_rows < as_min_row_bytes(row_kind, C)) return gnx_fail(ctx, GNX_EINVAL, w + ": the rows' stride is smaller than a row (C bytes, or ceil(C / 4) packed)");
-  if (ld_labels < W) return gnx_fail(ctx, GNX_EINVAL, w + ": the labels' row stride is smaller than W");
-  if (!rows || !labels || !y || !Z || !snp_f64 || !snp_i32 || !win_f64 || !win_i32) return gnx_fail(ctx, GNX_EINVAL, w + ": a null pointer (only use and n_bad may be NULL)");
+  if ((!built && !rows) || !labels || !y || !Z || !snp_f64 || !snp_i32 || !win_f64 || !win_i32)
+    return gnx_fail(ctx, GNX_EINVAL, w + ": a null pointer (only use and n_bad may be NULL)");
   if (A > AS_MAX_A) return gnx_fail(ctx, GNX_EUNSUPPORTED, w + ": A = " + std::to_string(A) + " ancestries, at most " + std::to_string(AS_MAX_A));
   if (K > AS_MAX_K) return gnx_fail(ctx, GNX_EUNSUPPORTED, w + ": K = " + std::to_string(K) + " covariates, at most " + std::to_string(AS_MAX_K));
   if (N > ((int64_t)1 << 28)) return gnx_fail(ctx, GNX_EUNSUPPORTED, w + ": N must not exceed 2^28 (the integer blocks are int32)");
@@ -248,6 +247,54 @@ hipError_t assoc_launch(const void* d_rows, int row_kind, int64_t ld_rows, const
   return hipGetLastError();
 }
 
+// the workspace of one call: zy | part in ws_p64, filled from DEVICE y, Z and use, and the zeroed counter of labels out of range
+struct AsWork {
+  double* zy;
+  uint8_t* part;
+  unsigned long long* d_bad;
+};
+
+int assoc_work(gnx_ctx* ctx, int64_t n_ind, int32_t K, const double* d_y, const double* d_Z, const uint8_t* d_use, AsWork* wk, hipStream_t s) {
+  int rc;
+  if ((rc = gnx_sum_zy_part(ctx, n_ind, K, &wk->zy, &wk->part)) != GNX_OK) return rc;
+  if ((rc = gnx_sum_bad_counter(ctx, 1, &wk->d_bad, s)) != GNX_OK) return rc;
+  if (n_ind > 0) {
+    hipLaunchKernelGGL(k_ancestry_assoc_prep, dim3((unsigned)((n_ind + 255) / 256)), dim3(256), 0, s, d_y, d_Z, d_use, n_ind, (int)K, wk->zy, wk->part);
+    HIPCHK(ctx, hipGetLastError());
+  }
+  return GNX_OK;
+}
+
+// host outputs of one call: the float64 blocks in ws_b64, the int32 blocks in ws_b32
+struct AsOut {
+  size_t sf, si, wf, wi;
+  double *d_sf, *d_wf;
+  int32_t *d_si, *d_wi;
+};
+
+int assoc_out(gnx_ctx* ctx, int32_t A, int32_t K, int64_t M, int64_t W, int64_t c0, int64_t c1, AsOut* o) {
+  const AsLayout L(A, K);
+  const size_t nc = (size_t)(c1 - c0), nw = (size_t)(as_win(c1 - 1, M, W) - as_win(c0, M, W) + 1);
+  const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  o->sf = nc * L.NF * 8, o->si = nc * L.NI * 4, o->wf = nw * L.NWF * 8, o->wi = nw * L.NWI * 4;
+  int rc;
+  if ((rc = gnx_ws_reserve(ctx, ctx->ws_b64, up(o->sf) + o->wf + 64)) != GNX_OK) return rc;
+  if ((rc = gnx_ws_reserve(ctx, ctx->ws_b32, up(o->si) + o->wi + 64)) != GNX_OK) return rc;
+  o->d_sf = (double*)ctx->ws_b64.p, o->d_wf = (double*)((char*)ctx->ws_b64.p + up(o->sf));
+  o->d_si = (int32_t*)ctx->ws_b32.p, o->d_wi = (int32_t*)((char*)ctx->ws_b32.p + up(o->si));
+  return GNX_OK;
+}
+
+// the four blocks -> the host; synchronises the stream
+int assoc_copy_out(gnx_ctx* ctx, const AsOut& o, double* snp_f64, int32_t* snp_i32, double* win_f64, int32_t* win_i32, hipStream_t s) {
+  HIPCHK(ctx, hipMemcpyAsync(snp_f64, o.d_sf, o.sf, hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipMemcpyAsync(snp_i32, o.d_si, o.si, hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipMemcpyAsync(win_f64, o.d_wf, o.wf, hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipMemcpyAsync(win_i32, o.d_wi, o.wi, hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipStreamSynchronize(s));
+  return GNX_OK;
+}
+
 }  // namespace
 
 extern "C" int gnx_ancestry_assoc_stats_dev(gnx_ctx* ctx, const void* d_rows, int row_kind, int64_t ld_rows, const int32_t* d_labels, int64_t ld_labels,
@@ -255,34 +302,16 @@ extern "C" int gnx_ancestry_assoc_stats_dev(gnx_ctx* ctx, const void* d_rows, in
                                             const uint8_t* d_use, int32_t min_ac, int64_t c0, int64_t c1, double* d_snp_f64, int32_t* d_snp_i32,
                                             double* d_win_f64, int32_t* d_win_i32, int64_t* n_bad) {
   if (!ctx) return GNX_EINVAL;
-  int rc = assoc_check(ctx, d_rows, row_kind, ld_rows, d_labels, ld_labels, N, C, M, W, A, d_y, d_Z, K, min_ac, c0, c1, d_snp_f64, d_snp_i32, d_win_f64,
-                       d_win_i32);
+  int rc = assoc_check(ctx, false, d_rows, row_kind, ld_rows, d_labels, ld_labels, N, C, M, W, A, d_y, d_Z, K, min_ac, c0, c1, d_snp_f64, d_snp_i32,
+                       d_win_f64, d_win_i32);
   if (rc != GNX_OK) return rc;
   GNX_BIND_DEVICE(ctx);
   hipStream_t s = ctx->stream;
-  const AsLayout L(A, K);
-  const int64_t n_ind = N / 2;
-  const size_t zy_bytes = (((size_t)n_ind * L.K1 * sizeof(double)) + 255) & ~(size_t)255;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_p64, zy_bytes + (size_t)n_ind + 256)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_misc, 256)) != GNX_OK) return rc;
-  double* zy = (double*)ctx->ws_p64.p;
-  uint8_t* part = (uint8_t*)ctx->ws_p64.p + zy_bytes;
-  unsigned long long* d_bad = (unsigned long long*)ctx->ws_misc.p;
-  HIPCHK(ctx, hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), s));
-  if (n_ind > 0) {
-    hipLaunchKernelGGL(k_ancestry_assoc_prep, dim3((unsigned)((n_ind + 255) / 256)), dim3(256), 0, s, d_y, d_Z, d_use, n_ind, (int)K, zy, part);
-    HIPCHK(ctx, hipGetLastError());
-  }
-  HIPCHK(ctx, assoc_launch(d_rows, row_kind, ld_rows, d_labels, ld_labels, n_ind, M, W, A, K, c0, c1, zy, part, 0, d_snp_f64, d_snp_i32, d_win_f64,
-                           d_win_i32, d_bad, s));
-  unsigned long long h_bad = 0;
-  HIPCHK(ctx, hipMemcpyAsync(&h_bad, d_bad, sizeof h_bad, hipMemcpyDeviceToHost, s));
-  HIPCHK(ctx, hipStreamSynchronize(s));
-  if (n_bad) *n_bad = (int64_t)h_bad;
-  if (h_bad)
-    return gnx_fail(ctx, GNX_EINVAL, "ancestry_assoc_stats: " + std::to_string(h_bad) + " labels lie outside [0, " + std::to_string(A) +
-                                         "); an individual with such a label takes no part at that window");
-  return GNX_OK;
+  AsWork wk;
+  if ((rc = assoc_work(ctx, N / 2, K, d_y, d_Z, d_use, &wk, s)) != GNX_OK) return rc;
+  HIPCHK(ctx, assoc_launch(d_rows, row_kind, ld_rows, d_labels, ld_labels, N / 2, M, W, A, K, c0, c1, wk.zy, wk.part, 0, d_snp_f64, d_snp_i32, d_win_f64,
+                           d_win_i32, wk.d_bad, s));
+  return gnx_sum_read_verdict(ctx, "ancestry_assoc_stats", wk.d_bad, A, AS_TAIL, n_bad, s);
 }
 
 extern "C" int gnx_ancestry_assoc_stats(gnx_ctx* ctx, const int8_t* X, int64_t ld_rows, const int32_t* labels, int64_t ld_labels, int64_t N, int64_t C,
@@ -290,53 +319,32 @@ extern "C" int gnx_ancestry_assoc_stats(gnx_ctx* ctx, const int8_t* X, int64_t l
                                         int32_t min_ac, int64_t c0, int64_t c1, double* snp_f64, int32_t* snp_i32, double* win_f64, int32_t* win_i32,
                                         int64_t* n_bad) {
   if (!ctx) return GNX_EINVAL;
-  int rc = assoc_check(ctx, X, GNX_ROWS_INT8, ld_rows, labels, ld_labels, N, C, M, W, A, y, Z, K, min_ac, c0, c1, snp_f64, snp_i32, win_f64, win_i32);
+  int rc = assoc_check(ctx, false, X, GNX_ROWS_INT8, ld_rows, labels, ld_labels, N, C, M, W, A, y, Z, K, min_ac, c0, c1, snp_f64, snp_i32, win_f64,
+                       win_i32);
   if (rc != GNX_OK) return rc;
   GNX_BIND_DEVICE(ctx);
   hipStream_t s = ctx->stream;
-  const AsLayout L(A, K);
-  const int64_t n_ind = N / 2, nc = c1 - c0, nw = as_win(c1 - 1, M, W) - as_win(c0, M, W) + 1;
-  const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
   // inputs: rows -> ws_xu, labels -> ws_lab, y | Z | use -> ws_scale; outputs: float64 blocks in ws_b64, int32 blocks in ws_b32
-  const size_t br = N > 0 ? (size_t)(N - 1) * (size_t)ld_rows + (size_t)C : 0;
-  const size_t bl = N > 0 ? ((size_t)(N - 1) * (size_t)ld_labels + (size_t)W) * sizeof(int32_t) : 0;
-  const size_t by = up((size_t)n_ind * 8), bz = up((size_t)n_ind * K * 8), bu = up((size_t)n_ind);
-  const size_t sf = (size_t)nc * L.NF * 8, si = (size_t)nc * L.NI * 4, wf = (size_t)nw * L.NWF * 8, wi = (size_t)nw * L.NWI * 4;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_xu, br + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_lab, bl + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_scale, by + bz + bu + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_b64, up(sf) + wf + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_b32, up(si) + wi + 64)) != GNX_OK) return rc;
-  char* sc = (char*)ctx->ws_scale.p;
-  double *d_y = (double*)sc, *d_Z = (double*)(sc + by);
-  uint8_t* d_use = use ? (uint8_t*)(sc + by + bz) : nullptr;
-  double *d_sf = (double*)ctx->ws_b64.p, *d_wf = (double*)((char*)ctx->ws_b64.p + up(sf));
-  int32_t *d_si = (int32_t*)ctx->ws_b32.p, *d_wi = (int32_t*)((char*)ctx->ws_b32.p + up(si));
-  if (N > 0) {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ws_xu.p, X, br, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ws_lab.p, labels, bl, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(d_y, y, (size_t)n_ind * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(d_Z, Z, (size_t)n_ind * K * 8, hipMemcpyHostToDevice, s));
-    if (use) HIPCHK(ctx, hipMemcpyAsync(d_use, use, (size_t)n_ind, hipMemcpyHostToDevice, s));
-  }
-  rc = gnx_ancestry_assoc_stats_dev(ctx, ctx->ws_xu.p, GNX_ROWS_INT8, ld_rows, (const int32_t*)ctx->ws_lab.p, ld_labels, N, C, M, W, A, d_y, d_Z, K, d_use,
-                                    min_ac, c0, c1, d_sf, d_si, d_wf, d_wi, n_bad);
+  gnx_sum_pheno ph;
+  AsOut o;
+  if ((rc = gnx_sum_stage_rows_labels(ctx, X, GNX_ROWS_INT8, ld_rows, labels, ld_labels, N, C, W, s)) != GNX_OK) return rc;
+  if ((rc = gnx_sum_stage_pheno(ctx, y, Z, K, use, N / 2, &ph, s)) != GNX_OK) return rc;
+  if ((rc = assoc_out(ctx, A, K, M, W, c0, c1, &o)) != GNX_OK) return rc;
+  rc = gnx_ancestry_assoc_stats_dev(ctx, ctx->ws_xu.p, GNX_ROWS_INT8, ld_rows, (const int32_t*)ctx->ws_lab.p, ld_labels, N, C, M, W, A, ph.d_y, ph.d_Z, K,
+                                    ph.d_use, min_ac, c0, c1, o.d_sf, o.d_si, o.d_wf, o.d_wi, n_bad);
   if (rc != GNX_OK && rc != GNX_EINVAL) return rc;
   // (GNX_EINVAL after the launch = labels out of range: the other values stand and are handed over)
   const std::string msg = ctx->err;
-  HIPCHK(ctx, hipMemcpyAsync(snp_f64, d_sf, sf, hipMemcpyDeviceToHost, s));
-  HIPCHK(ctx, hipMemcpyAsync(snp_i32, d_si, si, hipMemcpyDeviceToHost, s));
-  HIPCHK(ctx, hipMemcpyAsync(win_f64, d_wf, wf, hipMemcpyDeviceToHost, s));
-  HIPCHK(ctx, hipMemcpyAsync(win_i32, d_wi, wi, hipMemcpyDeviceToHost, s));
-  HIPCHK(ctx, hipStreamSynchronize(s));
+  const int rc2 = assoc_copy_out(ctx, o, snp_f64, snp_i32, win_f64, win_i32, s);
+  if (rc2 != GNX_OK) return rc2;
   ctx->err = msg;
   return rc;
 }
 
-// The file path's form: the packed rows of gnx_infer_gt2's batches (the staging, column map, row pitch and batch size of
-// gnx_ancestry_allele_counts_gt2), reduced against the caller's labels batch by batch.  A batch holds whole individuals in ascending
-// order and goes on from the blocks of the batches before it (accumulate), so every running sum is the one a single launch makes: the
-// blocks do not depend on the batch size.
+// The file path's form: the packed rows of gnx_infer_gt2's batches (gnx_summary_host.h: the staging, column map, row pitch and batch
+// size), reduced against the caller's labels batch by batch.  A batch holds whole individuals in ascending order and goes on from the
+// blocks of the batches before it (accumulate), so every running sum is the one a single launch makes: the blocks do not depend on the
+// batch size.
 extern "C" int gnx_ancestry_assoc_stats_gt2(gnx_model* m, const uint8_t* G, int64_t V, int64_t ldg, int64_t N, const int32_t* src,
                                             const int32_t* labels, const double* y, const double* Z, int32_t K, const uint8_t* use, int32_t min_ac,
                                             int64_t c0, int64_t c1, double* snp_f64, int32_t* snp_i32, double* win_f64, int32_t* win_i32,
@@ -345,79 +353,33 @@ extern "C" int gnx_ancestry_assoc_stats_gt2(gnx_model* m, const uint8_t* G, int6
   gnx_ctx* ctx = m->ctx;
   const int64_t C = m->info.C, M = m->info.M, W = m->info.W;
   const int32_t A = m->info.A;
-  if (N < 0 || V < 0 || ldg < (N + 3) / 4 || !src || (N > 0 && V > 0 && !G))
-    return gnx_fail(ctx, GNX_EINVAL, "ancestry_assoc_stats_gt2: bad G / V / ldg / N / src");
-  const int8_t* some_rows = (const int8_t*)src;   // (the rows are built here: any non-null pointer passes the shared check)
-  int rc = assoc_check(ctx, some_rows, GNX_ROWS_PACKED2, (C + 3) / 4, labels, W, N, C, M, W, A, y, Z, K, min_ac, c0, c1, snp_f64, snp_i32, win_f64, win_i32);
+  int rc = gnx_sum_gt2_args(ctx, "ancestry_assoc_stats_gt2", G, V, ldg, N, src);
   if (rc != GNX_OK) return rc;
-  for (int64_t c = 0; c < C; ++c) {
-    const int32_t sv = src[c];
-    if (sv != -1 && (sv < 0 || (int64_t)(sv & 0x3FFFFFFF) >= V))
-      return gnx_fail(ctx, GNX_EINVAL, "ancestry_assoc_stats_gt2: column map entry outside the variant rows");
-  }
+  if ((rc = assoc_check(ctx, true, nullptr, GNX_ROWS_PACKED2, (C + 3) / 4, labels, W, N, C, M, W, A, y, Z, K, min_ac, c0, c1, snp_f64, snp_i32, win_f64,
+                        win_i32)) != GNX_OK)
+    return rc;
+  if ((rc = gnx_sum_check_src(ctx, "ancestry_assoc_stats_gt2", src, C, V)) != GNX_OK) return rc;
   GNX_BIND_DEVICE(ctx);
   hipStream_t s = ctx->stream;
-  const AsLayout L(A, K);
-  const int64_t n_ind = N / 2, nc = c1 - c0, nw = as_win(c1 - 1, M, W) - as_win(c0, M, W) + 1;
-  const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t by = up((size_t)n_ind * 8), bz = up((size_t)n_ind * K * 8), bu = up((size_t)n_ind);
-  const size_t sf = (size_t)nc * L.NF * 8, si = (size_t)nc * L.NI * 4, wf = (size_t)nw * L.NWF * 8, wi = (size_t)nw * L.NWI * 4;
-  const size_t zy_bytes = up((size_t)n_ind * L.K1 * sizeof(double));
-  const int64_t ldp = (C + 255) / 256 * 64;  // 64-byte aligned packed rows
-  int64_t nb = (((int64_t)1 << 30) / ldp) / 1024 * 1024;
-  if (ctx->tune.host_batch > 0) nb = (ctx->tune.host_batch + 3) / 4 * 4;  // tests: several batches on small inputs
-  nb = std::min(std::max<int64_t>(4, nb), (N + 3) / 4 * 4);
-  const int64_t wbytes = (N + 3) / 4, ldg_d = wbytes == ldg ? ldg : (wbytes + 63) / 64 * 64;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_gt2, (size_t)V * ldg_d + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_src, (size_t)C * 4 + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_xu, (size_t)nb * ldp + 256)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_lab, (size_t)N * (size_t)W * 4 + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_scale, by + bz + bu + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_p64, zy_bytes + (size_t)n_ind + 256)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_b64, up(sf) + wf + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_b32, up(si) + wi + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_misc, 256)) != GNX_OK) return rc;
-  char* sc = (char*)ctx->ws_scale.p;
-  double *d_y = (double*)sc, *d_Z = (double*)(sc + by);
-  uint8_t* d_use = use ? (uint8_t*)(sc + by + bz) : nullptr;
-  double* zy = (double*)ctx->ws_p64.p;
-  uint8_t* part = (uint8_t*)ctx->ws_p64.p + zy_bytes;
-  double *d_sf = (double*)ctx->ws_b64.p, *d_wf = (double*)((char*)ctx->ws_b64.p + up(sf));
-  int32_t *d_si = (int32_t*)ctx->ws_b32.p, *d_wi = (int32_t*)((char*)ctx->ws_b32.p + up(si));
-  unsigned long long* d_bad = (unsigned long long*)ctx->ws_misc.p;
-  const int32_t* d_lab = (const int32_t*)ctx->ws_lab.p;
-  HIPCHK(ctx, hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), s));
-  if (N == 0) {  // no individuals: the blocks of nobody
-    HIPCHK(ctx, assoc_launch(ctx->ws_xu.p, GNX_ROWS_PACKED2, ldp, d_lab, W, 0, M, W, A, K, c0, c1, zy, part, 0, d_sf, d_si, d_wf, d_wi, d_bad, s));
-  } else {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ws_src.p, src, (size_t)C * 4, hipMemcpyHostToDevice, s));
-    if (V > 0) {
-      if (ldg_d == ldg) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_gt2.p, G, (size_t)V * ldg, hipMemcpyHostToDevice, s));
-      else HIPCHK(ctx, hipMemcpy2DAsync(ctx->ws_gt2.p, (size_t)ldg_d, G, (size_t)ldg, (size_t)wbytes, (size_t)V, hipMemcpyHostToDevice, s));
-    }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ws_lab.p, labels, (size_t)N * (size_t)W * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(d_y, y, (size_t)n_ind * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(d_Z, Z, (size_t)n_ind * K * 8, hipMemcpyHostToDevice, s));
-    if (use) HIPCHK(ctx, hipMemcpyAsync(d_use, use, (size_t)n_ind, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_ancestry_assoc_prep, dim3((unsigned)((n_ind + 255) / 256)), dim3(256), 0, s, d_y, d_Z, d_use, n_ind, (int)K, zy, part);
-    HIPCHK(ctx, hipGetLastError());
-    for (int64_t n0 = 0; n0 < N; n0 += nb) {   // (nb is a multiple of 4: a batch holds whole individuals)
-      const int64_t n = std::min(nb, N - n0);
-      HIPCHK(ctx, gnx_launch_gt2_to_p2((const uint8_t*)ctx->ws_gt2.p, V, ldg_d, n0, n, (const int32_t*)ctx->ws_src.p, C, (uint8_t*)ctx->ws_xu.p, ldp, s));
-      HIPCHK(ctx, assoc_launch(ctx->ws_xu.p, GNX_ROWS_PACKED2, ldp, d_lab + n0 * W, W, n / 2, M, W, A, K, c0, c1, zy + (n0 / 2) * L.K1, part + n0 / 2,
-                               n0 > 0, d_sf, d_si, d_wf, d_wi, d_bad, s));
-    }
+  gnx_sum_gt2 st;
+  gnx_sum_pheno ph;
+  AsWork wk;
+  AsOut o;
+  if ((rc = gnx_sum_gt2_stage(ctx, G, V, ldg, N, src, labels, C, W, true, &st, s)) != GNX_OK) return rc;
+  if ((rc = gnx_sum_stage_pheno(ctx, y, Z, K, use, N / 2, &ph, s)) != GNX_OK) return rc;
+  if ((rc = assoc_work(ctx, N / 2, K, ph.d_y, ph.d_Z, ph.d_use, &wk, s)) != GNX_OK) return rc;
+  if ((rc = assoc_out(ctx, A, K, M, W, c0, c1, &o)) != GNX_OK) return rc;
+  if (N == 0)   // no individuals: the blocks of nobody
+    HIPCHK(ctx, assoc_launch(ctx->ws_xu.p, GNX_ROWS_PACKED2, st.ldp, st.d_lab, W, 0, M, W, A, K, c0, c1, wk.zy, wk.part, 0, o.d_sf, o.d_si, o.d_wf, o.d_wi,
+                             wk.d_bad, s));
+  for (int64_t n0 = 0; n0 < N; n0 += st.nb) {   // (nb is a multiple of 4: a batch holds whole individuals)
+    const int64_t n = std::min(st.nb, N - n0);
+    HIPCHK(ctx, gnx_sum_gt2_batch(st, n0, n, C, ctx->ws_xu.p, s));
+    HIPCHK(ctx, assoc_launch(ctx->ws_xu.p, GNX_ROWS_PACKED2, st.ldp, st.d_lab + n0 * W, W, n / 2, M, W, A, K, c0, c1, wk.zy + (n0 / 2) * (K + 1),
+                             wk.part + n0 / 2, n0 > 0, o.d_sf, o.d_si, o.d_wf, o.d_wi, wk.d_bad, s));
   }
   unsigned long long h_bad = 0;
-  HIPCHK(ctx, hipMemcpyAsync(&h_bad, d_bad, sizeof h_bad, hipMemcpyDeviceToHost, s));
-  HIPCHK(ctx, hipMemcpyAsync(snp_f64, d_sf, sf, hipMemcpyDeviceToHost, s));
-  HIPCHK(ctx, hipMemcpyAsync(snp_i32, d_si, si, hipMemcpyDeviceToHost, s));
-  HIPCHK(ctx, hipMemcpyAsync(win_f64, d_wf, wf, hipMemcpyDeviceToHost, s));
-  HIPCHK(ctx, hipMemcpyAsync(win_i32, d_wi, wi, hipMemcpyDeviceToHost, s));
-  HIPCHK(ctx, hipStreamSynchronize(s));
-  if (n_bad) *n_bad = (int64_t)h_bad;
-  if (h_bad)
-    return gnx_fail(ctx, GNX_EINVAL, "ancestry_assoc_stats_gt2: " + std::to_string(h_bad) + " labels lie outside [0, " + std::to_string(A) +
-                                         "); an individual with such a label takes no part at that window");
-  return GNX_OK;
+  HIPCHK(ctx, hipMemcpyAsync(&h_bad, wk.d_bad, sizeof h_bad, hipMemcpyDeviceToHost, s));
+  if ((rc = assoc_copy_out(ctx, o, snp_f64, snp_i32, win_f64, win_i32, s)) != GNX_OK) return rc;
+  return gnx_sum_label_verdict(ctx, "ancestry_assoc_stats_gt2", h_bad, A, AS_TAIL, n_bad);
 }

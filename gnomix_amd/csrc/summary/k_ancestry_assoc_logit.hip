@@ -26,7 +26,7 @@
 // This is the VALU form.  The dense block H_UU = sum_i w_i u_i u_i^T of a tile is a float64 product (tile x n) (n x P (P + 1) / 2) that
 // v_mfma_f64_16x16x4 could carry; it is NOT built here (DESIGN.md section 4.19 says what that would take).
 #include "../gnx_exp.h"
-#include "gnx_assoc_rows.h"
+#include "gnx_summary_host.h"
 
 namespace {
 
@@ -377,23 +377,19 @@ int lg_tile_cols(int Q) {
   return (int)(tc > (size_t)LG_THREADS ? LG_THREADS : tc);
 }
 
-// every refusal before the launch; GNX_OK or the code
-int logit_check(gnx_ctx* ctx, const void* rows, int row_kind, int64_t ld_rows, const void* labels, int64_t ld_labels, int64_t N, int64_t C, int64_t M,
-                int64_t W, int32_t A, const void* y, const void* Z, int32_t K, int32_t min_ac, int64_t c0, int64_t c1, double tol, int32_t max_iter,
-                const void* snp_f64, const void* snp_i32, const void* win_f64, const void* win_i32) {
+// every refusal before the launch; GNX_OK or the code.  built: the rows are built by this call (the file path's form)
+int logit_check(gnx_ctx* ctx, bool built, const void* rows, int row_kind, int64_t ld_rows, const void* labels, int64_t ld_labels, int64_t N, int64_t C,
+                int64_t M, int64_t W, int32_t A, const void* y, const void* Z, int32_t K, int32_t min_ac, int64_t c0, int64_t c1, double tol,
+                int32_t max_iter, const void* snp_f64, const void* snp_i32, const void* win_f64, const void* win_i32) {
   const std::string w("ancestry_assoc_logit");
-  if (!ctx->usable) return gnx_fail(ctx, GNX_ESTATE, "context has no device (gnx_init failed)");
-  if (row_kind != GNX_ROWS_INT8 && row_kind != GNX_ROWS_PACKED2) return gnx_fail(ctx, GNX_EINVAL, w + ": row_kind is GNX_ROWS_INT8 or GNX_ROWS_PACKED2");
-  if (N < 0 || C < 1 || A < 1) return gnx_fail(ctx, GNX_EINVAL, w + ": need N >= 0, C >= 1 and A >= 1");
-  if (N & 1) return gnx_fail(ctx, GNX_EINVAL, w + ": N must be even (an individual has two haplotype rows)");
-  if (M < 1 || W < 1 || M > C || W > C / M) return gnx_fail(ctx, GNX_EINVAL, w + ": need M >= 1, W >= 1 and M * W <= C");
+  const int rc = gnx_sum_geometry_check(ctx, "ancestry_assoc_logit", GNX_SUM_N_EVEN | GNX_SUM_OWN_NULLS, rows, row_kind, ld_rows, labels, ld_labels, N, C,
+                                        M, W, A);
+  if (rc != GNX_OK) return rc;
   if (K < 1) return gnx_fail(ctx, GNX_EINVAL, w + ": need K >= 1 covariates (the caller supplies the intercept column)");
   if (min_ac < 1) return gnx_fail(ctx, GNX_EINVAL, w + ": need min_ac >= 1");
   if (!(tol >= 0.0) || !std::isfinite(tol) || max_iter < 1) return gnx_fail(ctx, GNX_EINVAL, w + ": need a finite tol >= 0 and max_iter >= 1");
   if (c0 < 0 || c1 > C || c0 >= c1) return gnx_fail(ctx, GNX_EINVAL, w + ": need 0 <= c0 < c1 <= C");
-  if (ld_rows < as_min_row_bytes(row_kind, C)) return gnx_fail(ctx, GNX_EINVAL, w + ": the rows' stride is smaller than a row (C bytes, or ceil(C / 4) packed)");
-  if (ld_labels < W) return gnx_fail(ctx, GNX_EINVAL, w + ": the labels' row stride is smaller than W");
-  if (!rows || !labels || !y || !Z || !snp_f64 || !snp_i32 || !win_f64 || !win_i32)
+  if ((!built && !rows) || !labels || !y || !Z || !snp_f64 || !snp_i32 || !win_f64 || !win_i32)
     return gnx_fail(ctx, GNX_EINVAL, w + ": a null pointer (only use, theta and n_bad may be NULL)");
   const int64_t Q = (int64_t)K + 2 * (int64_t)A - 1;
   if (K > GNX_ASSOC_MAX_K || Q > GNX_ASSOC_LOGIT_MAX_Q)
@@ -403,24 +399,7 @@ int logit_check(gnx_ctx* ctx, const void* rows, int row_kind, int64_t ld_rows, c
   return GNX_OK;
 }
 
-// the workspace of one call: zy | part in ws_p64, the two counters in ws_misc
-struct LgWork {
-  double* zy;
-  uint8_t* part;
-  unsigned long long *d_bad, *d_bad_y;
-};
-
-int logit_work(gnx_ctx* ctx, int64_t n_ind, int K, LgWork* wk) {
-  const size_t zy_bytes = (((size_t)n_ind * (K + 1) * sizeof(double)) + 255) & ~(size_t)255;
-  int rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_p64, zy_bytes + (size_t)n_ind + 256)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_misc, 256)) != GNX_OK) return rc;
-  wk->zy = (double*)ctx->ws_p64.p;
-  wk->part = (uint8_t*)ctx->ws_p64.p + zy_bytes;
-  wk->d_bad = (unsigned long long*)ctx->ws_misc.p;
-  wk->d_bad_y = wk->d_bad + 1;
-  return GNX_OK;
-}
+const char* const LG_TAIL = "an individual with such a label takes no part at that window";
 
 // prep, the verdict on y (GNX_EINVAL before any fit, nothing written), the null fits, the SNP fits, the verdict on the labels.
 // Device pointers throughout; arguments checked by the caller.  Synchronises the stream twice.  *ran: the fits ran and the outputs are
@@ -433,11 +412,16 @@ int logit_run(gnx_ctx* ctx, const char* who, const void* d_rows, int row_kind, i
   const LgLayout L(A, K);
   const int64_t n_ind = N / 2;
   *ran = false;
-  LgWork wk;
-  int rc = logit_work(ctx, n_ind, K, &wk);
-  if (rc != GNX_OK) return rc;
+  struct {   // the workspace of one call: zy | part in ws_p64, the two counters (labels, phenotypes) in ws_misc
+    double* zy;
+    uint8_t* part;
+    unsigned long long *d_bad, *d_bad_y;
+  } wk;
+  int rc;
+  if ((rc = gnx_sum_zy_part(ctx, n_ind, K, &wk.zy, &wk.part)) != GNX_OK) return rc;
+  if ((rc = gnx_sum_bad_counter(ctx, 2, &wk.d_bad, s)) != GNX_OK) return rc;
+  wk.d_bad_y = wk.d_bad + 1;
   if (n_bad) *n_bad = 0;
-  HIPCHK(ctx, hipMemsetAsync(wk.d_bad, 0, 2 * sizeof(unsigned long long), s));
   unsigned long long h_bad[2] = {0, 0};
   if (n_ind > 0) {
     hipLaunchKernelGGL(k_ancestry_assoc_logit_prep, dim3((unsigned)((n_ind + 255) / 256)), dim3(256), 0, s, d_y, d_Z, d_use, n_ind, (int)K, wk.zy, wk.part,
@@ -480,11 +464,7 @@ int logit_run(gnx_ctx* ctx, const char* who, const void* d_rows, int row_kind, i
   HIPCHK(ctx, hipMemcpyAsync(h_bad, wk.d_bad, sizeof h_bad, hipMemcpyDeviceToHost, s));
   HIPCHK(ctx, hipStreamSynchronize(s));
   *ran = true;
-  if (n_bad) *n_bad = (int64_t)h_bad[0];
-  if (h_bad[0])
-    return gnx_fail(ctx, GNX_EINVAL, std::string(who) + ": " + std::to_string(h_bad[0]) + " labels lie outside [0, " + std::to_string(A) +
-                                         "); an individual with such a label takes no part at that window");
-  return GNX_OK;
+  return gnx_sum_label_verdict(ctx, who, h_bad[0], A, LG_TAIL, n_bad);
 }
 
 // host outputs of one call, staged in ws_b64 / ws_b32
@@ -533,8 +513,8 @@ extern "C" int gnx_ancestry_assoc_logit_dev(gnx_ctx* ctx, const void* d_rows, in
                                             double* d_snp_f64, int32_t* d_snp_i32, double* d_theta, double* d_win_f64, int32_t* d_win_i32,
                                             int64_t* n_bad) {
   if (!ctx) return GNX_EINVAL;
-  int rc = logit_check(ctx, d_rows, row_kind, ld_rows, d_labels, ld_labels, N, C, M, W, A, d_y, d_Z, K, min_ac, c0, c1, tol, max_iter, d_snp_f64, d_snp_i32,
-                       d_win_f64, d_win_i32);
+  int rc = logit_check(ctx, false, d_rows, row_kind, ld_rows, d_labels, ld_labels, N, C, M, W, A, d_y, d_Z, K, min_ac, c0, c1, tol, max_iter, d_snp_f64,
+                       d_snp_i32, d_win_f64, d_win_i32);
   if (rc != GNX_OK) return rc;
   GNX_BIND_DEVICE(ctx);
   bool ran;
@@ -542,43 +522,19 @@ extern "C" int gnx_ancestry_assoc_logit_dev(gnx_ctx* ctx, const void* d_rows, in
                    max_iter, d_snp_f64, d_snp_i32, d_theta, d_win_f64, d_win_i32, n_bad, &ran);
 }
 
-extern "C" int gnx_ancestry_assoc_logit(gnx_ctx* ctx, const int8_t* X, int64_t ld_rows, const int32_t* labels, int64_t ld_labels, int64_t N, int64_t C,
-                                        int64_t M, int64_t W, int32_t A, const double* y, const double* Z, int32_t K, const uint8_t* use,
-                                        int32_t min_ac, int64_t c0, int64_t c1, double tol, int32_t max_iter, double* snp_f64, int32_t* snp_i32,
-                                        double* theta, double* win_f64, int32_t* win_i32, int64_t* n_bad) {
-  if (!ctx) return GNX_EINVAL;
-  int rc = logit_check(ctx, X, GNX_ROWS_INT8, ld_rows, labels, ld_labels, N, C, M, W, A, y, Z, K, min_ac, c0, c1, tol, max_iter, snp_f64, snp_i32, win_f64,
-                       win_i32);
-  if (rc != GNX_OK) return rc;
-  GNX_BIND_DEVICE(ctx);
-  hipStream_t s = ctx->stream;
-  const int64_t n_ind = N / 2, nc = c1 - c0, nw = as_win(c1 - 1, M, W) - as_win(c0, M, W) + 1;
-  const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  // inputs: rows -> ws_xu, labels -> ws_lab, y | Z | use -> ws_scale; outputs: float64 in ws_b64, int32 in ws_b32
-  const size_t br = N > 0 ? (size_t)(N - 1) * (size_t)ld_rows + (size_t)C : 0;
-  const size_t bl = N > 0 ? ((size_t)(N - 1) * (size_t)ld_labels + (size_t)W) * sizeof(int32_t) : 0;
-  const size_t by = up((size_t)n_ind * 8), bz = up((size_t)n_ind * K * 8), bu = up((size_t)n_ind);
-  LgOut o;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_xu, br + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_lab, bl + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_scale, by + bz + bu + 64)) != GNX_OK) return rc;
-  if ((rc = logit_out(ctx, A, K, nc, nw, theta != nullptr, &o)) != GNX_OK) return rc;
-  char* sc = (char*)ctx->ws_scale.p;
-  double *d_y = (double*)sc, *d_Z = (double*)(sc + by);
-  uint8_t* d_use = use ? (uint8_t*)(sc + by + bz) : nullptr;
-  if (N > 0) {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ws_xu.p, X, br, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ws_lab.p, labels, bl, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(d_y, y, (size_t)n_ind * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(d_Z, Z, (size_t)n_ind * K * 8, hipMemcpyHostToDevice, s));
-    if (use) HIPCHK(ctx, hipMemcpyAsync(d_use, use, (size_t)n_ind, hipMemcpyHostToDevice, s));
-  }
-  int64_t nb = 0;
+
+namespace {
+// the tail the two host forms share: the fits over DEVICE rows and labels with the staged phenotypes, then the outputs -> the host.
+// GNX_EINVAL for labels out of range (the fits ran): the results stand and are handed over; any other failure leaves the outputs alone.
+int logit_host_run(gnx_ctx* ctx, const char* who, const void* d_rows, int row_kind, int64_t ld_rows, const int32_t* d_labels, int64_t ld_labels, int64_t N,
+                   int64_t C, int64_t M, int64_t W, int32_t A, const gnx_sum_pheno& ph, int32_t K, int32_t min_ac, int64_t c0, int64_t c1, double tol,
+                   int32_t max_iter, const LgOut& o, double* snp_f64, int32_t* snp_i32, double* theta, double* win_f64, int32_t* win_i32,
+                   int64_t* n_bad) {
+  int64_t nbad = 0;
   bool ran;
-  rc = logit_run(ctx, "ancestry_assoc_logit", ctx->ws_xu.p, GNX_ROWS_INT8, ld_rows, (const int32_t*)ctx->ws_lab.p, ld_labels, N, C, M, W, A, d_y, d_Z, K,
-                 d_use, min_ac, c0, c1, tol, max_iter, o.d_sf, o.d_si, o.d_th, o.d_wf, o.d_wi, &nb, &ran);
-  if (n_bad) *n_bad = nb;
-  // GNX_EINVAL for labels out of range (the fits ran): the results stand and are handed over; any other failure leaves the outputs alone
+  const int rc = logit_run(ctx, who, d_rows, row_kind, ld_rows, d_labels, ld_labels, N, C, M, W, A, ph.d_y, ph.d_Z, K, ph.d_use, min_ac, c0, c1, tol,
+                           max_iter, o.d_sf, o.d_si, o.d_th, o.d_wf, o.d_wi, &nbad, &ran);
+  if (n_bad) *n_bad = nbad;
   if (!ran) return rc;
   const std::string msg = ctx->err;
   const int rc2 = logit_copy_out(ctx, o, snp_f64, snp_i32, theta, win_f64, win_i32);
@@ -586,10 +542,31 @@ extern "C" int gnx_ancestry_assoc_logit(gnx_ctx* ctx, const int8_t* X, int64_t l
   ctx->err = msg;
   return rc;
 }
+}  // namespace
+
+extern "C" int gnx_ancestry_assoc_logit(gnx_ctx* ctx, const int8_t* X, int64_t ld_rows, const int32_t* labels, int64_t ld_labels, int64_t N, int64_t C,
+                                        int64_t M, int64_t W, int32_t A, const double* y, const double* Z, int32_t K, const uint8_t* use,
+                                        int32_t min_ac, int64_t c0, int64_t c1, double tol, int32_t max_iter, double* snp_f64, int32_t* snp_i32,
+                                        double* theta, double* win_f64, int32_t* win_i32, int64_t* n_bad) {
+  if (!ctx) return GNX_EINVAL;
+  int rc = logit_check(ctx, false, X, GNX_ROWS_INT8, ld_rows, labels, ld_labels, N, C, M, W, A, y, Z, K, min_ac, c0, c1, tol, max_iter, snp_f64, snp_i32,
+                       win_f64, win_i32);
+  if (rc != GNX_OK) return rc;
+  GNX_BIND_DEVICE(ctx);
+  hipStream_t s = ctx->stream;
+  // inputs: rows -> ws_xu, labels -> ws_lab, y | Z | use -> ws_scale; outputs: float64 in ws_b64, int32 in ws_b32
+  gnx_sum_pheno ph;
+  LgOut o;
+  if ((rc = gnx_sum_stage_rows_labels(ctx, X, GNX_ROWS_INT8, ld_rows, labels, ld_labels, N, C, W, s)) != GNX_OK) return rc;
+  if ((rc = gnx_sum_stage_pheno(ctx, y, Z, K, use, N / 2, &ph, s)) != GNX_OK) return rc;
+  if ((rc = logit_out(ctx, A, K, c1 - c0, as_win(c1 - 1, M, W) - as_win(c0, M, W) + 1, theta != nullptr, &o)) != GNX_OK) return rc;
+  return logit_host_run(ctx, "ancestry_assoc_logit", ctx->ws_xu.p, GNX_ROWS_INT8, ld_rows, (const int32_t*)ctx->ws_lab.p, ld_labels, N, C, M, W, A, ph, K,
+                        min_ac, c0, c1, tol, max_iter, o, snp_f64, snp_i32, theta, win_f64, win_i32, n_bad);
+}
 
 // The file path's form.  A Newton step needs every individual, so the packed rows of ALL individuals are built in HBM first
-// (N ceil(C / 4) bytes, batch by batch with gnx_infer_gt2's staging: GNX_HOST_BATCH only governs how they are built), then the fits run
-// once over them: the results are gnx_ancestry_assoc_logit's of the vcf_to_npy matrix bit for bit.
+// (N rows of gnx_sum_gt2's pitch, batch by batch with gnx_infer_gt2's staging: GNX_HOST_BATCH only governs how they are built), then the
+// fits run once over them: the results are gnx_ancestry_assoc_logit's of the vcf_to_npy matrix bit for bit.
 extern "C" int gnx_ancestry_assoc_logit_gt2(gnx_model* m, const uint8_t* G, int64_t V, int64_t ldg, int64_t N, const int32_t* src,
                                             const int32_t* labels, const double* y, const double* Z, int32_t K, const uint8_t* use, int32_t min_ac,
                                             int64_t c0, int64_t c1, double tol, int32_t max_iter, double* snp_f64, int32_t* snp_i32, double* theta,
@@ -598,60 +575,22 @@ extern "C" int gnx_ancestry_assoc_logit_gt2(gnx_model* m, const uint8_t* G, int6
   gnx_ctx* ctx = m->ctx;
   const int64_t C = m->info.C, M = m->info.M, W = m->info.W;
   const int32_t A = m->info.A;
-  if (N < 0 || V < 0 || ldg < (N + 3) / 4 || !src || (N > 0 && V > 0 && !G))
-    return gnx_fail(ctx, GNX_EINVAL, "ancestry_assoc_logit_gt2: bad G / V / ldg / N / src");
-  const int8_t* some_rows = (const int8_t*)src;   // (the rows are built here: any non-null pointer passes the shared check)
-  int rc = logit_check(ctx, some_rows, GNX_ROWS_PACKED2, (C + 3) / 4, labels, W, N, C, M, W, A, y, Z, K, min_ac, c0, c1, tol, max_iter, snp_f64, snp_i32,
-                       win_f64, win_i32);
+  int rc = gnx_sum_gt2_args(ctx, "ancestry_assoc_logit_gt2", G, V, ldg, N, src);
   if (rc != GNX_OK) return rc;
-  for (int64_t c = 0; c < C; ++c) {
-    const int32_t sv = src[c];
-    if (sv != -1 && (sv < 0 || (int64_t)(sv & 0x3FFFFFFF) >= V))
-      return gnx_fail(ctx, GNX_EINVAL, "ancestry_assoc_logit_gt2: column map entry outside the variant rows");
-  }
+  if ((rc = logit_check(ctx, true, nullptr, GNX_ROWS_PACKED2, (C + 3) / 4, labels, W, N, C, M, W, A, y, Z, K, min_ac, c0, c1, tol, max_iter, snp_f64,
+                        snp_i32, win_f64, win_i32)) != GNX_OK)
+    return rc;
+  if ((rc = gnx_sum_check_src(ctx, "ancestry_assoc_logit_gt2", src, C, V)) != GNX_OK) return rc;
   GNX_BIND_DEVICE(ctx);
   hipStream_t s = ctx->stream;
-  const int64_t n_ind = N / 2, nc = c1 - c0, nw = as_win(c1 - 1, M, W) - as_win(c0, M, W) + 1;
-  const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t by = up((size_t)n_ind * 8), bz = up((size_t)n_ind * K * 8), bu = up((size_t)n_ind);
-  const int64_t ldp = (C + 255) / 256 * 64;  // 64-byte aligned packed rows
-  int64_t nb = (((int64_t)1 << 30) / ldp) / 1024 * 1024;
-  if (ctx->tune.host_batch > 0) nb = (ctx->tune.host_batch + 3) / 4 * 4;  // tests: several batches on small inputs
-  nb = std::min(std::max<int64_t>(4, nb), (N + 3) / 4 * 4);
-  const int64_t wbytes = (N + 3) / 4, ldg_d = wbytes == ldg ? ldg : (wbytes + 63) / 64 * 64;
+  gnx_sum_gt2 st;
+  gnx_sum_pheno ph;
   LgOut o;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_gt2, (size_t)V * ldg_d + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_src, (size_t)C * 4 + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_xu, (size_t)((N + 3) / 4 * 4) * ldp + 256)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_lab, (size_t)N * (size_t)W * 4 + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_scale, by + bz + bu + 64)) != GNX_OK) return rc;
-  if ((rc = logit_out(ctx, A, K, nc, nw, theta != nullptr, &o)) != GNX_OK) return rc;
-  char* sc = (char*)ctx->ws_scale.p;
-  double *d_y = (double*)sc, *d_Z = (double*)(sc + by);
-  uint8_t* d_use = use ? (uint8_t*)(sc + by + bz) : nullptr;
-  if (N > 0) {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ws_src.p, src, (size_t)C * 4, hipMemcpyHostToDevice, s));
-    if (V > 0) {
-      if (ldg_d == ldg) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_gt2.p, G, (size_t)V * ldg, hipMemcpyHostToDevice, s));
-      else HIPCHK(ctx, hipMemcpy2DAsync(ctx->ws_gt2.p, (size_t)ldg_d, G, (size_t)ldg, (size_t)wbytes, (size_t)V, hipMemcpyHostToDevice, s));
-    }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ws_lab.p, labels, (size_t)N * (size_t)W * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(d_y, y, (size_t)n_ind * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(d_Z, Z, (size_t)n_ind * K * 8, hipMemcpyHostToDevice, s));
-    if (use) HIPCHK(ctx, hipMemcpyAsync(d_use, use, (size_t)n_ind, hipMemcpyHostToDevice, s));
-    for (int64_t n0 = 0; n0 < N; n0 += nb)   // (nb is a multiple of 4: a batch holds whole individuals)
-      HIPCHK(ctx, gnx_launch_gt2_to_p2((const uint8_t*)ctx->ws_gt2.p, V, ldg_d, n0, std::min(nb, N - n0), (const int32_t*)ctx->ws_src.p, C,
-                                       (uint8_t*)ctx->ws_xu.p + (size_t)n0 * ldp, ldp, s));
-  }
-  int64_t nbad = 0;
-  bool ran;
-  rc = logit_run(ctx, "ancestry_assoc_logit_gt2", ctx->ws_xu.p, GNX_ROWS_PACKED2, ldp, (const int32_t*)ctx->ws_lab.p, W, N, C, M, W, A, d_y, d_Z, K, d_use,
-                 min_ac, c0, c1, tol, max_iter, o.d_sf, o.d_si, o.d_th, o.d_wf, o.d_wi, &nbad, &ran);
-  if (n_bad) *n_bad = nbad;
-  if (!ran) return rc;
-  const std::string msg = ctx->err;
-  const int rc2 = logit_copy_out(ctx, o, snp_f64, snp_i32, theta, win_f64, win_i32);
-  if (rc2 != GNX_OK) return rc2;
-  ctx->err = msg;
-  return rc;
+  if ((rc = gnx_sum_gt2_stage(ctx, G, V, ldg, N, src, labels, C, W, false, &st, s)) != GNX_OK) return rc;
+  if ((rc = gnx_ws_reserve(ctx, ctx->ws_xu, (size_t)N * st.ldp + 256)) != GNX_OK) return rc;
+  if ((rc = gnx_sum_stage_pheno(ctx, y, Z, K, use, N / 2, &ph, s)) != GNX_OK) return rc;
+  if ((rc = logit_out(ctx, A, K, c1 - c0, as_win(c1 - 1, M, W) - as_win(c0, M, W) + 1, theta != nullptr, &o)) != GNX_OK) return rc;
+  HIPCHK(ctx, gnx_sum_gt2_all_rows(st, N, C, ctx->ws_xu.p, s));
+  return logit_host_run(ctx, "ancestry_assoc_logit_gt2", ctx->ws_xu.p, GNX_ROWS_PACKED2, st.ldp, st.d_lab, W, N, C, M, W, A, ph, K, min_ac, c0, c1, tol,
+                        max_iter, o, snp_f64, snp_i32, theta, win_f64, win_i32, n_bad);
 }

@@ -39,7 +39,7 @@
 //    segment (the case of many individuals) uses plain stores and zeroes nothing.
 // k_ancestry_pairs_labels: the labels outside [0, A) in the windows that meet [c0, c1), counted for the verdict after the launch.
 // No scratch, no runtime-indexed register array, plain vector stores or vector atomics only.  Index arithmetic is 64-bit throughout.
-#include "gnx_assoc_rows.h"
+#include "gnx_summary_host.h"
 
 namespace {
 
@@ -174,21 +174,18 @@ __global__ __launch_bounds__(256) void k_ancestry_pairs_labels(const int32_t* __
   if (mine) atomicAdd(bad, (unsigned long long)mine);
 }
 
-// every refusal that needs no device memory; GNX_OK or the code
-int pairs_check(gnx_ctx* ctx, const char* who, const void* rows, int row_kind, int64_t ld_rows, const void* labels, int64_t ld_labels, int64_t N,
-                int64_t C, int64_t M, int64_t W, int32_t A, int32_t ancestry, int64_t c0, int64_t c1, int64_t ld, int64_t dbg) {
+const char* const PR_TAIL = "such a haplotype counts for no ancestry at that window";
+
+// every refusal that needs no device memory; GNX_OK or the code.  built: the rows are built by this call (the file path's form)
+int pairs_check(gnx_ctx* ctx, const char* who, bool built, const void* rows, int row_kind, int64_t ld_rows, const void* labels, int64_t ld_labels,
+                int64_t N, int64_t C, int64_t M, int64_t W, int32_t A, int32_t ancestry, int64_t c0, int64_t c1, int64_t ld, int64_t dbg) {
   const std::string w(who);
-  if (!ctx->usable) return gnx_fail(ctx, GNX_ESTATE, "context has no device (gnx_init failed)");
-  if (row_kind != GNX_ROWS_INT8 && row_kind != GNX_ROWS_PACKED2) return gnx_fail(ctx, GNX_EINVAL, w + ": row_kind is GNX_ROWS_INT8 or GNX_ROWS_PACKED2");
-  if (N < 0 || C < 1 || A < 1) return gnx_fail(ctx, GNX_EINVAL, w + ": need N >= 0, C >= 1 and A >= 1");
-  if (N & 1) return gnx_fail(ctx, GNX_EINVAL, w + ": N must be even (an individual has two haplotype rows)");
-  if (M < 1 || W < 1 || M > C || W > C / M) return gnx_fail(ctx, GNX_EINVAL, w + ": need M >= 1, W >= 1 and M * W <= C");
+  const int rc = gnx_sum_geometry_check(ctx, who, GNX_SUM_N_EVEN | (built ? GNX_SUM_ROWS_BUILT : 0u), rows, row_kind, ld_rows, labels, ld_labels, N, C, M,
+                                        W, A);
+  if (rc != GNX_OK) return rc;
   if (ancestry < 0 || ancestry >= A) return gnx_fail(ctx, GNX_EINVAL, w + ": ancestry outside [0, A)");
   if (c0 < 0 || c1 <= c0 || c1 > C) return gnx_fail(ctx, GNX_EINVAL, w + ": need 0 <= c0 < c1 <= C");
-  if (ld_rows < as_min_row_bytes(row_kind, C)) return gnx_fail(ctx, GNX_EINVAL, w + ": the rows' stride is smaller than a row (C bytes, or ceil(C / 4) packed)");
-  if (ld_labels < W) return gnx_fail(ctx, GNX_EINVAL, w + ": the labels' row stride is smaller than W");
   if (ld < N / 2) return gnx_fail(ctx, GNX_EINVAL, w + ": the tables' row stride is smaller than N / 2");
-  if (N > 0 && (!rows || !labels)) return gnx_fail(ctx, GNX_EINVAL, w + ": no rows or no labels");
   if (N >= ((int64_t)1 << 31)) return gnx_fail(ctx, GNX_EINVAL, w + ": N must be below 2^31");
   if (dbg < 0) return gnx_fail(ctx, GNX_EINVAL, w + ": the debug argument must be >= 0 (0 = the built-in choice)");
   if (A > GNX_ALLELE_MAX_A) return gnx_fail(ctx, GNX_EUNSUPPORTED, w + ": A = " + std::to_string(A) + " ancestries, at most " + std::to_string(GNX_ALLELE_MAX_A));
@@ -237,22 +234,13 @@ int pairs_run(gnx_ctx* ctx, const char* who, const void* d_rows, int row_kind, i
     for (int32_t* tb : tabs)
       if (tb) HIPCHK(ctx, hipMemset2DAsync(tb, (size_t)ld * 4, 0, (size_t)n * 4, (size_t)n, s));
   }
-  const uintptr_t al = row_kind == GNX_ROWS_PACKED2 ? 4 : 16;
-  const int aligned = ((uintptr_t)d_rows % al == 0) && (ld_rows % (int64_t)al == 0);
+  const int aligned = gnx_sum_rows_aligned(d_rows, row_kind, ld_rows);
   PairsLaunch L{(const uint8_t*)d_rows, d_labels, ld_rows, ld_labels, n, C, M, W, c0, c1, c0 / PR_KC * PR_KC, cpb, ld,
                 ancestry, (int32_t)nseg, atomic, aligned, d_DD, d_DO, d_OO};
   const dim3 grid((unsigned)(pairs * nseg));
   if (row_kind == GNX_ROWS_PACKED2) hipLaunchKernelGGL(k_ancestry_pairs<GNX_ROWS_PACKED2>, grid, dim3(256), 0, s, L);
   else hipLaunchKernelGGL(k_ancestry_pairs<GNX_ROWS_INT8>, grid, dim3(256), 0, s, L);
   HIPCHK(ctx, hipGetLastError());
-  return GNX_OK;
-}
-
-int pairs_verdict(gnx_ctx* ctx, const char* who, unsigned long long h_bad, int32_t A, int64_t* n_bad) {
-  if (n_bad) *n_bad = (int64_t)h_bad;
-  if (h_bad)
-    return gnx_fail(ctx, GNX_EINVAL, std::string(who) + ": " + std::to_string(h_bad) + " labels lie outside [0, " + std::to_string(A) +
-                                         "); such a haplotype counts for no ancestry at that window");
   return GNX_OK;
 }
 
@@ -290,60 +278,49 @@ extern "C" int gnx_ancestry_pair_counts_dev(gnx_ctx* ctx, const void* d_rows, in
                                             int64_t N, int64_t C, int64_t M, int64_t W, int32_t A, int32_t ancestry, int64_t c0, int64_t c1,
                                             int32_t* d_DD, int32_t* d_DO, int32_t* d_OO, int64_t ld, int64_t debug_snps_per_block, int64_t* n_bad) {
   if (!ctx) return GNX_EINVAL;
-  int rc = pairs_check(ctx, "ancestry_pair_counts", d_rows, row_kind, ld_rows, d_labels, ld_labels, N, C, M, W, A, ancestry, c0, c1, ld,
-                       debug_snps_per_block);
+  const char* who = "ancestry_pair_counts";
+  int rc = pairs_check(ctx, who, false, d_rows, row_kind, ld_rows, d_labels, ld_labels, N, C, M, W, A, ancestry, c0, c1, ld, debug_snps_per_block);
   if (rc != GNX_OK) return rc;
   if (n_bad) *n_bad = 0;
   if (N == 0) return GNX_OK;
   GNX_BIND_DEVICE(ctx);
   hipStream_t s = ctx->stream;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_misc, 256)) != GNX_OK) return rc;
-  unsigned long long* d_bad = (unsigned long long*)ctx->ws_misc.p;
-  HIPCHK(ctx, hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), s));
-  if ((rc = pairs_run(ctx, "ancestry_pair_counts", d_rows, row_kind, ld_rows, d_labels, ld_labels, N, C, M, W, A, ancestry, c0, c1, d_DD, d_DO, d_OO, ld,
+  unsigned long long* d_bad;
+  if ((rc = gnx_sum_bad_counter(ctx, 1, &d_bad, s)) != GNX_OK) return rc;
+  if ((rc = pairs_run(ctx, who, d_rows, row_kind, ld_rows, d_labels, ld_labels, N, C, M, W, A, ancestry, c0, c1, d_DD, d_DO, d_OO, ld,
                       debug_snps_per_block, d_bad, s)) != GNX_OK)
     return rc;
-  unsigned long long h_bad = 0;
-  HIPCHK(ctx, hipMemcpyAsync(&h_bad, d_bad, sizeof h_bad, hipMemcpyDeviceToHost, s));
-  HIPCHK(ctx, hipStreamSynchronize(s));
-  return pairs_verdict(ctx, "ancestry_pair_counts", h_bad, A, n_bad);
+  return gnx_sum_read_verdict(ctx, who, d_bad, A, PR_TAIL, n_bad, s);
 }
 
 extern "C" int gnx_ancestry_pair_counts(gnx_ctx* ctx, const void* rows, int row_kind, int64_t ld_rows, const int32_t* labels, int64_t ld_labels, int64_t N,
                                         int64_t C, int64_t M, int64_t W, int32_t A, int32_t ancestry, int64_t c0, int64_t c1, int32_t* DD, int32_t* DO,
                                         int32_t* OO, int64_t ld, int64_t debug_snps_per_block, int64_t* n_bad) {
   if (!ctx) return GNX_EINVAL;
-  int rc = pairs_check(ctx, "ancestry_pair_counts", rows, row_kind, ld_rows, labels, ld_labels, N, C, M, W, A, ancestry, c0, c1, ld, debug_snps_per_block);
+  const char* who = "ancestry_pair_counts";
+  int rc = pairs_check(ctx, who, false, rows, row_kind, ld_rows, labels, ld_labels, N, C, M, W, A, ancestry, c0, c1, ld, debug_snps_per_block);
   if (rc != GNX_OK) return rc;
   if (n_bad) *n_bad = 0;
   if (N == 0) return GNX_OK;
   GNX_BIND_DEVICE(ctx);
   hipStream_t s = ctx->stream;
   const int64_t n = N / 2;
-  // the last row ends after its own bytes / labels, not after a whole stride
-  const size_t br = (size_t)(N - 1) * (size_t)ld_rows + (size_t)as_min_row_bytes(row_kind, C);
-  const size_t bl = ((size_t)(N - 1) * (size_t)ld_labels + (size_t)W) * sizeof(int32_t);
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_xu, br + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_lab, bl + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_misc, 256)) != GNX_OK) return rc;
   PairsHostBufs B;
+  unsigned long long *d_bad, h_bad = 0;
+  if ((rc = gnx_sum_stage_rows_labels(ctx, rows, row_kind, ld_rows, labels, ld_labels, N, C, W, s)) != GNX_OK) return rc;
+  if ((rc = gnx_sum_bad_counter(ctx, 1, &d_bad, s)) != GNX_OK) return rc;
   if ((rc = pairs_host_bufs(ctx, n, DD, DO, OO, &B)) != GNX_OK) return rc;
-  unsigned long long* d_bad = (unsigned long long*)ctx->ws_misc.p;
-  HIPCHK(ctx, hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), s));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->ws_xu.p, rows, br, hipMemcpyHostToDevice, s));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->ws_lab.p, labels, bl, hipMemcpyHostToDevice, s));
-  if ((rc = pairs_run(ctx, "ancestry_pair_counts", ctx->ws_xu.p, row_kind, ld_rows, (const int32_t*)ctx->ws_lab.p, ld_labels, N, C, M, W, A, ancestry, c0,
-                      c1, B.d_DD, B.d_DO, B.d_OO, n, debug_snps_per_block, d_bad, s)) != GNX_OK)
+  if ((rc = pairs_run(ctx, who, ctx->ws_xu.p, row_kind, ld_rows, (const int32_t*)ctx->ws_lab.p, ld_labels, N, C, M, W, A, ancestry, c0, c1, B.d_DD, B.d_DO,
+                      B.d_OO, n, debug_snps_per_block, d_bad, s)) != GNX_OK)
     return rc;
-  unsigned long long h_bad = 0;
   if ((rc = pairs_copy_out(ctx, B, n, DD, DO, OO, ld, d_bad, &h_bad, s)) != GNX_OK) return rc;
   // (GNX_EINVAL here = labels out of range: the tables stand and were handed over)
-  return pairs_verdict(ctx, "ancestry_pair_counts", h_bad, A, n_bad);
+  return gnx_sum_label_verdict(ctx, who, h_bad, A, PR_TAIL, n_bad);
 }
 
 // The file path's form.  A pair needs every row at once, so the WHOLE packed matrix is built in HBM, in device memory of this call's own
-// (N rows of ldp bytes, freed on return), batch by batch with gnx_launch_gt2_to_p2 (the staging, column map, row pitch and batch size of
-// gnx_ancestry_score_gt2); the kernel then runs once.
+// (N rows of gnx_sum_gt2's pitch, freed on return), batch by batch with gnx_infer_gt2's staging (gnx_summary_host.h); the kernel then
+// runs once.
 extern "C" int gnx_ancestry_pair_counts_gt2(gnx_model* m, const uint8_t* G, int64_t V, int64_t ldg, int64_t N, const int32_t* src, const int32_t* labels,
                                             int32_t ancestry, int64_t c0, int64_t c1, int32_t* DD, int32_t* DO, int32_t* OO, int64_t ld,
                                             int64_t* n_bad) {
@@ -351,60 +328,38 @@ extern "C" int gnx_ancestry_pair_counts_gt2(gnx_model* m, const uint8_t* G, int6
   gnx_ctx* ctx = m->ctx;
   const int64_t C = m->info.C, M = m->info.M, W = m->info.W;
   const int32_t A = m->info.A;
-  if (N < 0 || V < 0 || ldg < (N + 3) / 4 || !src || (N > 0 && V > 0 && !G))
-    return gnx_fail(ctx, GNX_EINVAL, "ancestry_pair_counts_gt2: bad G / V / ldg / N / src");
-  // (the rows are built here: any non-null pointer passes the shared check)
-  int rc = pairs_check(ctx, "ancestry_pair_counts_gt2", src, GNX_ROWS_PACKED2, (C + 3) / 4, labels, W, N, C, M, W, A, ancestry, c0, c1, ld, 0);
+  const char* who = "ancestry_pair_counts_gt2";
+  int rc = gnx_sum_gt2_args(ctx, who, G, V, ldg, N, src);
   if (rc != GNX_OK) return rc;
-  for (int64_t c = 0; c < C; ++c) {
-    const int32_t sv = src[c];
-    if (sv != -1 && (sv < 0 || (int64_t)(sv & 0x3FFFFFFF) >= V))
-      return gnx_fail(ctx, GNX_EINVAL, "ancestry_pair_counts_gt2: column map entry outside the variant rows");
-  }
+  if ((rc = pairs_check(ctx, who, true, nullptr, GNX_ROWS_PACKED2, (C + 3) / 4, labels, W, N, C, M, W, A, ancestry, c0, c1, ld, 0)) != GNX_OK) return rc;
+  if ((rc = gnx_sum_check_src(ctx, who, src, C, V)) != GNX_OK) return rc;
   if (n_bad) *n_bad = 0;
   if (N == 0) return GNX_OK;
   GNX_BIND_DEVICE(ctx);
   hipStream_t s = ctx->stream;
   const int64_t n = N / 2;
-  const int64_t ldp = (C + 255) / 256 * 64;  // 64-byte aligned packed rows
-  int64_t nb = (((int64_t)1 << 30) / ldp) / 1024 * 1024;  // a batch of the transpose: <= ~1 GiB of packed rows, whole 1024-haplotype tiles
-  if (ctx->tune.host_batch > 0) nb = (ctx->tune.host_batch + 3) / 4 * 4;  // tests: several batches on small inputs
-  nb = std::min(std::max<int64_t>(4, nb), (N + 3) / 4 * 4);
-  const int64_t wbytes = (N + 3) / 4, ldg_d = wbytes == ldg ? ldg : (wbytes + 63) / 64 * 64;
-  const int64_t n_pad = (N + nb - 1) / nb * nb;          // the last batch's transpose may write whole tiles
+  gnx_sum_gt2 st;
+  gnx_sum_gt2_sizes(ctx, C, ldg, N, &st);
   {
     size_t free_b = 0, total_b = 0;
     HIPCHK(ctx, hipMemGetInfo(&free_b, &total_b));
-    const size_t need = (size_t)n_pad * ldp + (size_t)V * ldg_d + 3 * (size_t)n * n * 4 + (size_t)N * W * 4 + (size_t)C * 4;
+    const size_t need = (size_t)N * st.ldp + (size_t)V * st.ldg_d + 3 * (size_t)n * n * 4 + (size_t)N * W * 4 + (size_t)C * 4;
     if (need > total_b)
       return gnx_fail(ctx, GNX_EUNSUPPORTED, "ancestry_pair_counts_gt2: the packed rows of " + std::to_string(N) + " haplotypes plus the tables take " +
                                                  std::to_string(need) + " bytes, the device has " + std::to_string(total_b));
   }
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_gt2, (size_t)V * ldg_d + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_src, (size_t)C * 4 + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_lab, (size_t)N * (size_t)W * 4 + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_misc, 256)) != GNX_OK) return rc;
   PairsHostBufs B;
-  if ((rc = pairs_host_bufs(ctx, n, DD, DO, OO, &B)) != GNX_OK) return rc;
   gnx_dev_tmp P;
-  if (P.alloc((size_t)n_pad * ldp + 256) != hipSuccess)
-    return gnx_fail(ctx, GNX_ENOMEM, "ancestry_pair_counts_gt2: no device memory for " + std::to_string((size_t)n_pad * ldp) + " bytes of packed rows");
-  unsigned long long* d_bad = (unsigned long long*)ctx->ws_misc.p;
-  HIPCHK(ctx, hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), s));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->ws_src.p, src, (size_t)C * 4, hipMemcpyHostToDevice, s));
-  if (V > 0) {
-    if (ldg_d == ldg) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_gt2.p, G, (size_t)V * ldg, hipMemcpyHostToDevice, s));
-    else HIPCHK(ctx, hipMemcpy2DAsync(ctx->ws_gt2.p, (size_t)ldg_d, G, (size_t)ldg, (size_t)wbytes, (size_t)V, hipMemcpyHostToDevice, s));
-  }
-  HIPCHK(ctx, hipMemcpyAsync(ctx->ws_lab.p, labels, (size_t)N * (size_t)W * 4, hipMemcpyHostToDevice, s));
-  for (int64_t n0 = 0; n0 < N; n0 += nb)
-    HIPCHK(ctx, gnx_launch_gt2_to_p2((const uint8_t*)ctx->ws_gt2.p, V, ldg_d, n0, std::min(nb, N - n0), (const int32_t*)ctx->ws_src.p, C,
-                                     P.as<uint8_t>() + n0 * ldp, ldp, s));
-  unsigned long long h_bad = 0;
-  rc = pairs_run(ctx, "ancestry_pair_counts_gt2", P.p, GNX_ROWS_PACKED2, ldp, (const int32_t*)ctx->ws_lab.p, W, N, C, M, W, A, ancestry, c0, c1, B.d_DD,
-                 B.d_DO, B.d_OO, n, 0, d_bad, s);
+  unsigned long long *d_bad, h_bad = 0;
+  if ((rc = pairs_host_bufs(ctx, n, DD, DO, OO, &B)) != GNX_OK) return rc;
+  if (P.alloc((size_t)N * st.ldp + 256) != hipSuccess)   // (before anything is enqueued)
+    return gnx_fail(ctx, GNX_ENOMEM, "ancestry_pair_counts_gt2: no device memory for " + std::to_string((size_t)N * st.ldp) + " bytes of packed rows");
+  if ((rc = gnx_sum_gt2_stage(ctx, G, V, ldg, N, src, labels, C, W, false, &st, s)) != GNX_OK) return rc;
+  if ((rc = gnx_sum_bad_counter(ctx, 1, &d_bad, s)) != GNX_OK) return rc;
+  HIPCHK(ctx, gnx_sum_gt2_all_rows(st, N, C, P.p, s));
+  rc = pairs_run(ctx, who, P.p, GNX_ROWS_PACKED2, st.ldp, st.d_lab, W, N, C, M, W, A, ancestry, c0, c1, B.d_DD, B.d_DO, B.d_OO, n, 0, d_bad, s);
   if (rc == GNX_OK) rc = pairs_copy_out(ctx, B, n, DD, DO, OO, ld, d_bad, &h_bad, s);
   else (void)hipStreamSynchronize(s);   // the rows are freed on return: nothing may still read them
   if (rc != GNX_OK) return rc;
-  return pairs_verdict(ctx, "ancestry_pair_counts_gt2", h_bad, A, n_bad);
+  return gnx_sum_label_verdict(ctx, who, h_bad, A, PR_TAIL, n_bad);
 }

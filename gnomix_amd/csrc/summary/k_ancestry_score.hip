@@ -35,7 +35,7 @@
 //   also sums the three counts.
 // Rows go in passes of at most SC_WS_BYTES of partials (a multiple of SC_ROWS rows each); the order is per individual, so passes
 // change nothing.  No per-thread array is indexed at run time; no scratch.
-#include "gnx_assoc_rows.h"
+#include "gnx_summary_host.h"
 
 namespace {
 
@@ -258,20 +258,18 @@ int sc_wcols(int cols, int A, int SB) {
   return wc;
 }
 
-// every refusal that needs no device memory; GNX_OK or the code
-int score_check(gnx_ctx* ctx, const char* who, const void* rows, int row_kind, int64_t ld_rows, const void* labels, int64_t ld_labels, int64_t N,
-                int64_t C, int64_t M, int64_t W, int32_t A, const void* weights, int32_t S, const void* effect, int64_t dbg_wpb, int64_t dbg_rpp) {
+const char* const SC_TAIL = "such a haplotype counts for no ancestry at that window";
+
+// every refusal that needs no device memory; GNX_OK or the code.  built: the rows are built by this call (the file path's form)
+int score_check(gnx_ctx* ctx, const char* who, bool built, const void* rows, int row_kind, int64_t ld_rows, const void* labels, int64_t ld_labels,
+                int64_t N, int64_t C, int64_t M, int64_t W, int32_t A, const void* weights, int32_t S, const void* effect, int64_t dbg_wpb,
+                int64_t dbg_rpp) {
   const std::string w(who);
-  if (!ctx->usable) return gnx_fail(ctx, GNX_ESTATE, "context has no device (gnx_init failed)");
-  if (row_kind != GNX_ROWS_INT8 && row_kind != GNX_ROWS_PACKED2) return gnx_fail(ctx, GNX_EINVAL, w + ": row_kind is GNX_ROWS_INT8 or GNX_ROWS_PACKED2");
-  if (N < 0 || C < 1 || A < 1) return gnx_fail(ctx, GNX_EINVAL, w + ": need N >= 0, C >= 1 and A >= 1");
-  if (N & 1) return gnx_fail(ctx, GNX_EINVAL, w + ": N must be even (an individual has two haplotype rows)");
-  if (M < 1 || W < 1 || M > C || W > C / M) return gnx_fail(ctx, GNX_EINVAL, w + ": need M >= 1, W >= 1 and M * W <= C");
+  const int rc = gnx_sum_geometry_check(ctx, who, GNX_SUM_N_EVEN | (built ? GNX_SUM_ROWS_BUILT : 0u), rows, row_kind, ld_rows, labels, ld_labels, N, C, M,
+                                        W, A);
+  if (rc != GNX_OK) return rc;
   if (S < 1) return gnx_fail(ctx, GNX_EINVAL, w + ": need S >= 1 scores");
   if (!weights || !effect) return gnx_fail(ctx, GNX_EINVAL, w + ": no weights or no effect alleles");
-  if (ld_rows < as_min_row_bytes(row_kind, C)) return gnx_fail(ctx, GNX_EINVAL, w + ": the rows' stride is smaller than a row (C bytes, or ceil(C / 4) packed)");
-  if (ld_labels < W) return gnx_fail(ctx, GNX_EINVAL, w + ": the labels' row stride is smaller than W");
-  if (N > 0 && (!rows || !labels)) return gnx_fail(ctx, GNX_EINVAL, w + ": no rows or no labels");
   if (N >= ((int64_t)1 << 31)) return gnx_fail(ctx, GNX_EINVAL, w + ": N must be below 2^31");
   if (dbg_wpb < 0 || dbg_rpp < 0) return gnx_fail(ctx, GNX_EINVAL, w + ": the debug arguments must be >= 0 (0 = the built-in choice)");
   if (A > SC_MAX_A) return gnx_fail(ctx, GNX_EUNSUPPORTED, w + ": A = " + std::to_string(A) + " ancestries, at most " + std::to_string(SC_MAX_A));
@@ -280,10 +278,10 @@ int score_check(gnx_ctx* ctx, const char* who, const void* rows, int row_kind, i
   return GNX_OK;
 }
 
-// the checking pass over DEVICE weights and effect: GNX_EINVAL names the count.  Zeroes bad[0] (labels) as well.  Synchronises.
+// the checking pass over DEVICE weights and effect: GNX_EINVAL names the count.  d_bad: three zeroed slots (labels, effect bytes, weights).
+// Synchronises.
 int score_verify(gnx_ctx* ctx, const char* who, const double* d_weights, const uint8_t* d_effect, int64_t C, int32_t A, int32_t S,
                  unsigned long long* d_bad, hipStream_t s) {
-  HIPCHK(ctx, hipMemsetAsync(d_bad, 0, 3 * sizeof(unsigned long long), s));
   const int64_t AS = (int64_t)A * S, total = C * AS;
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, (int64_t)ctx->n_cu * 16));
   hipLaunchKernelGGL(k_ancestry_score_check, dim3(grid), dim3(256), 0, s, d_weights, d_effect, C, AS, d_bad);
@@ -346,8 +344,7 @@ hipError_t score_launch(gnx_ctx* ctx, const void* d_rows, int row_kind, int64_t 
                         int64_t C, int64_t M, int64_t W, int32_t A, const double* d_w, int32_t S, const uint8_t* d_eff, double* d_score,
                         int32_t* d_ne, int32_t* d_ns, int32_t* d_nm, int64_t dbg_wpb, int64_t rp, unsigned long long* d_bad, hipStream_t s) {
   const int SB = sc_pad(S);
-  const uintptr_t al = row_kind == GNX_ROWS_PACKED2 ? 4 : 16;
-  const int aligned = ((uintptr_t)d_rows % al == 0) && (ld_rows % (int64_t)al == 0);
+  const int aligned = gnx_sum_rows_aligned(d_rows, row_kind, ld_rows);
   double* part = (double*)ctx->ws_p64.p;
   int32_t* cnt = (int32_t*)ctx->ws_p32.p;
   for (int64_t r0 = 0; r0 < N; r0 += rp) {
@@ -378,17 +375,6 @@ hipError_t score_launch(gnx_ctx* ctx, const void* d_rows, int row_kind, int64_t 
   return hipSuccess;
 }
 
-int score_verdict(gnx_ctx* ctx, const char* who, unsigned long long h_bad, int32_t A, int64_t* n_bad) {
-  if (n_bad) *n_bad = (int64_t)h_bad;
-  if (h_bad)
-    return gnx_fail(ctx, GNX_EINVAL, std::string(who) + ": " + std::to_string(h_bad) + " labels lie outside [0, " + std::to_string(A) +
-                                         "); such a haplotype counts for no ancestry at that window");
-  return GNX_OK;
-}
-
-}  // namespace
-
-namespace {
 // the _dev entry after score_check, N > 0.  *wrote: the outputs were written (GNX_OK, or GNX_EINVAL for labels out of range).
 int score_dev_run(gnx_ctx* ctx, const void* d_rows, int row_kind, int64_t ld_rows, const int32_t* d_labels, int64_t ld_labels, int64_t N, int64_t C,
                   int64_t M, int64_t W, int32_t A, const double* d_weights, int32_t S, const uint8_t* d_effect, double* d_score, int32_t* d_n_effect,
@@ -396,8 +382,8 @@ int score_dev_run(gnx_ctx* ctx, const void* d_rows, int row_kind, int64_t ld_row
   *wrote = false;
   hipStream_t s = ctx->stream;
   int rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_misc, 256)) != GNX_OK) return rc;
-  unsigned long long* d_bad = (unsigned long long*)ctx->ws_misc.p;
+  unsigned long long* d_bad;
+  if ((rc = gnx_sum_bad_counter(ctx, 3, &d_bad, s)) != GNX_OK) return rc;
   if ((rc = score_verify(ctx, "ancestry_score", d_weights, d_effect, C, A, S, d_bad, s)) != GNX_OK) return rc;
   const int64_t rp = sc_rows_per_pass(N, W, S, dbg_rpp);
   if ((rc = score_reserve(ctx, rp, W, S)) != GNX_OK) return rc;
@@ -407,7 +393,7 @@ int score_dev_run(gnx_ctx* ctx, const void* d_rows, int row_kind, int64_t ld_row
   HIPCHK(ctx, hipMemcpyAsync(&h_bad, d_bad, sizeof h_bad, hipMemcpyDeviceToHost, s));
   HIPCHK(ctx, hipStreamSynchronize(s));
   *wrote = true;
-  return score_verdict(ctx, "ancestry_score", h_bad, A, n_bad);
+  return gnx_sum_label_verdict(ctx, "ancestry_score", h_bad, A, SC_TAIL, n_bad);
 }
 }  // namespace
 
@@ -416,7 +402,7 @@ extern "C" int gnx_ancestry_score_dev(gnx_ctx* ctx, const void* d_rows, int row_
                                       const uint8_t* d_effect, double* d_score, int32_t* d_n_effect, int32_t* d_n_scored, int32_t* d_n_miss,
                                       int64_t debug_windows_per_block, int64_t debug_rows_per_pass, int64_t* n_bad) {
   if (!ctx) return GNX_EINVAL;
-  int rc = score_check(ctx, "ancestry_score", d_rows, row_kind, ld_rows, d_labels, ld_labels, N, C, M, W, A, d_weights, S, d_effect,
+  int rc = score_check(ctx, "ancestry_score", false, d_rows, row_kind, ld_rows, d_labels, ld_labels, N, C, M, W, A, d_weights, S, d_effect,
                        debug_windows_per_block, debug_rows_per_pass);
   if (rc != GNX_OK) return rc;
   if (n_bad) *n_bad = 0;
@@ -474,22 +460,16 @@ extern "C" int gnx_ancestry_score(gnx_ctx* ctx, const void* rows, int row_kind, 
                                   int32_t* n_effect, int32_t* n_scored, int32_t* n_miss, int64_t debug_windows_per_block,
                                   int64_t debug_rows_per_pass, int64_t* n_bad) {
   if (!ctx) return GNX_EINVAL;
-  int rc = score_check(ctx, "ancestry_score", rows, row_kind, ld_rows, labels, ld_labels, N, C, M, W, A, weights, S, effect, debug_windows_per_block,
-                       debug_rows_per_pass);
+  int rc = score_check(ctx, "ancestry_score", false, rows, row_kind, ld_rows, labels, ld_labels, N, C, M, W, A, weights, S, effect,
+                       debug_windows_per_block, debug_rows_per_pass);
   if (rc != GNX_OK) return rc;
   if (n_bad) *n_bad = 0;
   if (N == 0) return GNX_OK;
   GNX_BIND_DEVICE(ctx);
   hipStream_t s = ctx->stream;
-  // the last row ends after its own bytes / labels, not after a whole stride
-  const size_t br = (size_t)(N - 1) * (size_t)ld_rows + (size_t)as_min_row_bytes(row_kind, C);
-  const size_t bl = ((size_t)(N - 1) * (size_t)ld_labels + (size_t)W) * sizeof(int32_t);
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_xu, br + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_lab, bl + 64)) != GNX_OK) return rc;
   ScoreHostBufs B;
+  if ((rc = gnx_sum_stage_rows_labels(ctx, rows, row_kind, ld_rows, labels, ld_labels, N, C, W, s)) != GNX_OK) return rc;
   if ((rc = score_host_bufs(ctx, N, C, A, S, weights, effect, score, n_effect, n_scored, n_miss, &B, s)) != GNX_OK) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->ws_xu.p, rows, br, hipMemcpyHostToDevice, s));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->ws_lab.p, labels, bl, hipMemcpyHostToDevice, s));
   bool wrote;
   rc = score_dev_run(ctx, ctx->ws_xu.p, row_kind, ld_rows, (const int32_t*)ctx->ws_lab.p, ld_labels, N, C, M, W, A, B.d_w, S, B.d_eff, B.d_score, B.d_ne,
                      B.d_ns, B.d_nm, debug_windows_per_block, debug_rows_per_pass, n_bad, &wrote);
@@ -502,9 +482,9 @@ extern "C" int gnx_ancestry_score(gnx_ctx* ctx, const void* rows, int row_kind, 
   return rc;
 }
 
-// The file path's form: the packed rows of gnx_infer_gt2's batches (the staging, column map, row pitch and batch size of
-// gnx_ancestry_allele_counts_gt2), scored against the caller's labels batch by batch.  A batch holds whole individuals (its size is a
-// multiple of 4 haplotypes) and an individual's sums never leave its batch, so the outputs do not depend on the batch size.
+// The file path's form: the packed rows of gnx_infer_gt2's batches (gnx_summary_host.h: the staging, column map, row pitch and batch
+// size), scored against the caller's labels batch by batch.  A batch holds whole individuals (its size is a multiple of 4 haplotypes)
+// and an individual's sums never leave its batch, so the outputs do not depend on the batch size.
 extern "C" int gnx_ancestry_score_gt2(gnx_model* m, const uint8_t* G, int64_t V, int64_t ldg, int64_t N, const int32_t* src, const int32_t* labels,
                                       const double* weights, int32_t S, const uint8_t* effect, double* score, int32_t* n_effect, int32_t* n_scored,
                                       int32_t* n_miss, int64_t* n_bad) {
@@ -512,52 +492,33 @@ extern "C" int gnx_ancestry_score_gt2(gnx_model* m, const uint8_t* G, int64_t V,
   gnx_ctx* ctx = m->ctx;
   const int64_t C = m->info.C, M = m->info.M, W = m->info.W;
   const int32_t A = m->info.A;
-  if (N < 0 || V < 0 || ldg < (N + 3) / 4 || !src || (N > 0 && V > 0 && !G))
-    return gnx_fail(ctx, GNX_EINVAL, "ancestry_score_gt2: bad G / V / ldg / N / src");
-  // (the rows are built here: any non-null pointer passes the shared check)
-  int rc = score_check(ctx, "ancestry_score_gt2", src, GNX_ROWS_PACKED2, (C + 3) / 4, labels, W, N, C, M, W, A, weights, S, effect, 0, 0);
+  const char* who = "ancestry_score_gt2";
+  int rc = gnx_sum_gt2_args(ctx, who, G, V, ldg, N, src);
   if (rc != GNX_OK) return rc;
-  for (int64_t c = 0; c < C; ++c) {
-    const int32_t sv = src[c];
-    if (sv != -1 && (sv < 0 || (int64_t)(sv & 0x3FFFFFFF) >= V))
-      return gnx_fail(ctx, GNX_EINVAL, "ancestry_score_gt2: column map entry outside the variant rows");
-  }
+  if ((rc = score_check(ctx, who, true, nullptr, GNX_ROWS_PACKED2, (C + 3) / 4, labels, W, N, C, M, W, A, weights, S, effect, 0, 0)) != GNX_OK) return rc;
+  if ((rc = gnx_sum_check_src(ctx, who, src, C, V)) != GNX_OK) return rc;
   if (n_bad) *n_bad = 0;
   if (N == 0) return GNX_OK;
   GNX_BIND_DEVICE(ctx);
   hipStream_t s = ctx->stream;
-  const int64_t ldp = (C + 255) / 256 * 64;  // 64-byte aligned packed rows
-  int64_t nb = (((int64_t)1 << 30) / ldp) / 1024 * 1024;  // a batch: <= ~1 GiB of packed rows, whole 1024-haplotype tiles of the transpose
-  if (ctx->tune.host_batch > 0) nb = (ctx->tune.host_batch + 3) / 4 * 4;  // tests: several batches on small inputs
-  nb = std::min(std::max<int64_t>(4, nb), (N + 3) / 4 * 4);
-  const int64_t wbytes = (N + 3) / 4, ldg_d = wbytes == ldg ? ldg : (wbytes + 63) / 64 * 64;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_gt2, (size_t)V * ldg_d + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_src, (size_t)C * 4 + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_xu, (size_t)nb * ldp + 256)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_lab, (size_t)N * (size_t)W * 4 + 64)) != GNX_OK) return rc;
-  if ((rc = gnx_ws_reserve(ctx, ctx->ws_misc, 256)) != GNX_OK) return rc;
+  gnx_sum_gt2 st;
   ScoreHostBufs B;
+  unsigned long long* d_bad;
   if ((rc = score_host_bufs(ctx, N, C, A, S, weights, effect, score, n_effect, n_scored, n_miss, &B, s)) != GNX_OK) return rc;
-  unsigned long long* d_bad = (unsigned long long*)ctx->ws_misc.p;
-  if ((rc = score_verify(ctx, "ancestry_score_gt2", B.d_w, B.d_eff, C, A, S, d_bad, s)) != GNX_OK) return rc;
-  const int64_t rp = sc_rows_per_pass(std::min(nb, N), W, S, 0);
+  if ((rc = gnx_sum_bad_counter(ctx, 3, &d_bad, s)) != GNX_OK) return rc;
+  if ((rc = score_verify(ctx, who, B.d_w, B.d_eff, C, A, S, d_bad, s)) != GNX_OK) return rc;
+  if ((rc = gnx_sum_gt2_stage(ctx, G, V, ldg, N, src, labels, C, W, true, &st, s)) != GNX_OK) return rc;
+  const int64_t rp = sc_rows_per_pass(std::min(st.nb, N), W, S, 0);
   if ((rc = score_reserve(ctx, rp, W, S)) != GNX_OK) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->ws_src.p, src, (size_t)C * 4, hipMemcpyHostToDevice, s));
-  if (V > 0) {
-    if (ldg_d == ldg) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_gt2.p, G, (size_t)V * ldg, hipMemcpyHostToDevice, s));
-    else HIPCHK(ctx, hipMemcpy2DAsync(ctx->ws_gt2.p, (size_t)ldg_d, G, (size_t)ldg, (size_t)wbytes, (size_t)V, hipMemcpyHostToDevice, s));
-  }
-  HIPCHK(ctx, hipMemcpyAsync(ctx->ws_lab.p, labels, (size_t)N * (size_t)W * 4, hipMemcpyHostToDevice, s));
-  const int32_t* d_lab = (const int32_t*)ctx->ws_lab.p;
-  for (int64_t n0 = 0; n0 < N; n0 += nb) {   // (nb is a multiple of 4: a batch holds whole individuals)
-    const int64_t n = std::min(nb, N - n0), i0 = n0 / 2;
-    HIPCHK(ctx, gnx_launch_gt2_to_p2((const uint8_t*)ctx->ws_gt2.p, V, ldg_d, n0, n, (const int32_t*)ctx->ws_src.p, C, (uint8_t*)ctx->ws_xu.p, ldp, s));
-    HIPCHK(ctx, score_launch(ctx, ctx->ws_xu.p, GNX_ROWS_PACKED2, ldp, d_lab + n0 * W, W, n, C, M, W, A, B.d_w, S, B.d_eff,
+  for (int64_t n0 = 0; n0 < N; n0 += st.nb) {   // (nb is a multiple of 4: a batch holds whole individuals)
+    const int64_t n = std::min(st.nb, N - n0), i0 = n0 / 2;
+    HIPCHK(ctx, gnx_sum_gt2_batch(st, n0, n, C, ctx->ws_xu.p, s));
+    HIPCHK(ctx, score_launch(ctx, ctx->ws_xu.p, GNX_ROWS_PACKED2, st.ldp, st.d_lab + n0 * W, W, n, C, M, W, A, B.d_w, S, B.d_eff,
                              B.d_score ? B.d_score + i0 * A * S : nullptr, B.d_ne ? B.d_ne + i0 * A : nullptr, B.d_ns ? B.d_ns + i0 * A : nullptr,
                              B.d_nm ? B.d_nm + i0 * A : nullptr, 0, rp, d_bad, s));
   }
   unsigned long long h_bad = 0;
   HIPCHK(ctx, hipMemcpyAsync(&h_bad, d_bad, sizeof h_bad, hipMemcpyDeviceToHost, s));
   if ((rc = score_copy_out(ctx, B, N, A, S, score, n_effect, n_scored, n_miss, s)) != GNX_OK) return rc;
-  return score_verdict(ctx, "ancestry_score_gt2", h_bad, A, n_bad);
+  return gnx_sum_label_verdict(ctx, who, h_bad, A, SC_TAIL, n_bad);
 }

@@ -569,10 +569,22 @@ def test_shared_helpers_have_one_definition():
         "det_exp": (r"\bdouble det_exp\(", os.path.join("forest", "gnx_det_exp.h")),
         "pair_index": (r"\bint pair_index\(", os.path.join("svm", "gnx_svc_rbf.h")),
         "hipFree in a destructor": (r"~\w+\(\)\s*\{[^}]*hipFree\(", "gnx_internal.h"),
+        # the host side of the ancestry-specific ops (summary/gnx_summary_host.h declares them)
+        "the column-map check": (r"sv != -1 && \(sv < 0", os.path.join("summary", "gnx_summary_host.hip")),
+        "the rows / labels staging": (qual + r"\w+\s+\w*stage_rows_labels\([^()]*\)\s*\{", os.path.join("summary", "gnx_summary_host.hip")),
+        # (gnx_api_vcf.hip keeps gnx_infer_gt2's own gt2_stage: DESIGN.md names it as the remaining copy)
+        "the file path's staging": (qual + r"\w+\s+\w+_gt2_stage\([^()]*\)\s*\{", os.path.join("summary", "gnx_summary_host.hip")),
+        "the label verdict": (qual + r"\w+\s+\w*label_verdict\([^()]*\)\s*\{", os.path.join("summary", "gnx_summary_host.hip")),
+        "as_min_row_bytes": (qual + r"\w+\s+\w*min_row_bytes\([^()]*\)\s*\{", os.path.join("summary", "gnx_assoc_rows.h")),
     }
     for what, (pattern, home) in once.items():
         found = homes(pattern)
         assert [name for name, _ in found] == [home], f"{what}: expected one definition, in {home}; found {found}"
+    # whatever a copy of the file path's staging were called, it would have to size a batch and launch the transpose: under summary/ one
+    # file does (the last two entries); and the two sentences are built in one place
+    for sentence in ("column map entry outside the variant rows", "labels lie outside [0, ", "tune.host_batch", "gnx_launch_gt2_to_p2("):
+        found = sorted({name for name, _ in homes(re.escape(sentence)) if name.startswith("summary" + os.sep)})
+        assert found == [os.path.join("summary", "gnx_summary_host.hip")], f"{sentence!r} is built in one place under summary/: {found}"
     for retired in ("GBT_HIP", "FBT_HIP", "RF_HIP", "TRCHK"):
         found = homes(r"#\s*define\s+%s\b" % retired)
         assert not found, f"{retired} is retired (GNX_HIPRET in gnx_internal.h): {found}"
