@@ -18,6 +18,7 @@ GNX_ABI_VERSION = 16
 GNX_OK, GNX_EINVAL, GNX_ENOMEM, GNX_EHIP, GNX_EUNSUPPORTED, GNX_ESTATE, GNX_ESTALE = 0, -1, -2, -3, -4, -5, -6
 GNX_ROWS_INT8, GNX_ROWS_PACKED2 = 0, 1   # row_kind of gnx_ancestry_allele_counts / gnx_ancestry_dosage
 GNX_ALLELE_MAX_A = 32
+GNX_LD_MAX_BAND = 4096                   # offsets per SNP of gnx_ancestry_ld_counts
 GNX_SCORE_MAX_S = 16                     # scores per call of gnx_ancestry_score (the Python layer chunks a wider table)
 BASE_NONE, BASE_LOGISTIC, BASE_COVRSK_SVC, BASE_FOREST, BASE_RFOREST, BASE_KNN, BASE_NB, BASE_LDA = 0, 1, 2, 3, 4, 5, 6, 7
 SVC_KERNEL_SUBSTRINGS, SVC_KERNEL_POLY, SVC_KERNEL_ALL_LENGTHS, SVC_KERNEL_RBF = 0, 1, 2, 3
@@ -266,6 +267,12 @@ SYMBOLS = {
     "gnx_ancestry_pair_counts": (C.c_int, [_VP, _VP, _I, _I64, _VP, _I64, _I64, _I64, _I64, _I64, C.c_int32, C.c_int32, _I64, _I64, _VP, _VP, _VP,
                                            _I64, _I64, C.POINTER(_I64)]),
     "gnx_ancestry_pair_counts_gt2": (C.c_int, [_VP, _VP, _I64, _I64, _I64, _VP, _VP, C.c_int32, _I64, _I64, _VP, _VP, _VP, _I64, C.POINTER(_I64)]),
+    "gnx_ancestry_ld_counts_dev": (C.c_int, [_VP, _VP, _I, _I64, _VP, _I64, _I64, _I64, _I64, _I64, C.c_int32, C.c_int32, _I64, _I64, _I64, _VP, _VP, _VP,
+                                             _VP, _I64, _I64, C.POINTER(_I64)]),
+    "gnx_ancestry_ld_counts": (C.c_int, [_VP, _VP, _I, _I64, _VP, _I64, _I64, _I64, _I64, _I64, C.c_int32, C.c_int32, _I64, _I64, _I64, _VP, _VP, _VP,
+                                         _VP, _I64, _I64, C.POINTER(_I64)]),
+    "gnx_ancestry_ld_counts_gt2": (C.c_int, [_VP, _VP, _I64, _I64, _I64, _VP, _VP, C.c_int32, _I64, _I64, _I64, _VP, _VP, _VP, _VP, _I64,
+                                             C.POINTER(_I64)]),
     # include/gnomix_io.h: the file side
     "gnx_io_last_error": (C.c_char_p, []),
     "gnx_vcf_read": (C.c_int, [_VP, C.c_char_p, C.c_char_p, _I, C.POINTER(_VP)]),

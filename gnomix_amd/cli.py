@@ -135,7 +135,8 @@ class _Prefetch:
 def run_inference(base_args, model, snp_level=False, bed_file_output=False, verbose=False, timings=None, query=None, devices=None,
                   global_ancestry_output=False, ancestry_allele_freq_output=False, ancestry_assoc_output=False, phenotype_file=None,
                   ancestry_assoc_model="linear", ancestry_score_output=False, score_file=None, ancestry_mds_output=False,
-                  ancestry_mds_components=None, ancestry_mds_min_sites=None):
+                  ancestry_mds_components=None, ancestry_mds_min_sites=None, ancestry_clump_output=False, ancestry_clump_p1=None,
+                  ancestry_clump_p2=None, ancestry_clump_r2=None, ancestry_clump_kb=None):
     """gnomix.py:37-100 with the HIP model behind the same steps.  The query never becomes an (N, C) host matrix: the library
     parses the text into 2-bit rows (gnx_vcf_read), `column_map` keeps vcf_to_npy's bookkeeping (SNP intersection, REF flips,
     absent SNPs) as one int32 per model SNP, the GPU builds X and runs base + smoother (or Gnofix) on it, and the library
@@ -168,10 +169,22 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
     ancestry: the pair count tables from the model's own GPU, from the query's 2-bit rows and the labels the .msp gets
     (gnx_ancestry_pair_counts_gt2), the embedding on the host (gnomix_amd.asmds).  An ancestry with fewer than
     components + 1 individuals kept gets a header line and no rows.  Not with phase=True (ValueError before any work), for the same
-    reason."""
+    reason.
+    `ancestry_clump_output` (config key inference.ancestry_clump_output, off unless set; it needs ancestry_assoc_output; optional
+    inference.ancestry_clump_p1, _p2, _r2, _kb, defaults 1e-4, 1e-2, 0.5, 250): query_results.clumped.tsv as well, the association
+    result clumped ancestry by ancestry (gnomix_amd.ld.clump) with that ancestry's LD, counted on the model's own GPU from the query's
+    2-bit rows and the labels the .msp gets (gnx_ancestry_ld_counts_gt2).  Not with phase=True (ValueError before any
+    work), for the same reason."""
     from time import perf_counter as clock
     from . import postprocess as pp
     from . import vcfio
+    if ancestry_clump_output and base_args["phase"]:
+        raise ValueError("inference.ancestry_clump_output with phase=True: the phased haplotypes are not kept on this path; "
+                         "use HipGnomix.phase followed by HipGnomix.ancestry_association and HipGnomix.ancestry_clump")
+    if ancestry_clump_output and not ancestry_assoc_output:
+        raise ValueError("inference.ancestry_clump_output needs inference.ancestry_assoc_output (the p-values it clumps)")
+    clump_kw = {k: float(v) for k, v in (("p1", ancestry_clump_p1), ("p2", ancestry_clump_p2), ("r2", ancestry_clump_r2),
+                                         ("kb", ancestry_clump_kb)) if v is not None}
     if ancestry_allele_freq_output and base_args["phase"]:
         raise ValueError("inference.ancestry_allele_freq_output with phase=True: the phased haplotypes are not kept on this path; "
                          "use HipGnomix.phase followed by HipGnomix.allele_frequencies")
@@ -226,7 +239,8 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
         return _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out, T, t0, snp_level, bed_file_output, verbose,
                               global_ancestry_output, ancestry_allele_freq_output, ancestry_assoc_output, phenotype_file, ancestry_assoc_model,
                               ancestry_score_output=ancestry_score_output, score_file=score_file,
-                              ancestry_mds=(mds_k, mds_sites) if ancestry_mds_output else None)
+                              ancestry_mds=(mds_k, mds_sites) if ancestry_mds_output else None,
+                              ancestry_clump=clump_kw if ancestry_clump_output else None)
     finally:
         if own_group is not None:
             own_group.close()
@@ -234,7 +248,7 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
 
 def _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out, T, t0, snp_level, bed_file_output, verbose,
                    global_ancestry_output=False, ancestry_allele_freq_output=False, ancestry_assoc_output=False, phenotype_file=None,
-                   ancestry_assoc_model="linear", ancestry_score_output=False, score_file=None, ancestry_mds=None):
+                   ancestry_assoc_model="linear", ancestry_score_output=False, score_file=None, ancestry_mds=None, ancestry_clump=None):
     from time import perf_counter as clock
     from . import postprocess as pp
     from . import vcfio
@@ -304,6 +318,18 @@ def _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out,
             result = model.dev.ancestry_assoc_gt2(vcf.gt2, N, src, labels, y, Z, use)     # one GPU: the model's own
             pp.write_assoc(out_prefix, chm, model.snp_pos, model.M, model.W, result, model.population_order)
         T["write_assoc"] = clock() - t0
+        if ancestry_clump is not None:
+            t0 = clock()
+            from . import ld
+            pos = np.asarray(model.snp_pos).astype(np.int64)
+            band = ld.band_for(pos, ancestry_clump.get("kb", 250))
+            pv = np.asarray(result.p, dtype=np.float64)
+            index_of = np.full(pv.shape, -1, np.int64)
+            for a in range(model.A):                                                              # one GPU: the model's own
+                fetch = lambda c0, c1, a=a: model.dev.ancestry_ld_counts_gt2(vcf.gt2, N, src, labels, a, c0, c1, band)
+                index_of[:, a] = ld.clump(pv[:, a], pos, ld.BlockCache(fetch, model.C, max(4096, 4 * band)), **ancestry_clump)
+            pp.write_clumps(out_prefix, chm, model.snp_pos, index_of, pv, model.population_order)
+            T["write_clumps"] = clock() - t0
     if ancestry_score_output:
         t0 = clock()
         from . import score
@@ -390,7 +416,10 @@ def main(argv=None):
                       ancestry_assoc_model=inf.get("ancestry_assoc_model") or "linear",
                       ancestry_score_output=bool(inf.get("ancestry_score_output")), score_file=inf.get("score_file"),
                       ancestry_mds_output=bool(inf.get("ancestry_mds_output")), ancestry_mds_components=inf.get("ancestry_mds_components"),
-                      ancestry_mds_min_sites=inf.get("ancestry_mds_min_sites"))
+                      ancestry_mds_min_sites=inf.get("ancestry_mds_min_sites"),
+                      ancestry_clump_output=bool(inf.get("ancestry_clump_output")), ancestry_clump_p1=inf.get("ancestry_clump_p1"),
+                      ancestry_clump_p2=inf.get("ancestry_clump_p2"), ancestry_clump_r2=inf.get("ancestry_clump_r2"),
+                      ancestry_clump_kb=inf.get("ancestry_clump_kb"))
         if os.environ.get("GNX_CLI_TIMING"):
             T["since_process_start"] = _since_process_start()
             sys.stderr.write("gnomix_amd timings (s): " + ", ".join("%s %.3f" % kv for kv in T.items()) + "\n")
@@ -556,7 +585,10 @@ def train_main(argv):
                       ancestry_assoc_model=inf.get("ancestry_assoc_model") or "linear",
                       ancestry_score_output=bool(inf.get("ancestry_score_output")), score_file=inf.get("score_file"),
                       ancestry_mds_output=bool(inf.get("ancestry_mds_output")), ancestry_mds_components=inf.get("ancestry_mds_components"),
-                      ancestry_mds_min_sites=inf.get("ancestry_mds_min_sites"))
+                      ancestry_mds_min_sites=inf.get("ancestry_mds_min_sites"),
+                      ancestry_clump_output=bool(inf.get("ancestry_clump_output")), ancestry_clump_p1=inf.get("ancestry_clump_p1"),
+                      ancestry_clump_p2=inf.get("ancestry_clump_p2"), ancestry_clump_r2=inf.get("ancestry_clump_r2"),
+                      ancestry_clump_kb=inf.get("ancestry_clump_kb"))
     return 0
 
 

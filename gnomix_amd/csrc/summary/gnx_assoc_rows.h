@@ -1,6 +1,6 @@
 // summary/gnx_assoc_rows.h — what the files of this folder share about rows and windows (k_ancestry_assoc.hip, the linear model's
-// sufficient statistics; k_ancestry_assoc_logit.hip, the logistic fits; k_allele_counts.hip, k_ancestry_score.hip and
-// k_ancestry_pairs.hip, which read a row 16 columns at a time): one definition of each.
+// sufficient statistics; k_ancestry_assoc_logit.hip, the logistic fits; k_allele_counts.hip, k_ancestry_score.hip,
+// k_ancestry_pairs.hip and k_ancestry_ld.hip, which read a row 16 columns at a time): one definition of each.
 #pragma once
 #include "../gnx_internal.h"
 

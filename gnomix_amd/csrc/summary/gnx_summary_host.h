@@ -1,5 +1,5 @@
 // summary/gnx_summary_host.h — the host side the ancestry-specific ops of this folder share (k_allele_counts.hip, k_ancestry_assoc.hip,
-// k_ancestry_assoc_logit.hip, k_ancestry_score.hip, k_ancestry_pairs.hip): the refusals on the geometry, the staging of host rows, labels
+// k_ancestry_assoc_logit.hip, k_ancestry_score.hip, k_ancestry_pairs.hip, k_ancestry_ld.hip): the refusals on the geometry, the staging of host rows, labels
 // and phenotypes, the file path's staging (gnx_infer_gt2's: gnx_api_vcf.hip keeps its own copy), the counter of labels out of range and
 // its verdict.  One definition of each, in gnx_summary_host.hip; the device-side row helpers stay in gnx_assoc_rows.h.
 #pragma once

@@ -324,6 +324,55 @@ class HipGnomix:
         counts = asmds.PairCounts(*(t.cpu().numpy() if hasattr(t, "is_cuda") else t for t in counts))
         return asmds.ancestry_mds(counts, k=k, min_sites=min_sites, min_pair_sites=min_pair_sites)
 
+    def _resident_rows_labels(self, X):
+        """X (numpy or CUDA) and the labels predict returns (mode_filter applied when set), both as CUDA tensors of the model's device"""
+        import torch
+        mf = self.smooth.mode_filter
+        if not resident.is_cuda(X):
+            X = torch.from_numpy(np.ascontiguousarray(self.dev._x(X))).to("cuda:%d" % self.dev.ctx.device)
+        X = resident.check_x(X, self.C, self.dev.ctx.device)
+        _, lab = self.dev.infer_device(X, want_proba=False, want_labels=True)
+        if mf:
+            lab = self.dev.mode_filter_device(lab, mf)
+        return X, lab
+
+    def ancestry_ld(self, X, ancestry, c0=0, c1=None, band=256):
+        """ancestry-specific LD: the banded count tables of one ancestry (index into population_order) of X under the labels predict
+        returns (mode_filter applied when set), for the SNPs [c0, c1) and the offsets 0 .. band - 1 -> ld.LDCounts(n11, n1o, no1, noo, c0,
+        band) of (c1 - c0, band) int32 arrays (.r(), .r2(), .pair(c, c')): sums over the haplotypes labelled `ancestry` at both SNPs with
+        both calls observed.  One fused pass on the int8 matrix cores (k_ancestry_ld); with a CUDA tensor neither X nor the labels leave
+        HBM and CUDA tensors come back."""
+        if resident.is_cuda(X):
+            with resident.torch_stream(self.dev.ctx):
+                Xt, lab = self._resident_rows_labels(X)
+                return self.dev.ancestry_ld_counts_device(Xt, lab, ancestry, c0, c1, band)
+        mf = self.smooth.mode_filter
+        _, lab = self.dev.infer(X, want_proba=False, want_labels=True)
+        if mf:
+            lab = self.dev.mode_filter(lab, mf)
+        return self.dev.ancestry_ld_counts(self.dev._x(X), lab, ancestry, c0, c1, band)
+
+    def ancestry_clump(self, X, res, p1=1e-4, p2=1e-2, r2=0.5, kb=250):
+        """clumping of an association result (assoc.AncestryAssoc / AncestryAssocLogit of these SNPs) ancestry by ancestry -> index_of
+        (C, A) int64: column a is ld.clump of res.p[:, a] with ancestry a's LD under the labels predict returns, at the model's SNP
+        positions (an index SNP holds its own position in the SNP order, a clumped SNP its index's, -1 neither).  X and the labels stay
+        in HBM; only the tables around index SNPs are computed and read back.  score.weights_from_assoc(res, index_of=...) takes it."""
+        from . import ld
+        pos = np.asarray(self.snp_pos).astype(np.int64)
+        p = np.asarray(res.p, dtype=np.float64)
+        if p.shape != (self.C, self.A):
+            raise ValueError(f"res.p must be (C={self.C}, A={self.A}), got {p.shape}")
+        band = ld.band_for(pos, kb)
+        out = np.full((self.C, self.A), -1, np.int64)
+        with resident.torch_stream(self.dev.ctx):
+            Xt, lab = self._resident_rows_labels(X)
+            for a in range(self.A):
+                def counts_for(c0, c1, a=a):
+                    t = self.dev.ancestry_ld_counts_device(Xt, lab, a, c0, c1, band)
+                    return ld.LDCounts(*(v.cpu().numpy() for v in t[:4]), t.c0, t.band)
+                out[:, a] = ld.clump(p[:, a], pos, counts_for, p1=p1, p2=p2, r2=r2, kb=kb)
+        return out
+
     def phase(self, X, B=None, verbose=False, **gnofix_kw):
         """Gnofix re-phasing (model.py:188-214): -> X_phased (N, C) int, Y_phased (N, W) int.  `gnofix_kw`: gnofix()'s search
         options (check_criterion, max_center_offset, non_lin_s, prob_comp, prior_switch_prob, padding, max_it); the reference's

@@ -676,6 +676,47 @@ class DeviceModel:
                                                              ctypes.byref(n_bad)))
         return PairCounts(DD, DO, OO)
 
+    def ancestry_ld_counts(self, X, labels, ancestry, c0=0, c1=None, band=256, packed=False):
+        """the banded LD count tables n11, n1o, no1, noo of one ancestry for the SNPs [c0, c1) and the offsets 0 .. band - 1, X (N, C) int8
+        (packed=True: the 2-bit rows pack_x returns) under (N, W) labels, on the int8 matrix cores (gnx_ancestry_ld_counts;
+        gnomix_amd.postprocess.ld_counts) -> ld.LDCounts of (c1 - c0, band) int32 arrays"""
+        from .postprocess import ld_counts
+        return ld_counts(self.ctx, X, labels, self.M, self.A, ancestry, c0, c1, band, packed=packed, C=self.C)
+
+    def ancestry_ld_counts_device(self, X_t, lab_t, ancestry, c0=0, c1=None, band=256, debug_haps_per_block=0):
+        """the same on CUDA tensors: X_t int8 (N, C) or the uint8 tensor pack_device returns, lab_t (N, W) int32 with any row stride
+        (gnx_ancestry_ld_counts_dev) -> ld.LDCounts of (c1 - c0, band) int32 CUDA tensors"""
+        import ctypes
+        import torch
+        from .ld import LDCounts
+        kind, ld, ldl, N = self._allele_device_args(X_t, lab_t)
+        c0, c1, band = int(c0), self.C if c1 is None else int(c1), int(band)
+        self._bind_torch_stream()
+        tabs = [torch.zeros((max(c1 - c0, 0), max(band, 0)), dtype=torch.int32, device=X_t.device) for _ in range(4)]
+        n_bad = ctypes.c_int64(0)
+        self.ctx.check(self.lib.gnx_ancestry_ld_counts_dev(self.ctx.h, X_t.data_ptr(), kind, ld, lab_t.data_ptr(), ldl, N, self.C, self.M, self.W,
+                                                           self.A, int(ancestry), c0, c1, band, tabs[0].data_ptr(), tabs[1].data_ptr(),
+                                                           tabs[2].data_ptr(), tabs[3].data_ptr(), band, int(debug_haps_per_block),
+                                                           ctypes.byref(n_bad)))
+        return LDCounts(*tabs, c0, band)
+
+    def ancestry_ld_counts_gt2(self, G, N, src, labels, ancestry, c0=0, c1=None, band=256):
+        """ancestry_ld_counts of the parsed query (G, N, src as infer_gt2 takes them) under host labels (N, W): the whole packed matrix is
+        built in HBM and the kernel runs once (gnx_ancestry_ld_counts_gt2) -> ld.LDCounts of numpy arrays"""
+        import ctypes
+        from .ld import LDCounts
+        G, N, src = self._gt2_args(G, N, src)
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.shape != (N, self.W):
+            raise ValueError(f"labels must be (N={N}, W={self.W}), got {lab.shape}")
+        c0, c1, band = int(c0), self.C if c1 is None else int(c1), int(band)
+        tabs = [np.zeros((max(c1 - c0, 0), max(band, 0)), np.int32) for _ in range(4)]
+        n_bad = ctypes.c_int64(0)
+        self.ctx.check(self.lib.gnx_ancestry_ld_counts_gt2(self.h, G.ctypes.data, G.shape[0], G.shape[1], N, src.ctypes.data, lab.ctypes.data,
+                                                           int(ancestry), c0, c1, band, tabs[0].ctypes.data, tabs[1].ctypes.data,
+                                                           tabs[2].ctypes.data, tabs[3].ctypes.data, band, ctypes.byref(n_bad)))
+        return LDCounts(*tabs, c0, band)
+
     def ancestry_assoc_stats(self, X, labels, y, Z=None, use=None, c0=0, c1=None, min_ac=1, check=True):
         """the sufficient statistics of the ancestry-specific association model for the SNPs [c0, c1) (gnx_ancestry_assoc_stats[_dev];
         include/gnomix_hip.h states the blocks) -> gnomix_amd.assoc.AssocStats of numpy arrays.  X (N, C) int8 and labels (N, W) int32 as

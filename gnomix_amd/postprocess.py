@@ -452,6 +452,52 @@ def pair_counts(ctx, X_or_packed, labels, M, A, ancestry, snp_range=None, packed
     return PairCounts(DD, DO, OO)
 
 
+def ld_counts(ctx, X_or_packed, labels, M, A, ancestry, c0=0, c1=None, band=256, packed=False, C=None, debug_haps_per_block=0, check=True):
+    """ancestry-specific LD counts on the device (gnx_ancestry_ld_counts; include/gnomix_hip.h states the tables): X (N, C) int8 in the
+    model's coding, or with packed=True the 2-bit rows of DeviceModel.pack_x and C; labels (N, W); the SNPs [c0, c1) (c1 None: to the
+    last) and the offsets 0 .. band - 1 -> ld.LDCounts of (c1 - c0, band) int32 arrays.  check=False: labels outside [0, A) do not raise
+    (they count for no ancestry)"""
+    import ctypes
+    from .ld import LDCounts
+    rows, kind, C = _allele_rows(X_or_packed, packed, C)
+    N = rows.shape[0]
+    lab = _allele_labels(labels, N)
+    W = lab.shape[1]
+    c0, c1, band = int(c0), C if c1 is None else int(c1), int(band)
+    tabs = [np.zeros((max(c1 - c0, 0), max(band, 0)), np.int32) for _ in range(4)]
+    n_bad = ctypes.c_int64(0)
+    rc = ctx.lib.gnx_ancestry_ld_counts(ctx.h, rows.ctypes.data, kind, rows.shape[1], lab.ctypes.data, W, N, C, int(M), W, int(A), int(ancestry),
+                                        c0, c1, band, tabs[0].ctypes.data, tabs[1].ctypes.data, tabs[2].ctypes.data, tabs[3].ctypes.data, band,
+                                        int(debug_haps_per_block), ctypes.byref(n_bad))
+    if check or not n_bad.value:
+        ctx.check(rc)
+    return LDCounts(*tabs, c0, band)
+
+
+def write_clumps(prefix, chm, snp_pos, index_of, p, populations):
+    """<prefix>.clumped.tsv from the clumps of every ancestry: index_of (C, A) int64 as ld.clump returns it per column, p (C, A) the
+    p-values it was made from.  One header line `chm  pos  population  p  n_members  members`, then one line per index SNP, population
+    by population in population order and within one in SNP order: members = the positions of the SNPs clumped with it (itself not
+    among them), ascending and comma-separated, `.` when there are none.  p is written with repr, the shortest text that reads back to
+    the same float64."""
+    pos = np.asarray(snp_pos)
+    idx = np.asarray(index_of)
+    pv = np.asarray(p, dtype=np.float64)
+    if idx.shape != (len(pos), len(populations)) or pv.shape != idx.shape:
+        raise ValueError(f"index_of and p must be ({len(pos)} SNPs, {len(populations)} populations), got {idx.shape} and {pv.shape}")
+    with open(prefix + ".clumped.tsv", "w") as f:
+        f.write("chm\tpos\tpopulation\tp\tn_members\tmembers\n")
+        for a, pop in enumerate(populations):
+            col = idx[:, a]
+            order = np.argsort(col, kind="stable")
+            col_s = col[order]
+            for c in np.nonzero(col == np.arange(len(pos)))[0]:
+                mem = order[np.searchsorted(col_s, c, side="left"):np.searchsorted(col_s, c, side="right")]
+                mem = mem[mem != c]
+                f.write("%s\t%d\t%s\t%s\t%d\t%s\n" % (chm, int(pos[c]), pop, repr(float(pv[c, a])), mem.size,
+                                                      ",".join(str(int(pos[m])) for m in mem) if mem.size else "."))
+
+
 def write_asmds(prefix, results, population_order, samples):
     """<prefix>.asmds.tsv from the ancestry-specific MDS of every ancestry: results[a] is an asmds.AncestryMDS over the len(samples)
     individuals (kept = the indices embedded, n_sites = their OO[i, i]) or None (fewer than k + 1 individuals kept: the ancestry gets

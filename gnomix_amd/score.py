@@ -8,15 +8,21 @@ import numpy as np
 EFFECT_REF, EFFECT_ALT, EFFECT_NONE = 0, 1, 255    # the bytes of gnx_ancestry_score's effect array
 
 
-def weights_from_assoc(res, p_max=None):
+def weights_from_assoc(res, p_max=None, index_of=None):
     """(C, A) float64 weights from an assoc.AncestryAssoc or assoc.AncestryAssocLogit: its beta (per ALT allele on a haplotype of that
     ancestry, so the effect allele is ALT everywhere), 0 where beta is NaN (a dropped term, a SNP that was not fitted) or not finite;
-    with p_max also 0 where p > p_max or p is NaN"""
+    with p_max also 0 where p > p_max or p is NaN; with index_of ((C, A) int64, HipGnomix.ancestry_clump's: column a from ld.clump) also 0
+    wherever the SNP is not its own index SNP in that ancestry, so that of every clump only the strongest SNP is scored"""
     beta = np.array(res.beta, dtype=np.float64)
     keep = np.isfinite(beta)
     if p_max is not None:
         p = np.asarray(res.p, dtype=np.float64)
         keep &= np.isfinite(p) & (p <= float(p_max))
+    if index_of is not None:
+        idx = np.asarray(index_of)
+        if idx.shape != beta.shape:
+            raise ValueError(f"index_of must be {beta.shape} as beta is, got {idx.shape}")
+        keep &= idx == np.arange(beta.shape[0])[:, None]
     return np.where(keep, beta, 0.0)
 
 

@@ -1097,6 +1097,54 @@ int gnx_ancestry_pair_counts_gt2(gnx_model* m, const uint8_t* G, int64_t n_varia
                                  const int32_t* labels, int32_t ancestry, int64_t c0, int64_t c1, int32_t* DD, int32_t* DO, int32_t* OO,
                                  int64_t ld, int64_t* n_bad);
 
+/* ---- ancestry-specific linkage disequilibrium on the int8 matrix cores (csrc/summary/k_ancestry_ld.hip) -------------------
+ * INPUTS.  rows, row_kind, the codes, labels (N, W) int32, ld_rows, ld_labels, M, W, A, win(c) = min(c / M, W - 1) and the requirement
+ *   M W <= C are EXACTLY gnx_ancestry_allele_counts'.  N need not be even: everything here is per haplotype.  For ONE ancestry
+ *   `ancestry`, haplotype h and SNP c:
+ *     o[h, c] = 1 if labels[h, win(c)] == ancestry AND the call is observed (code 0 or 1), else 0
+ *     d[h, c] = 1 if o[h, c] and the code is 1, else 0
+ * OUTPUTS.  Four int32 tables over the SNP range [c0, c1) and the offsets 0 <= k < band, of shape (c1 - c0, band), rows ld >= band ELEMENTS
+ *   apart, OVERWRITTEN (the band columns of the c1 - c0 rows; what lies between band and ld is not touched); any may be NULL.  Entry
+ *   [c - c0, k] speaks of the pair (c, c' = c + k) and is 0 where c + k >= C.  c + k may lie beyond c1: the tables of a partition of a
+ *   range are the rows of the range's tables.
+ *     n11 = sum_h d[h, c] d[h, c']     n1o = sum_h d[h, c] o[h, c']
+ *     no1 = sum_h o[h, c] d[h, c']     noo = sum_h o[h, c] o[h, c']
+ *   noo counts the haplotypes that carry the ancestry at BOTH SNPs (which may lie in different windows) with both calls observed, n1o and
+ *   no1 the ALT calls at c and at c' among those, n11 the haplotypes ALT at both.  Every term is 0 or 1, so int32 is exact for every N the
+ *   entry accepts.  All device arithmetic is integer: the tables depend on nothing but the inputs, not on the grid, the row form or the
+ *   debug argument.  The caller derives r = (noo n11 - n1o no1) / sqrt(n1o (noo - n1o) no1 (noo - no1)) (gnomix_amd/ld.py).
+ *   debug_haps_per_block: 0 in production (the split of the haplotypes over workgroups is taken from the number of tile pairs).  > 0
+ *   (tests): the haplotypes one workgroup walks, rounded up to the kernel's chunk of 128.
+ * GNX_EINVAL before any launch, nothing written: the conditions of gnx_ancestry_allele_counts (N < 0 or >= 2^31, C < 1, A < 1, M < 1,
+ *   W < 1, M W > C, a stride too small, an unknown row_kind), ancestry outside [0, A), c0 < 0, c1 <= c0, c1 > C, band < 1, ld < band, a
+ *   negative debug argument.
+ * GNX_EUNSUPPORTED, nothing written: A > GNX_ALLELE_MAX_A, band > GNX_LD_MAX_BAND, more than 2^31 - 1 workgroups (tile pairs x haplotype
+ *   segments).  GNX_LD_MAX_BAND is 4096: the kernel's layout sets no limit of its own (a band is walked in tiles of 64 SNPs, 66 of them
+ *   at 4096), the bound keeps a table row at 16 KiB and a whole-chromosome call from asking for terabytes by a slip.
+ * GNX_EINVAL after the launch, *n_bad set (0 otherwise; n_bad may be NULL): labels outside [0, A) were met in the windows of the SNPs
+ *   c0 .. min(c1 - 1 + band - 1, C - 1), those the range AND its band reach, *n_bad of them.  Labels are only compared, never used as an
+ *   index: such a haplotype counts for no ancestry at that window; the tables are as stated.
+ * N == 0: nothing is launched, nothing is written.  Every form synchronises the context stream ONCE (the verdict on the labels, with the
+ *   tables' copies of the host forms in front of it).  In the _dev form every pointer but n_bad is a device pointer.
+ * gnx_ancestry_ld_counts_gt2: the file path's form.  G, n_variants, ldg, src as gnx_infer_gt2 takes them; labels (N, W) on the HOST,
+ *   contiguous rows; the model's C, M, W and A.  The sums run over every row, so the WHOLE packed matrix is built in HBM, in device
+ *   memory the call allocates and frees, batch by batch as gnx_ancestry_pair_counts_gt2 builds it, and the kernel runs once: the tables
+ *   equal the matrix path's whatever GNX_HOST_BATCH is.  A model SNP the query lacks is missing in every row.  GNX_EUNSUPPORTED with the
+ *   byte count in the message if the rows plus the tables exceed the device's memory; GNX_EINVAL before the launch also for a column map
+ *   entry outside G.
+ * OUT OF SCOPE: genotype (unphased) r^2, D', LD scores, pruning, several devices. */
+#define GNX_LD_MAX_BAND 4096
+int gnx_ancestry_ld_counts_dev(gnx_ctx* ctx, const void* d_rows, int row_kind, int64_t ld_rows, const int32_t* d_labels, int64_t ld_labels,
+                               int64_t N, int64_t C, int64_t M, int64_t W, int32_t A, int32_t ancestry, int64_t c0, int64_t c1, int64_t band,
+                               int32_t* d_n11, int32_t* d_n1o, int32_t* d_no1, int32_t* d_noo, int64_t ld, int64_t debug_haps_per_block,
+                               int64_t* n_bad);
+int gnx_ancestry_ld_counts(gnx_ctx* ctx, const void* rows, int row_kind, int64_t ld_rows, const int32_t* labels, int64_t ld_labels, int64_t N,
+                           int64_t C, int64_t M, int64_t W, int32_t A, int32_t ancestry, int64_t c0, int64_t c1, int64_t band, int32_t* n11,
+                           int32_t* n1o, int32_t* no1, int32_t* noo, int64_t ld, int64_t debug_haps_per_block, int64_t* n_bad);
+int gnx_ancestry_ld_counts_gt2(gnx_model* m, const uint8_t* G, int64_t n_variants, int64_t ldg, int64_t N, const int32_t* src,
+                               const int32_t* labels, int32_t ancestry, int64_t c0, int64_t c1, int64_t band, int32_t* n11, int32_t* n1o,
+                               int32_t* no1, int32_t* noo, int64_t ld, int64_t* n_bad);
+
 /* per-kernel device time, measured with hipEvents on the context stream around every launch */
 int gnx_profile_enable(gnx_ctx* ctx, int on);
 int gnx_profile_reset(gnx_ctx* ctx);
