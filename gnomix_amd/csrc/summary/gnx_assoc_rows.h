@@ -1,6 +1,6 @@
 // summary/gnx_assoc_rows.h — what the files of this folder share about rows and windows (k_ancestry_assoc.hip, the linear model's
-// sufficient statistics; k_ancestry_assoc_logit.hip, the logistic fits; k_allele_counts.hip, k_ancestry_score.hip,
-// k_ancestry_pairs.hip and k_ancestry_ld.hip, which read a row 16 columns at a time): one definition of each.
+// sufficient statistics; k_ancestry_assoc_logit.hip, the logistic fits; k_allele_counts.hip, k_ancestry_score.hip and, through
+// gnx_as_gram.h, k_ancestry_pairs.hip and k_ancestry_ld.hip, which read a row 16 columns at a time): one definition of each.
 #pragma once
 #include "../gnx_internal.h"
 
@@ -49,11 +49,37 @@ __device__ __forceinline__ uint32_t as_fields16(const uint8_t* __restrict__ row,
   }
 }
 
+constexpr uint32_t AS_EVEN = 0x55555555u;   // bit 0 of each of the 16 fields
+
 // the even bits of the fields lo .. hi - 1 of a group of 16 (0 <= lo < 16, lo < hi <= 16).  Shared by k_ancestry_score.hip and
-// k_ancestry_pairs.hip.
+// as_label_mask16.
 __device__ __forceinline__ uint32_t as_range16(int lo, int hi) {
   const uint32_t below_hi = hi >= 16 ? 0xFFFFFFFFu : ((1u << (2 * hi)) - 1u);
-  return below_hi & ~((1u << (2 * lo)) - 1u) & 0x55555555u;
+  return below_hi & ~((1u << (2 * lo)) - 1u) & AS_EVEN;
+}
+
+// the even bits of those columns of [lo, hi) whose window carries label a in the row of labels lh; [lo, hi) lies inside the group of 16
+// that starts at cg (an empty range gives 0).  A loop over the windows that meet the range: one turn unless a boundary falls inside,
+// 16 turns at M = 1; the last window takes the remainder of the C columns.  A label is compared with a, never used as an index.  Shared
+// by k_ancestry_pairs.hip and k_ancestry_ld.hip (k_ancestry_score.hip keeps a window running along its row instead).
+__device__ __forceinline__ uint32_t as_label_mask16(const int32_t* lh, int32_t a, int64_t cg, int64_t lo, int64_t hi, int64_t C, int64_t M, int64_t W) {
+  uint32_t m = 0;
+  int64_t c = lo, k = lo / M;
+  if (k > W - 1) k = W - 1;
+  while (c < hi) {          // the columns [c, se) lie in window k
+    const int64_t wend = (k == W - 1) ? C : (k + 1) * M;
+    const int64_t se = hi < wend ? hi : wend;
+    if (lh[k] == a) m |= as_range16((int)(c - cg), (int)(se - cg));
+    c = se;
+    ++k;
+  }
+  return m;
+}
+
+// of a group's fields f: the even bits of the observed calls (code 0 or 1), and of those of them that are ALT
+__device__ __forceinline__ void as_obs_alt(uint32_t f, uint32_t* obs, uint32_t* alt) {
+  *obs = ~(f >> 1) & AS_EVEN;
+  *alt = f & *obs;
 }
 
 inline int64_t as_min_row_bytes(int row_kind, int64_t C) { return row_kind == GNX_ROWS_PACKED2 ? (C + 3) / 4 : C; }

@@ -1,7 +1,8 @@
 // summary/gnx_summary_host.h — the host side the ancestry-specific ops of this folder share (k_allele_counts.hip, k_ancestry_assoc.hip,
-// k_ancestry_assoc_logit.hip, k_ancestry_score.hip, k_ancestry_pairs.hip, k_ancestry_ld.hip): the refusals on the geometry, the staging of host rows, labels
-// and phenotypes, the file path's staging (gnx_infer_gt2's: gnx_api_vcf.hip keeps its own copy), the counter of labels out of range and
-// its verdict.  One definition of each, in gnx_summary_host.hip; the device-side row helpers stay in gnx_assoc_rows.h.
+// k_ancestry_assoc_logit.hip, k_ancestry_score.hip and, through gnx_as_gram.h, k_ancestry_pairs.hip and k_ancestry_ld.hip): the refusals
+// on the geometry, the staging of host rows, labels and phenotypes, the file path's staging (gnx_infer_gt2's: gnx_api_vcf.hip keeps its
+// own copy), the counter of labels out of range and its verdict.  One definition of each, in gnx_summary_host.hip, which also defines
+// the host side of gnx_as_gram.h (what the two Gram ops share beyond this); the device-side row helpers stay in gnx_assoc_rows.h.
 #pragma once
 #include "gnx_assoc_rows.h"
 

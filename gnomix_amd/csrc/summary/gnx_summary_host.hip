@@ -1,5 +1,6 @@
-// summary/gnx_summary_host.hip — the only definitions of what gnx_summary_host.h declares.  Host code throughout: no kernel lives here.
-#include "gnx_summary_host.h"
+// summary/gnx_summary_host.hip — the only definitions of what gnx_summary_host.h declares and of the host side of gnx_as_gram.h.  Host code
+// but for one kernel: k_ancestry_gram_labels, the label count of the two Gram ops.
+#include "gnx_as_gram.h"
 
 int gnx_sum_geometry_check(gnx_ctx* ctx, const char* who, unsigned flags, const void* rows, int row_kind, int64_t ld_rows, const void* labels,
                            int64_t ld_labels, int64_t N, int64_t C, int64_t M, int64_t W, int32_t A) {
@@ -143,4 +144,97 @@ int gnx_sum_read_verdict(gnx_ctx* ctx, const char* who, const unsigned long long
   HIPCHK(ctx, hipMemcpyAsync(&h_bad, d_bad, sizeof h_bad, hipMemcpyDeviceToHost, s));
   HIPCHK(ctx, hipStreamSynchronize(s));
   return gnx_sum_label_verdict(ctx, who, h_bad, A, tail, n_bad);
+}
+
+// ---- the host side of gnx_as_gram.h --------------------------------------------------------------------------------------------------------
+const char* const GNX_GRAM_TAIL = "such a haplotype counts for no ancestry at that window";
+
+void gnx_gram_split(int64_t chunks, int64_t pairs, int n_cu, int64_t dbg, int64_t min_chunks, int64_t* cpb, int64_t* nseg) {
+  int64_t per = chunks;
+  if (dbg > 0) {
+    per = (dbg + GRAM_KC - 1) / GRAM_KC;
+  } else {
+    const int64_t want = (int64_t)n_cu * 4;            // about four workgroups per CU
+    if (pairs < want) {
+      const int64_t ns = (want + pairs - 1) / pairs;   // segments that would fill the chip
+      per = std::max(min_chunks, (chunks + ns - 1) / ns);
+    }
+  }
+  per = std::min(per, chunks);
+  *cpb = per;
+  *nseg = (chunks + per - 1) / per;
+}
+
+int gnx_gram_grid_check(gnx_ctx* ctx, const char* who, int64_t pairs, int64_t nseg, const char* what) {
+  if (nseg > (((int64_t)1 << 31) - 1) / pairs)
+    return gnx_fail(ctx, GNX_EUNSUPPORTED, std::string(who) + ": " + std::to_string(pairs) + " tile pairs x " + std::to_string(nseg) + " " + what +
+                                               " segments exceed one grid");
+  return GNX_OK;
+}
+
+namespace {
+// labels outside [0, A) among the rows' windows [k0, k1)
+__global__ __launch_bounds__(256) void k_ancestry_gram_labels(const int32_t* __restrict__ lab, int64_t ldl, int64_t N, int64_t k0, int64_t k1, int A,
+                                                              unsigned long long* __restrict__ bad) {
+  const int64_t nk = k1 - k0, total = N * nk;
+  unsigned int mine = 0;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t h = e / nk, k = k0 + (e - h * nk);
+    const int32_t v = lab[h * ldl + k];
+    if (v < 0 || v >= A) ++mine;
+  }
+  if (mine) atomicAdd(bad, (unsigned long long)mine);
+}
+}  // namespace
+
+int gnx_gram_count_labels(gnx_ctx* ctx, const int32_t* d_labels, int64_t ld_labels, int64_t N, int64_t k0, int64_t k1, int32_t A,
+                          unsigned long long* d_bad, hipStream_t s) {
+  const int64_t total = N * (k1 - k0);
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, (int64_t)ctx->n_cu * 8));
+  hipLaunchKernelGGL(k_ancestry_gram_labels, dim3(grid), dim3(256), 0, s, d_labels, ld_labels, N, k0, k1, (int)A, d_bad);
+  HIPCHK(ctx, hipGetLastError());
+  return GNX_OK;
+}
+
+int gnx_gram_zero(gnx_ctx* ctx, int32_t* const tabs[], int n_tabs, int64_t ld, int64_t r0, int64_t rows, int64_t cols, hipStream_t s) {
+  for (int q = 0; q < n_tabs; ++q)
+    if (tabs[q]) HIPCHK(ctx, hipMemset2DAsync(tabs[q] + (size_t)r0 * (size_t)ld, (size_t)ld * 4, 0, (size_t)cols * 4, (size_t)rows, s));
+  return GNX_OK;
+}
+
+int gnx_gram_check_range(gnx_ctx* ctx, const gnx_gram_call& c, unsigned flags, const gnx_gram_rows& R) {
+  const std::string w(c.who);
+  const int rc = gnx_sum_geometry_check(ctx, c.who, flags, R.rows, R.row_kind, R.ld_rows, R.labels, R.ld_labels, c.N, c.C, c.M, c.W, c.A);
+  if (rc != GNX_OK) return rc;
+  if (c.ancestry < 0 || c.ancestry >= c.A) return gnx_fail(ctx, GNX_EINVAL, w + ": ancestry outside [0, A)");
+  if (c.c0 < 0 || c.c1 <= c.c0 || c.c1 > c.C) return gnx_fail(ctx, GNX_EINVAL, w + ": need 0 <= c0 < c1 <= C");
+  return GNX_OK;
+}
+
+int gnx_gram_check_sizes(gnx_ctx* ctx, const gnx_gram_call& c, int64_t dbg) {
+  const std::string w(c.who);
+  if (c.N >= ((int64_t)1 << 31)) return gnx_fail(ctx, GNX_EINVAL, w + ": N must be below 2^31");
+  if (dbg < 0) return gnx_fail(ctx, GNX_EINVAL, w + ": the debug argument must be >= 0 (0 = the built-in choice)");
+  if (c.A > GNX_ALLELE_MAX_A)
+    return gnx_fail(ctx, GNX_EUNSUPPORTED, w + ": A = " + std::to_string(c.A) + " ancestries, at most " + std::to_string(GNX_ALLELE_MAX_A));
+  return GNX_OK;
+}
+
+int gnx_gram_tabs_reserve(gnx_ctx* ctx, const gnx_gram_call& c, int32_t* dev[4]) {
+  const size_t tb = (((size_t)c.t_rows * (size_t)c.t_cols * 4) + 255) & ~(size_t)255;
+  const int rc = gnx_ws_reserve(ctx, ctx->ws_b32, (size_t)c.n_tabs * tb + 64);
+  if (rc != GNX_OK) return rc;
+  char* o = (char*)ctx->ws_b32.p;
+  for (int q = 0; q < c.n_tabs; ++q) dev[q] = c.tabs[q] ? (int32_t*)(o + q * tb) : nullptr;
+  return GNX_OK;
+}
+
+int gnx_gram_tabs_copy_out(gnx_ctx* ctx, const gnx_gram_call& c, int32_t* const dev[4], const unsigned long long* d_bad, unsigned long long* h_bad,
+                           hipStream_t s) {
+  const size_t wb = (size_t)c.t_cols * 4;
+  for (int q = 0; q < c.n_tabs; ++q)
+    if (c.tabs[q]) HIPCHK(ctx, hipMemcpy2DAsync(c.tabs[q], (size_t)c.ld * 4, dev[q], wb, wb, (size_t)c.t_rows, hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipMemcpyAsync(h_bad, d_bad, sizeof *h_bad, hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipStreamSynchronize(s));
+  return GNX_OK;
 }

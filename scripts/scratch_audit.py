@@ -43,8 +43,7 @@ MUST_BE_CLEAN = [
     r"k_ancestry_assoc_",
     r"k_ancestry_assoc_logit_prep", r"k_ancestry_assoc_logit_null", r"k_ancestry_assoc_logit_snp<",
     r"k_ancestry_score_check", r"k_ancestry_score_partial<", r"k_ancestry_score_reduce",
-    r"k_ancestry_pairs<", r"k_ancestry_pairs_labels",
-    r"k_ancestry_ld<", r"k_ancestry_ld_labels",
+    r"k_ancestry_pairs<", r"k_ancestry_ld<", r"k_ancestry_gram_labels",
 ]
 
 

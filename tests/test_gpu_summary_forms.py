@@ -1,4 +1,4 @@
-"""What the five ancestry-specific ops of csrc/summary/ share on the host side (gnx_summary_host.h), pinned across all of them at once: the
+"""What the six ancestry-specific ops of csrc/summary/ share on the host side (gnx_summary_host.h), pinned across all of them at once: the
 refusals on the geometry, on the file path's arguments and on the column map, with their literal messages, and the verdict on a label
 outside [0, A) (count, the op's own sentence, n_bad, outputs handed over all the same).
 
@@ -16,6 +16,7 @@ import allele_counts_exact as AE
 pytestmark = pytest.mark.gpu
 
 N, C, M, W, A, K, S = 8, 37, 9, 4, 3, 2, 2
+BAND = 5                                        # of the LD tables: the bands of the last four SNPs reach past C (no owner, zeroed first)
 LD, LDP, LDL = C + 7, (C + 3) // 4 + 3, W + 3
 POISON = -7
 NI = A * (A + 1) // 2 + A * (A - 1) + A + 1     # int32 words of one SNP's block of the linear statistics
@@ -46,6 +47,9 @@ FORMS = {
     "pairs": ("gnx_ancestry_pair_counts", "ancestry_pair_counts", TAIL_HAP, NULL_ROWS, True),
     "pairs_dev": ("gnx_ancestry_pair_counts_dev", "ancestry_pair_counts", TAIL_HAP, NULL_ROWS, True),
     "pairs_gt2": ("gnx_ancestry_pair_counts_gt2", "ancestry_pair_counts_gt2", TAIL_HAP, None, True),
+    "ld": ("gnx_ancestry_ld_counts", "ancestry_ld_counts", TAIL_HAP, NULL_ROWS, False),
+    "ld_dev": ("gnx_ancestry_ld_counts_dev", "ancestry_ld_counts", TAIL_HAP, NULL_ROWS, False),
+    "ld_gt2": ("gnx_ancestry_ld_counts_gt2", "ancestry_ld_counts_gt2", TAIL_HAP, None, False),
 }
 HAS_ROW_KIND = {f for f in FORMS if not f.endswith("gt2") and f not in ("assoc", "logit")}
 HAS_N_BAD = {f for f in FORMS if not f.startswith(("counts", "dosage"))}
@@ -95,6 +99,8 @@ def _outputs(form):
                   "wf": ((W, K + A), np.float64), "wi": ((W, A + 4), np.int32)}
     elif op == "score":
         shapes = {"score": ((n, A, S), np.float64), "ne": ((n, A), np.int32), "ns": ((n, A), np.int32), "nm": ((n, A), np.int32)}
+    elif op == "ld":
+        shapes = {k: ((C, BAND), np.int32) for k in ("n11", "n1o", "no1", "noo")}
     else:
         shapes = {k: ((n, n), np.int32) for k in ("DD", "DO", "OO")}
     return {k: np.full(s, _poison(t), t) for k, (s, t) in shapes.items()}
@@ -149,6 +155,8 @@ def _call(e, form, lab=None, **v):
         tail = (p["y"], p["Z"], K, None, 1, 0, C, 1e-8, 5, o["sf"], o["si"], o["th"], o["wf"], o["wi"], nb)
     elif op == "score":
         tail = (p["w"], S, p["eff"], o["score"], o["ne"], o["ns"], o["nm"]) + (() if kind == "gt2" else (0, 0)) + (nb,)
+    elif op == "ld":
+        tail = (1, 0, C, BAND, o["n11"], o["n1o"], o["no1"], o["noo"], BAND) + (() if kind == "gt2" else (0,)) + (nb,)
     else:
         tail = (1, 0, C, o["DD"], o["DO"], o["OO"], N // 2) + (() if kind == "gt2" else (0,)) + (nb,)
     rc = getattr(lib, FORMS[form][0])(*head, *tail)
@@ -210,7 +218,7 @@ def test_one_label_out_of_range_is_counted_and_the_outputs_are_handed_over(env, 
             assert not (a == _poison(a.dtype)).any(), (form, v, k)     # every output was written
 
 
-@pytest.mark.parametrize("op", ["counts", "assoc", "logit", "score", "pairs"])
+@pytest.mark.parametrize("op", ["counts", "assoc", "logit", "score", "pairs", "ld"])
 def test_the_forms_of_an_op_agree_bit_for_bit(env, op):
     """host rows, device rows (int8, and 2-bit where the form takes a row_kind) and the rows the file path builds (two batches) are the
     same matrix: so are the outputs"""
