@@ -85,16 +85,15 @@ def _lower_inverse_batched(L):
     return Li
 
 
-def _finish_chunk(st, sl, A, K, min_ac):
+def _factor_chunk(st, sl, A, K, min_ac):
+    """the trait-independent half of a chunk's finish: the kept columns, the unit-diagonal normal matrix of every SNP and its Cholesky
+    factor -> w, keep (nc, Q), n, df (int64), s (the column scales), Li (L^-1, (nc, Q, Q)), bad (nc,)"""
     P, Q = K + A - 1, K + 2 * A - 1
     w = st.window[sl]
     nc = len(w)
     gram = st.gram[w]                                  # (nc, P + 1, P + 1)
     G = np.zeros((nc, Q, Q))
-    b = np.zeros((nc, Q))
     G[:, :P, :P] = gram[:, :P, :P]
-    b[:, :P] = gram[:, :P, P]
-    yty = gram[:, P, P]
     G[:, P:, :K] = st.dtz[sl]
     G[:, P:, K:P] = st.dth[sl]
     G[:, :P, P:] = np.transpose(G[:, P:, :P], (0, 2, 1))
@@ -103,7 +102,6 @@ def _finish_chunk(st, sl, A, K, min_ac):
     DD[:, iu[0], iu[1]] = st.dtd[sl]
     DD[:, iu[1], iu[0]] = st.dtd[sl]
     G[:, P:, P:] = DD
-    b[:, P:] = st.dty[sl]
     keep = np.ones((nc, Q), bool)
     keep[:, K:P] = st.sum_h[w][:, :A - 1] > 0
     keep[:, P:] = st.sum_d[sl] >= min_ac
@@ -112,7 +110,6 @@ def _finish_chunk(st, sl, A, K, min_ac):
     # a dropped column becomes a unit row / column with a zero right-hand side: one batch shape for every SNP
     kk = keep[:, :, None] & keep[:, None, :]
     G = np.where(kk, G, 0.0)
-    b = np.where(keep, b, 0.0)
     diag = np.einsum("bqq->bq", G)
     s = np.sqrt(np.where(keep & (diag > 0), diag, 1.0))
     zero_col = keep & ~(diag > 0)                       # a kept column of zeros (a covariate): never positive definite
@@ -120,7 +117,18 @@ def _finish_chunk(st, sl, A, K, min_ac):
     Gs[:, np.arange(Q), np.arange(Q)] = np.where(keep & (diag > 0), 1.0, np.where(keep, 0.0, 1.0))
     L, bad = _cholesky_batched(Gs)
     bad |= zero_col.any(1)
-    Li = _lower_inverse_batched(L)
+    return w, keep, n, df, s, _lower_inverse_batched(L), bad
+
+
+def _finish_chunk(st, sl, A, K, min_ac):
+    P, Q = K + A - 1, K + 2 * A - 1
+    w, keep, n, df, s, Li, bad = _factor_chunk(st, sl, A, K, min_ac)
+    gram = st.gram[w]
+    b = np.zeros((len(w), Q))
+    b[:, :P] = gram[:, :P, P]
+    yty = gram[:, P, P]
+    b[:, P:] = st.dty[sl]
+    b = np.where(keep, b, 0.0)
     inv = np.einsum("bkq,bkr->bqr", Li, Li)
     beta_s = np.einsum("bqr,br->bq", inv, b / s)
     beta = beta_s / s
@@ -161,6 +169,213 @@ def assoc_from_stats(stats_fn, C, A, K, min_ac=1):
     parts = [finish(stats_fn(c0, min(c0 + step, C)), A, K, min_ac) for c0 in range(0, C, step)]
     beta, se, tt, n_alt, n_hap, n, df, n_miss, status = (np.concatenate([p[i] for p in parts]) for i in range(9))
     return AncestryAssoc(beta, se, tt, p_values(tt, df), n_alt, n_hap, n, df, n_miss, status)
+
+
+AncestryAssocTraits = collections.namedtuple("AncestryAssocTraits", "beta se t p n_alt n_hap n df n_miss status")
+AncestryAssocTraits.__doc__ = """what ancestry_assoc_traits returns for T quantitative traits.  beta, se, t, p: (C, A, T) float64, NaN for a dropped
+dosage term and for a SNP with status != 0; the integer fields and status do not depend on the trait and are shaped as in AncestryAssoc:
+n_alt, n_hap (C, A) int32; n, df, n_miss, status (C,) int32"""
+
+TraitStats = collections.namedtuple("TraitStats", "dty ry yty window n_bad")
+TraitStats.__doc__ = """the trait-dependent blocks of SNPs [c0, c1) (gnx_ancestry_assoc_traits): dty (nc, A, T) = D^T Y; per window of the range ry
+(nw, K + A - 1, T) = [Z, h_0 .. h_{A-2}]^T Y and yty (nw, T) = diag(Y^T Y); window (nc,): the row of the window blocks a SNP uses;
+n_bad: labels outside [0, A).  Views of the padded arrays of the C ABI (their last axis is T rounded up to a multiple of 16)."""
+
+MAX_T = 65536                     # GNX_ASSOC_MAX_T of include/gnomix_hip.h
+TRAITS_MAX_BYTES = 2 << 30        # what ancestry_assoc_traits agrees to concatenate by default
+
+
+def trait_ldt(T):
+    return (int(T) + 15) // 16 * 16
+
+
+def trait_buffers(A, K, T, c0, c1, M, W, empty=None):
+    """zeroed (or empty(shape, dtype)) arrays of one call, in the order of the C ABI: snp_y, win_y, win_yy"""
+    ldt = trait_ldt(T)
+    nc = max(c1 - c0, 0)
+    nw = int(min((c1 - 1) // M, W - 1) - min(c0 // M, W - 1) + 1) if 0 <= c0 < c1 and M >= 1 else 1
+    new = empty or (lambda shape, dtype: np.zeros(shape, dtype))
+    return new((nc, A, ldt), np.float64), new((nw, K + A - 1, ldt), np.float64), new((nw, ldt), np.float64)
+
+
+def split_traits(sy, wy, wyy, T, c0, c1, M, W, n_bad=0):
+    """the three arrays of the C ABI -> TraitStats (views)"""
+    w = np.minimum(np.arange(c0, c1) // M, W - 1)
+    return TraitStats(sy[:, :, :T], wy[:, :, :T], wyy[:, :T], w - w[0], int(n_bad))
+
+
+def trait_covariates(n_ind, Y, Z=None, use=None):
+    """Y (n_ind, T), Z (n_ind, K) or None (the intercept only), use (n_ind,) or None -> contiguous float64 / float64 / uint8 arrays and
+    use2 = use & (every entry of Y[i, :] finite): the participation byte of the trait-independent blocks (complete cases across the
+    batch of traits; traits with different missingness patterns go in separate calls)"""
+    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    if Y.ndim != 2 or Y.shape[0] != n_ind or Y.shape[1] < 1:
+        raise ValueError(f"Y must be (n_ind={n_ind}, T >= 1), got {Y.shape}")
+    if Y.shape[1] > MAX_T:
+        raise ValueError(f"at most {MAX_T} traits per call, got {Y.shape[1]}")
+    _, Z, use = covariates(n_ind, np.zeros(n_ind), Z, use)
+    use2 = np.ascontiguousarray(use & np.isfinite(Y).all(1), dtype=np.uint8)
+    return Y, Z, use, use2
+
+
+def traits_snps_per_chunk(A, K, T, max_bytes=STATS_CHUNK_BYTES):
+    """SNPs per chunk such that the device blocks of the chunk (both entries) and its four (nc, A, T) float64 results each stay below
+    max_bytes"""
+    NF, NI, _, _ = layout(A, K)
+    return max(1, max_bytes // max(NF * 8 + NI * 4 + A * trait_ldt(T) * 8, 4 * A * T * 8))
+
+
+def traits_result_bytes(C, A, T):
+    """bytes of an AncestryAssocTraits of C SNPs"""
+    return C * (4 * A * T * 8 + 2 * A * 4 + 4 * 4)
+
+
+def _finish_traits_chunk(st, ts, sl, A, K, min_ac):
+    P, Q = K + A - 1, K + 2 * A - 1
+    w, keep, n, df, s, Li, bad = _factor_chunk(st, sl, A, K, min_ac)     # one factorisation per SNP, whatever T
+    nc, T = len(w), ts.dty.shape[2]
+    b = np.empty((nc, Q, T))
+    b[:, :P] = ts.ry[w]
+    b[:, P:] = ts.dty[sl]
+    b = np.where(keep[:, :, None], b, 0.0)
+    v = np.matmul(Li, b / s[:, :, None])                                 # L v = b / s, then L^T beta_s = v: two triangular products
+    beta = np.matmul(np.transpose(Li, (0, 2, 1)), v) / s[:, :, None]
+    rss = np.maximum(ts.yty[w] - np.einsum("bqt,bqt->bt", b, beta), 0.0)
+    status = np.where(df < 1, 2, np.where(bad, 1, 0)).astype(np.int32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        s2 = rss / df[:, None]
+        se = np.sqrt(s2[:, None, :] * np.einsum("bkq,bkq->bq", Li, Li)[:, :, None]) / s[:, :, None]
+        tt = beta / se
+    dead = ((status != 0)[:, None] | ~keep)[:, :, None]
+    beta, se, tt = (np.where(dead, np.nan, x)[:, P:] for x in (beta, se, tt))
+    return beta, se, tt, n.astype(np.int32), df.astype(np.int32), status
+
+
+def finish_traits(st, ts, A, K, min_ac=1, max_bytes=FINISH_CHUNK_BYTES):
+    """AssocStats (the trait-independent blocks: gnx_ancestry_assoc_stats under the traits' participation, its phenotype ignored) and
+    TraitStats of the same range of SNPs -> (beta, se, t (nc, A, T), n_alt, n_hap, n, df, n_miss, status): per chunk of SNPs the normal
+    matrix is assembled and factored ONCE, all T right-hand sides are solved with batched triangular products, RSS_t = Y^T Y_t - b_t^T beta_t"""
+    if min_ac < 1:
+        raise ValueError("min_ac must be >= 1")
+    nc = len(st.window)
+    Q, T = K + 2 * A - 1, ts.dty.shape[2]
+    step = max(1, max_bytes // (Q * Q * 8 * 6 + Q * T * 8 * 4))
+    parts = [_finish_traits_chunk(st, ts, slice(i, min(i + step, nc)), A, K, min_ac) for i in range(0, nc, step)]
+    beta, se, tt, n, df, status = (np.concatenate([p[i] for p in parts]) for i in range(6))
+    return beta, se, tt, np.asarray(st.sum_d, np.int32).copy(), np.asarray(st.sum_h[st.window], np.int32), n, df, np.asarray(st.n_miss, np.int32).copy(), status
+
+
+def p_values_traits(t, df):
+    """two-sided p of t (C, A, T) with df (C,) degrees of freedom; NaN where t is"""
+    from scipy import stats
+    with np.errstate(invalid="ignore"):
+        return 2.0 * stats.t.sf(np.abs(t), np.maximum(df, 1)[:, None, None].astype(np.float64))
+
+
+def traits_chunks(blocks_fn, C, A, K, T, min_ac=1, p_max=None, chunk_bytes=None):
+    """blocks_fn(c0, c1) -> (AssocStats, TraitStats); a generator of (c0, c1, AncestryAssocTraits) per chunk of
+    traits_snps_per_chunk(A, K, T, chunk_bytes) SNPs.  p_max: the float results of every (SNP, ancestry, trait) whose p is not <= p_max
+    are set to NaN (what remains is the list of hits)."""
+    step = traits_snps_per_chunk(A, K, T, STATS_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes))
+    for c0 in range(0, C, step):
+        c1 = min(c0 + step, C)
+        st, ts = blocks_fn(c0, c1)
+        beta, se, tt, n_alt, n_hap, n, df, n_miss, status = finish_traits(st, ts, A, K, min_ac)
+        p = p_values_traits(tt, df)
+        if p_max is not None:
+            with np.errstate(invalid="ignore"):
+                drop = ~(p <= p_max)
+            beta, se, tt, p = (np.where(drop, np.nan, x) for x in (beta, se, tt, p))
+        yield c0, c1, AncestryAssocTraits(beta, se, tt, p, n_alt, n_hap, n, df, n_miss, status)
+
+
+def traits_concat(chunks, C, A, T, max_bytes=TRAITS_MAX_BYTES):
+    """the chunks of traits_chunks -> one AncestryAssocTraits; ValueError before any work when it would exceed max_bytes"""
+    need = traits_result_bytes(C, A, T)
+    if max_bytes is not None and need > max_bytes:
+        raise ValueError(f"the result of {C} SNPs x {A} ancestries x {T} traits takes {need} bytes, above max_bytes = {max_bytes}: "
+                         "walk ancestry_assoc_traits_chunks instead, or pass fewer traits")
+    parts = [r for _, _, r in chunks]
+    return AncestryAssocTraits(*(np.concatenate([getattr(r, f) for r in parts]) for f in AncestryAssocTraits._fields))
+
+
+def traits_host(ctx, X, labels, M, A, Y, Z, use, c0, c1, min_ac=1, check=True):
+    """gnx_ancestry_assoc_traits on host arrays: X (N, C) int8, labels (N, W) int32, Y (N / 2, T) -> TraitStats of [c0, c1)"""
+    import ctypes
+    X = np.asarray(X)
+    if X.dtype != np.int8 or X.ndim != 2 or X.strides[1] != 1:
+        X = np.ascontiguousarray(X, dtype=np.int8)
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    N, C = X.shape
+    W = lab.shape[1]
+    Y, Z, use, _ = trait_covariates(N // 2, Y, Z, use)
+    K, T = Z.shape[1], Y.shape[1]
+    sy, wy, wyy = trait_buffers(A, K, T, c0, c1, M, W)
+    n_bad = ctypes.c_int64(0)
+    rc = ctx.lib.gnx_ancestry_assoc_traits(ctx.h, X.ctypes.data, X.strides[0] if N > 1 else C, lab.ctypes.data, W, N, C, int(M), W, int(A), Y.ctypes.data,
+                                           T, T, Z.ctypes.data, K, use.ctypes.data, int(min_ac), c0, c1, sy.ctypes.data, wy.ctypes.data,
+                                           wyy.ctypes.data, ctypes.byref(n_bad))
+    if check or (rc != _lib.GNX_OK and not n_bad.value):
+        ctx.check(rc)
+    return split_traits(sy, wy, wyy, T, c0, c1, M, W, n_bad.value)
+
+
+def read_table(path, samples, what="trait"):
+    """a TSV with the header `sample<TAB>name...` matched to `samples` by name, as read_phenotypes matches -> (values (n, len(names))
+    float64, present (n,) bool, names).  A query sample the file lacks has present = False and NaN values; a cell that is empty, NA, NaN
+    or '.' is NaN; file samples the query lacks are ignored; a sample listed twice is an error."""
+    with open(path) as f:
+        lines = [ln.rstrip("\n").rstrip("\r") for ln in f if ln.strip()]
+    if not lines:
+        raise ValueError(f"{path}: empty {what} file")
+    head = lines[0].split("\t")
+    if len(head) < 2 or head[0] != "sample":
+        raise ValueError(f"{path}: the header must be 'sample<TAB>name...', got {head[:2]}")
+    names = head[1:]
+    if len(set(names)) != len(names):
+        raise ValueError(f"{path}: a {what} name is listed twice in the header")
+
+    def num(cell):
+        cell = cell.strip()
+        if cell == "" or cell.upper() in ("NA", "NAN", "."):
+            return np.nan
+        try:
+            return float(cell)
+        except ValueError:
+            raise ValueError(f"{path}: '{cell}' is not a number") from None
+
+    rows = {}
+    for ln in lines[1:]:
+        cells = ln.split("\t")
+        if len(cells) != len(head):
+            raise ValueError(f"{path}: a line has {len(cells)} cells, the header {len(head)}")
+        if cells[0] in rows:
+            raise ValueError(f"{path}: sample '{cells[0]}' is listed twice")
+        rows[cells[0]] = [num(c) for c in cells[1:]]
+    vals = np.full((len(samples), len(names)), np.nan)
+    present = np.zeros(len(samples), bool)
+    for i, name in enumerate(samples):
+        r = rows.get(str(name))
+        if r is not None:
+            vals[i] = r
+            present[i] = True
+    return vals, present, names
+
+
+def read_traits(trait_file, samples, covariate_file=None):
+    """inference.trait_file (header `sample<TAB>name...`, one column per trait) and the optional inference.covariate_file (header
+    `sample<TAB>cov...`) -> (Y (n, T), Z (n, 1 + covariates) with the intercept in front, use (n,) uint8, trait names, covariate names).
+    A sample absent from the trait file (or, where one is given, from the covariate file) has use = 0.  NA cells stay NaN: the model's
+    participation rule (complete cases across the traits, finite covariates) drops those individuals."""
+    Y, present, names = read_table(trait_file, samples, "trait")
+    n = len(samples)
+    Z = np.ones((n, 1))
+    cov_names = []
+    if covariate_file:
+        cov, cpresent, cov_names = read_table(covariate_file, samples, "covariate")
+        Z = np.concatenate([Z, cov], 1)
+        present = present & cpresent
+    return Y, Z, present.astype(np.uint8), names, ["intercept"] + cov_names
 
 
 def logit_layout(A, K):

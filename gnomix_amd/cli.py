@@ -136,7 +136,7 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
                   global_ancestry_output=False, ancestry_allele_freq_output=False, ancestry_assoc_output=False, phenotype_file=None,
                   ancestry_assoc_model="linear", ancestry_score_output=False, score_file=None, ancestry_mds_output=False,
                   ancestry_mds_components=None, ancestry_mds_min_sites=None, ancestry_clump_output=False, ancestry_clump_p1=None,
-                  ancestry_clump_p2=None, ancestry_clump_r2=None, ancestry_clump_kb=None):
+                  ancestry_clump_p2=None, ancestry_clump_r2=None, ancestry_clump_kb=None, trait_file=None, covariate_file=None):
     """gnomix.py:37-100 with the HIP model behind the same steps.  The query never becomes an (N, C) host matrix: the library
     parses the text into 2-bit rows (gnx_vcf_read), `column_map` keeps vcf_to_npy's bookkeeping (SNP intersection, REF flips,
     absent SNPs) as one int32 per model SNP, the GPU builds X and runs base + smoother (or Gnofix) on it, and the library
@@ -159,6 +159,12 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
     `ancestry_assoc_model` (config key inference.ancestry_assoc_model: linear | logistic; absent = linear): with logistic the
     phenotype is a case / control trait coded 0 / 1 (another value on a used sample: ValueError naming the sample) and the file is
     query_results.assoc.logistic.tsv instead, one logistic fit per SNP on the device (gnx_ancestry_assoc_logit_gt2).
+    `trait_file` (config key inference.trait_file: a TSV with the header `sample  name...`, one column per quantitative trait, matched by
+    sample name; a query sample it lacks takes no part) with ancestry_assoc_output, and optionally `covariate_file`
+    (inference.covariate_file: header `sample  cov...`; an intercept is added): one query_results.assoc.<name>.tsv per trait, in
+    write_assoc's format, all traits fitted at once chunk of SNPs by chunk (gnx_ancestry_assoc_traits_gt2, DESIGN.md section 4.23;
+    complete cases across the traits) and appended chunk by chunk.  It takes the place of phenotype_file (both may be given); linear
+    model only; not with phase=True (the ValueError above); clumping needs phenotype_file.
     `ancestry_score_output` (config key inference.ancestry_score_output, off unless set) with `score_file` (inference.score_file: a TSV
     with the header `chm  pos  effect_allele` and weight columns NAME or NAME:POP, score.read_score_file): query_results.sscore.tsv as
     well, the ancestry-partitioned polygenic scores of every individual, summed on the model's own GPU from the query's 2-bit rows
@@ -193,8 +199,14 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
     if ancestry_assoc_output and base_args["phase"]:
         raise ValueError("inference.ancestry_assoc_output with phase=True: the phased haplotypes are not kept on this path; "
                          "use HipGnomix.phase followed by HipGnomix.ancestry_association")
-    if ancestry_assoc_output and not phenotype_file:
+    if ancestry_assoc_output and not phenotype_file and not trait_file:
         raise ValueError("inference.ancestry_assoc_output needs inference.phenotype_file (a TSV: sample, pheno, then covariates)")
+    if ancestry_assoc_output and trait_file and ancestry_assoc_model != "linear":
+        raise ValueError("inference.trait_file: several traits at once are fitted with inference.ancestry_assoc_model linear only")
+    if ancestry_clump_output and not phenotype_file:
+        raise ValueError("inference.ancestry_clump_output clumps the result of inference.phenotype_file, not those of inference.trait_file")
+    if covariate_file and not trait_file:
+        raise ValueError("inference.covariate_file goes with inference.trait_file (inference.phenotype_file carries its own covariates)")
     if ancestry_score_output and base_args["phase"]:
         raise ValueError("inference.ancestry_score_output with phase=True: the phased haplotypes are not kept on this path; "
                          "use HipGnomix.phase followed by HipGnomix.ancestry_scores")
@@ -240,7 +252,7 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
                               global_ancestry_output, ancestry_allele_freq_output, ancestry_assoc_output, phenotype_file, ancestry_assoc_model,
                               ancestry_score_output=ancestry_score_output, score_file=score_file,
                               ancestry_mds=(mds_k, mds_sites) if ancestry_mds_output else None,
-                              ancestry_clump=clump_kw if ancestry_clump_output else None)
+                              ancestry_clump=clump_kw if ancestry_clump_output else None, trait_file=trait_file, covariate_file=covariate_file)
     finally:
         if own_group is not None:
             own_group.close()
@@ -248,7 +260,8 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
 
 def _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out, T, t0, snp_level, bed_file_output, verbose,
                    global_ancestry_output=False, ancestry_allele_freq_output=False, ancestry_assoc_output=False, phenotype_file=None,
-                   ancestry_assoc_model="linear", ancestry_score_output=False, score_file=None, ancestry_mds=None, ancestry_clump=None):
+                   ancestry_assoc_model="linear", ancestry_score_output=False, score_file=None, ancestry_mds=None, ancestry_clump=None,
+                   trait_file=None, covariate_file=None):
     from time import perf_counter as clock
     from . import postprocess as pp
     from . import vcfio
@@ -305,7 +318,20 @@ def _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out,
         counts = runner.allele_counts_gt2(vcf.gt2, N, src, labels)
         pp.write_afreq(out_prefix, chm, model.snp_pos, model.M, model.W, counts, model.population_order)
         T["write_afreq"] = clock() - t0
-    if ancestry_assoc_output:
+    if ancestry_assoc_output and trait_file:
+        t0 = clock()
+        from . import assoc
+        Y, Z, use, trait_names, _ = assoc.read_traits(trait_file, [str(s) for s in samples], covariate_file)
+        for name in trait_names:
+            if not name or os.sep in name or name in (".", ".."):
+                raise ValueError(f"{trait_file}: the trait name '{name}' cannot be part of a file name")
+        for c0, c1, res in model.dev.ancestry_assoc_traits_gt2_chunks(vcf.gt2, N, src, labels, Y, Z, use):     # one GPU: the model's own
+            for t, name in enumerate(trait_names):
+                one = assoc.AncestryAssoc(res.beta[:, :, t], res.se[:, :, t], res.t[:, :, t], res.p[:, :, t], res.n_alt, res.n_hap, res.n, res.df,
+                                          res.n_miss, res.status)
+                pp.write_assoc(out_prefix, chm, model.snp_pos, model.M, model.W, one, model.population_order, c0=c0, name=name)
+        T["write_assoc_traits"] = clock() - t0
+    if ancestry_assoc_output and phenotype_file:
         t0 = clock()
         from . import assoc
         names = [str(s) for s in samples]
@@ -419,7 +445,8 @@ def main(argv=None):
                       ancestry_mds_min_sites=inf.get("ancestry_mds_min_sites"),
                       ancestry_clump_output=bool(inf.get("ancestry_clump_output")), ancestry_clump_p1=inf.get("ancestry_clump_p1"),
                       ancestry_clump_p2=inf.get("ancestry_clump_p2"), ancestry_clump_r2=inf.get("ancestry_clump_r2"),
-                      ancestry_clump_kb=inf.get("ancestry_clump_kb"))
+                      ancestry_clump_kb=inf.get("ancestry_clump_kb"), trait_file=inf.get("trait_file"),
+                      covariate_file=inf.get("covariate_file"))
         if os.environ.get("GNX_CLI_TIMING"):
             T["since_process_start"] = _since_process_start()
             sys.stderr.write("gnomix_amd timings (s): " + ", ".join("%s %.3f" % kv for kv in T.items()) + "\n")
@@ -588,7 +615,8 @@ def train_main(argv):
                       ancestry_mds_min_sites=inf.get("ancestry_mds_min_sites"),
                       ancestry_clump_output=bool(inf.get("ancestry_clump_output")), ancestry_clump_p1=inf.get("ancestry_clump_p1"),
                       ancestry_clump_p2=inf.get("ancestry_clump_p2"), ancestry_clump_r2=inf.get("ancestry_clump_r2"),
-                      ancestry_clump_kb=inf.get("ancestry_clump_kb"))
+                      ancestry_clump_kb=inf.get("ancestry_clump_kb"), trait_file=inf.get("trait_file"),
+                      covariate_file=inf.get("covariate_file"))
     return 0
 
 

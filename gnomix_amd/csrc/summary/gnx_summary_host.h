@@ -30,6 +30,13 @@ struct gnx_sum_pheno {
   uint8_t* d_use;
 };
 int gnx_sum_stage_pheno(gnx_ctx* ctx, const double* y, const double* Z, int32_t K, const uint8_t* use, int64_t n_ind, gnx_sum_pheno* p, hipStream_t s);
+// the many-trait form (k_ancestry_assoc_traits.hip): Y (n_ind, T) with row stride ldy -> compact (n_ind, T) | Z | use in ws_scale
+struct gnx_sum_traits {
+  double *d_Y, *d_Z;
+  uint8_t* d_use;
+};
+int gnx_sum_stage_traits(gnx_ctx* ctx, const double* Y, int64_t ldy, int32_t T, const double* Z, int32_t K, const uint8_t* use, int64_t n_ind,
+                         gnx_sum_traits* p, hipStream_t s);
 // room in ws_p64 for what the two prep kernels write: zy (n_ind, K + 1) float64, padded to 256 bytes, then part, a byte per individual
 int gnx_sum_zy_part(gnx_ctx* ctx, int64_t n_ind, int32_t K, double** zy, uint8_t** part);
 

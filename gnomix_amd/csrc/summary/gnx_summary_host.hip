@@ -55,6 +55,24 @@ int gnx_sum_stage_pheno(gnx_ctx* ctx, const double* y, const double* Z, int32_t 
   return GNX_OK;
 }
 
+int gnx_sum_stage_traits(gnx_ctx* ctx, const double* Y, int64_t ldy, int32_t T, const double* Z, int32_t K, const uint8_t* use, int64_t n_ind,
+                         gnx_sum_traits* p, hipStream_t s) {
+  const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t by = up((size_t)n_ind * T * 8), bz = up((size_t)n_ind * K * 8), bu = up((size_t)n_ind);
+  const int rc = gnx_ws_reserve(ctx, ctx->ws_scale, by + bz + bu + 64);
+  if (rc != GNX_OK) return rc;
+  char* sc = (char*)ctx->ws_scale.p;
+  p->d_Y = (double*)sc;
+  p->d_Z = (double*)(sc + by);
+  p->d_use = use ? (uint8_t*)(sc + by + bz) : nullptr;
+  if (n_ind > 0) {
+    HIPCHK(ctx, hipMemcpy2DAsync(p->d_Y, (size_t)T * 8, Y, (size_t)ldy * 8, (size_t)T * 8, (size_t)n_ind, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(p->d_Z, Z, (size_t)n_ind * K * 8, hipMemcpyHostToDevice, s));
+    if (use) HIPCHK(ctx, hipMemcpyAsync(p->d_use, use, (size_t)n_ind, hipMemcpyHostToDevice, s));
+  }
+  return GNX_OK;
+}
+
 int gnx_sum_zy_part(gnx_ctx* ctx, int64_t n_ind, int32_t K, double** zy, uint8_t** part) {
   const size_t zy_bytes = (((size_t)n_ind * (K + 1) * sizeof(double)) + 255) & ~(size_t)255;
   const int rc = gnx_ws_reserve(ctx, ctx->ws_p64, zy_bytes + (size_t)n_ind + 256);

@@ -258,11 +258,20 @@ class HipGnomix:
         column (None = the intercept only), use (N / 2,) bytes.  The sufficient statistics are reduced on the device
         (k_ancestry_assoc_snp); with a CUDA tensor neither X nor the labels leave HBM.  Results are numpy arrays.
         model="logistic": a case / control trait (y coded 0 / 1), the same terms with a logit link, fitted by maximum likelihood on the
-        device (k_ancestry_assoc_logit_snp) -> assoc.AncestryAssocLogit.  Any other value: ValueError."""
+        device (k_ancestry_assoc_logit_snp) -> assoc.AncestryAssocLogit.  Any other value: ValueError.
+        A 2-D y is Y (N / 2, T): T quantitative traits at once (DeviceModel.ancestry_assoc_traits: D^T Y on the float64 matrix cores, one
+        factorisation per SNP for all traits; complete cases across the traits) -> assoc.AncestryAssocTraits with beta, se, t, p shaped
+        (C, A, T); ValueError where that exceeds 2 GiB (walk dev.ancestry_assoc_traits_chunks instead); with model="logistic":
+        NotImplementedError."""
         if model not in ("linear", "logistic"):
             raise ValueError(f"model must be 'linear' or 'logistic', got {model!r}")
-        fit = (lambda X, lab: self.dev.ancestry_assoc(X, lab, y, Z, use, min_ac)) if model == "linear" else (
-            lambda X, lab: self.dev.ancestry_assoc_logit(X, lab, y, Z, use, min_ac))
+        if np.ndim(y) == 2:
+            if model == "logistic":
+                raise NotImplementedError("ancestry_association: several traits at once (a 2-D y) are fitted with model='linear' only")
+            fit = lambda X, lab: self.dev.ancestry_assoc_traits(X, lab, y, Z, use, min_ac)
+        else:
+            fit = (lambda X, lab: self.dev.ancestry_assoc(X, lab, y, Z, use, min_ac)) if model == "linear" else (
+                lambda X, lab: self.dev.ancestry_assoc_logit(X, lab, y, Z, use, min_ac))
         mf = self.smooth.mode_filter
         if resident.is_cuda(X):
             with resident.torch_stream(self.dev.ctx):

@@ -800,6 +800,108 @@ class DeviceModel:
         return assoc.assoc_from_stats(lambda c0, c1: self.ancestry_assoc_stats_gt2(G, N, src, labels, y, Z, use, c0, c1, min_ac), self.C, self.A,
                                       Z.shape[1], min_ac)
 
+    def ancestry_assoc_traits_stats(self, X, labels, Y, Z=None, use=None, c0=0, c1=None, min_ac=1, check=True):
+        """the trait-dependent blocks of T quantitative traits for the SNPs [c0, c1) (gnx_ancestry_assoc_traits[_dev], the float64 matrix
+        cores; include/gnomix_hip.h states them) -> gnomix_amd.assoc.TraitStats of numpy arrays.  Y (N / 2, T); X and labels as
+        ancestry_assoc_stats takes them (numpy arrays, or CUDA tensors that never leave HBM).  check=False: labels out of range do not
+        raise, their count is TraitStats.n_bad."""
+        from . import assoc
+        c1 = self.C if c1 is None else int(c1)
+        c0 = int(c0)
+        if not hasattr(X, "is_cuda"):
+            X = self._x(X)
+            lab = np.ascontiguousarray(labels, dtype=np.int32)
+            if lab.shape != (X.shape[0], self.W):
+                raise ValueError(f"labels must be (N={X.shape[0]}, W={self.W}), got {lab.shape}")
+            return assoc.traits_host(self.ctx, X, lab, self.M, self.A, Y, Z, use, c0, c1, min_ac=min_ac, check=check)
+        import ctypes
+        import torch
+        kind, ld, ldl, N = self._allele_device_args(X, labels)
+        Yh, Zh, uh, _ = assoc.trait_covariates(N // 2, Y, Z, use)
+        K, T = Zh.shape[1], Yh.shape[1]
+        dev = X.device
+        Y_t, Z_t, u_t = (torch.from_numpy(v).to(dev) for v in (Yh, Zh, uh))
+        sy, wy, wyy = assoc.trait_buffers(self.A, K, T, c0, c1, self.M, self.W, empty=lambda shape, dt: torch.empty(shape, dtype=torch.float64, device=dev))
+        n_bad = ctypes.c_int64(0)
+        self._bind_torch_stream()
+        rc = self.lib.gnx_ancestry_assoc_traits_dev(self.ctx.h, X.data_ptr(), kind, ld, labels.data_ptr(), ldl, N, self.C, self.M, self.W, self.A,
+                                                    Y_t.data_ptr(), T, T, Z_t.data_ptr(), K, u_t.data_ptr(), int(min_ac), c0, c1, sy.data_ptr(),
+                                                    wy.data_ptr(), wyy.data_ptr(), ctypes.byref(n_bad))
+        if check or (rc != _lib.GNX_OK and not n_bad.value):
+            self.ctx.check(rc)
+        return assoc.split_traits(sy.cpu().numpy(), wy.cpu().numpy(), wyy.cpu().numpy(), T, c0, c1, self.M, self.W, n_bad.value)
+
+    def ancestry_assoc_traits_chunks(self, X, labels, Y, Z=None, use=None, min_ac=1, p_max=None, chunk_bytes=None, check=True):
+        """ancestry-specific association (the Tractor model, as ancestry_assoc states it) of T quantitative traits Y (N / 2, T) at once: a
+        generator of (c0, c1, gnomix_amd.assoc.AncestryAssocTraits) per chunk of SNPs, beta, se, t, p shaped (c1 - c0, A, T).  An
+        individual takes part when use says so, Z[i, :] is finite and EVERY trait of Y[i, :] is finite (complete cases across the batch;
+        group traits by missingness pattern and call once per group).  Per chunk the device computes D^T Y on the float64 matrix cores
+        (gnx_ancestry_assoc_traits) and the trait-independent blocks once (gnx_ancestry_assoc_stats with a zero phenotype); the host
+        factors each SNP's normal matrix once and solves all T traits.  The chunks are sized so that the device blocks and the results
+        of one chunk stay below chunk_bytes (default assoc.STATS_CHUNK_BYTES): the full result is never materialised here.  p_max: the
+        float results of every (SNP, ancestry, trait) whose p is not <= p_max are NaN.  X and labels: numpy arrays or CUDA tensors.
+        check=False: labels out of range do not raise (such an individual takes no part at that window)."""
+        from . import assoc
+        if min_ac < 1:
+            raise ValueError("min_ac must be >= 1")
+        n_ind = X.shape[0] // 2
+        Y, Z, use, use2 = assoc.trait_covariates(n_ind, Y, Z, use)
+        y0 = np.zeros(n_ind)
+
+        def blocks(c0, c1):
+            return (self.ancestry_assoc_stats(X, labels, y0, Z, use2, c0, c1, min_ac, check),
+                    self.ancestry_assoc_traits_stats(X, labels, Y, Z, use, c0, c1, min_ac, check))
+        return assoc.traits_chunks(blocks, self.C, self.A, Z.shape[1], Y.shape[1], min_ac, p_max, chunk_bytes)
+
+    def ancestry_assoc_traits(self, X, labels, Y, Z=None, use=None, min_ac=1, p_max=None, max_bytes=2 << 30, check=True):
+        """the chunks of ancestry_assoc_traits_chunks concatenated -> assoc.AncestryAssocTraits of all C SNPs.  ValueError naming the byte
+        count, before any work, when the result would exceed max_bytes (chr22 x 7 ancestries x 1024 traits is 18 GB per field)."""
+        from . import assoc
+        T = np.asarray(Y).shape[1] if np.asarray(Y).ndim == 2 else 0
+        return assoc.traits_concat(self.ancestry_assoc_traits_chunks(X, labels, Y, Z, use, min_ac, p_max, check=check), self.C, self.A, T, max_bytes)
+
+    def ancestry_assoc_traits_stats_gt2(self, G, N, src, labels, Y, Z=None, use=None, c0=0, c1=None, min_ac=1, check=True):
+        """ancestry_assoc_traits_stats of the parsed query (G, N, src as infer_gt2 takes them) under host labels (N, W): the packed rows
+        are built and reduced in HBM, batch of whole groups of 4 individuals by batch (gnx_ancestry_assoc_traits_gt2) -> assoc.TraitStats"""
+        import ctypes
+        from . import assoc
+        G, N, src = self._gt2_args(G, N, src)
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.shape != (N, self.W):
+            raise ValueError(f"labels must be (N={N}, W={self.W}), got {lab.shape}")
+        c1 = self.C if c1 is None else int(c1)
+        c0 = int(c0)
+        Y, Z, use, _ = assoc.trait_covariates(N // 2, Y, Z, use)
+        K, T = Z.shape[1], Y.shape[1]
+        sy, wy, wyy = assoc.trait_buffers(self.A, K, T, c0, c1, self.M, self.W)
+        n_bad = ctypes.c_int64(0)
+        rc = self.lib.gnx_ancestry_assoc_traits_gt2(self.h, G.ctypes.data, G.shape[0], G.shape[1], N, src.ctypes.data, lab.ctypes.data, Y.ctypes.data,
+                                                    T, T, Z.ctypes.data, K, use.ctypes.data, int(min_ac), c0, c1, sy.ctypes.data, wy.ctypes.data,
+                                                    wyy.ctypes.data, ctypes.byref(n_bad))
+        if check or (rc != _lib.GNX_OK and not n_bad.value):
+            self.ctx.check(rc)
+        return assoc.split_traits(sy, wy, wyy, T, c0, c1, self.M, self.W, n_bad.value)
+
+    def ancestry_assoc_traits_gt2_chunks(self, G, N, src, labels, Y, Z=None, use=None, min_ac=1, p_max=None, chunk_bytes=None):
+        """ancestry_assoc_traits_chunks of the parsed query under host labels (the command line's path)"""
+        from . import assoc
+        if min_ac < 1:
+            raise ValueError("min_ac must be >= 1")
+        n_ind = int(N) // 2
+        Y, Z, use, use2 = assoc.trait_covariates(n_ind, Y, Z, use)
+        y0 = np.zeros(n_ind)
+
+        def blocks(c0, c1):
+            return (self.ancestry_assoc_stats_gt2(G, N, src, labels, y0, Z, use2, c0, c1, min_ac),
+                    self.ancestry_assoc_traits_stats_gt2(G, N, src, labels, Y, Z, use, c0, c1, min_ac))
+        return assoc.traits_chunks(blocks, self.C, self.A, Z.shape[1], Y.shape[1], min_ac, p_max, chunk_bytes)
+
+    def ancestry_assoc_traits_gt2(self, G, N, src, labels, Y, Z=None, use=None, min_ac=1, p_max=None, max_bytes=2 << 30):
+        """ancestry_assoc_traits of the parsed query under host labels -> assoc.AncestryAssocTraits; ValueError above max_bytes"""
+        from . import assoc
+        T = np.asarray(Y).shape[1] if np.asarray(Y).ndim == 2 else 0
+        return assoc.traits_concat(self.ancestry_assoc_traits_gt2_chunks(G, N, src, labels, Y, Z, use, min_ac, p_max), self.C, self.A, T, max_bytes)
+
     def ancestry_assoc_logit_fit(self, X, labels, y, Z=None, use=None, c0=0, c1=None, min_ac=1, tol=None, max_iter=None, check=True):
         """the logistic fits of the SNPs [c0, c1) (gnx_ancestry_assoc_logit[_dev]; include/gnomix_hip.h states the model and the iteration)
         -> gnomix_amd.assoc.LogitFit of numpy arrays.  X and labels as ancestry_assoc_stats takes them (numpy arrays, or CUDA tensors

@@ -547,24 +547,31 @@ def write_afreq(prefix, chm, snp_pos, M, W, counts, populations):
             f.write("\t".join(cells) + "\n")
 
 
-def write_assoc(prefix, chm, snp_pos, M, W, result, populations):
+def write_assoc(prefix, chm, snp_pos, M, W, result, populations, c0=None, name=None):
     """<prefix>.assoc.tsv from an assoc.AncestryAssoc: one header line, then one line per model SNP in model order: chm, pos, window,
     n, df, status, n_miss, then per population <pop>.n_hap, .n_alt, .beta, .se, .t, .p (floats with six significant digits, nan for a
-    dropped term or a SNP that was not fitted), tab-separated"""
+    dropped term or a SNP that was not fitted), tab-separated.  name: the file is <prefix>.assoc.<name>.tsv (one trait of several).
+    c0 (None: `result` holds all C SNPs): `result` holds the SNPs c0 .. c0 + len(result.beta) - 1 only, a result that arrives chunk of
+    SNPs by chunk: the chunk at c0 = 0 starts the file, a later one goes behind the lines the file has."""
     pos = np.asarray(snp_pos)
     A, C = len(populations), len(pos)
-    if np.asarray(result.beta).shape != (C, A):
-        raise ValueError(f"result must be ({C} SNPs, {A} populations), got {np.asarray(result.beta).shape}")
+    nc = C if c0 is None else len(result.beta)
+    append = c0 is not None and int(c0) > 0
+    c0 = 0 if c0 is None else int(c0)
+    if np.asarray(result.beta).shape != (nc, A) or c0 < 0 or c0 + nc > C:
+        raise ValueError(f"result must be ({nc} SNPs, {A} populations), got {np.asarray(result.beta).shape}")
     num = lambda v: format(float(v), ".6g") if np.isfinite(v) else "nan"
-    with open(prefix + ".assoc.tsv", "w") as f:
-        f.write("chm\tpos\twindow\tn\tdf\tstatus\tn_miss\t" +
-                "\t".join("\t".join(p + s for s in (".n_hap", ".n_alt", ".beta", ".se", ".t", ".p")) for p in populations) + "\n")
-        for c in range(C):
-            cells = [str(chm), str(int(pos[c])), str(min(c // int(M), int(W) - 1)), str(int(result.n[c])), str(int(result.df[c])),
-                     str(int(result.status[c])), str(int(result.n_miss[c]))]
+    with open(prefix + (".assoc.tsv" if name is None else ".assoc.%s.tsv" % name), "a" if append else "w") as f:
+        if not append:
+            f.write("chm\tpos\twindow\tn\tdf\tstatus\tn_miss\t" +
+                    "\t".join("\t".join(p + s for s in (".n_hap", ".n_alt", ".beta", ".se", ".t", ".p")) for p in populations) + "\n")
+        for i in range(nc):
+            c = c0 + i
+            cells = [str(chm), str(int(pos[c])), str(min(c // int(M), int(W) - 1)), str(int(result.n[i])), str(int(result.df[i])),
+                     str(int(result.status[i])), str(int(result.n_miss[i]))]
             for a in range(A):
-                cells += [str(int(result.n_hap[c, a])), str(int(result.n_alt[c, a])), num(result.beta[c, a]), num(result.se[c, a]),
-                          num(result.t[c, a]), num(result.p[c, a])]
+                cells += [str(int(result.n_hap[i, a])), str(int(result.n_alt[i, a])), num(result.beta[i, a]), num(result.se[i, a]),
+                          num(result.t[i, a]), num(result.p[i, a])]
             f.write("\t".join(cells) + "\n")
 
 

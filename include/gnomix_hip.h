@@ -939,6 +939,54 @@ int gnx_ancestry_assoc_stats_gt2(gnx_model* m, const uint8_t* G, int64_t n_varia
                                  int64_t c0, int64_t c1, double* snp_f64, int32_t* snp_i32, double* win_f64, int32_t* win_i32,
                                  int64_t* n_bad);
 
+/* ---- ancestry-specific association for MANY quantitative traits at once: the trait-dependent statistics on the float64 matrix cores --
+ * (csrc/summary/k_ancestry_assoc_traits.hip)
+ * Everything not stated here is EXACTLY as gnx_ancestry_assoc_stats has it: rows, labels, M, W, A, win(c), h[i, a], d[i, a], Z, K, use,
+ *   min_ac, [c0, c1), the row forms, the model, the column rule, status 1 and 2, n, df, n_alt, n_hap and n_miss.
+ * INPUTS.  Y (N / 2, T) float64, row-major with row stride ldy >= T (in elements), 1 <= T <= GNX_ASSOC_MAX_T: column t is trait t.
+ * PARTICIPATION.  Individual i takes part at window k when use[i] != 0, Z[i, :] is finite, EVERY entry of Y[i, :] is finite and both its
+ *   labels at k lie in [0, A): complete cases across the batch of traits (for T = 1 exactly gnx_ancestry_assoc_stats' rule).  A trait's
+ *   own missingness pattern is not modelled: the caller groups traits by pattern and calls once per group.
+ * THE MODEL, per SNP c and trait t: gnx_ancestry_assoc_stats' model with y = Y[:, t] over the participants.  The integer quantities, the
+ *   column rule and the status do not depend on t; neither do D^T Z, D^T D, D^T H and the Gram matrix of [Z, h_0 .. h_{A-2}].  These
+ *   entries do NOT write them: gnx_ancestry_assoc_stats with use'[i] = use[i] && (Y[i, :] all finite) and a zero phenotype gives exactly
+ *   those blocks under exactly this participation (gnomix_amd/assoc.py: finish_traits factors once per SNP and solves all T traits).
+ * THE STATISTICS these entries write, for the SNPs [c0, c1) and the windows w0 = win(c0) .. w1 = win(c1 - 1), all OVERWRITTEN, one owner
+ *   per value, plain stores.  With ldt = T rounded up to a multiple of 16 and P = K + A - 1, sums over the participants of the window:
+ *     snp_y  (c1 - c0, A, ldt)      [a, t] = sum_i d[i, a] Y[i, t]                                  (D^T Y)
+ *     win_y  (w1 - w0 + 1, P, ldt)  [p, t] = sum_i u[i, p] Y[i, t],  u = [Z, h_0 .. h_{A-2}]         ([Z, H]^T Y)
+ *     win_yy (w1 - w0 + 1, ldt)     [t]    = sum_i Y[i, t]^2                                       (diag(Y^T Y))
+ *   Columns t >= T of every block are written as 0.0.  No NaN or infinity enters a sum: an entry all of whose terms are zero is 0.0.
+ * SUMMATION ORDER.  d * Y with d in {0, 1, 2} is exact.  snp_y: v_mfma_f64_16x16x4_f64 over the individuals in ascending groups of 4
+ *   (i = 4 g .. 4 g + 3; individuals that take no part enter as zeros), the accumulator starting at +0.0; the order of the four terms
+ *   inside one instruction is the hardware's and is not documented, so snp_y is NOT promised to equal gnx_ancestry_assoc_stats' D^T y bit
+ *   for bit (DESIGN.md 4.23 records what was observed).  win_y and win_yy: ascending i, one product per participant rounded once, no
+ *   fused multiply-add.  Every value is a function of N and the data alone: not of the grid, the tile sizes, [c0, c1) or the row form
+ *   (a sub-range equals the slice of the whole range, int8 rows equal 2-bit rows, bit for bit).
+ * GNX_ASSOC_MAX_T = 65536: the kernels index a window's (P + 1) ldt entries with an int (48 * 2^16 < 2^31) and put (ancestry groups) x
+ *   (groups of 4 trait tiles) <= 4 * 1024 on grid.y (< 65536).  The blocks of one call are the caller's to size: chunk the SNPs.
+ * GNX_EINVAL before the launch, nothing written: as gnx_ancestry_assoc_stats, and T < 1 or ldy < T.  GNX_EUNSUPPORTED:
+ *   A > GNX_ALLELE_MAX_A, K > GNX_ASSOC_MAX_K, T > GNX_ASSOC_MAX_T, N > 2^28.
+ * GNX_EINVAL after the launch: labels outside [0, A) among ALL rows at the windows w0 .. w1, *n_bad their count; labels are only
+ *   compared, such an individual takes no part at that window and every value is as stated.
+ * Both forms synchronise the context stream once.  In the _dev form every pointer but n_bad is a device pointer.
+ * gnx_ancestry_assoc_traits_gt2: the file path's form, arguments as gnx_ancestry_assoc_stats_gt2.  The packed rows are built batch by
+ *   batch; a batch holds whole groups of 4 individuals (8 haplotypes) whatever GNX_HOST_BATCH says and goes on from the accumulators
+ *   of the batches before it, so the blocks equal gnx_ancestry_assoc_traits' of the vcf_to_npy matrix bit for bit at any batch size. */
+#define GNX_ASSOC_MAX_T 65536
+int gnx_ancestry_assoc_traits_dev(gnx_ctx* ctx, const void* d_rows, int row_kind, int64_t ld_rows, const int32_t* d_labels, int64_t ld_labels,
+                                  int64_t N, int64_t C, int64_t M, int64_t W, int32_t A, const double* d_Y, int64_t ldy, int32_t T,
+                                  const double* d_Z, int32_t K, const uint8_t* d_use, int32_t min_ac, int64_t c0, int64_t c1, double* d_snp_y,
+                                  double* d_win_y, double* d_win_yy, int64_t* n_bad);
+int gnx_ancestry_assoc_traits(gnx_ctx* ctx, const int8_t* X, int64_t ld_rows, const int32_t* labels, int64_t ld_labels, int64_t N, int64_t C,
+                              int64_t M, int64_t W, int32_t A, const double* Y, int64_t ldy, int32_t T, const double* Z, int32_t K,
+                              const uint8_t* use, int32_t min_ac, int64_t c0, int64_t c1, double* snp_y, double* win_y, double* win_yy,
+                              int64_t* n_bad);
+int gnx_ancestry_assoc_traits_gt2(gnx_model* m, const uint8_t* G, int64_t n_variants, int64_t ldg, int64_t N, const int32_t* src,
+                                  const int32_t* labels, const double* Y, int64_t ldy, int32_t T, const double* Z, int32_t K,
+                                  const uint8_t* use, int32_t min_ac, int64_t c0, int64_t c1, double* snp_y, double* win_y, double* win_yy,
+                                  int64_t* n_bad);
+
 /* ---- ancestry-specific association for case / control traits: one logistic fit per SNP, on the device ---------------------------------
  * (csrc/summary/k_ancestry_assoc_logit.hip)
  * Everything not stated here is EXACTLY as gnx_ancestry_assoc_stats has it: rows, labels, M, W, A, win(c), h[i, a], d[i, a], y, Z, K, use,
