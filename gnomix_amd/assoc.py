@@ -6,8 +6,6 @@ import collections
 
 import numpy as np
 
-from . import _lib
-
 STATS_CHUNK_BYTES = 64 << 20      # the statistics of one chunk of SNPs (the blocks that leave the device per call) stay below this
 FINISH_CHUNK_BYTES = 64 << 20     # ... and so do the assembled normal matrices of one batched factorisation
 PIVOT_MIN = 2.0 ** -40            # a pivot of the unit-diagonal normal matrix at or below this: not positive definite (status 1)
@@ -44,6 +42,19 @@ def layout(A, K):
 def snps_per_chunk(A, K, max_bytes=STATS_CHUNK_BYTES):
     NF, NI, _, _ = layout(A, K)
     return max(1, max_bytes // (NF * 8 + NI * 4))
+
+
+def window_span(c0, c1, M, W):
+    """the number of windows the SNPs [c0, c1) touch (the window of SNP c is min(c // M, W - 1)); 1 for a range that is empty or not valid"""
+    return int(min((c1 - 1) // M, W - 1) - min(c0 // M, W - 1) + 1) if 0 <= c0 < c1 and M >= 1 else 1
+
+
+def stats_buffers(A, K, c0, c1, M, W, empty=None):
+    """zeroed (or empty(shape, dtype)) arrays of one call, in the order of the C ABI: snp_f64, snp_i32, win_f64, win_i32"""
+    NF, NI, NWF, NWI = layout(A, K)
+    nc, nw = max(c1 - c0, 0), window_span(c0, c1, M, W)
+    new = empty or (lambda shape, dtype: np.zeros(shape, dtype))
+    return new((nc, NF), np.float64), new((nc, NI), np.int32), new((nw, NWF), np.float64), new((nw, NWI), np.int32)
 
 
 def split_blocks(snp_f, snp_i, win_f, win_i, A, K, c0, c1, M, W, n_bad=0):
@@ -192,8 +203,7 @@ def trait_ldt(T):
 def trait_buffers(A, K, T, c0, c1, M, W, empty=None):
     """zeroed (or empty(shape, dtype)) arrays of one call, in the order of the C ABI: snp_y, win_y, win_yy"""
     ldt = trait_ldt(T)
-    nc = max(c1 - c0, 0)
-    nw = int(min((c1 - 1) // M, W - 1) - min(c0 // M, W - 1) + 1) if 0 <= c0 < c1 and M >= 1 else 1
+    nc, nw = max(c1 - c0, 0), window_span(c0, c1, M, W)
     new = empty or (lambda shape, dtype: np.zeros(shape, dtype))
     return new((nc, A, ldt), np.float64), new((nw, K + A - 1, ldt), np.float64), new((nw, ldt), np.float64)
 
@@ -300,24 +310,9 @@ def traits_concat(chunks, C, A, T, max_bytes=TRAITS_MAX_BYTES):
 
 
 def traits_host(ctx, X, labels, M, A, Y, Z, use, c0, c1, min_ac=1, check=True):
-    """gnx_ancestry_assoc_traits on host arrays: X (N, C) int8, labels (N, W) int32, Y (N / 2, T) -> TraitStats of [c0, c1)"""
-    import ctypes
-    X = np.asarray(X)
-    if X.dtype != np.int8 or X.ndim != 2 or X.strides[1] != 1:
-        X = np.ascontiguousarray(X, dtype=np.int8)
-    lab = np.ascontiguousarray(labels, dtype=np.int32)
-    N, C = X.shape
-    W = lab.shape[1]
-    Y, Z, use, _ = trait_covariates(N // 2, Y, Z, use)
-    K, T = Z.shape[1], Y.shape[1]
-    sy, wy, wyy = trait_buffers(A, K, T, c0, c1, M, W)
-    n_bad = ctypes.c_int64(0)
-    rc = ctx.lib.gnx_ancestry_assoc_traits(ctx.h, X.ctypes.data, X.strides[0] if N > 1 else C, lab.ctypes.data, W, N, C, int(M), W, int(A), Y.ctypes.data,
-                                           T, T, Z.ctypes.data, K, use.ctypes.data, int(min_ac), c0, c1, sy.ctypes.data, wy.ctypes.data,
-                                           wyy.ctypes.data, ctypes.byref(n_bad))
-    if check or (rc != _lib.GNX_OK and not n_bad.value):
-        ctx.check(rc)
-    return split_traits(sy, wy, wyy, T, c0, c1, M, W, n_bad.value)
+    """gnx_ancestry_assoc_traits on host arrays: X (N, C) int8 (any row stride), labels (N, W) int32, Y (N / 2, T) -> TraitStats of [c0, c1)"""
+    from . import ancestry_ops as ops
+    return ops.assoc_traits(ops.host_front(ctx, X, labels, M, A, strided=True), Y, Z, use, c0, c1, min_ac, check)
 
 
 def read_table(path, samples, what="trait"):
@@ -391,8 +386,7 @@ def logit_snps_per_chunk(A, K, max_bytes=STATS_CHUNK_BYTES):
 def logit_buffers(A, K, c0, c1, M, W, want_theta=True, empty=None):
     """zeroed (or empty(shape, dtype)) arrays of one call, in the order of the C ABI: snp_f64, snp_i32, theta or None, win_f64, win_i32"""
     SF, SI, Q, WF, WI = logit_layout(A, K)
-    nc = max(c1 - c0, 0)
-    nw = int(min((c1 - 1) // M, W - 1) - min(c0 // M, W - 1) + 1) if 0 <= c0 < c1 and M >= 1 else 1
+    nc, nw = max(c1 - c0, 0), window_span(c0, c1, M, W)
     new = empty or (lambda shape, dtype: np.zeros(shape, dtype))
     return new((nc, SF), np.float64), new((nc, SI), np.int32), new((nc, Q), np.float64) if want_theta else None, new((nw, WF), np.float64), new((nw, WI), np.int32)
 
@@ -455,24 +449,9 @@ def check_binary(y, use, names=None):
 
 
 def logit_host(ctx, X, labels, M, A, y, Z, use, c0, c1, min_ac=1, tol=LOGIT_TOL, max_iter=LOGIT_MAX_ITER, check=True, want_theta=True):
-    """gnx_ancestry_assoc_logit on host arrays: X (N, C) int8, labels (N, W) int32 -> LogitFit of [c0, c1)"""
-    import ctypes
-    X = np.asarray(X)
-    if X.dtype != np.int8 or X.ndim != 2 or X.strides[1] != 1:
-        X = np.ascontiguousarray(X, dtype=np.int8)
-    lab = np.ascontiguousarray(labels, dtype=np.int32)
-    N, C = X.shape
-    W = lab.shape[1]
-    y, Z, use = covariates(N // 2, y, Z, use)
-    K = Z.shape[1]
-    sf, si, th, wf, wi = logit_buffers(A, K, c0, c1, M, W, want_theta)
-    n_bad = ctypes.c_int64(0)
-    rc = ctx.lib.gnx_ancestry_assoc_logit(ctx.h, X.ctypes.data, X.strides[0] if N > 1 else C, lab.ctypes.data, W, N, C, int(M), W, int(A), y.ctypes.data,
-                                          Z.ctypes.data, K, use.ctypes.data, int(min_ac), c0, c1, float(tol), int(max_iter), sf.ctypes.data,
-                                          si.ctypes.data, th.ctypes.data if want_theta else None, wf.ctypes.data, wi.ctypes.data, ctypes.byref(n_bad))
-    if check or rc not in (_lib.GNX_OK, _lib.GNX_EINVAL) or (rc != _lib.GNX_OK and not n_bad.value):
-        ctx.check(rc)
-    return split_logit(sf, si, th, wf, wi, A, K, c0, c1, M, W, n_bad.value)
+    """gnx_ancestry_assoc_logit on host arrays: X (N, C) int8 (any row stride), labels (N, W) int32 -> LogitFit of [c0, c1)"""
+    from . import ancestry_ops as ops
+    return ops.assoc_logit(ops.host_front(ctx, X, labels, M, A, strided=True), y, Z, use, c0, c1, min_ac, tol, max_iter, check, want_theta)
 
 
 def covariates(n_ind, y, Z=None, use=None):
@@ -536,25 +515,6 @@ def read_phenotypes(path, samples):
 
 
 def stats_host(ctx, X, labels, M, A, y, Z, use, c0, c1, min_ac=1, check=True):
-    """gnx_ancestry_assoc_stats on host arrays: X (N, C) int8, labels (N, W) int32 -> AssocStats of [c0, c1)"""
-    import ctypes
-    X = np.asarray(X)
-    if X.dtype != np.int8 or X.ndim != 2 or X.strides[1] != 1:
-        X = np.ascontiguousarray(X, dtype=np.int8)
-    lab = np.ascontiguousarray(labels, dtype=np.int32)
-    N, C = X.shape
-    W = lab.shape[1]
-    y, Z, use = covariates(N // 2, y, Z, use)
-    K = Z.shape[1]
-    NF, NI, NWF, NWI = layout(A, K)
-    nc = c1 - c0
-    nw = int(min((c1 - 1) // M, W - 1) - min(c0 // M, W - 1) + 1) if 0 <= c0 < c1 and M >= 1 else 1
-    sf, si = np.zeros((max(nc, 0), NF)), np.zeros((max(nc, 0), NI), np.int32)
-    wf, wi = np.zeros((nw, NWF)), np.zeros((nw, NWI), np.int32)
-    n_bad = ctypes.c_int64(0)
-    rc = ctx.lib.gnx_ancestry_assoc_stats(ctx.h, X.ctypes.data, X.strides[0] if N > 1 else C, lab.ctypes.data, W, N, C, int(M), W, int(A), y.ctypes.data,
-                                          Z.ctypes.data, K, use.ctypes.data, int(min_ac), c0, c1, sf.ctypes.data, si.ctypes.data, wf.ctypes.data,
-                                          wi.ctypes.data, ctypes.byref(n_bad))
-    if check or (rc != _lib.GNX_OK and not n_bad.value):
-        ctx.check(rc)
-    return split_blocks(sf, si, wf, wi, A, K, c0, c1, M, W, n_bad.value)
+    """gnx_ancestry_assoc_stats on host arrays: X (N, C) int8 (any row stride), labels (N, W) int32 -> AssocStats of [c0, c1)"""
+    from . import ancestry_ops as ops
+    return ops.assoc_stats(ops.host_front(ctx, X, labels, M, A, strided=True), y, Z, use, c0, c1, min_ac, check)

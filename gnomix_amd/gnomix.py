@@ -4,6 +4,7 @@ predict / predict_proba / phase and the attributes run_inference() and the write
 from __future__ import annotations
 
 import sys
+from contextlib import contextmanager
 
 import numpy as np
 
@@ -238,18 +239,8 @@ class HipGnomix:
         int32 tables n_obs / n_alt / n_miss (postprocess.AlleleCounts; .freq() = n_alt / n_obs, NaN where nothing was observed), counted
         on the device (k_ancestry_allele_counts); with a CUDA tensor neither X nor the labels leave HBM and CUDA tensors come back.
         For re-phased haplotypes: X_phased, _ = model.phase(X); model.allele_frequencies(X_phased)"""
-        mf = self.smooth.mode_filter
-        if resident.is_cuda(X):
-            with resident.torch_stream(self.dev.ctx):
-                X = resident.check_x(X, self.C, self.dev.ctx.device)
-                _, lab = self.dev.infer_device(X, want_proba=False, want_labels=True)
-                if mf:
-                    lab = self.dev.mode_filter_device(lab, mf)
-                return self.dev.ancestry_allele_counts_device(X, lab)
-        _, lab = self.dev.infer(X, want_proba=False, want_labels=True)
-        if mf:
-            lab = self.dev.mode_filter(lab, mf)
-        return self.dev.ancestry_allele_counts(self.dev._x(X), lab)
+        with self._rows_and_labels(X) as (rows, lab, on_device):
+            return (self.dev.ancestry_allele_counts_device if on_device else self.dev.ancestry_allele_counts)(rows, lab)
 
     def ancestry_association(self, X, y, Z=None, use=None, min_ac=1, model="linear"):
         """ancestry-specific association (the Tractor model) of X under the labels predict returns (mode_filter applied when set):
@@ -272,18 +263,8 @@ class HipGnomix:
         else:
             fit = (lambda X, lab: self.dev.ancestry_assoc(X, lab, y, Z, use, min_ac)) if model == "linear" else (
                 lambda X, lab: self.dev.ancestry_assoc_logit(X, lab, y, Z, use, min_ac))
-        mf = self.smooth.mode_filter
-        if resident.is_cuda(X):
-            with resident.torch_stream(self.dev.ctx):
-                X = resident.check_x(X, self.C, self.dev.ctx.device)
-                _, lab = self.dev.infer_device(X, want_proba=False, want_labels=True)
-                if mf:
-                    lab = self.dev.mode_filter_device(lab, mf)
-                return fit(X, lab)
-        _, lab = self.dev.infer(X, want_proba=False, want_labels=True)
-        if mf:
-            lab = self.dev.mode_filter(lab, mf)
-        return fit(self.dev._x(X), lab)
+        with self._rows_and_labels(X) as (rows, lab, _):
+            return fit(rows, lab)
 
     def ancestry_scores(self, X, weights, effect=None):
         """ancestry-partitioned polygenic scores ("partial PRS") of X under the labels predict returns (mode_filter applied when set):
@@ -292,36 +273,16 @@ class HipGnomix:
         n_scored, n_miss (N / 2, A); .avg() = score / n_scored).  weights (C,), (C, A) or (C, A, S) (score.weights_from_assoc,
         score.read_score_file); effect None (ALT everywhere) or (C,) of 1 (ALT), 0 (REF), 255 (not scored).  One fused pass on the
         device (k_ancestry_score_partial); with a CUDA tensor neither X nor the labels leave HBM and CUDA tensors come back."""
-        mf = self.smooth.mode_filter
-        if resident.is_cuda(X):
-            with resident.torch_stream(self.dev.ctx):
-                X = resident.check_x(X, self.C, self.dev.ctx.device)
-                _, lab = self.dev.infer_device(X, want_proba=False, want_labels=True)
-                if mf:
-                    lab = self.dev.mode_filter_device(lab, mf)
-                return self.dev.ancestry_scores_device(X, lab, weights, effect)
-        _, lab = self.dev.infer(X, want_proba=False, want_labels=True)
-        if mf:
-            lab = self.dev.mode_filter(lab, mf)
-        return self.dev.ancestry_scores(self.dev._x(X), lab, weights, effect)
+        with self._rows_and_labels(X) as (rows, lab, on_device):
+            return (self.dev.ancestry_scores_device if on_device else self.dev.ancestry_scores)(rows, lab, weights, effect)
 
     def ancestry_pair_counts(self, X, ancestry, snp_range=None):
         """the pairwise count tables of one ancestry (index into population_order) of X under the labels predict returns (mode_filter
         applied when set) -> asmds.PairCounts(DD, DO, OO), (N / 2, N / 2) int32 each: sums over the SNPs of d[i] d[j], d[i] o[j] and
         o[i] o[j], o = an individual's haplotypes labelled `ancestry` with an observed call, d = those of them that are ALT.  One fused
         pass on the int8 matrix cores (k_ancestry_pairs); with a CUDA tensor neither X nor the labels leave HBM and CUDA tensors come back."""
-        mf = self.smooth.mode_filter
-        if resident.is_cuda(X):
-            with resident.torch_stream(self.dev.ctx):
-                X = resident.check_x(X, self.C, self.dev.ctx.device)
-                _, lab = self.dev.infer_device(X, want_proba=False, want_labels=True)
-                if mf:
-                    lab = self.dev.mode_filter_device(lab, mf)
-                return self.dev.ancestry_pair_counts_device(X, lab, ancestry, snp_range)
-        _, lab = self.dev.infer(X, want_proba=False, want_labels=True)
-        if mf:
-            lab = self.dev.mode_filter(lab, mf)
-        return self.dev.ancestry_pair_counts(self.dev._x(X), lab, ancestry, snp_range)
+        with self._rows_and_labels(X) as (rows, lab, on_device):
+            return (self.dev.ancestry_pair_counts_device if on_device else self.dev.ancestry_pair_counts)(rows, lab, ancestry, snp_range)
 
     def ancestry_mds(self, X, ancestry, k=4, min_sites=1000, min_pair_sites=None):
         """ancestry-specific MDS: the structure inside one ancestry component.  ancestry_pair_counts, then on the host (gnomix_amd.asmds)
@@ -333,17 +294,23 @@ class HipGnomix:
         counts = asmds.PairCounts(*(t.cpu().numpy() if hasattr(t, "is_cuda") else t for t in counts))
         return asmds.ancestry_mds(counts, k=k, min_sites=min_sites, min_pair_sites=min_pair_sites)
 
-    def _resident_rows_labels(self, X):
-        """X (numpy or CUDA) and the labels predict returns (mode_filter applied when set), both as CUDA tensors of the model's device"""
-        import torch
+    @contextmanager
+    def _rows_and_labels(self, X, resident_rows=False):
+        """X and the labels predict returns (mode_filter applied when set) -> (rows, labels, on_device) for the block.  A CUDA tensor is
+        labelled in HBM (so is a numpy X with resident_rows: it is uploaded first) and the library stays bound to torch's current stream
+        until the block ends, the op's own launch included; a numpy X is labelled through the host entry points"""
         mf = self.smooth.mode_filter
-        if not resident.is_cuda(X):
-            X = torch.from_numpy(np.ascontiguousarray(self.dev._x(X))).to("cuda:%d" % self.dev.ctx.device)
-        X = resident.check_x(X, self.C, self.dev.ctx.device)
-        _, lab = self.dev.infer_device(X, want_proba=False, want_labels=True)
-        if mf:
-            lab = self.dev.mode_filter_device(lab, mf)
-        return X, lab
+        if resident_rows or resident.is_cuda(X):
+            import torch
+            with resident.torch_stream(self.dev.ctx):
+                if not resident.is_cuda(X):
+                    X = torch.from_numpy(self.dev._x(X)).to("cuda:%d" % self.dev.ctx.device)
+                X = resident.check_x(X, self.C, self.dev.ctx.device)
+                _, lab = self.dev.infer_device(X, want_proba=False, want_labels=True)
+                yield X, self.dev.mode_filter_device(lab, mf) if mf else lab, True
+            return
+        _, lab = self.dev.infer(X, want_proba=False, want_labels=True)
+        yield self.dev._x(X), self.dev.mode_filter(lab, mf) if mf else lab, False
 
     def ancestry_ld(self, X, ancestry, c0=0, c1=None, band=256):
         """ancestry-specific LD: the banded count tables of one ancestry (index into population_order) of X under the labels predict
@@ -351,15 +318,8 @@ class HipGnomix:
         band) of (c1 - c0, band) int32 arrays (.r(), .r2(), .pair(c, c')): sums over the haplotypes labelled `ancestry` at both SNPs with
         both calls observed.  One fused pass on the int8 matrix cores (k_ancestry_ld); with a CUDA tensor neither X nor the labels leave
         HBM and CUDA tensors come back."""
-        if resident.is_cuda(X):
-            with resident.torch_stream(self.dev.ctx):
-                Xt, lab = self._resident_rows_labels(X)
-                return self.dev.ancestry_ld_counts_device(Xt, lab, ancestry, c0, c1, band)
-        mf = self.smooth.mode_filter
-        _, lab = self.dev.infer(X, want_proba=False, want_labels=True)
-        if mf:
-            lab = self.dev.mode_filter(lab, mf)
-        return self.dev.ancestry_ld_counts(self.dev._x(X), lab, ancestry, c0, c1, band)
+        with self._rows_and_labels(X) as (rows, lab, on_device):
+            return (self.dev.ancestry_ld_counts_device if on_device else self.dev.ancestry_ld_counts)(rows, lab, ancestry, c0, c1, band)
 
     def ancestry_clump(self, X, res, p1=1e-4, p2=1e-2, r2=0.5, kb=250):
         """clumping of an association result (assoc.AncestryAssoc / AncestryAssocLogit of these SNPs) ancestry by ancestry -> index_of
@@ -373,8 +333,7 @@ class HipGnomix:
             raise ValueError(f"res.p must be (C={self.C}, A={self.A}), got {p.shape}")
         band = ld.band_for(pos, kb)
         out = np.full((self.C, self.A), -1, np.int64)
-        with resident.torch_stream(self.dev.ctx):
-            Xt, lab = self._resident_rows_labels(X)
+        with self._rows_and_labels(X, resident_rows=True) as (Xt, lab, _):
             for a in range(self.A):
                 def counts_for(c0, c1, a=a):
                     t = self.dev.ancestry_ld_counts_device(Xt, lab, a, c0, c1, band)

@@ -13,6 +13,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
+from .ancestry_ops import AncestryOps
 
 GNX_FILE_VERSION = 1
 
@@ -359,8 +360,9 @@ class GnxModelData:
         return d, keep
 
 
-class DeviceModel:
-    """gnx_model handle: the model resident in HBM of one device."""
+class DeviceModel(AncestryOps):
+    """gnx_model handle: the model resident in HBM of one device.  Loading, inference, packing, phasing and the smoother live here;
+    the ancestry-specific ops are AncestryOps' (gnomix_amd/ancestry_ops.py)."""
 
     def __init__(self, data: GnxModelData, ctx: _lib.Context | None = None, device: int = 0, prepared=None):
         """prepared: the logistic base's planes as export_prepared() of the SAME model wrote them (uint8 array / buffer): skips their
@@ -471,532 +473,6 @@ class DeviceModel:
         self.ctx.check(self.lib.gnx_mode_filter_dev(self.ctx.h, lab_t.data_ptr(), lab_t.stride(0) if N > 1 else W, out.data_ptr(), W, N, W,
                                                     self.A, int(size)))
         return out
-
-    def ancestry_summary(self, lab, weights=None, proba=None):
-        """global ancestry and tract statistics of (N, W) labels (and (N, W, A) probabilities) on the device (gnx_ancestry_summary;
-        gnomix_amd.postprocess.ancestry_summary) -> AncestrySummary of numpy arrays"""
-        from .postprocess import ancestry_summary
-        return ancestry_summary(self.ctx, lab, self.A, weights, proba)
-
-    def ancestry_summary_device(self, lab_t, weights=None, proba_t=None):
-        """the same on an (N, W) int32 CUDA tensor with contiguous rows (any row stride) and, optionally, a contiguous (N, W, A)
-        float32 / float64 CUDA tensor (gnx_ancestry_summary_dev) -> AncestrySummary of CUDA tensors; the weights are a host array"""
-        import torch
-        from .postprocess import AncestrySummary, _summary_weights
-        assert lab_t.is_cuda and lab_t.dtype == torch.int32 and lab_t.dim() == 2 and (lab_t.shape[1] == 0 or lab_t.stride(1) == 1)
-        N, W = lab_t.shape
-        if proba_t is not None:
-            assert proba_t.is_cuda and proba_t.dtype in (torch.float32, torch.float64) and proba_t.is_contiguous()
-            if tuple(proba_t.shape) != (N, W, self.A):
-                raise ValueError(f"proba must be (N={N}, W={W}, A={self.A}), got {tuple(proba_t.shape)}")
-        w = _summary_weights(weights, W)
-        self._bind_torch_stream()
-        new = lambda dt: torch.zeros((N, self.A), dtype=dt, device=lab_t.device)
-        hard, total, longest, count = new(torch.float64), new(torch.float64), new(torch.float64), new(torch.int32)
-        soft = new(torch.float64) if proba_t is not None else None
-        self.ctx.check(self.lib.gnx_ancestry_summary_dev(
-            self.ctx.h, lab_t.data_ptr(), lab_t.stride(0) if N > 1 else W, proba_t.data_ptr() if proba_t is not None else None,
-            int(proba_t is not None and proba_t.dtype == torch.float64), w.ctypes.data, N, W, self.A, hard.data_ptr(),
-            soft.data_ptr() if soft is not None else None, count.data_ptr(), total.data_ptr(), longest.data_ptr()))
-        return AncestrySummary(hard, soft, count, total, longest, w)
-
-    def ancestry_allele_counts(self, X, labels, packed=False):
-        """ancestry-specific allele counts of X (N, C) int8 (packed=True: the 2-bit rows pack_x returns) under (N, W) labels, on the
-        device (gnx_ancestry_allele_counts; gnomix_amd.postprocess.allele_counts) -> AlleleCounts of (A, C) int32 arrays"""
-        from .postprocess import allele_counts
-        return allele_counts(self.ctx, X, labels, self.M, self.A, packed=packed, C=self.C)
-
-    def ancestry_dosage(self, X, labels, ancestry, packed=False):
-        """(dosage, hapcount) of one ancestry, (N / 2, C) uint8 each (gnx_ancestry_dosage; gnomix_amd.postprocess.ancestry_dosage)"""
-        from .postprocess import ancestry_dosage
-        return ancestry_dosage(self.ctx, X, labels, self.M, self.A, ancestry, packed=packed, C=self.C)
-
-    def _allele_device_args(self, X_t, lab_t):
-        import torch
-        assert X_t.is_cuda and X_t.dim() == 2 and (X_t.shape[1] == 0 or X_t.stride(1) == 1)
-        assert lab_t.is_cuda and lab_t.dtype == torch.int32 and lab_t.dim() == 2 and (lab_t.shape[1] == 0 or lab_t.stride(1) == 1)
-        N = X_t.shape[0]
-        if X_t.dtype == torch.int8:
-            kind, need = _lib.GNX_ROWS_INT8, self.C
-            if X_t.shape[1] != self.C:
-                raise ValueError(f"X must be (N, C={self.C}) int8, got {tuple(X_t.shape)}")
-        elif X_t.dtype == torch.uint8:
-            kind, need = _lib.GNX_ROWS_PACKED2, (self.C + 3) // 4
-            if X_t.shape[1] < need:
-                raise ValueError(f"packed X must be (N, >= {need}) uint8, got {tuple(X_t.shape)}")
-        else:
-            raise ValueError("X must be an int8 (N, C) tensor or the uint8 tensor pack_device returns")
-        if tuple(lab_t.shape) != (N, self.W):
-            raise ValueError(f"labels must be (N={N}, W={self.W}) int32, got {tuple(lab_t.shape)}")
-        ld = X_t.stride(0) if N > 1 else max(X_t.shape[1], need)
-        return kind, ld, (lab_t.stride(0) if N > 1 else self.W), N
-
-    def ancestry_allele_counts_device(self, X_t, lab_t):
-        """the same on CUDA tensors: X_t int8 (N, C) or the uint8 tensor pack_device returns, lab_t (N, W) int32 with any row stride
-        (gnx_ancestry_allele_counts_dev) -> AlleleCounts of (A, C) int32 CUDA tensors"""
-        import torch
-        from .postprocess import AlleleCounts
-        kind, ld, ldl, N = self._allele_device_args(X_t, lab_t)
-        self._bind_torch_stream()
-        obs, alt, miss = (torch.zeros((self.A, self.C), dtype=torch.int32, device=X_t.device) for _ in range(3))
-        self.ctx.check(self.lib.gnx_ancestry_allele_counts_dev(self.ctx.h, X_t.data_ptr(), kind, ld, lab_t.data_ptr(), ldl, N, self.C, self.M,
-                                                               self.W, self.A, obs.data_ptr(), alt.data_ptr(), miss.data_ptr(), 0, 0))
-        return AlleleCounts(obs, alt, miss)
-
-    def ancestry_dosage_device(self, X_t, lab_t, ancestry):
-        """(dosage, hapcount) uint8 (N / 2, C) CUDA tensors of one ancestry (gnx_ancestry_dosage_dev)"""
-        import torch
-        kind, ld, ldl, N = self._allele_device_args(X_t, lab_t)
-        self._bind_torch_stream()
-        dos, hap = (torch.zeros((N // 2, self.C), dtype=torch.uint8, device=X_t.device) for _ in range(2))
-        self.ctx.check(self.lib.gnx_ancestry_dosage_dev(self.ctx.h, X_t.data_ptr(), kind, ld, lab_t.data_ptr(), ldl, N, self.C, self.M, self.W,
-                                                        self.A, int(ancestry), dos.data_ptr(), self.C, hap.data_ptr(), self.C))
-        return dos, hap
-
-    def ancestry_scores(self, X, labels, weights, effect=None, packed=False):
-        """ancestry-partitioned polygenic scores of X (N, C) int8 (packed=True: the 2-bit rows pack_x returns) under (N, W) labels, on the
-        device (gnx_ancestry_score; gnomix_amd.postprocess.ancestry_scores) -> AncestryScores of numpy arrays.  weights (C,), (C, A) or
-        (C, A, S) float64; effect None (ALT everywhere) or (C,) of 1 (ALT), 0 (REF), 255 (not scored)"""
-        from .postprocess import ancestry_scores
-        return ancestry_scores(self.ctx, X, labels, self.M, self.A, weights, effect, packed=packed, C=self.C)
-
-    def ancestry_scores_device(self, X_t, lab_t, weights, effect=None):
-        """the same on CUDA tensors: X_t int8 (N, C) or the uint8 tensor pack_device returns, lab_t (N, W) int32 with any row stride;
-        weights and effect as numpy arrays or CUDA tensors (gnx_ancestry_score_dev) -> AncestryScores of CUDA tensors"""
-        import ctypes
-        import torch
-        from .postprocess import AncestryScores, score_tables, score_chunks
-        kind, ld, ldl, N = self._allele_device_args(X_t, lab_t)
-        if N % 2:
-            raise ValueError("N must be even (an individual has two haplotype rows)")
-        dev = X_t.device
-        if hasattr(weights, "is_cuda") and (effect is None or hasattr(effect, "is_cuda")):
-            w_t = weights.to(device=dev, dtype=torch.float64)
-            w_t = w_t[:, None].expand(-1, self.A)[:, :, None] if w_t.dim() == 1 else w_t[:, :, None] if w_t.dim() == 2 else w_t
-            if w_t.dim() != 3 or tuple(w_t.shape[:2]) != (self.C, self.A) or w_t.shape[2] < 1:
-                raise ValueError(f"weights must be (C={self.C},), (C, A={self.A}) or (C, A, S >= 1), got {tuple(weights.shape)}")
-            w_t = w_t.contiguous()
-            e_t = torch.ones(self.C, dtype=torch.uint8, device=dev) if effect is None else effect.to(device=dev, dtype=torch.uint8).contiguous()
-            if tuple(e_t.shape) != (self.C,):
-                raise ValueError(f"effect must be (C={self.C},), got {tuple(e_t.shape)}")
-        else:
-            to_host = lambda v: v.cpu().numpy() if hasattr(v, "is_cuda") else v
-            w, eff = score_tables(to_host(weights), None if effect is None else to_host(effect), self.C, self.A)
-            w_t, e_t = torch.from_numpy(w).to(dev), torch.from_numpy(eff).to(dev)
-        S = w_t.shape[2]
-        self._bind_torch_stream()
-        score = torch.zeros((N // 2, self.A, S), dtype=torch.float64, device=dev)
-        ne, ns, nm = (torch.zeros((N // 2, self.A), dtype=torch.int32, device=dev) for _ in range(3))
-        for s0, s1 in score_chunks(S):
-            whole = (s0, s1) == (0, S)
-            wc = w_t if whole else w_t[:, :, s0:s1].contiguous()
-            out = score if whole else torch.zeros((N // 2, self.A, s1 - s0), dtype=torch.float64, device=dev)
-            first = s0 == 0
-            n_bad = ctypes.c_int64(0)
-            self.ctx.check(self.lib.gnx_ancestry_score_dev(self.ctx.h, X_t.data_ptr(), kind, ld, lab_t.data_ptr(), ldl, N, self.C, self.M, self.W, self.A,
-                                                           wc.data_ptr(), s1 - s0, e_t.data_ptr(), out.data_ptr(), ne.data_ptr() if first else None,
-                                                           ns.data_ptr() if first else None, nm.data_ptr() if first else None, 0, 0,
-                                                           ctypes.byref(n_bad)))
-            if not whole:
-                score[:, :, s0:s1] = out
-        return AncestryScores(score, ne, ns, nm)
-
-    def ancestry_scores_gt2(self, G, N, src, labels, weights, effect=None):
-        """ancestry_scores of the parsed query (G, N, src as infer_gt2 takes them) under host labels (N, W): the packed rows are built and
-        scored in HBM, batch of individuals by batch (gnx_ancestry_score_gt2) -> AncestryScores of numpy arrays"""
-        import ctypes
-        from .postprocess import AncestryScores, score_tables, score_chunks
-        G, N, src = self._gt2_args(G, N, src)
-        if N % 2:
-            raise ValueError("N must be even (an individual has two haplotype rows)")
-        lab = np.ascontiguousarray(labels, dtype=np.int32)
-        if lab.shape != (N, self.W):
-            raise ValueError(f"labels must be (N={N}, W={self.W}), got {lab.shape}")
-        w, eff = score_tables(weights, effect, self.C, self.A)
-        S = w.shape[2]
-        score = np.zeros((N // 2, self.A, S))
-        ne, ns, nm = (np.zeros((N // 2, self.A), np.int32) for _ in range(3))
-        for s0, s1 in score_chunks(S):
-            whole = (s0, s1) == (0, S)
-            wc = w if whole else np.ascontiguousarray(w[:, :, s0:s1])
-            out = score if whole else np.zeros((N // 2, self.A, s1 - s0))
-            first = s0 == 0
-            n_bad = ctypes.c_int64(0)
-            self.ctx.check(self.lib.gnx_ancestry_score_gt2(self.h, G.ctypes.data, G.shape[0], G.shape[1], N, src.ctypes.data, lab.ctypes.data,
-                                                           wc.ctypes.data, s1 - s0, eff.ctypes.data, out.ctypes.data,
-                                                           ne.ctypes.data if first else None, ns.ctypes.data if first else None,
-                                                           nm.ctypes.data if first else None, ctypes.byref(n_bad)))
-            if not whole:
-                score[:, :, s0:s1] = out
-        return AncestryScores(score, ne, ns, nm)
-
-    def ancestry_pair_counts(self, X, labels, ancestry, snp_range=None, packed=False):
-        """the pairwise count tables DD, DO, OO of one ancestry over the SNPs snp_range = (c0, c1) (None: all), X (N, C) int8
-        (packed=True: the 2-bit rows pack_x returns) under (N, W) labels, on the int8 matrix cores (gnx_ancestry_pair_counts;
-        gnomix_amd.postprocess.pair_counts) -> asmds.PairCounts of (N / 2, N / 2) int32 arrays"""
-        from .postprocess import pair_counts
-        return pair_counts(self.ctx, X, labels, self.M, self.A, ancestry, snp_range, packed=packed, C=self.C)
-
-    def ancestry_pair_counts_device(self, X_t, lab_t, ancestry, snp_range=None, debug_snps_per_block=0):
-        """the same on CUDA tensors: X_t int8 (N, C) or the uint8 tensor pack_device returns, lab_t (N, W) int32 with any row stride
-        (gnx_ancestry_pair_counts_dev) -> asmds.PairCounts of (N / 2, N / 2) int32 CUDA tensors"""
-        import ctypes
-        import torch
-        from .asmds import PairCounts
-        kind, ld, ldl, N = self._allele_device_args(X_t, lab_t)
-        if N % 2:
-            raise ValueError("N must be even (an individual has two haplotype rows)")
-        c0, c1 = (0, self.C) if snp_range is None else (int(snp_range[0]), int(snp_range[1]))
-        n = N // 2
-        self._bind_torch_stream()
-        DD, DO, OO = (torch.zeros((n, n), dtype=torch.int32, device=X_t.device) for _ in range(3))
-        n_bad = ctypes.c_int64(0)
-        self.ctx.check(self.lib.gnx_ancestry_pair_counts_dev(self.ctx.h, X_t.data_ptr(), kind, ld, lab_t.data_ptr(), ldl, N, self.C, self.M, self.W,
-                                                             self.A, int(ancestry), c0, c1, DD.data_ptr(), DO.data_ptr(), OO.data_ptr(), n,
-                                                             int(debug_snps_per_block), ctypes.byref(n_bad)))
-        return PairCounts(DD, DO, OO)
-
-    def ancestry_pair_counts_gt2(self, G, N, src, labels, ancestry, snp_range=None):
-        """ancestry_pair_counts of the parsed query (G, N, src as infer_gt2 takes them) under host labels (N, W): the whole packed matrix is
-        built in HBM and the kernel runs once (gnx_ancestry_pair_counts_gt2) -> asmds.PairCounts of numpy arrays"""
-        import ctypes
-        from .asmds import PairCounts
-        G, N, src = self._gt2_args(G, N, src)
-        if N % 2:
-            raise ValueError("N must be even (an individual has two haplotype rows)")
-        lab = np.ascontiguousarray(labels, dtype=np.int32)
-        if lab.shape != (N, self.W):
-            raise ValueError(f"labels must be (N={N}, W={self.W}), got {lab.shape}")
-        c0, c1 = (0, self.C) if snp_range is None else (int(snp_range[0]), int(snp_range[1]))
-        n = N // 2
-        DD, DO, OO = (np.zeros((n, n), np.int32) for _ in range(3))
-        n_bad = ctypes.c_int64(0)
-        self.ctx.check(self.lib.gnx_ancestry_pair_counts_gt2(self.h, G.ctypes.data, G.shape[0], G.shape[1], N, src.ctypes.data, lab.ctypes.data,
-                                                             int(ancestry), c0, c1, DD.ctypes.data, DO.ctypes.data, OO.ctypes.data, n,
-                                                             ctypes.byref(n_bad)))
-        return PairCounts(DD, DO, OO)
-
-    def ancestry_ld_counts(self, X, labels, ancestry, c0=0, c1=None, band=256, packed=False):
-        """the banded LD count tables n11, n1o, no1, noo of one ancestry for the SNPs [c0, c1) and the offsets 0 .. band - 1, X (N, C) int8
-        (packed=True: the 2-bit rows pack_x returns) under (N, W) labels, on the int8 matrix cores (gnx_ancestry_ld_counts;
-        gnomix_amd.postprocess.ld_counts) -> ld.LDCounts of (c1 - c0, band) int32 arrays"""
-        from .postprocess import ld_counts
-        return ld_counts(self.ctx, X, labels, self.M, self.A, ancestry, c0, c1, band, packed=packed, C=self.C)
-
-    def ancestry_ld_counts_device(self, X_t, lab_t, ancestry, c0=0, c1=None, band=256, debug_haps_per_block=0):
-        """the same on CUDA tensors: X_t int8 (N, C) or the uint8 tensor pack_device returns, lab_t (N, W) int32 with any row stride
-        (gnx_ancestry_ld_counts_dev) -> ld.LDCounts of (c1 - c0, band) int32 CUDA tensors"""
-        import ctypes
-        import torch
-        from .ld import LDCounts
-        kind, ld, ldl, N = self._allele_device_args(X_t, lab_t)
-        c0, c1, band = int(c0), self.C if c1 is None else int(c1), int(band)
-        self._bind_torch_stream()
-        tabs = [torch.zeros((max(c1 - c0, 0), max(band, 0)), dtype=torch.int32, device=X_t.device) for _ in range(4)]
-        n_bad = ctypes.c_int64(0)
-        self.ctx.check(self.lib.gnx_ancestry_ld_counts_dev(self.ctx.h, X_t.data_ptr(), kind, ld, lab_t.data_ptr(), ldl, N, self.C, self.M, self.W,
-                                                           self.A, int(ancestry), c0, c1, band, tabs[0].data_ptr(), tabs[1].data_ptr(),
-                                                           tabs[2].data_ptr(), tabs[3].data_ptr(), band, int(debug_haps_per_block),
-                                                           ctypes.byref(n_bad)))
-        return LDCounts(*tabs, c0, band)
-
-    def ancestry_ld_counts_gt2(self, G, N, src, labels, ancestry, c0=0, c1=None, band=256):
-        """ancestry_ld_counts of the parsed query (G, N, src as infer_gt2 takes them) under host labels (N, W): the whole packed matrix is
-        built in HBM and the kernel runs once (gnx_ancestry_ld_counts_gt2) -> ld.LDCounts of numpy arrays"""
-        import ctypes
-        from .ld import LDCounts
-        G, N, src = self._gt2_args(G, N, src)
-        lab = np.ascontiguousarray(labels, dtype=np.int32)
-        if lab.shape != (N, self.W):
-            raise ValueError(f"labels must be (N={N}, W={self.W}), got {lab.shape}")
-        c0, c1, band = int(c0), self.C if c1 is None else int(c1), int(band)
-        tabs = [np.zeros((max(c1 - c0, 0), max(band, 0)), np.int32) for _ in range(4)]
-        n_bad = ctypes.c_int64(0)
-        self.ctx.check(self.lib.gnx_ancestry_ld_counts_gt2(self.h, G.ctypes.data, G.shape[0], G.shape[1], N, src.ctypes.data, lab.ctypes.data,
-                                                           int(ancestry), c0, c1, band, tabs[0].ctypes.data, tabs[1].ctypes.data,
-                                                           tabs[2].ctypes.data, tabs[3].ctypes.data, band, ctypes.byref(n_bad)))
-        return LDCounts(*tabs, c0, band)
-
-    def ancestry_assoc_stats(self, X, labels, y, Z=None, use=None, c0=0, c1=None, min_ac=1, check=True):
-        """the sufficient statistics of the ancestry-specific association model for the SNPs [c0, c1) (gnx_ancestry_assoc_stats[_dev];
-        include/gnomix_hip.h states the blocks) -> gnomix_amd.assoc.AssocStats of numpy arrays.  X (N, C) int8 and labels (N, W) int32 as
-        numpy arrays, or as CUDA tensors (X int8 or the uint8 tensor pack_device returns, labels with any row stride): those never leave
-        HBM.  check=False: labels out of range do not raise, their count is AssocStats.n_bad."""
-        from . import assoc
-        c1 = self.C if c1 is None else int(c1)
-        c0 = int(c0)
-        if not hasattr(X, "is_cuda"):
-            X = self._x(X)
-            lab = np.ascontiguousarray(labels, dtype=np.int32)
-            if lab.shape != (X.shape[0], self.W):
-                raise ValueError(f"labels must be (N={X.shape[0]}, W={self.W}), got {lab.shape}")
-            return assoc.stats_host(self.ctx, X, lab, self.M, self.A, y, Z, use, c0, c1, min_ac=min_ac, check=check)
-        import ctypes
-        import torch
-        kind, ld, ldl, N = self._allele_device_args(X, labels)
-        yh, Zh, uh = assoc.covariates(N // 2, y, Z, use)
-        K = Zh.shape[1]
-        NF, NI, NWF, NWI = assoc.layout(self.A, K)
-        nc = max(c1 - c0, 0)
-        nw = int(min((c1 - 1) // self.M, self.W - 1) - min(c0 // self.M, self.W - 1) + 1) if 0 <= c0 < c1 else 1
-        dev = X.device
-        y_t, Z_t, u_t = (torch.from_numpy(v).to(dev) for v in (yh, Zh, uh))
-        sf, wf = torch.empty((nc, NF), dtype=torch.float64, device=dev), torch.empty((nw, NWF), dtype=torch.float64, device=dev)
-        si, wi = torch.empty((nc, NI), dtype=torch.int32, device=dev), torch.empty((nw, NWI), dtype=torch.int32, device=dev)
-        n_bad = ctypes.c_int64(0)
-        self._bind_torch_stream()
-        rc = self.lib.gnx_ancestry_assoc_stats_dev(self.ctx.h, X.data_ptr(), kind, ld, labels.data_ptr(), ldl, N, self.C, self.M, self.W, self.A,
-                                                   y_t.data_ptr(), Z_t.data_ptr(), K, u_t.data_ptr(), int(min_ac), c0, c1, sf.data_ptr(), si.data_ptr(),
-                                                   wf.data_ptr(), wi.data_ptr(), ctypes.byref(n_bad))
-        if check or (rc != _lib.GNX_OK and not n_bad.value):
-            self.ctx.check(rc)
-        return assoc.split_blocks(sf.cpu().numpy(), si.cpu().numpy(), wf.cpu().numpy(), wi.cpu().numpy(), self.A, K, c0, c1, self.M, self.W, n_bad.value)
-
-    def ancestry_assoc(self, X, labels, y, Z=None, use=None, min_ac=1):
-        """ancestry-specific association (the Tractor model: y = Z g + sum_{a < A-1} alpha_a hapcount_a + sum_a beta_a dosage_a, OLS per
-        SNP over the individuals that take part) -> gnomix_amd.assoc.AncestryAssoc.  y (N / 2,), Z (N / 2, K) float64 with the intercept
-        column (None = the intercept only), use (N / 2,) (0 = takes no part).  The device reduces X and the labels to per-SNP blocks, chunk
-        of SNPs by chunk (gnx_ancestry_assoc_stats); the host factors them (gnomix_amd/assoc.py).  X and labels: numpy arrays or CUDA
-        tensors, as ancestry_assoc_stats takes them."""
-        from . import assoc
-        if min_ac < 1:
-            raise ValueError("min_ac must be >= 1")
-        n_ind = X.shape[0] // 2
-        y, Z, use = assoc.covariates(n_ind, y, Z, use)
-        return assoc.assoc_from_stats(lambda c0, c1: self.ancestry_assoc_stats(X, labels, y, Z, use, c0, c1, min_ac), self.C, self.A, Z.shape[1], min_ac)
-
-    def ancestry_assoc_stats_gt2(self, G, N, src, labels, y, Z=None, use=None, c0=0, c1=None, min_ac=1, check=True):
-        """ancestry_assoc_stats of the parsed query (G, N, src as infer_gt2 takes them) under host labels (N, W): the packed rows are
-        built and reduced in HBM, batch of individuals by batch (gnx_ancestry_assoc_stats_gt2) -> assoc.AssocStats of [c0, c1)"""
-        import ctypes
-        from . import assoc
-        G, N, src = self._gt2_args(G, N, src)
-        lab = np.ascontiguousarray(labels, dtype=np.int32)
-        if lab.shape != (N, self.W):
-            raise ValueError(f"labels must be (N={N}, W={self.W}), got {lab.shape}")
-        c1 = self.C if c1 is None else int(c1)
-        c0 = int(c0)
-        y, Z, use = assoc.covariates(N // 2, y, Z, use)
-        K = Z.shape[1]
-        NF, NI, NWF, NWI = assoc.layout(self.A, K)
-        nc = max(c1 - c0, 0)
-        nw = int(min((c1 - 1) // self.M, self.W - 1) - min(c0 // self.M, self.W - 1) + 1) if 0 <= c0 < c1 else 1
-        sf, si = np.zeros((nc, NF)), np.zeros((nc, NI), np.int32)
-        wf, wi = np.zeros((nw, NWF)), np.zeros((nw, NWI), np.int32)
-        n_bad = ctypes.c_int64(0)
-        rc = self.lib.gnx_ancestry_assoc_stats_gt2(self.h, G.ctypes.data, G.shape[0], G.shape[1], N, src.ctypes.data, lab.ctypes.data, y.ctypes.data,
-                                                   Z.ctypes.data, K, use.ctypes.data, int(min_ac), c0, c1, sf.ctypes.data, si.ctypes.data,
-                                                   wf.ctypes.data, wi.ctypes.data, ctypes.byref(n_bad))
-        if check or (rc != _lib.GNX_OK and not n_bad.value):
-            self.ctx.check(rc)
-        return assoc.split_blocks(sf, si, wf, wi, self.A, K, c0, c1, self.M, self.W, n_bad.value)
-
-    def ancestry_assoc_gt2(self, G, N, src, labels, y, Z=None, use=None, min_ac=1):
-        """ancestry_assoc of the parsed query under host labels (the command line's path) -> assoc.AncestryAssoc"""
-        from . import assoc
-        if min_ac < 1:
-            raise ValueError("min_ac must be >= 1")
-        y, Z, use = assoc.covariates(int(N) // 2, y, Z, use)
-        return assoc.assoc_from_stats(lambda c0, c1: self.ancestry_assoc_stats_gt2(G, N, src, labels, y, Z, use, c0, c1, min_ac), self.C, self.A,
-                                      Z.shape[1], min_ac)
-
-    def ancestry_assoc_traits_stats(self, X, labels, Y, Z=None, use=None, c0=0, c1=None, min_ac=1, check=True):
-        """the trait-dependent blocks of T quantitative traits for the SNPs [c0, c1) (gnx_ancestry_assoc_traits[_dev], the float64 matrix
-        cores; include/gnomix_hip.h states them) -> gnomix_amd.assoc.TraitStats of numpy arrays.  Y (N / 2, T); X and labels as
-        ancestry_assoc_stats takes them (numpy arrays, or CUDA tensors that never leave HBM).  check=False: labels out of range do not
-        raise, their count is TraitStats.n_bad."""
-        from . import assoc
-        c1 = self.C if c1 is None else int(c1)
-        c0 = int(c0)
-        if not hasattr(X, "is_cuda"):
-            X = self._x(X)
-            lab = np.ascontiguousarray(labels, dtype=np.int32)
-            if lab.shape != (X.shape[0], self.W):
-                raise ValueError(f"labels must be (N={X.shape[0]}, W={self.W}), got {lab.shape}")
-            return assoc.traits_host(self.ctx, X, lab, self.M, self.A, Y, Z, use, c0, c1, min_ac=min_ac, check=check)
-        import ctypes
-        import torch
-        kind, ld, ldl, N = self._allele_device_args(X, labels)
-        Yh, Zh, uh, _ = assoc.trait_covariates(N // 2, Y, Z, use)
-        K, T = Zh.shape[1], Yh.shape[1]
-        dev = X.device
-        Y_t, Z_t, u_t = (torch.from_numpy(v).to(dev) for v in (Yh, Zh, uh))
-        sy, wy, wyy = assoc.trait_buffers(self.A, K, T, c0, c1, self.M, self.W, empty=lambda shape, dt: torch.empty(shape, dtype=torch.float64, device=dev))
-        n_bad = ctypes.c_int64(0)
-        self._bind_torch_stream()
-        rc = self.lib.gnx_ancestry_assoc_traits_dev(self.ctx.h, X.data_ptr(), kind, ld, labels.data_ptr(), ldl, N, self.C, self.M, self.W, self.A,
-                                                    Y_t.data_ptr(), T, T, Z_t.data_ptr(), K, u_t.data_ptr(), int(min_ac), c0, c1, sy.data_ptr(),
-                                                    wy.data_ptr(), wyy.data_ptr(), ctypes.byref(n_bad))
-        if check or (rc != _lib.GNX_OK and not n_bad.value):
-            self.ctx.check(rc)
-        return assoc.split_traits(sy.cpu().numpy(), wy.cpu().numpy(), wyy.cpu().numpy(), T, c0, c1, self.M, self.W, n_bad.value)
-
-    def ancestry_assoc_traits_chunks(self, X, labels, Y, Z=None, use=None, min_ac=1, p_max=None, chunk_bytes=None, check=True):
-        """ancestry-specific association (the Tractor model, as ancestry_assoc states it) of T quantitative traits Y (N / 2, T) at once: a
-        generator of (c0, c1, gnomix_amd.assoc.AncestryAssocTraits) per chunk of SNPs, beta, se, t, p shaped (c1 - c0, A, T).  An
-        individual takes part when use says so, Z[i, :] is finite and EVERY trait of Y[i, :] is finite (complete cases across the batch;
-        group traits by missingness pattern and call once per group).  Per chunk the device computes D^T Y on the float64 matrix cores
-        (gnx_ancestry_assoc_traits) and the trait-independent blocks once (gnx_ancestry_assoc_stats with a zero phenotype); the host
-        factors each SNP's normal matrix once and solves all T traits.  The chunks are sized so that the device blocks and the results
-        of one chunk stay below chunk_bytes (default assoc.STATS_CHUNK_BYTES): the full result is never materialised here.  p_max: the
-        float results of every (SNP, ancestry, trait) whose p is not <= p_max are NaN.  X and labels: numpy arrays or CUDA tensors.
-        check=False: labels out of range do not raise (such an individual takes no part at that window)."""
-        from . import assoc
-        if min_ac < 1:
-            raise ValueError("min_ac must be >= 1")
-        n_ind = X.shape[0] // 2
-        Y, Z, use, use2 = assoc.trait_covariates(n_ind, Y, Z, use)
-        y0 = np.zeros(n_ind)
-
-        def blocks(c0, c1):
-            return (self.ancestry_assoc_stats(X, labels, y0, Z, use2, c0, c1, min_ac, check),
-                    self.ancestry_assoc_traits_stats(X, labels, Y, Z, use, c0, c1, min_ac, check))
-        return assoc.traits_chunks(blocks, self.C, self.A, Z.shape[1], Y.shape[1], min_ac, p_max, chunk_bytes)
-
-    def ancestry_assoc_traits(self, X, labels, Y, Z=None, use=None, min_ac=1, p_max=None, max_bytes=2 << 30, check=True):
-        """the chunks of ancestry_assoc_traits_chunks concatenated -> assoc.AncestryAssocTraits of all C SNPs.  ValueError naming the byte
-        count, before any work, when the result would exceed max_bytes (chr22 x 7 ancestries x 1024 traits is 18 GB per field)."""
-        from . import assoc
-        T = np.asarray(Y).shape[1] if np.asarray(Y).ndim == 2 else 0
-        return assoc.traits_concat(self.ancestry_assoc_traits_chunks(X, labels, Y, Z, use, min_ac, p_max, check=check), self.C, self.A, T, max_bytes)
-
-    def ancestry_assoc_traits_stats_gt2(self, G, N, src, labels, Y, Z=None, use=None, c0=0, c1=None, min_ac=1, check=True):
-        """ancestry_assoc_traits_stats of the parsed query (G, N, src as infer_gt2 takes them) under host labels (N, W): the packed rows
-        are built and reduced in HBM, batch of whole groups of 4 individuals by batch (gnx_ancestry_assoc_traits_gt2) -> assoc.TraitStats"""
-        import ctypes
-        from . import assoc
-        G, N, src = self._gt2_args(G, N, src)
-        lab = np.ascontiguousarray(labels, dtype=np.int32)
-        if lab.shape != (N, self.W):
-            raise ValueError(f"labels must be (N={N}, W={self.W}), got {lab.shape}")
-        c1 = self.C if c1 is None else int(c1)
-        c0 = int(c0)
-        Y, Z, use, _ = assoc.trait_covariates(N // 2, Y, Z, use)
-        K, T = Z.shape[1], Y.shape[1]
-        sy, wy, wyy = assoc.trait_buffers(self.A, K, T, c0, c1, self.M, self.W)
-        n_bad = ctypes.c_int64(0)
-        rc = self.lib.gnx_ancestry_assoc_traits_gt2(self.h, G.ctypes.data, G.shape[0], G.shape[1], N, src.ctypes.data, lab.ctypes.data, Y.ctypes.data,
-                                                    T, T, Z.ctypes.data, K, use.ctypes.data, int(min_ac), c0, c1, sy.ctypes.data, wy.ctypes.data,
-                                                    wyy.ctypes.data, ctypes.byref(n_bad))
-        if check or (rc != _lib.GNX_OK and not n_bad.value):
-            self.ctx.check(rc)
-        return assoc.split_traits(sy, wy, wyy, T, c0, c1, self.M, self.W, n_bad.value)
-
-    def ancestry_assoc_traits_gt2_chunks(self, G, N, src, labels, Y, Z=None, use=None, min_ac=1, p_max=None, chunk_bytes=None):
-        """ancestry_assoc_traits_chunks of the parsed query under host labels (the command line's path)"""
-        from . import assoc
-        if min_ac < 1:
-            raise ValueError("min_ac must be >= 1")
-        n_ind = int(N) // 2
-        Y, Z, use, use2 = assoc.trait_covariates(n_ind, Y, Z, use)
-        y0 = np.zeros(n_ind)
-
-        def blocks(c0, c1):
-            return (self.ancestry_assoc_stats_gt2(G, N, src, labels, y0, Z, use2, c0, c1, min_ac),
-                    self.ancestry_assoc_traits_stats_gt2(G, N, src, labels, Y, Z, use, c0, c1, min_ac))
-        return assoc.traits_chunks(blocks, self.C, self.A, Z.shape[1], Y.shape[1], min_ac, p_max, chunk_bytes)
-
-    def ancestry_assoc_traits_gt2(self, G, N, src, labels, Y, Z=None, use=None, min_ac=1, p_max=None, max_bytes=2 << 30):
-        """ancestry_assoc_traits of the parsed query under host labels -> assoc.AncestryAssocTraits; ValueError above max_bytes"""
-        from . import assoc
-        T = np.asarray(Y).shape[1] if np.asarray(Y).ndim == 2 else 0
-        return assoc.traits_concat(self.ancestry_assoc_traits_gt2_chunks(G, N, src, labels, Y, Z, use, min_ac, p_max), self.C, self.A, T, max_bytes)
-
-    def ancestry_assoc_logit_fit(self, X, labels, y, Z=None, use=None, c0=0, c1=None, min_ac=1, tol=None, max_iter=None, check=True):
-        """the logistic fits of the SNPs [c0, c1) (gnx_ancestry_assoc_logit[_dev]; include/gnomix_hip.h states the model and the iteration)
-        -> gnomix_amd.assoc.LogitFit of numpy arrays.  X and labels as ancestry_assoc_stats takes them (numpy arrays, or CUDA tensors
-        that never leave HBM).  check=False: labels out of range do not raise, their count is LogitFit.n_bad."""
-        from . import assoc
-        c1 = self.C if c1 is None else int(c1)
-        c0 = int(c0)
-        tol = assoc.LOGIT_TOL if tol is None else float(tol)
-        max_iter = assoc.LOGIT_MAX_ITER if max_iter is None else int(max_iter)
-        if not hasattr(X, "is_cuda"):
-            X = self._x(X)
-            lab = np.ascontiguousarray(labels, dtype=np.int32)
-            if lab.shape != (X.shape[0], self.W):
-                raise ValueError(f"labels must be (N={X.shape[0]}, W={self.W}), got {lab.shape}")
-            return assoc.logit_host(self.ctx, X, lab, self.M, self.A, y, Z, use, c0, c1, min_ac=min_ac, tol=tol, max_iter=max_iter, check=check)
-        import ctypes
-        import torch
-        kind, ld, ldl, N = self._allele_device_args(X, labels)
-        yh, Zh, uh = assoc.covariates(N // 2, y, Z, use)
-        K = Zh.shape[1]
-        dev = X.device
-        y_t, Z_t, u_t = (torch.from_numpy(v).to(dev) for v in (yh, Zh, uh))
-        sf, si, th, wf, wi = assoc.logit_buffers(self.A, K, c0, c1, self.M, self.W, empty=lambda shape, dt: torch.zeros(
-            shape, dtype=torch.float64 if dt == np.float64 else torch.int32, device=dev))
-        n_bad = ctypes.c_int64(0)
-        self._bind_torch_stream()
-        rc = self.lib.gnx_ancestry_assoc_logit_dev(self.ctx.h, X.data_ptr(), kind, ld, labels.data_ptr(), ldl, N, self.C, self.M, self.W, self.A,
-                                                   y_t.data_ptr(), Z_t.data_ptr(), K, u_t.data_ptr(), int(min_ac), c0, c1, tol, max_iter,
-                                                   sf.data_ptr(), si.data_ptr(), th.data_ptr(), wf.data_ptr(), wi.data_ptr(), ctypes.byref(n_bad))
-        if check or rc not in (_lib.GNX_OK, _lib.GNX_EINVAL) or (rc != _lib.GNX_OK and not n_bad.value):
-            self.ctx.check(rc)
-        return assoc.split_logit(sf.cpu().numpy(), si.cpu().numpy(), th.cpu().numpy(), wf.cpu().numpy(), wi.cpu().numpy(), self.A, K, c0, c1, self.M,
-                                 self.W, n_bad.value)
-
-    def ancestry_assoc_logit(self, X, labels, y, Z=None, use=None, min_ac=1, tol=None, max_iter=None):
-        """ancestry-specific association of a case / control trait (the Tractor model with a logit link: logit P(y = 1) = Z g +
-        sum_{a < A-1} alpha_a hapcount_a + sum_a beta_a dosage_a, maximum likelihood per SNP over the individuals that take part, fitted
-        on the device: k_ancestry_assoc_logit_snp) -> gnomix_amd.assoc.AncestryAssocLogit.  y (N / 2,) coded 0 / 1, Z, use as
-        ancestry_assoc takes them; X and labels numpy arrays or CUDA tensors.  The SNPs are walked in chunks whose outputs stay below
-        assoc.STATS_CHUNK_BYTES."""
-        from . import assoc
-        if min_ac < 1:
-            raise ValueError("min_ac must be >= 1")
-        n_ind = X.shape[0] // 2
-        y, Z, use = assoc.covariates(n_ind, y, Z, use)
-        assoc.check_binary(y, use)
-        return assoc.logit_from_fits(lambda c0, c1: self.ancestry_assoc_logit_fit(X, labels, y, Z, use, c0, c1, min_ac, tol, max_iter), self.C, self.A,
-                                     Z.shape[1])
-
-    def ancestry_assoc_logit_fit_gt2(self, G, N, src, labels, y, Z=None, use=None, c0=0, c1=None, min_ac=1, tol=None, max_iter=None, check=True):
-        """ancestry_assoc_logit_fit of the parsed query (G, N, src as infer_gt2 takes them) under host labels (N, W): the packed rows of
-        all individuals are built in HBM and fitted there (gnx_ancestry_assoc_logit_gt2) -> assoc.LogitFit of [c0, c1)"""
-        import ctypes
-        from . import assoc
-        G, N, src = self._gt2_args(G, N, src)
-        lab = np.ascontiguousarray(labels, dtype=np.int32)
-        if lab.shape != (N, self.W):
-            raise ValueError(f"labels must be (N={N}, W={self.W}), got {lab.shape}")
-        c1 = self.C if c1 is None else int(c1)
-        c0 = int(c0)
-        tol = assoc.LOGIT_TOL if tol is None else float(tol)
-        max_iter = assoc.LOGIT_MAX_ITER if max_iter is None else int(max_iter)
-        y, Z, use = assoc.covariates(N // 2, y, Z, use)
-        K = Z.shape[1]
-        sf, si, th, wf, wi = assoc.logit_buffers(self.A, K, c0, c1, self.M, self.W)
-        n_bad = ctypes.c_int64(0)
-        rc = self.lib.gnx_ancestry_assoc_logit_gt2(self.h, G.ctypes.data, G.shape[0], G.shape[1], N, src.ctypes.data, lab.ctypes.data, y.ctypes.data,
-                                                   Z.ctypes.data, K, use.ctypes.data, int(min_ac), c0, c1, tol, max_iter, sf.ctypes.data, si.ctypes.data,
-                                                   th.ctypes.data, wf.ctypes.data, wi.ctypes.data, ctypes.byref(n_bad))
-        if check or rc not in (_lib.GNX_OK, _lib.GNX_EINVAL) or (rc != _lib.GNX_OK and not n_bad.value):
-            self.ctx.check(rc)
-        return assoc.split_logit(sf, si, th, wf, wi, self.A, K, c0, c1, self.M, self.W, n_bad.value)
-
-    def ancestry_assoc_logit_gt2(self, G, N, src, labels, y, Z=None, use=None, min_ac=1, tol=None, max_iter=None):
-        """ancestry_assoc_logit of the parsed query under host labels (the command line's path) -> assoc.AncestryAssocLogit"""
-        from . import assoc
-        if min_ac < 1:
-            raise ValueError("min_ac must be >= 1")
-        y, Z, use = assoc.covariates(int(N) // 2, y, Z, use)
-        assoc.check_binary(y, use)
-        return assoc.logit_from_fits(lambda c0, c1: self.ancestry_assoc_logit_fit_gt2(G, N, src, labels, y, Z, use, c0, c1, min_ac, tol, max_iter),
-                                     self.C, self.A, Z.shape[1])
-
-    def allele_counts_gt2(self, G, N, src, labels):
-        """ancestry-specific allele counts of the parsed query (G, N, src as infer_gt2 takes them) under host labels (N, W): the
-        packed rows are built and counted in HBM, batch by batch (gnx_ancestry_allele_counts_gt2) -> AlleleCounts"""
-        from .postprocess import AlleleCounts
-        G, N, src = self._gt2_args(G, N, src)
-        lab = np.ascontiguousarray(labels, dtype=np.int32)
-        if lab.shape != (N, self.W):
-            raise ValueError(f"labels must be (N={N}, W={self.W}), got {lab.shape}")
-        obs, alt, miss = (np.zeros((self.A, self.C), np.int32) for _ in range(3))
-        self.ctx.check(self.lib.gnx_ancestry_allele_counts_gt2(self.h, G.ctypes.data, G.shape[0], G.shape[1], N, src.ctypes.data, lab.ctypes.data,
-                                                               obs.ctypes.data, alt.ctypes.data, miss.ctypes.data))
-        return AlleleCounts(obs, alt, miss)
 
     def proba_dtype(self):
         """dtype of the probabilities this model's smoother returns: float64 for CRF and for calibrated output, else float32"""

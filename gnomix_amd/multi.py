@@ -236,14 +236,13 @@ class DeviceGroup:
         """DeviceModel.allele_counts_gt2 with the individuals cut over the group's devices: every device counts its own haplotypes
         (its bytes of G's rows, its rows of the labels) into tables of its own; counts are additive, the tables are added on the host
         -> AlleleCounts"""
+        from .ancestry_ops import check_labels
         from .postprocess import AlleleCounts
         m0 = self.models[0]
         G, N, src = m0._gt2_args(G, N, src)
         if N % 2:
             raise ValueError("N = 2 * samples")
-        lab = np.ascontiguousarray(labels, dtype=np.int32)
-        if lab.shape != (N, self.W):
-            raise ValueError(f"labels must be (N={N}, W={self.W}), got {lab.shape}")
+        lab = check_labels(labels, N, self.W)
         C = m0.C
         parts, jobs = [], []
         for m, (i0, n) in zip(self.models, shard_individuals(N // 2, len(self.models))):

@@ -272,60 +272,26 @@ def _to_host(a):
     return a.cpu().numpy() if hasattr(a, "is_cuda") else a
 
 
-def _allele_rows(X_or_packed, packed, C):
-    """-> (C-contiguous rows, row_kind, C).  int8 rows keep their bytes (anything but 0 / 1 is a missing call); other integer dtypes
-    are re-coded to 0 / 1 / 2 first; packed rows (gnx_pack_x layout) need C"""
-    if packed:
-        rows = np.ascontiguousarray(X_or_packed, dtype=np.uint8)
-        if C is None:
-            raise ValueError("packed rows: pass C, the number of SNPs a row holds")
-        if rows.ndim != 2 or rows.shape[1] < (int(C) + 3) // 4:
-            raise ValueError(f"packed X must be (N, >= ceil(C / 4) = {(int(C) + 3) // 4}) uint8, got {rows.shape}")
-        return rows, _lib.GNX_ROWS_PACKED2, int(C)
-    X = np.asarray(X_or_packed)
-    if X.ndim != 2:
-        raise ValueError(f"X must be (N, C), got {X.shape}")
-    if C is not None and int(C) != X.shape[1]:
-        raise ValueError(f"X has {X.shape[1]} columns, C = {C}")
-    if X.dtype != np.int8:
-        X = np.where((X == 0) | (X == 1), X, 2).astype(np.int8)
-    return np.ascontiguousarray(X), _lib.GNX_ROWS_INT8, X.shape[1]
-
-
-def _allele_labels(labels, N):
-    lab = np.ascontiguousarray(labels, dtype=np.int32)
-    if lab.ndim != 2 or lab.shape[0] != N:
-        raise ValueError(f"labels must be (N={N}, W), got {lab.shape}")
-    return lab
+def _front(ctx, X_or_packed, labels, M, A, packed, C, even=False):
+    """the host front of the ops below (ancestry_ops.host_front: the rows re-coded and made contiguous, W taken from the labels)"""
+    from .ancestry_ops import host_front
+    return host_front(ctx, X_or_packed, labels, M, A, packed, C, even=even)
 
 
 def allele_counts(ctx, X_or_packed, labels, M, A, packed=False, C=None, debug_rows_per_chunk=0, debug_flush_every=0):
     """ancestry-specific allele counts on the device (gnx_ancestry_allele_counts): X (N, C) int8 in the model's coding (0 REF, 1 ALT,
     anything else missing), or with packed=True the 2-bit rows of DeviceModel.pack_x and C; labels (N, W) in [0, A); the window of SNP c
     is min(c // M, W - 1) -> AlleleCounts of (A, C) int32 arrays"""
-    rows, kind, C = _allele_rows(X_or_packed, packed, C)
-    N = rows.shape[0]
-    lab = _allele_labels(labels, N)
-    W = lab.shape[1]
-    obs, alt, miss = (np.zeros((int(A), C), np.int32) for _ in range(3))
-    ctx.check(ctx.lib.gnx_ancestry_allele_counts(ctx.h, rows.ctypes.data, kind, rows.shape[1], lab.ctypes.data, W, N, C, int(M), W, int(A),
-                                                 obs.ctypes.data, alt.ctypes.data, miss.ctypes.data, int(debug_rows_per_chunk),
-                                                 int(debug_flush_every)))
-    return AlleleCounts(obs, alt, miss)
+    from . import ancestry_ops
+    return ancestry_ops.allele_counts(_front(ctx, X_or_packed, labels, M, A, packed, C), debug_rows_per_chunk, debug_flush_every)
 
 
 def ancestry_dosage(ctx, X, labels, M, A, ancestry, packed=False, C=None):
     """per-individual dosage of one ancestry on the device (gnx_ancestry_dosage): for individual i = rows 2 i, 2 i + 1 and SNP c,
     hapcount = how many of the two haplotypes carry label `ancestry` at c's window, dosage = how many of those are ALT (a missing call
     counts in hapcount only) -> (dosage, hapcount), (N / 2, C) uint8 arrays"""
-    rows, kind, C = _allele_rows(X, packed, C)
-    N = rows.shape[0]
-    lab = _allele_labels(labels, N)
-    W = lab.shape[1]
-    dos, hap = (np.zeros((N // 2, C), np.uint8) for _ in range(2))
-    ctx.check(ctx.lib.gnx_ancestry_dosage(ctx.h, rows.ctypes.data, kind, rows.shape[1], lab.ctypes.data, W, N, C, int(M), W, int(A),
-                                          int(ancestry), dos.ctypes.data, C, hap.ctypes.data, C))
-    return dos, hap
+    from . import ancestry_ops
+    return ancestry_ops.dosage(_front(ctx, X, labels, M, A, packed, C), ancestry)
 
 
 class AncestryScores(collections.namedtuple("AncestryScores", "score n_effect n_scored n_miss")):
@@ -378,29 +344,9 @@ def ancestry_scores(ctx, X_or_packed, labels, M, A, weights, effect=None, packed
     summation order): X (N, C) int8 in the model's coding, or with packed=True the 2-bit rows of DeviceModel.pack_x and C; labels (N, W)
     in [0, A); weights and effect as score_tables takes them -> AncestryScores of numpy arrays.  More than GNX_SCORE_MAX_S scores are
     served in chunks; every score's bits are those of a call with that score alone."""
-    import ctypes
-    rows, kind, C = _allele_rows(X_or_packed, packed, C)
-    N = rows.shape[0]
-    if N % 2:
-        raise ValueError("N must be even (an individual has two haplotype rows)")
-    lab = _allele_labels(labels, N)
-    W = lab.shape[1]
-    w, eff = score_tables(weights, effect, C, A)
-    S = w.shape[2]
-    score = np.zeros((N // 2, int(A), S))
-    ne, ns, nm = (np.zeros((N // 2, int(A)), np.int32) for _ in range(3))
-    for s0, s1 in score_chunks(S):
-        wc = w if (s0, s1) == (0, S) else np.ascontiguousarray(w[:, :, s0:s1])
-        out = score if (s0, s1) == (0, S) else np.zeros((N // 2, int(A), s1 - s0))
-        first = s0 == 0
-        n_bad = ctypes.c_int64(0)
-        ctx.check(ctx.lib.gnx_ancestry_score(ctx.h, rows.ctypes.data, kind, rows.shape[1], lab.ctypes.data, W, N, C, int(M), W, int(A),
-                                             wc.ctypes.data, s1 - s0, eff.ctypes.data, out.ctypes.data, ne.ctypes.data if first else None,
-                                             ns.ctypes.data if first else None, nm.ctypes.data if first else None,
-                                             int(debug_windows_per_block), int(debug_rows_per_pass), ctypes.byref(n_bad)))
-        if out is not score:
-            score[:, :, s0:s1] = out
-    return AncestryScores(score, ne, ns, nm)
+    from . import ancestry_ops
+    f = _front(ctx, X_or_packed, labels, M, A, packed, C, even=True)
+    return ancestry_ops.scores(f, *score_tables(weights, effect, f.C, A), debug_windows_per_block, debug_rows_per_pass)
 
 
 def write_sscore(prefix, scores, names, populations, samples):
@@ -433,23 +379,8 @@ def pair_counts(ctx, X_or_packed, labels, M, A, ancestry, snp_range=None, packed
     """ancestry-specific pairwise counts on the device (gnx_ancestry_pair_counts; include/gnomix_hip.h states the tables): X (N, C) int8
     in the model's coding, or with packed=True the 2-bit rows of DeviceModel.pack_x and C; labels (N, W); snp_range (c0, c1), None = every
     SNP -> asmds.PairCounts of (N / 2, N / 2) int32 arrays.  check=False: labels outside [0, A) do not raise (they count for no ancestry)"""
-    import ctypes
-    from .asmds import PairCounts
-    rows, kind, C = _allele_rows(X_or_packed, packed, C)
-    N = rows.shape[0]
-    if N % 2:
-        raise ValueError("N must be even (an individual has two haplotype rows)")
-    lab = _allele_labels(labels, N)
-    W = lab.shape[1]
-    c0, c1 = (0, C) if snp_range is None else (int(snp_range[0]), int(snp_range[1]))
-    n = N // 2
-    DD, DO, OO = (np.zeros((n, n), np.int32) for _ in range(3))
-    n_bad = ctypes.c_int64(0)
-    rc = ctx.lib.gnx_ancestry_pair_counts(ctx.h, rows.ctypes.data, kind, rows.shape[1], lab.ctypes.data, W, N, C, int(M), W, int(A), int(ancestry),
-                                          c0, c1, DD.ctypes.data, DO.ctypes.data, OO.ctypes.data, n, int(debug_snps_per_block), ctypes.byref(n_bad))
-    if check or not n_bad.value:
-        ctx.check(rc)
-    return PairCounts(DD, DO, OO)
+    from . import ancestry_ops
+    return ancestry_ops.pair_counts(_front(ctx, X_or_packed, labels, M, A, packed, C, even=True), ancestry, snp_range, debug_snps_per_block, check)
 
 
 def ld_counts(ctx, X_or_packed, labels, M, A, ancestry, c0=0, c1=None, band=256, packed=False, C=None, debug_haps_per_block=0, check=True):
@@ -457,21 +388,8 @@ def ld_counts(ctx, X_or_packed, labels, M, A, ancestry, c0=0, c1=None, band=256,
     model's coding, or with packed=True the 2-bit rows of DeviceModel.pack_x and C; labels (N, W); the SNPs [c0, c1) (c1 None: to the
     last) and the offsets 0 .. band - 1 -> ld.LDCounts of (c1 - c0, band) int32 arrays.  check=False: labels outside [0, A) do not raise
     (they count for no ancestry)"""
-    import ctypes
-    from .ld import LDCounts
-    rows, kind, C = _allele_rows(X_or_packed, packed, C)
-    N = rows.shape[0]
-    lab = _allele_labels(labels, N)
-    W = lab.shape[1]
-    c0, c1, band = int(c0), C if c1 is None else int(c1), int(band)
-    tabs = [np.zeros((max(c1 - c0, 0), max(band, 0)), np.int32) for _ in range(4)]
-    n_bad = ctypes.c_int64(0)
-    rc = ctx.lib.gnx_ancestry_ld_counts(ctx.h, rows.ctypes.data, kind, rows.shape[1], lab.ctypes.data, W, N, C, int(M), W, int(A), int(ancestry),
-                                        c0, c1, band, tabs[0].ctypes.data, tabs[1].ctypes.data, tabs[2].ctypes.data, tabs[3].ctypes.data, band,
-                                        int(debug_haps_per_block), ctypes.byref(n_bad))
-    if check or not n_bad.value:
-        ctx.check(rc)
-    return LDCounts(*tabs, c0, band)
+    from . import ancestry_ops
+    return ancestry_ops.ld_counts(_front(ctx, X_or_packed, labels, M, A, packed, C), ancestry, c0, c1, band, debug_haps_per_block, check)
 
 
 def write_clumps(prefix, chm, snp_pos, index_of, p, populations):
