@@ -109,6 +109,7 @@ static void read_tune(gnx_tune& t) {
   if (const char* e = std::getenv("GNX_CRF_FLAGS")) t.crf_flags = atoi(e);
   if (const char* e = std::getenv("GNX_LDS_PAD")) std::sscanf(e, "%d,%d", &t.lr_lds_pad, &t.sm_lds_pad);
   if (const char* e = std::getenv("GNX_CRF_IMPL")) t.crf_impl = !std::strcmp(e, "scan") ? 1 : !std::strcmp(e, "row") ? 2 : !std::strcmp(e, "lanes") ? 3 : 0;
+  t.crf_nwb = geti("GNX_CRF_NWB", 1) == 4 ? 4 : 1;
   t.forest_threads = geti("GNX_FOREST_T", 0);
   t.forest_wrun = geti("GNX_FOREST_WRUN", 0);
   t.forest_halves = geti("GNX_FOREST_H", 0);

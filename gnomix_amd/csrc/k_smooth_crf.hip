@@ -980,8 +980,7 @@ hipError_t gnx_launch_smooth_crf(const SmoothCRFLaunch& L, const gnx_tune& tune,
       // (measured: 1-2 % at 25 000 chr1 haplotypes = 6 250 waves on 4 096 slots, nothing at chr22; scripts/dev/crf_nsweep.py shows the
       // rounds: 4 096 waves 2.42 ms, 6 144 3.63 ms, 6 250 4.05 ms, 8 192 4.76 ms — a SIMD with three waves in the second round is the
       // critical path of the launch)
-      static const int nwb_env = [] { const char* e = std::getenv("GNX_CRF_NWB"); return e ? atoi(e) : 1; }();
-      const int nwb = nwb_env == 4 ? 4 : 1;   // (GNX_CRF_NWB=4: the four-wave workgroups of the first version, kept for comparison)
+      const int nwb = tune.crf_nwb == 4 ? 4 : 1;   // (GNX_CRF_NWB=4: the four-wave workgroups of the first version, kept for comparison)
       const dim3 gridw((unsigned)((L.N + 4 * nwb - 1) / (4 * nwb)));
 #define GNX_CK1(AT_, F_, W_) hipLaunchKernelGGL((k_smooth_crf_ck<AT_, F_, W_>), gridw, dim3(64 * W_), 0, s, L)
 #define GNX_CK(AT_) \
