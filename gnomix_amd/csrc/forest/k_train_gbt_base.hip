@@ -14,11 +14,11 @@
 //   objective A >= 3: multi:softprob, K = A trees per round, tree k of a round adds to class k; margins start at base_score.
 //             A == 2: binary:logistic, K = 1 tree per round on the label y == 1; the margin starts at float(log(bs / (1 - bs))) (= 0).
 //             Margins are float32 and take each round's leaf with one float32 addition.
-//   gradients det_exp is gnx_det_exp.h's: the fixed-order float64 exp this trainer shares with the smoother's.
+//   gradients gnx_gbt_core.h's, shared with the smoother's trainer; det_exp is gnx_det_exp.h's fixed-order float64 exp.
 //             multi:  m = max_c F_c (float32), e_c = det_exp(double(F_c - m)), s = sum e_c in class order, p_c = e_c / s,
-//                     g = p_c - [y == c], h = max(2 p_c (1 - p_c), 1e-16)              (k_train_gbt.hip's pair)
+//                     g = p_c - [y == c], h = max(2 p_c (1 - p_c), 1e-16)              (gbt_softprob_row)
 //             binary: z = double(F), e = det_exp(-|z|), p = z >= 0 ? 1 / (1 + e) : e / (1 + e), g = p - [y == 1],
-//                     h = max(p (1 - p), 1e-16)
+//                     h = max(p (1 - p), 1e-16)                                        (gbt_logistic_row)
 //             both rounded to multiples of 2^-30: gi = llrint(g 2^30), hi = llrint(h 2^30).  EVERY sum below is an int64 of those, so
 //             no result depends on scheduling, atomics order or tile order.
 //   loss[r]   mean over the N W problems of -log(max(p_y, 1e-300)) before round r (r = n_rounds: after the last), float64
@@ -28,10 +28,10 @@
 //               1: cond 0.5, missing right  {0} | {1, missing}       2: cond 0.5, missing left  {0, missing} | {1}
 //               3: cond 1.5, missing right  {0, 1} | {missing}
 //             gain = (GL^2 / (HL + lambda) + GR^2 / (HR + lambda)) - G^2 / (H + lambda) in float64 on the sums / 2^30, operations in
-//             that order.  A candidate is valid if HL >= min_child_weight, HR >= min_child_weight and gain > max(gamma, 1e-6) (the
-//             smoother trainer's floor).  The largest gain wins; ties go to the lowest feature, then the lowest candidate: a node
-//             without missing rows learns "default right".  No valid candidate, or depth max_depth reached: a leaf,
-//             value float32(eta * (-(G / 2^30) / (H / 2^30 + lambda))).
+//             that order.  A candidate is valid if HL >= min_child_weight, HR >= min_child_weight and gain > max(gamma, 1e-6)
+//             (gbt_split_gain, gbt_gain_floor).  The largest gain wins; ties go to the lowest feature, then the lowest candidate
+//             (gbt_beats): a node without missing rows learns "default right".  No valid candidate, or depth max_depth reached: a
+//             leaf, value float32(eta * (-(G / 2^30) / (H / 2^30 + lambda))) (gbt_leaf_value).
 //
 // THE STRUCTURE.  The hot loop is the per-level table of (G1, H1, Gm, Hm) for every (window, tree of the round, node, feature).  A row
 // sits in exactly ONE node of a tree, so the dense form of that table — indicator planes times node-masked gradient columns on the
@@ -52,12 +52,10 @@
 
 #include "../gnx_internal.h"
 #include "../gnx_window.h"
-#include "gnx_det_exp.h"
+#include "gnx_gbt_core.h"
 
 namespace {
 
-constexpr double FIX = 1073741824.0;  // 2^30
-constexpr int MAXN = 63;               // heap positions of a tree of depth <= 5
 constexpr int FBT_CHUNK = 256;         // features of one histogram block (one per thread)
 constexpr int FBT_SLICE = 2048;        // rows of one histogram block: (index, g, h) = 20 bytes each, 40 KB of LDS
 
@@ -68,13 +66,8 @@ struct FGeom {
 
 __device__ __forceinline__ int fbt_width(int w, const FGeom& G) { return (int)(G.M + 2 * G.ctx) + (w == G.W - 1 ? G.rem : 0); }
 
-__global__ __launch_bounds__(256) void k_fbt_fill(float* p, float v, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) p[i] = v;
-}
-
-// node tables of tree (w, round r, k): [((w R + r) K + k)][MAXN]
-__device__ __forceinline__ size_t fbt_tab(int w, int r, int k, const FGeom& G) { return (((size_t)w * G.R + r) * G.K + k) * MAXN; }
+// node tables of tree (w, round r, k): [((w R + r) K + k)][GBT_MAXN]
+__device__ __forceinline__ size_t fbt_tab(int w, int r, int k, const FGeom& G) { return (((size_t)w * G.R + r) * G.K + k) * GBT_MAXN; }
 
 // gradients of one round: block = 256 rows of one window.  Root sums per tree (int64, exact), the block's loss in a fixed order.
 // fit == 0: only the loss (the pass after the last round).
@@ -92,46 +85,14 @@ __global__ __launch_bounds__(256) void k_fbt_grad(const float* Fm, const int32_t
   if (n < G.N) {
     const float* f = Fm + ((size_t)w * G.N + n) * K;
     const int yi = y[n * G.W + w];
-    double py = 0.0;
-    if (K == 1) {
-      const double z = (double)f[0];
-      const double e = det_exp(z >= 0.0 ? -z : z);
-      const double p = z >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
-      const double g = p - (yi == 1 ? 1.0 : 0.0);
-      double h = p * (1.0 - p);
-      if (h < 1e-16) h = 1e-16;
-      py = yi == 1 ? p : 1.0 - p;
-      if (fit) {
-        const long long gi = llrint(g * FIX), hi = llrint(h * FIX);
-        const size_t o = (size_t)w * G.N + n;
-        gq[o] = gi; hq[o] = hi; pos[o] = 0;
-        atomicAdd(reinterpret_cast<unsigned long long*>(&sg[0]), (unsigned long long)gi);
-        atomicAdd(reinterpret_cast<unsigned long long*>(&sh[0]), (unsigned long long)hi);
-      }
-    } else {
-      float m = f[0];
-      for (int c = 1; c < A; ++c) m = f[c] > m ? f[c] : m;
-      double e[AMAX], sum = 0.0;
-#pragma unroll
-      for (int c = 0; c < AMAX; ++c)
-        if (c < A) { e[c] = det_exp((double)(f[c] - m)); sum += e[c]; }
-#pragma unroll
-      for (int c = 0; c < AMAX; ++c)
-        if (c < A) {
-          const double p = e[c] / sum;
-          if (yi == c) py = p;
-          if (fit) {
-            const double g = p - (yi == c ? 1.0 : 0.0);
-            double h = 2.0 * p * (1.0 - p);
-            if (h < 1e-16) h = 1e-16;
-            const long long gi = llrint(g * FIX), hi = llrint(h * FIX);
-            const size_t o = ((size_t)w * K + c) * G.N + n;
-            gq[o] = gi; hq[o] = hi; pos[o] = 0;
-            atomicAdd(reinterpret_cast<unsigned long long*>(&sg[c]), (unsigned long long)gi);
-            atomicAdd(reinterpret_cast<unsigned long long*>(&sh[c]), (unsigned long long)hi);
-          }
-        }
-    }
+    auto emit = [&](int c, long long gi, long long hi) {  // tree c of the round
+      if (!fit) return;
+      const size_t o = ((size_t)w * K + c) * G.N + n;
+      gq[o] = gi; hq[o] = hi; pos[o] = 0;
+      atomicAdd(reinterpret_cast<unsigned long long*>(&sg[c]), (unsigned long long)gi);
+      atomicAdd(reinterpret_cast<unsigned long long*>(&sh[c]), (unsigned long long)hi);
+    };
+    const double py = K == 1 ? gbt_logistic_row(f[0], yi, emit) : gbt_softprob_row<AMAX>(f, A, yi, emit);
     l = -log(py > 1e-300 ? py : 1e-300);
   }
   sl[threadIdx.x] = l;
@@ -209,18 +170,16 @@ __global__ __launch_bounds__(FBT_CHUNK) void k_fbt_hist(const int8_t* __restrict
 }
 
 // best split of every open node of the level: grid (w K + k, node of level); a thread per feature, three candidates each
-__global__ __launch_bounds__(256) void k_fbt_split(const long long* __restrict__ hist, long long* tG, long long* tH, int32_t* tF, int32_t* tC,
-                                                    int32_t* tS, int r, int d, double lambda, double gamma, double mcw, FGeom G) {
+__global__ __launch_bounds__(256) void k_fbt_split(const long long* __restrict__ hist, GbtTables t, int r, int d, double lambda, double gamma,
+                                                    double mcw, FGeom G) {
   const int nl = 1 << d, kk = blockIdx.y, node = nl - 1 + kk;
   const int wk = blockIdx.x, w = wk / G.K, k = wk - w * G.K;
   const size_t o = fbt_tab(w, r, k, G);
-  if (tS[o + node] != 1) return;
+  if (t.S[o + node] != 1) return;
   const int width = fbt_width(w, G);
-  const long long Gn = tG[o + node], Hn = tH[o + node];
-  const double Gd = (double)Gn / FIX, Hd = (double)Hn / FIX;
-  const double root_term = Gd * Gd / (Hd + lambda);
-  const double floor_ = gamma > 1e-6 ? gamma : 1e-6;
-  // the running best as scalars; a candidate exists iff bf >= 0.  key = 4 f + candidate: lower key wins a tie
+  const long long Gn = t.G[o + node], Hn = t.H[o + node];
+  const double root_term = gbt_root_term(Gn, Hn, lambda), floor_ = gbt_gain_floor(gamma);
+  // the running best as scalars (see gbt_block_best); a candidate exists iff bf >= 0
   double bg = 0.0;
   int bf = -1, bc = 0;
   long long bGL = 0, bHL = 0;
@@ -231,43 +190,13 @@ __global__ __launch_bounds__(256) void k_fbt_split(const long long* __restrict__
     for (int c = 1; c <= 3; ++c) {
       const long long GL = c == 1 ? Gn - G1 - Gm : (c == 2 ? Gn - G1 : Gn - Gm);
       const long long HL = c == 1 ? Hn - H1 - Hm : (c == 2 ? Hn - H1 : Hn - Hm);
-      const double gl = (double)GL / FIX, hl = (double)HL / FIX;
-      const double gr = (double)(Gn - GL) / FIX, hr = (double)(Hn - HL) / FIX;
-      if (hl < mcw || hr < mcw) continue;
-      const double gain = (gl * gl / (hl + lambda) + gr * gr / (hr + lambda)) - root_term;
-      if (!(gain > floor_)) continue;
+      double gain;
+      if (!gbt_split_gain(GL, HL, Gn, Hn, root_term, lambda, mcw, &gain) || !(gain > floor_)) continue;
       if (bf < 0 || gain > bg) { bg = gain; bf = j; bc = c; bGL = GL; bHL = HL; }  // (j and c ascend: the first of equals stays)
     }
   }
-  auto beats = [](double g1, int f1, int c1, double g2, int f2, int c2) {
-    return g1 > g2 || (g1 == g2 && (f1 < f2 || (f1 == f2 && c1 < c2)));
-  };
-  for (int s = 32; s > 0; s >>= 1) {
-    const double tg = __shfl_down(bg, s);
-    const int tf = __shfl_down(bf, s), tc = __shfl_down(bc, s);
-    const long long tGL = __shfl_down(bGL, s), tHL = __shfl_down(bHL, s);
-    if (tf >= 0 && (bf < 0 || beats(tg, tf, tc, bg, bf, bc))) { bg = tg; bf = tf; bc = tc; bGL = tGL; bHL = tHL; }
-  }
-  __shared__ double wg[4];
-  __shared__ int wf[4], wc[4];
-  __shared__ long long wGL[4], wHL[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) { wg[wave] = bg; wf[wave] = bf; wc[wave] = bc; wGL[wave] = bGL; wHL[wave] = bHL; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int bw = -1;
-    for (int q = 0; q < 4; ++q)
-      if (wf[q] >= 0 && (bw < 0 || beats(wg[q], wf[q], wc[q], wg[bw], wf[bw], wc[bw]))) bw = q;
-    if (bw >= 0) {
-      const long long GL = wGL[bw], HL = wHL[bw];
-      tS[o + node] = 2; tF[o + node] = wf[bw]; tC[o + node] = wc[bw];
-      const int l = 2 * node + 1, rr = 2 * node + 2;
-      tS[o + l] = 1; tS[o + rr] = 1;
-      tG[o + l] = GL; tH[o + l] = HL; tG[o + rr] = Gn - GL; tH[o + rr] = Hn - HL;
-    } else {
-      tS[o + node] = 3;
-    }
-  }
+  gbt_block_best(bg, bf, bc, bGL, bHL);
+  if (threadIdx.x == 0) gbt_commit_split(t, o, node, bf >= 0, bf, bc, bGL, bHL);
 }
 
 // rows of the nodes split at level d move to their children: grid (blocks of rows, w K + k)
@@ -288,18 +217,12 @@ __global__ __launch_bounds__(256) void k_fbt_partition(const int8_t* __restrict_
 }
 
 // leaves of the round: every node still open becomes one
-__global__ __launch_bounds__(256) void k_fbt_close(const long long* tG, const long long* tH, int32_t* tS, float* tV, int r, int64_t total, double eta,
-                                                    double lambda, FGeom G) {
+__global__ __launch_bounds__(256) void k_fbt_close(GbtTables t, int r, int64_t total, double eta, double lambda, FGeom G) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= total) return;
-  const int64_t wk = e / MAXN;
-  const int node = (int)(e - wk * MAXN), w = (int)(wk / G.K), k = (int)(wk - (int64_t)w * G.K);
-  const size_t i = fbt_tab(w, r, k, G) + node;
-  if (tS[i] == 1) tS[i] = 3;
-  if (tS[i] == 3) {
-    const double Gd = (double)tG[i] / FIX, Hd = (double)tH[i] / FIX;
-    tV[i] = (float)(eta * (-Gd / (Hd + lambda)));
-  }
+  const int64_t wk = e / GBT_MAXN;
+  const int node = (int)(e - wk * GBT_MAXN), w = (int)(wk / G.K), k = (int)(wk - (int64_t)w * G.K);
+  gbt_close_node(t, fbt_tab(w, r, k, G) + node, eta, lambda);
 }
 
 __global__ __launch_bounds__(256) void k_fbt_margin(float* Fm, const uint8_t* pos, const float* tV, int r, int64_t total, FGeom G) {
@@ -326,7 +249,7 @@ static hipError_t gnx_train_gbt_base_run(const int8_t* dX, int64_t N, int64_t ld
   G.R = P.n_rounds;
   const int D = P.max_depth, W = G.W, K = G.K, R = G.R;
   const int64_t WK = (int64_t)W * K, rows = WK * N;
-  const size_t tab_n = (size_t)WK * R * MAXN;
+  const size_t tab_n = (size_t)WK * R * GBT_MAXN;
   const int nb = (int)((N + 255) / 256);
   const int n_chunks = (G.maxw + FBT_CHUNK - 1) / FBT_CHUNK, n_slices = (int)((N + FBT_SLICE - 1) / FBT_SLICE);
   const size_t hist_n = (size_t)WK * ((size_t)1 << (D - 1)) * G.maxw * 4;
@@ -335,19 +258,13 @@ static hipError_t gnx_train_gbt_base_run(const int8_t* dX, int64_t N, int64_t ld
   GNX_HIPRET(bG.alloc((size_t)rows * 8));
   GNX_HIPRET(bH.alloc((size_t)rows * 8));
   GNX_HIPRET(bPos.alloc((size_t)rows));
-  GNX_HIPRET(bTab.alloc(tab_n * 32));
+  GbtTables t;
+  GNX_HIPRET(gbt_tables_alloc(bTab, t, tab_n, s));
   GNX_HIPRET(bHist.alloc(hist_n * 8));
   GNX_HIPRET(bPart.alloc((size_t)W * nb * 8));
   GNX_HIPRET(bLoss.alloc((size_t)(R + 1) * 8));
-  long long* tG = bTab.as<long long>();
-  long long* tH = tG + tab_n;
-  int32_t* tF = reinterpret_cast<int32_t*>(tH + tab_n);
-  int32_t* tC = tF + tab_n;
-  int32_t* tS = tC + tab_n;
-  float* tV = reinterpret_cast<float*>(tS + tab_n);
-  GNX_HIPRET(hipMemsetAsync(bTab.p, 0, tab_n * 32, s));
   const float m0 = K == 1 ? (float)std::log(P.base_score / (1.0 - P.base_score)) : (float)P.base_score;
-  hipLaunchKernelGGL(k_fbt_fill, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, bFm.as<float>(), m0, rows);
+  hipLaunchKernelGGL(k_gbt_fill,dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, bFm.as<float>(), m0, rows);
   GNX_HIPRET(hipGetLastError());
 
   const bool prof = g_phases_on;
@@ -365,7 +282,7 @@ static hipError_t gnx_train_gbt_base_run(const int8_t* dX, int64_t N, int64_t ld
   auto grad = [&](int r, int fit) {
     const int rr = r < R ? r : R - 1;
 #define FBT_GRAD(AM) hipLaunchKernelGGL(k_fbt_grad<AM>, dim3((unsigned)((int64_t)W * nb)), dim3(256), 0, s, bFm.as<float>(), dy, bG.as<long long>(), \
-                                        bH.as<long long>(), bPos.as<uint8_t>(), tG, tH, tS, bPart.as<double>(), rr, fit, nb, G)
+                                        bH.as<long long>(), bPos.as<uint8_t>(), t.G, t.H, t.S, bPart.as<double>(), rr, fit, nb, G)
     if (A <= 8) FBT_GRAD(8);
     else if (A <= 16) FBT_GRAD(16);
     else FBT_GRAD(32);
@@ -381,16 +298,16 @@ static hipError_t gnx_train_gbt_base_run(const int8_t* dX, int64_t N, int64_t ld
       const int nl = 1 << d;
       if (n_slices > 1) GNX_HIPRET(hipMemsetAsync(bHist.p, 0, (size_t)WK * nl * G.maxw * 32, s));
       hipLaunchKernelGGL(k_fbt_hist, dim3((unsigned)WK, (unsigned)(n_chunks * n_slices), (unsigned)nl), dim3(FBT_CHUNK), 0, s, dX, bG.as<long long>(),
-                         bH.as<long long>(), bPos.as<uint8_t>(), tS, bHist.as<long long>(), r, d, n_chunks, n_slices, G);
+                         bH.as<long long>(), bPos.as<uint8_t>(), t.S, bHist.as<long long>(), r, d, n_chunks, n_slices, G);
       phase(1);
-      hipLaunchKernelGGL(k_fbt_split, dim3((unsigned)WK, (unsigned)nl), dim3(256), 0, s, bHist.as<long long>(), tG, tH, tF, tC, tS, r, d, P.lambda,
-                         P.gamma, P.min_child_weight, G);
+      hipLaunchKernelGGL(k_fbt_split, dim3((unsigned)WK, (unsigned)nl), dim3(256), 0, s, bHist.as<long long>(), t, r, d, P.lambda, P.gamma,
+                         P.min_child_weight, G);
       phase(2);
-      hipLaunchKernelGGL(k_fbt_partition, dim3((unsigned)(WK * nb)), dim3(256), 0, s, dX, bPos.as<uint8_t>(), tS, tF, tC, r, d, nb, G);
+      hipLaunchKernelGGL(k_fbt_partition, dim3((unsigned)(WK * nb)), dim3(256), 0, s, dX, bPos.as<uint8_t>(), t.S, t.F, t.C, r, d, nb, G);
       phase(3);
     }
-    hipLaunchKernelGGL(k_fbt_close, dim3((unsigned)((WK * MAXN + 255) / 256)), dim3(256), 0, s, tG, tH, tS, tV, r, WK * MAXN, P.eta, P.lambda, G);
-    hipLaunchKernelGGL(k_fbt_margin, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, bFm.as<float>(), bPos.as<uint8_t>(), tV, r, rows, G);
+    hipLaunchKernelGGL(k_fbt_close, dim3((unsigned)((WK * GBT_MAXN + 255) / 256)), dim3(256), 0, s, t, r, WK * GBT_MAXN, P.eta, P.lambda, G);
+    hipLaunchKernelGGL(k_fbt_margin, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, bFm.as<float>(), bPos.as<uint8_t>(), t.V, r, rows, G);
     GNX_HIPRET(hipGetLastError());
     phase(4);
   }
@@ -400,40 +317,20 @@ static hipError_t gnx_train_gbt_base_run(const int8_t* dX, int64_t N, int64_t ld
   GNX_HIPRET(perr);
 
   // ---- trees back to the host: window-major, round-major, nodes in heap order ----
-  std::vector<int32_t> hF(tab_n), hC(tab_n), hS(tab_n);
-  std::vector<float> hV(tab_n);
+  GbtHostTables h;
   std::vector<double> hL((size_t)R + 1);
-  GNX_HIPRET(hipMemcpyAsync(hF.data(), tF, tab_n * 4, hipMemcpyDeviceToHost, s));
-  GNX_HIPRET(hipMemcpyAsync(hC.data(), tC, tab_n * 4, hipMemcpyDeviceToHost, s));
-  GNX_HIPRET(hipMemcpyAsync(hS.data(), tS, tab_n * 4, hipMemcpyDeviceToHost, s));
-  GNX_HIPRET(hipMemcpyAsync(hV.data(), tV, tab_n * 4, hipMemcpyDeviceToHost, s));
+  GNX_HIPRET(h.fetch(t, tab_n, s));
   GNX_HIPRET(hipMemcpyAsync(hL.data(), bLoss.p, hL.size() * 8, hipMemcpyDeviceToHost, s));
   GNX_HIPRET(hipStreamSynchronize(s));
-  int64_t nn = 0;
   const int64_t T = WK * R;
-  tree_off[0] = 0;
-  for (int64_t t = 0; t < T; ++t) {
-    const size_t o = (size_t)t * MAXN;
-    int32_t idx[MAXN];
-    int32_t cntn = 0;
-    for (int node = 0; node < MAXN; ++node) idx[node] = (hS[o + node] >= 2) ? cntn++ : -1;
-    for (int node = 0; node < MAXN; ++node) {
-      if (hS[o + node] < 2) continue;
-      const int64_t q = nn + idx[node];
-      if (hS[o + node] == 2) {
-        left[q] = idx[2 * node + 1]; right[q] = idx[2 * node + 2]; feat[q] = hF[o + node];
-        cond[q] = hC[o + node] == 3 ? 1.5f : 0.5f;
-        default_left[q] = hC[o + node] == 2 ? 1 : 0;
-      } else {
-        left[q] = -1; right[q] = -1; feat[q] = 0; cond[q] = hV[o + node]; default_left[q] = 0;
-      }
-    }
-    nn += cntn;
-    tree_off[t + 1] = (int32_t)nn;
-    tree_class[t] = (int32_t)(t % K);
-  }
+  *n_nodes_out = gbt_compact_trees(
+      h.S, T, tree_off, left, right,
+      [&](int64_t q, size_t i) {  // candidate 1: 0.5, missing right; 2: 0.5, missing left; 3: 1.5, missing right
+        feat[q] = h.F[i]; cond[q] = h.B[i] == 3 ? 1.5f : 0.5f; default_left[q] = h.B[i] == 2 ? 1 : 0;
+      },
+      [&](int64_t q, size_t i) { feat[q] = 0; cond[q] = h.V[i]; default_left[q] = 0; });
+  for (int64_t tr = 0; tr < T; ++tr) tree_class[tr] = (int32_t)(tr % K);
   for (int w = 0; w <= W; ++w) win_tree0[w] = w * R * K;
-  *n_nodes_out = nn;
   if (loss_out)
     for (int r = 0; r <= R; ++r) loss_out[r] = hL[(size_t)r];
   if (prof) std::memcpy(g_phase_ms, ms, sizeof(ms));

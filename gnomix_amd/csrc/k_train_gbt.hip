@@ -14,8 +14,8 @@
 //     x a slice of the rows, its 128 KB of LDS holding [feature][node][bin] sums) that visits only the rows of the SMALLER child of
 //     every split (the sibling's histogram is parent - built, exact in int64), one split search (a wave per feature: prefix sums
 //     over the bins, gains in float64, ties to the lowest feature then the lowest bin), one partition pass;
-//   * the softmax goes through det_exp (forest/gnx_det_exp.h: plain IEEE operations in a fixed order) because the oracle must
-//     reproduce p exactly.
+//   * the objective, the gain, the tie rule, the split commit and the leaf are forest/gnx_gbt_core.h's (shared with the base's trainer);
+//     the softmax goes through det_exp (plain IEEE operations in a fixed order) because the oracle must reproduce p exactly.
 // The trees come back in the layout gnx_model_desc takes (tree_off / left / right / feat / cond / tree_class), thresholds on
 // the 1/65536 grid, so the trained smoother runs on k_smooth_xgb_rk like any other.
 #include <algorithm>
@@ -27,12 +27,10 @@
 
 #include "gnx_internal.h"
 #include "gnx_window.h"
-#include "forest/gnx_det_exp.h"
+#include "forest/gnx_gbt_core.h"
 
 namespace {
 
-constexpr double FIX = 1073741824.0;  // 2^30
-constexpr int MAXN = 63;               // heap positions of a tree of depth <= 5
 constexpr int HIST_ENTRIES = 8192;     // (g, h) int64 pairs of LDS per histogram block = 128 KB
 
 struct Geom {
@@ -65,11 +63,6 @@ __global__ __launch_bounds__(256) void k_gbt_quantise(const float* Bf, const uin
   Bq[e] = lut[(size_t)a * 65536 + bucket_of(v)];
 }
 
-__global__ __launch_bounds__(256) void k_gbt_fill(float* p, float v, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) p[i] = v;
-}
-
 // one softmax per row for the A trees of the round; root sums per class; log loss (fixed point, informational)
 template <int AMAX>
 __global__ __launch_bounds__(256) void k_gbt_grad(const float* Fm, const int32_t* y, long long* gq, long long* hq, long long* rootG,
@@ -81,36 +74,20 @@ __global__ __launch_bounds__(256) void k_gbt_grad(const float* Fm, const int32_t
   __syncthreads();
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < G.R) {
-    float m = Fm[i * A];
-    for (int c = 1; c < A; ++c) m = Fm[i * A + c] > m ? Fm[i * A + c] : m;
-    double e[AMAX], sum = 0.0;
-#pragma unroll
-    for (int c = 0; c < AMAX; ++c)
-      if (c < A) { e[c] = det_exp((double)(Fm[i * A + c] - m)); sum += e[c]; }
-    const int yi = y[i];
-    double py = 0.0;
-#pragma unroll
-    for (int c = 0; c < AMAX; ++c)
-      if (c < A) {
-        const double p = e[c] / sum;
-        const double g = p - (yi == c ? 1.0 : 0.0);
-        double h = 2.0 * p * (1.0 - p);
-        if (h < 1e-16) h = 1e-16;
-        const long long gi = llrint(g * FIX), hi = llrint(h * FIX);
-        gq[(size_t)c * G.R + i] = gi;
-        hq[(size_t)c * G.R + i] = hi;
-        pos[(size_t)c * G.R + i] = 0;
-        atomicAdd(reinterpret_cast<unsigned long long*>(&sg[c]), (unsigned long long)gi);
-        atomicAdd(reinterpret_cast<unsigned long long*>(&sh[c]), (unsigned long long)hi);
-        if (yi == c) py = p;
-      }
+    const double py = gbt_softprob_row<AMAX>(Fm + i * A, A, y[i], [&](int c, long long gi, long long hi) {
+      gq[(size_t)c * G.R + i] = gi;
+      hq[(size_t)c * G.R + i] = hi;
+      pos[(size_t)c * G.R + i] = 0;
+      atomicAdd(reinterpret_cast<unsigned long long*>(&sg[c]), (unsigned long long)gi);
+      atomicAdd(reinterpret_cast<unsigned long long*>(&sh[c]), (unsigned long long)hi);
+    });
     atomicAdd(reinterpret_cast<unsigned long long*>(&sl), (unsigned long long)llrint(-log(py > 1e-300 ? py : 1e-300) * 16777216.0));
   }
   __syncthreads();
   if (threadIdx.x < A) {
-    atomicAdd(reinterpret_cast<unsigned long long*>(&rootG[threadIdx.x * MAXN]), (unsigned long long)sg[threadIdx.x]);
-    atomicAdd(reinterpret_cast<unsigned long long*>(&rootH[threadIdx.x * MAXN]), (unsigned long long)sh[threadIdx.x]);
-    st[threadIdx.x * MAXN] = 1;  // (every block writes the same value)
+    atomicAdd(reinterpret_cast<unsigned long long*>(&rootG[threadIdx.x * GBT_MAXN]), (unsigned long long)sg[threadIdx.x]);
+    atomicAdd(reinterpret_cast<unsigned long long*>(&rootH[threadIdx.x * GBT_MAXN]), (unsigned long long)sh[threadIdx.x]);
+    st[threadIdx.x * GBT_MAXN] = 1;  // (every block writes the same value)
   }
   if (threadIdx.x == 0) atomicAdd(reinterpret_cast<unsigned long long*>(loss_fix), (unsigned long long)sl);
 }
@@ -132,8 +109,8 @@ __global__ __launch_bounds__(HIST_T) void k_gbt_hist(const uint8_t* Bq, const lo
   __syncthreads();
   const int64_t r0 = G.R * slice / n_slices, r1 = G.R * (slice + 1) / n_slices;
   const uint8_t* posc = pos + (size_t)c * G.R;
-  const int32_t* stc = st + c * MAXN;
-  const int32_t* bldc = build + c * MAXN;
+  const int32_t* stc = st + c * GBT_MAXN;
+  const int32_t* bldc = build + c * GBT_MAXN;
   for (int64_t i = r0 + threadIdx.x; i < r1; i += HIST_T) {
     const int node = posc[i], k = node - base;
     if (k < 0 || k >= nl || stc[node] != 1 || !bldc[node]) continue;  // (the sibling of a built node is derived: parent - built)
@@ -177,21 +154,17 @@ __global__ __launch_bounds__(256) void k_gbt_split(const long long* part, const 
                                                     int n_slices, double lambda, double gamma, double mcw, Geom G) {
   const int nl = 1 << d, base = nl - 1;
   const int k = blockIdx.x, c = blockIdx.y, node = base + k;
-  if (st[c * MAXN + node] != 1) return;
+  if (st[c * GBT_MAXN + node] != 1) return;
   const int fchunk = (G.F + SPLIT_CHUNKS - 1) / SPLIT_CHUNKS, fbeg = blockIdx.z * fchunk, fend = min(G.F, fbeg + fchunk);
-  const bool built = build[c * MAXN + node] != 0;
+  const bool built = build[c * GBT_MAXN + node] != 0;
   const int ks = built ? k : (k ^ 1);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long Gn = nG[c * MAXN + node], Hn = nH[c * MAXN + node];
-  const double Gd = (double)Gn / FIX, Hd = (double)Hn / FIX;
-  const double root_term = Gd * Gd / (Hd + lambda);
-  // the running best as scalars (see k_gbt_split_pick: no struct selects); a candidate exists iff bf >= 0
-  double bg = gamma > 1e-6 ? gamma : 1e-6;
+  const long long Gn = nG[c * GBT_MAXN + node], Hn = nH[c * GBT_MAXN + node];
+  const double root_term = gbt_root_term(Gn, Hn, lambda);
+  // the running best as scalars (see gbt_block_best: no struct selects); a candidate exists iff bf >= 0
+  double bg = gbt_gain_floor(gamma);
   int bf = -1, bj = -1;
   long long bGL = 0, bHL = 0;
-  auto beats = [](double g1, int f1, int j1, double g2, int f2, int j2) {  // larger gain, then lower feature, then lower bin
-    return g1 > g2 || (g1 == g2 && (f1 < f2 || (f1 == f2 && j1 < j2)));
-  };
   for (int f = fbeg + wave; f < fend; f += 4) {
     const int nc = ncut[f % G.A];
     long long g4[4], h4[4];
@@ -226,64 +199,35 @@ __global__ __launch_bounds__(256) void k_gbt_split(const long long* part, const 
       const int j = lane * 4 + q;
       if (j >= nc) continue;
       const long long GL = eg + g4[q], HL = eh + h4[q];
-      const double gl = (double)GL / FIX, hl = (double)HL / FIX;
-      const double gr = (double)(Gn - GL) / FIX, hr = (double)(Hn - HL) / FIX;
-      if (hl < mcw || hr < mcw) continue;
-      const double gain = (gl * gl / (hl + lambda) + gr * gr / (hr + lambda)) - root_term;
-      if (bf < 0 ? gain > bg : beats(gain, f, j, bg, bf, bj)) { bg = gain; bf = f; bj = j; bGL = GL; bHL = HL; }
+      double gain;
+      if (!gbt_split_gain(GL, HL, Gn, Hn, root_term, lambda, mcw, &gain)) continue;
+      if (bf < 0 ? gain > bg : gbt_beats(gain, f, j, bg, bf, bj)) { bg = gain; bf = f; bj = j; bGL = GL; bHL = HL; }
     }
   }
-  // wave reduction, then the four waves through LDS
-  for (int o = 32; o > 0; o >>= 1) {
-    const double tg = __shfl_down(bg, o);
-    const int tf = __shfl_down(bf, o), tj = __shfl_down(bj, o);
-    const long long tGL = __shfl_down(bGL, o), tHL = __shfl_down(bHL, o);
-    if (tf >= 0 && (bf < 0 || beats(tg, tf, tj, bg, bf, bj))) { bg = tg; bf = tf; bj = tj; bGL = tGL; bHL = tHL; }
-  }
-  __shared__ double wg[4];
-  __shared__ int wf[4], wj[4];
-  __shared__ long long wGL[4], wHL[4];
-  if (lane == 0) { wg[wave] = bg; wf[wave] = bf; wj[wave] = bj; wGL[wave] = bGL; wHL[wave] = bHL; }
-  __syncthreads();
+  gbt_block_best(bg, bf, bj, bGL, bHL);
   if (threadIdx.x == 0) {
-    int bw = -1;
-    for (int w = 0; w < 4; ++w)
-      if (wf[w] >= 0 && (bw < 0 || beats(wg[w], wf[w], wj[w], wg[bw], wf[bw], wj[bw]))) bw = w;
     Best* dst = cand + ((size_t)c * nl + k) * SPLIT_CHUNKS + blockIdx.z;
-    dst->gain = bw >= 0 ? wg[bw] : 0.0;
-    dst->f = bw >= 0 ? wf[bw] : -1;
-    dst->j = bw >= 0 ? wj[bw] : -1;
-    dst->GL = bw >= 0 ? wGL[bw] : 0;
-    dst->HL = bw >= 0 ? wHL[bw] : 0;
+    dst->gain = bg; dst->f = bf; dst->j = bj; dst->GL = bGL; dst->HL = bHL;
   }
 }
 
-__global__ void k_gbt_split_pick(const Best* cand, long long* nG, long long* nH, int32_t* nF, int32_t* nB, int32_t* st, int d, int A) {
+__global__ void k_gbt_split_pick(const Best* cand, GbtTables t, int d, int A) {
   const int nl = 1 << d, base = nl - 1;
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= A * nl) return;
-  const int c = e / nl, k = e - c * nl, node = base + k, o = c * MAXN;
-  if (st[o + node] != 1) return;
-  // (scalars and an index, not struct copies: hipcc 7.2 mixed the fields of two `Best` values in the select it built for `b = t`)
-  const Best* cq = cand + (size_t)e * SPLIT_CHUNKS;
-  int bi = -1, bf = -1, bj = -1;
+  const int c = e / nl, k = e - c * nl, node = base + k, o = c * GBT_MAXN;
+  if (t.S[o + node] != 1) return;
+  const Best* cq = cand + (size_t)e * SPLIT_CHUNKS;  // (scalars, not struct copies: see gbt_block_best)
+  int bf = -1, bj = -1;
   double bg = 0.0;
+  long long bGL = 0, bHL = 0;
   for (int q = 0; q < SPLIT_CHUNKS; ++q) {
     const double tg = cq[q].gain;
     const int tf = cq[q].f, tj = cq[q].j;
     if (tf < 0) continue;
-    if (bi < 0 || tg > bg || (tg == bg && (tf < bf || (tf == bf && tj < bj)))) { bi = q; bg = tg; bf = tf; bj = tj; }
+    if (bf < 0 || gbt_beats(tg, tf, tj, bg, bf, bj)) { bg = tg; bf = tf; bj = tj; bGL = cq[q].GL; bHL = cq[q].HL; }
   }
-  if (bi >= 0) {
-    const long long GL = cq[bi].GL, HL = cq[bi].HL;
-    const long long Gn = nG[o + node], Hn = nH[o + node];
-    st[o + node] = 2; nF[o + node] = bf; nB[o + node] = bj;
-    const int l = 2 * node + 1, r = 2 * node + 2;
-    st[o + l] = 1; st[o + r] = 1;
-    nG[o + l] = GL; nH[o + l] = HL; nG[o + r] = Gn - GL; nH[o + r] = Hn - HL;
-  } else {
-    st[o + node] = 3;
-  }
+  gbt_commit_split(t, o, node, bf >= 0, bf, bj, bGL, bHL);
 }
 
 __global__ __launch_bounds__(256) void k_gbt_partition(const uint8_t* Bq, uint8_t* pos, const int32_t* st, const int32_t* nF, const int32_t* nB,
@@ -295,17 +239,17 @@ __global__ __launch_bounds__(256) void k_gbt_partition(const uint8_t* Bq, uint8_
   const int c = blockIdx.y;
   if (i < G.R) {
     const int node = pos[(size_t)c * G.R + i];
-    if (node >= (1 << d) - 1 && st[c * MAXN + node] == 2) {
+    if (node >= (1 << d) - 1 && st[c * GBT_MAXN + node] == 2) {
       const int64_t n = i / G.W;
       const int w = (int)(i - n * G.W);
-      const uint8_t q = Bq[((size_t)n * G.Wp + w) * G.A + nF[c * MAXN + node]];
-      const int child = q <= nB[c * MAXN + node] ? 2 * node + 1 : 2 * node + 2;
+      const uint8_t q = Bq[((size_t)n * G.Wp + w) * G.A + nF[c * GBT_MAXN + node]];
+      const int child = q <= nB[c * GBT_MAXN + node] ? 2 * node + 1 : 2 * node + 2;
       pos[(size_t)c * G.R + i] = (uint8_t)child;
       atomicAdd(&lc[child], 1);  // rows per child: the smaller child of a pair gets its histogram built, the other derived
     }
   }
   __syncthreads();
-  if (threadIdx.x < MAXN && lc[threadIdx.x]) atomicAdd(&cnt[c * MAXN + threadIdx.x], lc[threadIdx.x]);
+  if (threadIdx.x < GBT_MAXN && lc[threadIdx.x]) atomicAdd(&cnt[c * GBT_MAXN + threadIdx.x], lc[threadIdx.x]);
 }
 
 // which child of every node split at level d gets its histogram built at level d + 1 (the one with fewer rows; ties: the left)
@@ -313,7 +257,7 @@ __global__ void k_gbt_choose(const int32_t* st, const int32_t* cnt, int32_t* bui
   const int nl = 1 << d, base = nl - 1;
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= A * nl) return;
-  const int c = e / nl, node = base + (e - c * nl), o = c * MAXN;
+  const int c = e / nl, node = base + (e - c * nl), o = c * GBT_MAXN;
   if (st[o + node] != 2) return;
   const int l = 2 * node + 1, r = 2 * node + 2;
   const bool left = cnt[o + l] <= cnt[o + r];
@@ -321,14 +265,9 @@ __global__ void k_gbt_choose(const int32_t* st, const int32_t* cnt, int32_t* bui
   build[o + r] = left ? 0 : 1;
 }
 
-__global__ void k_gbt_close(const long long* nG, const long long* nH, int32_t* st, float* nV, int A, double eta, double lambda) {
+__global__ void k_gbt_close(GbtTables t, int A, double eta, double lambda) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= A * MAXN) return;
-  if (st[e] == 1) st[e] = 3;
-  if (st[e] == 3) {
-    const double Gd = (double)nG[e] / FIX, Hd = (double)nH[e] / FIX;
-    nV[e] = (float)(eta * (-Gd / (Hd + lambda)));
-  }
+  if (e < A * GBT_MAXN) gbt_close_node(t, e, eta, lambda);
 }
 
 __global__ __launch_bounds__(256) void k_gbt_margin(float* Fm, const uint8_t* pos, const float* nV, Geom G) {
@@ -336,7 +275,7 @@ __global__ __launch_bounds__(256) void k_gbt_margin(float* Fm, const uint8_t* po
   if (e >= G.R * G.A) return;
   const int c = (int)(e % G.A);
   const int64_t i = e / G.A;
-  Fm[e] += nV[c * MAXN + pos[(size_t)c * G.R + i]];
+  Fm[e] += nV[c * GBT_MAXN + pos[(size_t)c * G.R + i]];
 }
 
 // ---- exact greedy (gnx_gbt_params::tree_method = 1) ------------------------------------------------------------------------------
@@ -374,9 +313,9 @@ __global__ __launch_bounds__(64) void k_gbt_exact_scan(const int32_t* __restrict
   if (lane < nl) {
     const int node = base + lane;
     accG[lane] = 0; accH[lane] = 0; seen[lane] = 0; found[lane] = 0;
-    open_[lane] = st[c * MAXN + node] == 1;
-    nodeG[lane] = nG[c * MAXN + node]; nodeH[lane] = nH[c * MAXN + node];
-    bgain[lane] = gamma > 1e-6 ? gamma : 1e-6;
+    open_[lane] = st[c * GBT_MAXN + node] == 1;
+    nodeG[lane] = nG[c * GBT_MAXN + node]; nodeH[lane] = nH[c * GBT_MAXN + node];
+    bgain[lane] = gbt_gain_floor(gamma);
   }
   __syncthreads();
   const int64_t NP = G.N * G.Wp, col = (int64_t)a * NP;
@@ -416,13 +355,9 @@ __global__ __launch_bounds__(64) void k_gbt_exact_scan(const int32_t* __restrict
       if (mask && hasp && vp < v) {
         GL = accG[kcur] + (sg - ig);
         HL = accH[kcur] + (sh - ih);
-        const double gl = (double)GL / FIX, hl = (double)HL / FIX;
-        const double gr = (double)(nodeG[kcur] - GL) / FIX, hr = (double)(nodeH[kcur] - HL) / FIX;
-        if (!(hl < mcw || hr < mcw)) {
-          const double Gd = (double)nodeG[kcur] / FIX, Hd = (double)nodeH[kcur] / FIX;
-          gain = (gl * gl / (hl + lambda) + gr * gr / (hr + lambda)) - Gd * Gd / (Hd + lambda);
-          ok = gain > bgain[kcur];   // strictly better than every earlier candidate of this node on this feature
-        }
+        const long long Gn = nodeG[kcur], Hn = nodeH[kcur];
+        // strictly better than every earlier candidate of this node on this feature
+        ok = gbt_split_gain(GL, HL, Gn, Hn, gbt_root_term(Gn, Hn, lambda), lambda, mcw, &gain) && gain > bgain[kcur];
       }
       const unsigned long long cb = __ballot(ok);
       if (cb) {  // the largest gain of the step, the earliest lane among equals
@@ -449,12 +384,12 @@ __global__ __launch_bounds__(64) void k_gbt_exact_scan(const int32_t* __restrict
 }
 
 // best feature of every open node: features in ascending order, strictly larger gain replaces (first best wins)
-__global__ void k_gbt_exact_pick(const ExBest* cand, long long* nG, long long* nH, int32_t* nF, int32_t* nB, int32_t* st, int d, int A, int F) {
+__global__ void k_gbt_exact_pick(const ExBest* cand, GbtTables t, int d, int A, int F) {
   const int nl = 1 << d, base = nl - 1;
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= A * nl) return;
-  const int c = e / nl, k = e - c * nl, node = base + k, o = c * MAXN;
-  if (st[o + node] != 1) return;
+  const int c = e / nl, k = e - c * nl, node = base + k, o = c * GBT_MAXN;
+  if (t.S[o + node] != 1) return;
   const ExBest* cq = cand + (size_t)e * F;
   int bf = -1;
   double bg = 0.0;
@@ -463,16 +398,8 @@ __global__ void k_gbt_exact_pick(const ExBest* cand, long long* nG, long long* n
     if (tg < 0.0) continue;
     if (bf < 0 || tg > bg) { bf = f; bg = tg; }
   }
-  if (bf >= 0) {
-    const long long GL = cq[bf].GL, HL = cq[bf].HL;
-    const long long Gn = nG[o + node], Hn = nH[o + node];
-    st[o + node] = 2; nF[o + node] = bf; nB[o + node] = __float_as_int(cq[bf].thr);
-    const int l = 2 * node + 1, r = 2 * node + 2;
-    st[o + l] = 1; st[o + r] = 1;
-    nG[o + l] = GL; nH[o + l] = HL; nG[o + r] = Gn - GL; nH[o + r] = Hn - HL;
-  } else {
-    st[o + node] = 3;
-  }
+  if (bf < 0) { gbt_commit_split(t, o, node, false, 0, 0, 0, 0); return; }
+  gbt_commit_split(t, o, node, true, bf, __float_as_int(cq[bf].thr), cq[bf].GL, cq[bf].HL);  // (the threshold's bits where the histogram form keeps a bin)
 }
 
 __global__ __launch_bounds__(256) void k_gbt_exact_partition(const float* Bf, uint8_t* pos, const int32_t* st, const int32_t* nF, const int32_t* nB, int d, Geom G) {
@@ -480,12 +407,12 @@ __global__ __launch_bounds__(256) void k_gbt_exact_partition(const float* Bf, ui
   const int c = blockIdx.y;
   if (i >= G.R) return;
   const int node = pos[(size_t)c * G.R + i];
-  if (node >= (1 << d) - 1 && st[c * MAXN + node] == 2) {
+  if (node >= (1 << d) - 1 && st[c * GBT_MAXN + node] == 2) {
     const int64_t n = i / G.W;
     const int w = (int)(i - n * G.W);
-    const int f = nF[c * MAXN + node], sft = f / G.A, a = f - sft * G.A;
+    const int f = nF[c * GBT_MAXN + node], sft = f / G.A, a = f - sft * G.A;
     const float v = Bf[(n * G.W + gnx_slide_src(w + sft, G.W, G.pad)) * G.A + a];
-    pos[(size_t)c * G.R + i] = (uint8_t)(v < __int_as_float(nB[c * MAXN + node]) ? 2 * node + 1 : 2 * node + 2);
+    pos[(size_t)c * G.R + i] = (uint8_t)(v < __int_as_float(nB[c * GBT_MAXN + node]) ? 2 * node + 1 : 2 * node + 2);
   }
 }
 
@@ -511,16 +438,9 @@ hipError_t gnx_train_gbt_run(const void* dB, int b_is_f64, const int32_t* dy, in
   GNX_HIPRET(bNcut.alloc((size_t)A * 4));
   GNX_HIPRET(bLoss.alloc((size_t)(P.n_rounds + 1) * 8));
   GNX_HIPRET(bCand.alloc((size_t)A * 32 * SPLIT_CHUNKS * sizeof(Best)));
-  // node tables of every tree: [T][63] x {G, H (int64), F, B, st (int32), V (float)}
-  const size_t tab_n = (size_t)T * MAXN;
-  GNX_HIPRET(bTab.alloc(tab_n * (8 + 8 + 4 + 4 + 4 + 4)));
-  long long* tG = bTab.as<long long>();
-  long long* tH = tG + tab_n;
-  int32_t* tF = reinterpret_cast<int32_t*>(tH + tab_n);
-  int32_t* tB = tF + tab_n;
-  int32_t* tS = tB + tab_n;
-  float* tV = reinterpret_cast<float*>(tS + tab_n);
-  GNX_HIPRET(hipMemsetAsync(bTab.p, 0, tab_n * 32, s));
+  const size_t tab_n = (size_t)T * GBT_MAXN;  // node tables of every tree, and one more round's that the last loss pass writes unread
+  GbtTables tab;
+  GNX_HIPRET(gbt_tables_alloc(bTab, tab, tab_n + (size_t)A * GBT_MAXN, s));
   GNX_HIPRET(hipMemsetAsync(bCnt.p, 0, (size_t)A * 65536 * 4, s));
   GNX_HIPRET(hipMemsetAsync(bLoss.p, 0, (size_t)(P.n_rounds + 1) * 8, s));
 
@@ -619,97 +539,72 @@ hipError_t gnx_train_gbt_run(const void* dB, int b_is_f64, const int32_t* dy, in
   GNX_HIPRET(bPart.alloc(part_entries * 8));
   // rows per node and "build this node's histogram" flags of the round's trees; the level's summed histograms, this level's and the
   // previous one's (a derived node reads its parent's)
-  GNX_HIPRET(bRows.alloc((size_t)2 * A * MAXN * 4));
+  GNX_HIPRET(bRows.alloc((size_t)2 * A * GBT_MAXN * 4));
   int32_t* dCnt = bRows.as<int32_t>();
-  int32_t* dBuild = dCnt + (size_t)A * MAXN;
+  int32_t* dBuild = dCnt + (size_t)A * GBT_MAXN;
   const size_t lev_entries = (size_t)A * ((size_t)1 << (D - 1)) * G.F * 512;
   GNX_HIPRET(bLev.alloc(2 * lev_entries * 8));
   GNX_LDS_OPTIN((size_t)HIST_ENTRIES * 16, k_gbt_hist);
 
   const unsigned gR = (unsigned)((G.R + 255) / 256);
-  for (int r = 0; r <= P.n_rounds; ++r) {
-    const size_t o = (size_t)std::min(r, P.n_rounds - 1) * A * MAXN;  // (the extra pass after the last round only reports the loss)
-    long long* rG = tG + o;
-    long long* rH = tH + o;
-    int32_t* rF = tF + o;
-    int32_t* rB = tB + o;
-    int32_t* rS = tS + o;
-    float* rV = tV + o;
-    if (r == P.n_rounds) {  // loss after the last round: gradients into scratch tables that are not read again
-      gnx_dev_tmp scratch;
-      GNX_HIPRET(scratch.alloc((size_t)A * MAXN * 24));
-      GNX_HIPRET(hipMemsetAsync(scratch.p, 0, (size_t)A * MAXN * 24, s));
-      long long* sG = scratch.as<long long>();
-      if (A <= 8) hipLaunchKernelGGL(k_gbt_grad<8>, dim3(gR), dim3(256), 0, s, bFm.as<float>(), dy, bG.as<long long>(), bH.as<long long>(), sG, sG + A * MAXN, bLoss.as<long long>() + r, bPos.as<uint8_t>(), reinterpret_cast<int32_t*>(sG + 2 * A * MAXN), G);
-      else if (A <= 16) hipLaunchKernelGGL(k_gbt_grad<16>, dim3(gR), dim3(256), 0, s, bFm.as<float>(), dy, bG.as<long long>(), bH.as<long long>(), sG, sG + A * MAXN, bLoss.as<long long>() + r, bPos.as<uint8_t>(), reinterpret_cast<int32_t*>(sG + 2 * A * MAXN), G);
-      else hipLaunchKernelGGL(k_gbt_grad<32>, dim3(gR), dim3(256), 0, s, bFm.as<float>(), dy, bG.as<long long>(), bH.as<long long>(), sG, sG + A * MAXN, bLoss.as<long long>() + r, bPos.as<uint8_t>(), reinterpret_cast<int32_t*>(sG + 2 * A * MAXN), G);
-      GNX_HIPRET(hipGetLastError());
-      GNX_HIPRET(hipStreamSynchronize(s));
-      break;
-    }
-    if (A <= 8) hipLaunchKernelGGL(k_gbt_grad<8>, dim3(gR), dim3(256), 0, s, bFm.as<float>(), dy, bG.as<long long>(), bH.as<long long>(), rG, rH, bLoss.as<long long>() + r, bPos.as<uint8_t>(), rS, G);
-    else if (A <= 16) hipLaunchKernelGGL(k_gbt_grad<16>, dim3(gR), dim3(256), 0, s, bFm.as<float>(), dy, bG.as<long long>(), bH.as<long long>(), rG, rH, bLoss.as<long long>() + r, bPos.as<uint8_t>(), rS, G);
-    else hipLaunchKernelGGL(k_gbt_grad<32>, dim3(gR), dim3(256), 0, s, bFm.as<float>(), dy, bG.as<long long>(), bH.as<long long>(), rG, rH, bLoss.as<long long>() + r, bPos.as<uint8_t>(), rS, G);
-    GNX_HIPRET(hipMemsetAsync(dCnt, 0, (size_t)A * MAXN * 4, s));
-    GNX_HIPRET(hipMemsetAsync(dBuild, 0xff, (size_t)A * MAXN * 4, s));  // (the roots are built; children are decided by k_gbt_choose)
+  // gradients before round r: root sums and open roots into (rG, rH, rS), the loss into slot r
+  auto grad = [&](int r, long long* rG, long long* rH, int32_t* rS) {
+#define GBT_GRAD(AM) hipLaunchKernelGGL(k_gbt_grad<AM>, dim3(gR), dim3(256), 0, s, bFm.as<float>(), dy, bG.as<long long>(), bH.as<long long>(), rG, rH, \
+                                        bLoss.as<long long>() + r, bPos.as<uint8_t>(), rS, G)
+    if (A <= 8) GBT_GRAD(8);
+    else if (A <= 16) GBT_GRAD(16);
+    else GBT_GRAD(32);
+#undef GBT_GRAD
+  };
+  for (int r = 0; r < P.n_rounds; ++r) {
+    const GbtTables rt = tab.at((size_t)r * A * GBT_MAXN);  // the round's A trees
+    grad(r, rt.G, rt.H, rt.S);
+    GNX_HIPRET(hipMemsetAsync(dCnt, 0, (size_t)A * GBT_MAXN * 4, s));
+    GNX_HIPRET(hipMemsetAsync(dBuild, 0xff, (size_t)A * GBT_MAXN * 4, s));  // (the roots are built; children are decided by k_gbt_choose)
     for (int d = 0; exact && d < D; ++d) {
       const int nl = 1 << d;
       hipLaunchKernelGGL(k_gbt_exact_scan, dim3((unsigned)G.F, (unsigned)A), dim3(64), 0, s, bOrdN.as<int32_t>(), bOrdJ.as<int32_t>(), bVal.as<float>(),
-                         bG.as<long long>(), bH.as<long long>(), bPos.as<uint8_t>(), rS, rG, rH, bEx.as<ExBest>(), d, P.lambda, P.gamma, P.min_child_weight, G);
-      hipLaunchKernelGGL(k_gbt_exact_pick, dim3((unsigned)((A * nl + 63) / 64)), dim3(64), 0, s, bEx.as<ExBest>(), rG, rH, rF, rB, rS, d, A, (int)G.F);
-      hipLaunchKernelGGL(k_gbt_exact_partition, dim3(gR, (unsigned)A), dim3(256), 0, s, bBf.as<float>(), bPos.as<uint8_t>(), rS, rF, rB, d, G);
+                         bG.as<long long>(), bH.as<long long>(), bPos.as<uint8_t>(), rt.S, rt.G, rt.H, bEx.as<ExBest>(), d, P.lambda, P.gamma, P.min_child_weight, G);
+      hipLaunchKernelGGL(k_gbt_exact_pick, dim3((unsigned)((A * nl + 63) / 64)), dim3(64), 0, s, bEx.as<ExBest>(), rt, d, A, (int)G.F);
+      hipLaunchKernelGGL(k_gbt_exact_partition, dim3(gR, (unsigned)A), dim3(256), 0, s, bBf.as<float>(), bPos.as<uint8_t>(), rt.S, rt.F, rt.B, d, G);
     }
     for (int d = 0; !exact && d < D; ++d) {
       const int nl = 1 << d, fg = (G.F + fpb[d] - 1) / fpb[d];
       long long* Hcur = bLev.as<long long>() + (size_t)(d & 1) * lev_entries;
       const long long* Hprev = bLev.as<long long>() + (size_t)((d & 1) ^ 1) * lev_entries;
       hipLaunchKernelGGL(k_gbt_hist, dim3((unsigned)fg, (unsigned)A, (unsigned)nsl[d]), dim3(HIST_T), (size_t)fpb[d] * nl * 512 * 8, s, bBq.as<uint8_t>(),
-                         bG.as<long long>(), bH.as<long long>(), bPos.as<uint8_t>(), rS, dBuild, bPart.as<long long>(), d, fpb[d], nsl[d], G);
-      hipLaunchKernelGGL(k_gbt_split, dim3((unsigned)nl, (unsigned)A, SPLIT_CHUNKS), dim3(256), 0, s, bPart.as<long long>(), bNcut.as<int32_t>(), rG,
-                         rH, rS, dBuild, Hprev, Hcur, bCand.as<Best>(), d, nsl[d], P.lambda, P.gamma, P.min_child_weight, G);
-      hipLaunchKernelGGL(k_gbt_split_pick, dim3((unsigned)((A * nl + 63) / 64)), dim3(64), 0, s, bCand.as<Best>(), rG, rH, rF, rB, rS, d, A);
-      hipLaunchKernelGGL(k_gbt_partition, dim3(gR, (unsigned)A), dim3(256), 0, s, bBq.as<uint8_t>(), bPos.as<uint8_t>(), rS, rF, rB, dCnt, d, G);
-      if (d + 1 < D) hipLaunchKernelGGL(k_gbt_choose, dim3((unsigned)((A * nl + 63) / 64)), dim3(64), 0, s, rS, dCnt, dBuild, d, A);
+                         bG.as<long long>(), bH.as<long long>(), bPos.as<uint8_t>(), rt.S, dBuild, bPart.as<long long>(), d, fpb[d], nsl[d], G);
+      hipLaunchKernelGGL(k_gbt_split, dim3((unsigned)nl, (unsigned)A, SPLIT_CHUNKS), dim3(256), 0, s, bPart.as<long long>(), bNcut.as<int32_t>(), rt.G,
+                         rt.H, rt.S, dBuild, Hprev, Hcur, bCand.as<Best>(), d, nsl[d], P.lambda, P.gamma, P.min_child_weight, G);
+      hipLaunchKernelGGL(k_gbt_split_pick, dim3((unsigned)((A * nl + 63) / 64)), dim3(64), 0, s, bCand.as<Best>(), rt, d, A);
+      hipLaunchKernelGGL(k_gbt_partition, dim3(gR, (unsigned)A), dim3(256), 0, s, bBq.as<uint8_t>(), bPos.as<uint8_t>(), rt.S, rt.F, rt.B, dCnt, d, G);
+      if (d + 1 < D) hipLaunchKernelGGL(k_gbt_choose, dim3((unsigned)((A * nl + 63) / 64)), dim3(64), 0, s, rt.S, dCnt, dBuild, d, A);
     }
-    hipLaunchKernelGGL(k_gbt_close, dim3((unsigned)((A * MAXN + 255) / 256)), dim3(256), 0, s, rG, rH, rS, rV, A, P.eta, P.lambda);
-    hipLaunchKernelGGL(k_gbt_margin, dim3(gRA), dim3(256), 0, s, bFm.as<float>(), bPos.as<uint8_t>(), rV, G);
+    hipLaunchKernelGGL(k_gbt_close, dim3((unsigned)((A * GBT_MAXN + 255) / 256)), dim3(256), 0, s, rt, A, P.eta, P.lambda);
+    hipLaunchKernelGGL(k_gbt_margin, dim3(gRA), dim3(256), 0, s, bFm.as<float>(), bPos.as<uint8_t>(), rt.V, G);
     GNX_HIPRET(hipGetLastError());
   }
+  const GbtTables unread = tab.at(tab_n);  // the loss after the last round: the same pass, its root sums where no tree is
+  grad(P.n_rounds, unread.G, unread.H, unread.S);
+  GNX_HIPRET(hipGetLastError());
 
   // ---- trees back to the host, nodes in heap order ----
-  std::vector<int32_t> hF(tab_n), hB(tab_n), hS(tab_n);
-  std::vector<float> hV(tab_n);
+  GbtHostTables h;
   std::vector<long long> hL((size_t)P.n_rounds + 1);
-  GNX_HIPRET(hipMemcpyAsync(hF.data(), tF, tab_n * 4, hipMemcpyDeviceToHost, s));
-  GNX_HIPRET(hipMemcpyAsync(hB.data(), tB, tab_n * 4, hipMemcpyDeviceToHost, s));
-  GNX_HIPRET(hipMemcpyAsync(hS.data(), tS, tab_n * 4, hipMemcpyDeviceToHost, s));
-  GNX_HIPRET(hipMemcpyAsync(hV.data(), tV, tab_n * 4, hipMemcpyDeviceToHost, s));
+  GNX_HIPRET(h.fetch(tab, tab_n, s));
   GNX_HIPRET(hipMemcpyAsync(hL.data(), bLoss.p, hL.size() * 8, hipMemcpyDeviceToHost, s));
   GNX_HIPRET(hipStreamSynchronize(s));
-  int64_t nn = 0;
-  tree_off[0] = 0;
-  for (int t = 0; t < T; ++t) {
-    const size_t o = (size_t)t * MAXN;
-    int32_t idx[MAXN];
-    int32_t cntn = 0;
-    for (int node = 0; node < MAXN; ++node) idx[node] = (hS[o + node] >= 2) ? cntn++ : -1;
-    for (int node = 0; node < MAXN; ++node) {
-      if (hS[o + node] < 2) continue;
-      const int64_t q = nn + idx[node];
-      if (hS[o + node] == 2) {
-        left[q] = idx[2 * node + 1]; right[q] = idx[2 * node + 2]; feat[q] = hF[o + node];
-        if (exact) std::memcpy(&cond[q], &hB[o + node], 4);   // the threshold's float32 bits
-        else cond[q] = cuts[(size_t)(hF[o + node] % A) * 256 + hB[o + node]];
-      } else {
-        left[q] = -1; right[q] = -1; feat[q] = 0; cond[q] = hV[o + node];
-      }
-    }
-    nn += cntn;
-    tree_off[t + 1] = (int32_t)nn;
-    tree_class[t] = t % A;
-  }
-  *n_nodes_out = nn;
+  *n_nodes_out = gbt_compact_trees(
+      h.S, T, tree_off, left, right,
+      [&](int64_t q, size_t i) {
+        feat[q] = h.F[i];
+        if (exact) std::memcpy(&cond[q], &h.B[i], 4);   // the threshold's float32 bits
+        else cond[q] = cuts[(size_t)(h.F[i] % A) * 256 + h.B[i]];
+      },
+      [&](int64_t q, size_t i) { feat[q] = 0; cond[q] = h.V[i]; });
+  for (int t = 0; t < T; ++t) tree_class[t] = t % A;
   if (loss_out)
     for (int r = 0; r <= P.n_rounds; ++r) loss_out[r] = ((double)hL[(size_t)r] / 16777216.0) / (double)G.R;
   return hipSuccess;
 }
+

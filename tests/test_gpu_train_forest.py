@@ -57,7 +57,12 @@ CASES = {
     "depth5": dict(C=79, M=24, ctx=12, N=130, A=3, kw=dict(n_rounds=4, max_depth=5)),
     # a window wider than one block's feature chunk (320 and 327 > FBT_CHUNK) and more rows than one block's slice (2100 > FBT_SLICE)
     "chunks_and_slices": dict(C=607, M=300, ctx=10, N=FBT_SLICE + 52, A=3, kw=dict(n_rounds=2, max_depth=2)),
+    # the gradient kernel's wider instantiations: A in (8, 16] and (16, 32], and 32, the most the entry accepts
+    "A9": dict(C=41, M=20, ctx=0, N=130, A=9, kw=dict(n_rounds=2, max_depth=2)),
+    "A17": dict(C=41, M=20, ctx=0, N=130, A=17, kw=dict(n_rounds=2, max_depth=2)),
+    "A32": dict(C=41, M=20, ctx=0, N=130, A=32, kw=dict(n_rounds=2, max_depth=2)),
 }
+WIDE_A = ("A9", "A17", "A32")
 assert CASES["chunks_and_slices"]["M"] + 2 * CASES["chunks_and_slices"]["ctx"] > FBT_CHUNK
 
 
@@ -84,6 +89,8 @@ def test_trees_equal_the_restatement(ga, name):
     from gnomix_amd.train import train_forest_arrays
     c = CASES[name]
     X, y, ref, ref_loss = _case(name)
+    if name in WIDE_A:      # not a degenerate input: at least A of the reference's trees split
+        assert np.count_nonzero(ref["fb_left"][ref["fb_tree_off"][:-1]] >= 0) >= c["A"]
     host, loss_h = train_forest_arrays(X, y, c["M"], c["ctx"], c["A"], **c["kw"])
     _assert_equal_trees(host, ref, "host entry")
     assert np.max(np.abs(loss_h - ref_loss)) <= 1e-12

@@ -568,6 +568,12 @@ def test_shared_helpers_have_one_definition():
         "slide_src": (qual + r"\w+\s+\w*slide_src\([^()]*\)\s*\{", "gnx_window.h"),
         "det_exp": (r"\bdouble det_exp\(", os.path.join("forest", "gnx_det_exp.h")),
         "pair_index": (r"\bint pair_index\(", os.path.join("svm", "gnx_svc_rbf.h")),
+        # what the two boosted-tree trainers share: each CPU restatement checks one trainer, so each statement has one copy
+        "the GBT fixed point": (r"1073741824\.0", os.path.join("forest", "gnx_gbt_core.h")),
+        "the GBT gain": (r"gl \* gl / \(hl \+ lambda\)", os.path.join("forest", "gnx_gbt_core.h")),
+        "the GBT tie rule": (r"g1 == g2 &&", os.path.join("forest", "gnx_gbt_core.h")),
+        "the GBT split commit": (r"\.S\[o \+ l\] = 1", os.path.join("forest", "gnx_gbt_core.h")),
+        "the GBT leaf value": (r"-Gd / \(Hd \+ lambda\)", os.path.join("forest", "gnx_gbt_core.h")),
         "hipFree in a destructor": (r"~\w+\(\)\s*\{[^}]*hipFree\(", "gnx_internal.h"),
         # the host side of the ancestry-specific ops (summary/gnx_summary_host.h declares them)
         "the column-map check": (r"sv != -1 && \(sv < 0", os.path.join("summary", "gnx_summary_host.hip")),

@@ -111,7 +111,16 @@ CASES = [
     dict(N=20, W=70, A=4, S=21, kw=dict(n_rounds=4, max_depth=5, max_bin=64)),
     dict(N=18, W=48, A=3, S=9, kw=dict(n_rounds=6, gamma=0.5, min_child_weight=3.0, reg_lambda=0.0, learning_rate=0.3)),
     dict(N=9, W=170, A=12, S=75, kw=dict(n_rounds=2)),
+    # A > 16: the gradient kernel's widest instantiation; 32 is the most the entry accepts
+    dict(N=8, W=40, A=17, S=5, kw=dict(n_rounds=2, max_depth=3)),
+    dict(N=8, W=70, A=32, S=5, kw=dict(n_rounds=2, max_depth=3)),
 ]
+
+
+def _assert_not_degenerate(T, case):
+    """the A > 16 cases: at least A of the reference's trees split, so an input that grows no tree cannot pass silently"""
+    if case["A"] > 16:
+        assert np.count_nonzero(T.left[T.tree_off[:-1]] >= 0) >= case["A"]
 
 
 @pytest.mark.gpu
@@ -126,6 +135,7 @@ def test_gbt_trees_identical_to_oracle(ga, oracle, case, dtype):
     if "reg_lambda" in okw: okw["lam"] = okw.pop("reg_lambda")
     if "learning_rate" in okw: okw["eta"] = okw.pop("learning_rate")
     T, loss_ref = oracle.train_gbt(B, y, case["S"], **okw)
+    _assert_not_degenerate(T, case)
     trees, loss = train.train_gbt_arrays(B, y, case["S"], **kw)
     assert np.array_equal(trees["tree_off"], T.tree_off)
     assert np.array_equal(trees["left"], T.left) and np.array_equal(trees["right"], T.right)
@@ -142,6 +152,7 @@ EXACT_CASES = [
     dict(N=8, W=60, A=4, S=21, kw=dict(n_rounds=2, max_depth=5)),
     dict(N=12, W=36, A=3, S=9, kw=dict(n_rounds=5, gamma=0.5, min_child_weight=3.0, reg_lambda=0.0, learning_rate=0.3)),
     dict(N=3, W=170, A=12, S=75, kw=dict(n_rounds=1)),
+    dict(N=8, W=40, A=17, S=5, kw=dict(n_rounds=2, max_depth=3)),
 ]
 
 
@@ -163,6 +174,7 @@ def test_gbt_exact_greedy_trees_identical_to_oracle(ga, oracle, case, dtype):
     if "reg_lambda" in okw: okw["lam"] = okw.pop("reg_lambda")
     if "learning_rate" in okw: okw["eta"] = okw.pop("learning_rate")
     T, loss_ref = oracle.train_gbt(B, y, case["S"], exact=True, **okw)
+    _assert_not_degenerate(T, case)
     trees, loss = train.train_gbt_arrays(B, y, case["S"], tree_method="exact", **kw)
     assert np.array_equal(trees["tree_off"], T.tree_off)
     assert np.array_equal(trees["left"], T.left) and np.array_equal(trees["right"], T.right)
