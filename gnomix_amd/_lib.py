@@ -257,6 +257,10 @@ SYMBOLS = {
                                             C.c_int32, _I64, _I64, _VP, _VP, _VP, C.POINTER(_I64)]),
     "gnx_ancestry_assoc_traits_gt2": (C.c_int, [_VP, _VP, _I64, _I64, _I64, _VP, _VP, _VP, _I64, C.c_int32, _VP, C.c_int32, _VP, C.c_int32, _I64, _I64,
                                                 _VP, _VP, _VP, C.POINTER(_I64)]),
+    "gnx_ancestry_admixmap_dev": (C.c_int, [_VP, _VP, _I64, _I64, _I64, C.c_int32, _VP, _I64, C.c_int32, _VP, C.c_int32, _VP, _I64, _I64, _VP, _VP, _VP, _VP,
+                                            C.POINTER(_I64)]),
+    "gnx_ancestry_admixmap": (C.c_int, [_VP, _VP, _I64, _I64, _I64, C.c_int32, _VP, _I64, C.c_int32, _VP, C.c_int32, _VP, _I64, _I64, _VP, _VP, _VP, _VP,
+                                        C.POINTER(_I64)]),
     "gnx_ancestry_assoc_logit_dev": (C.c_int, [_VP, _VP, _I, _I64, _VP, _I64, _I64, _I64, _I64, _I64, C.c_int32, _VP, _VP, C.c_int32, _VP, C.c_int32,
                                                _I64, _I64, C.c_double, C.c_int32, _VP, _VP, _VP, _VP, _VP, C.POINTER(_I64)]),
     "gnx_ancestry_assoc_logit": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _I64, _I64, _I64, _I64, C.c_int32, _VP, _VP, C.c_int32, _VP, C.c_int32, _I64, _I64,

@@ -238,6 +238,56 @@ def assoc_logit(f, y, Z, use, c0, c1, min_ac=1, tol=None, max_iter=None, check=T
     return assoc.split_logit(*(f.host(b) for b in bufs), f.A, K, c0, c1, f.M, f.W, n_bad.value)
 
 
+# ---- admixture mapping: the labels alone, no rows and no model ------------------------------------------------------------------------
+def admixmap_stats(ctx, labels, A, Y, Z, use, w0=0, w1=None, check=True):
+    """gnx_ancestry_admixmap[_dev] for the windows [w0, w1) -> admixmap.AdmixStats of numpy arrays.  labels (N, W) int32: a numpy array
+    (contiguous rows, any row stride) or a CUDA tensor (the same), which never leaves HBM: Y, Z and use then go to its device and the
+    blocks are allocated there.  Y (N / 2, T) float64 may have any row stride too."""
+    from . import admixmap
+    dev = hasattr(labels, "is_cuda")
+    if dev:
+        import torch
+        if labels.dim() != 2:
+            raise ValueError(f"labels must be (N, W), got {tuple(labels.shape)}")
+        lab = labels if labels.dtype == torch.int32 and (labels.shape[1] == 0 or labels.stride(1) == 1) else labels.to(torch.int32).contiguous()
+        N, W = lab.shape
+        ldl = lab.stride(0) if N > 1 else W
+    else:
+        lab = np.asarray(labels)
+        if lab.ndim != 2 or lab.dtype != np.int32 or (lab.shape[1] and lab.strides[1] != 4) or lab.strides[0] % 4 or lab.strides[0] < 4 * lab.shape[1]:
+            lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.ndim != 2:
+            raise ValueError(f"labels must be (N, W), got {lab.shape}")
+        N, W = lab.shape
+        ldl = lab.strides[0] // 4 if N > 1 else W
+    check_even(N)
+    w0, w1 = int(w0), int(W) if w1 is None else int(w1)
+    Ya = np.asarray(Y)
+    strided = Ya.ndim == 2 and Ya.dtype == np.float64 and Ya.shape[1] and Ya.strides[1] == 8 and Ya.strides[0] % 8 == 0 and Ya.strides[0] >= 8 * Ya.shape[1]
+    Yc, Z, use, _ = assoc.trait_covariates(N // 2, Y, Z, use)
+    if strided and not dev:
+        Yc = Ya                                    # the caller's row stride goes to the library as it is
+    K, T = Z.shape[1], Yc.shape[1]
+    ldy = Yc.strides[0] // 8 if N // 2 > 1 else T
+    n_bad = ctypes.c_int64(0)
+    if dev:
+        import torch
+        dtypes = {np.int32: torch.int32, np.float64: torch.float64}
+        bufs = admixmap.stats_buffers(int(A), K, T, w0, w1, empty=lambda shape, dtype: torch.empty(shape, dtype=dtypes[dtype], device=lab.device))
+        Yd, Zd, ud = (torch.from_numpy(np.ascontiguousarray(v)).to(lab.device) for v in (Yc, Z, use))
+        ctx.set_stream(torch.cuda.current_stream(ctx.device).cuda_stream)
+        rc = ctx.lib.gnx_ancestry_admixmap_dev(ctx.h, lab.data_ptr(), ldl, N, W, int(A), Yd.data_ptr(), T, T, Zd.data_ptr(), K, ud.data_ptr(), w0, w1,
+                                               *(b.data_ptr() for b in bufs), ctypes.byref(n_bad))
+        verdict(ctx, rc, n_bad.value, check, handed=(_lib.GNX_EINVAL,))
+        bufs = [b.cpu().numpy() for b in bufs]
+    else:
+        bufs = admixmap.stats_buffers(int(A), K, T, w0, w1)
+        rc = ctx.lib.gnx_ancestry_admixmap(ctx.h, lab.ctypes.data, ldl, N, W, int(A), Yc.ctypes.data, ldy, T, Z.ctypes.data, K, use.ctypes.data, w0, w1,
+                                           *(b.ctypes.data for b in bufs), ctypes.byref(n_bad))
+        verdict(ctx, rc, n_bad.value, check, handed=(_lib.GNX_EINVAL,))
+    return admixmap.split_blocks(*bufs, int(A), K, T, n_bad.value)
+
+
 # ---- DeviceModel's half ----------------------------------------------------------------------------------------------------------------
 class AncestryOps:
     """the ancestry-specific methods of DeviceModel (which supplies ctx, lib, h, C, M, W, A, _x, _gt2_args, _bind_torch_stream).  The
@@ -280,6 +330,23 @@ class AncestryOps:
             int(proba_t is not None and proba_t.dtype == torch.float64), w.ctypes.data, N, W, self.A, hard.data_ptr(),
             soft.data_ptr() if soft is not None else None, count.data_ptr(), total.data_ptr(), longest.data_ptr()))
         return AncestrySummary(hard, soft, count, total, longest, w)
+
+    # ---- admixture mapping (the labels alone)
+    def admixture_map_stats(self, labels, Y, Z=None, use=None, w0=0, w1=None, check=True):
+        """the blocks of admixture mapping for the windows [w0, w1) of (N, W) host labels (gnx_ancestry_admixmap, the float64 matrix
+        cores; include/gnomix_hip.h states them) -> gnomix_amd.admixmap.AdmixStats"""
+        return admixmap_stats(self.ctx, check_labels(labels, np.asarray(labels).shape[0], self.W), self.A, Y, Z, use, w0, w1, check)
+
+    def admixture_map_stats_device(self, lab_t, Y, Z=None, use=None, w0=0, w1=None, check=True):
+        """the same on an (N, W) int32 CUDA tensor with contiguous rows (any row stride): the labels stay in HBM
+        (gnx_ancestry_admixmap_dev) -> admixmap.AdmixStats of numpy arrays"""
+        return admixmap_stats(self.ctx, check_labels(lab_t, lab_t.shape[0], self.W), self.A, Y, Z, use, w0, w1, check)
+
+    def admixture_map(self, labels, Y, Z=None, use=None, min_hap=1, n_perm=0, seed=0, check=True):
+        """admixture mapping of the traits Y on (N, W) labels, a numpy array or a CUDA tensor (gnomix_amd.admixmap.admixture_mapping states
+        the model, the permutations and the result) -> admixmap.AdmixMap"""
+        from . import admixmap
+        return admixmap.admixture_mapping(self.ctx, check_labels(labels, labels.shape[0], self.W), self.A, Y, Z, use, min_hap, n_perm, seed, check)
 
     # ---- allele counts and dosage
     def ancestry_allele_counts(self, X, labels, packed=False):

@@ -136,7 +136,8 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
                   global_ancestry_output=False, ancestry_allele_freq_output=False, ancestry_assoc_output=False, phenotype_file=None,
                   ancestry_assoc_model="linear", ancestry_score_output=False, score_file=None, ancestry_mds_output=False,
                   ancestry_mds_components=None, ancestry_mds_min_sites=None, ancestry_clump_output=False, ancestry_clump_p1=None,
-                  ancestry_clump_p2=None, ancestry_clump_r2=None, ancestry_clump_kb=None, trait_file=None, covariate_file=None):
+                  ancestry_clump_p2=None, ancestry_clump_r2=None, ancestry_clump_kb=None, trait_file=None, covariate_file=None,
+                  admixture_mapping_output=False, admixture_mapping_perms=None, admixture_mapping_seed=None, admixture_mapping_min_hap=None):
     """gnomix.py:37-100 with the HIP model behind the same steps.  The query never becomes an (N, C) host matrix: the library
     parses the text into 2-bit rows (gnx_vcf_read), `column_map` keeps vcf_to_npy's bookkeeping (SNP intersection, REF flips,
     absent SNPs) as one int32 per model SNP, the GPU builds X and runs base + smoother (or Gnofix) on it, and the library
@@ -180,7 +181,13 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
     inference.ancestry_clump_p1, _p2, _r2, _kb, defaults 1e-4, 1e-2, 0.5, 250): query_results.clumped.tsv as well, the association
     result clumped ancestry by ancestry (gnomix_amd.ld.clump) with that ancestry's LD, counted on the model's own GPU from the query's
     2-bit rows and the labels the .msp gets (gnx_ancestry_ld_counts_gt2).  Not with phase=True (ValueError before any
-    work), for the same reason."""
+    work), for the same reason.
+    `admixture_mapping_output` (config key inference.admixture_mapping_output, off unless set) with `phenotype_file` or `trait_file`
+    (plus `covariate_file`), read as above: admixture mapping, the regression of the trait(s) on the local ancestry itself window by
+    window (gnx_ancestry_admixmap), from the labels the .msp gets: query_results.admixmap.tsv for phenotype_file,
+    query_results.admixmap.<name>.tsv per trait of trait_file (postprocess.write_admixmap).  inference.admixture_mapping_perms (default
+    0: no permutations), _seed (default 0) and _min_hap (default 1) go to admixmap.admixture_mapping.  No genotypes are needed, so it
+    works with phase False AND True (Gnofix's labels then).  A missing file or a bad value is a ValueError before any work."""
     from time import perf_counter as clock
     from . import postprocess as pp
     from . import vcfio
@@ -215,6 +222,20 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
     if ancestry_mds_output and base_args["phase"]:
         raise ValueError("inference.ancestry_mds_output with phase=True: the phased haplotypes are not kept on this path; "
                          "use HipGnomix.phase followed by HipGnomix.ancestry_mds")
+    am_perms = 0 if admixture_mapping_perms is None else int(admixture_mapping_perms)
+    am_seed = 0 if admixture_mapping_seed is None else int(admixture_mapping_seed)
+    am_min_hap = 1 if admixture_mapping_min_hap is None else int(admixture_mapping_min_hap)
+    if admixture_mapping_output:
+        if not phenotype_file and not trait_file:
+            raise ValueError("inference.admixture_mapping_output needs inference.phenotype_file (a TSV: sample, pheno, then covariates) or "
+                             "inference.trait_file")
+        for key, path in (("phenotype_file", phenotype_file), ("trait_file", trait_file), ("covariate_file", covariate_file)):
+            if path and not os.path.isfile(path):
+                raise ValueError(f"inference.{key}: no such file: {path}")
+        if am_perms < 0:
+            raise ValueError("inference.admixture_mapping_perms must be >= 0")
+        if am_min_hap < 1:
+            raise ValueError("inference.admixture_mapping_min_hap must be >= 1")
     mds_k = 4 if ancestry_mds_components is None else int(ancestry_mds_components)
     mds_sites = 1000 if ancestry_mds_min_sites is None else int(ancestry_mds_min_sites)
     if ancestry_mds_output and (mds_k < 1 or mds_sites < 1):
@@ -252,7 +273,8 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
                               global_ancestry_output, ancestry_allele_freq_output, ancestry_assoc_output, phenotype_file, ancestry_assoc_model,
                               ancestry_score_output=ancestry_score_output, score_file=score_file,
                               ancestry_mds=(mds_k, mds_sites) if ancestry_mds_output else None,
-                              ancestry_clump=clump_kw if ancestry_clump_output else None, trait_file=trait_file, covariate_file=covariate_file)
+                              ancestry_clump=clump_kw if ancestry_clump_output else None, trait_file=trait_file, covariate_file=covariate_file,
+                              admixture_mapping=(am_perms, am_seed, am_min_hap) if admixture_mapping_output else None)
     finally:
         if own_group is not None:
             own_group.close()
@@ -261,7 +283,7 @@ def run_inference(base_args, model, snp_level=False, bed_file_output=False, verb
 def _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out, T, t0, snp_level, bed_file_output, verbose,
                    global_ancestry_output=False, ancestry_allele_freq_output=False, ancestry_assoc_output=False, phenotype_file=None,
                    ancestry_assoc_model="linear", ancestry_score_output=False, score_file=None, ancestry_mds=None, ancestry_clump=None,
-                   trait_file=None, covariate_file=None):
+                   trait_file=None, covariate_file=None, admixture_mapping=None):
     from time import perf_counter as clock
     from . import postprocess as pp
     from . import vcfio
@@ -318,6 +340,24 @@ def _run_and_write(model, base_args, runner, vcf, src, vcf_idx, fmt_idx, N, out,
         counts = runner.allele_counts_gt2(vcf.gt2, N, src, labels)
         pp.write_afreq(out_prefix, chm, model.snp_pos, model.M, model.W, counts, model.population_order)
         T["write_afreq"] = clock() - t0
+    if admixture_mapping is not None:
+        t0 = clock()
+        from . import admixmap, assoc
+        n_perm, seed, min_hap = admixture_mapping
+        names = [str(s) for s in samples]
+        lab32 = np.ascontiguousarray(labels, dtype=np.int32)
+        if trait_file:
+            Y, Z, use, trait_names, _ = assoc.read_traits(trait_file, names, covariate_file)
+            for name in trait_names:
+                if not name or os.sep in name or name in (".", ".."):
+                    raise ValueError(f"{trait_file}: the trait name '{name}' cannot be part of a file name")
+            res = admixmap.admixture_mapping(model.dev.ctx, lab32, model.A, Y, Z, use, min_hap, n_perm, seed)     # one GPU: the model's own
+            pp.write_admixmap(out_prefix, meta, res, model.population_order, trait_names)
+        if phenotype_file:
+            y, Z, use, _ = assoc.read_phenotypes(phenotype_file, names)
+            res = admixmap.admixture_mapping(model.dev.ctx, lab32, model.A, y, Z, use, min_hap, n_perm, seed)
+            pp.write_admixmap(out_prefix, meta, res, model.population_order)
+        T["write_admixmap"] = clock() - t0
     if ancestry_assoc_output and trait_file:
         t0 = clock()
         from . import assoc
@@ -446,7 +486,9 @@ def main(argv=None):
                       ancestry_clump_output=bool(inf.get("ancestry_clump_output")), ancestry_clump_p1=inf.get("ancestry_clump_p1"),
                       ancestry_clump_p2=inf.get("ancestry_clump_p2"), ancestry_clump_r2=inf.get("ancestry_clump_r2"),
                       ancestry_clump_kb=inf.get("ancestry_clump_kb"), trait_file=inf.get("trait_file"),
-                      covariate_file=inf.get("covariate_file"))
+                      covariate_file=inf.get("covariate_file"), admixture_mapping_output=bool(inf.get("admixture_mapping_output")),
+                      admixture_mapping_perms=inf.get("admixture_mapping_perms"), admixture_mapping_seed=inf.get("admixture_mapping_seed"),
+                      admixture_mapping_min_hap=inf.get("admixture_mapping_min_hap"))
         if os.environ.get("GNX_CLI_TIMING"):
             T["since_process_start"] = _since_process_start()
             sys.stderr.write("gnomix_amd timings (s): " + ", ".join("%s %.3f" % kv for kv in T.items()) + "\n")
@@ -616,7 +658,9 @@ def train_main(argv):
                       ancestry_clump_output=bool(inf.get("ancestry_clump_output")), ancestry_clump_p1=inf.get("ancestry_clump_p1"),
                       ancestry_clump_p2=inf.get("ancestry_clump_p2"), ancestry_clump_r2=inf.get("ancestry_clump_r2"),
                       ancestry_clump_kb=inf.get("ancestry_clump_kb"), trait_file=inf.get("trait_file"),
-                      covariate_file=inf.get("covariate_file"))
+                      covariate_file=inf.get("covariate_file"), admixture_mapping_output=bool(inf.get("admixture_mapping_output")),
+                      admixture_mapping_perms=inf.get("admixture_mapping_perms"), admixture_mapping_seed=inf.get("admixture_mapping_seed"),
+                      admixture_mapping_min_hap=inf.get("admixture_mapping_min_hap"))
     return 0
 
 

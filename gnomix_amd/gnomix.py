@@ -266,6 +266,18 @@ class HipGnomix:
         with self._rows_and_labels(X) as (rows, lab, _):
             return fit(rows, lab)
 
+    def admixture_mapping(self, X, y_or_Y, Z=None, use=None, labels=None, min_hap=1, n_perm=0, seed=0):
+        """admixture mapping: the regression of the trait(s) on the LOCAL ANCESTRY itself, window by window, under the labels predict
+        returns for X (mode_filter applied when set), or under `labels` (N, W) (a numpy array or a CUDA tensor), in which case X is not
+        looked at and no prediction runs.  y_or_Y (N / 2,) or (N / 2, T) (a 1-D y gives a trait axis of length 1); Z, use as
+        ancestry_association takes them.  n_perm > 0: Freedman-Lane max-T permutations.  The blocks are reduced on the float64 matrix
+        cores (k_ancestry_assoc_admix_main); with a CUDA tensor the labels never leave HBM -> admixmap.AdmixMap (numpy arrays; the
+        module states the model, the status codes and how runs on several chromosomes combine)."""
+        if labels is not None:
+            return self.dev.admixture_map(labels, y_or_Y, Z, use, min_hap, n_perm, seed)
+        with self._rows_and_labels(X) as (_, lab, _on_device):
+            return self.dev.admixture_map(lab, y_or_Y, Z, use, min_hap, n_perm, seed)
+
     def ancestry_scores(self, X, weights, effect=None):
         """ancestry-partitioned polygenic scores ("partial PRS") of X under the labels predict returns (mode_filter applied when set):
         per individual (rows 2 i, 2 i + 1), ancestry a and score s, the sum of weights[c, a, s] over the SNPs c and the individual's

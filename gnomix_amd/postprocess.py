@@ -95,6 +95,78 @@ def write_msp(msp_prefix, meta_data, pred_labels, populations, query_samples, n_
                                             lab.shape[0], lab.shape[1], lab.shape[1], int(n_threads)))
 
 
+Msp = collections.namedtuple("Msp", "labels populations samples meta")
+Msp.__doc__ = """what read_msp returns: labels (N, W) int32 (rows 2 i and 2 i + 1 are samples[i]); the populations in code order; the samples; meta:
+the window table as write_msp takes it (chm: strings; spos, epos, n snps: int64; sgpos, egpos: float64)"""
+
+
+def read_msp(path):
+    """the inverse of write_msp, in plain Python / numpy: <prefix>.msp -> Msp.  With it admixmap.admixture_mapping runs from an .msp alone:
+    no model, no VCF."""
+    with open(path) as f:
+        first = f.readline().rstrip("\n")
+        second = f.readline().rstrip("\n")
+        body = [ln.rstrip("\n").split("\t") for ln in f if ln.strip()]
+    if ":" not in first or not first.startswith("#") or not second.startswith("#"):
+        raise ValueError(f"{path}: not an .msp file (two header lines starting with '#')")
+    pops = {}
+    for cell in first.split(":", 1)[1].strip().split("\t"):
+        name, _, code = cell.rpartition("=")
+        pops[int(code)] = name
+    if sorted(pops) != list(range(len(pops))):
+        raise ValueError(f"{path}: the population codes are not 0 .. {len(pops) - 1}")
+    cols = second[1:].split("\t")
+    nm = len(META_COLUMNS)
+    if cols[:nm] != META_COLUMNS or (len(cols) - nm) % 2:
+        raise ValueError(f"{path}: the second header line must hold {META_COLUMNS} and two columns per sample")
+    haps = cols[nm:]
+    samples = [h[:-2] for h in haps[0::2]]
+    if any(a != s + ".0" or b != s + ".1" for s, a, b in zip(samples, haps[0::2], haps[1::2])):
+        raise ValueError(f"{path}: the haplotype columns must come as <sample>.0, <sample>.1")
+    if any(len(r) != len(cols) for r in body):
+        raise ValueError(f"{path}: a line does not have {len(cols)} cells")
+    W = len(body)
+    labels = np.array([r[nm:] for r in body], dtype=np.int32).reshape(W, len(haps)).T
+    meta = {"chm": [r[0] for r in body]}
+    for j, (name, dt) in enumerate(zip(META_COLUMNS[1:], (np.int64, np.int64, np.float64, np.float64, np.int64)), 1):
+        meta[name] = np.array([r[j] for r in body], dtype=np.float64).astype(dt) if W else np.zeros(0, dt)
+    return Msp(np.ascontiguousarray(labels), [pops[i] for i in range(len(pops))], samples, meta)
+
+
+def write_admixmap(prefix, meta_data, result, populations, trait_names=None):
+    """<prefix>.admixmap.tsv from an admixmap.AdmixMap, or <prefix>.admixmap.<trait>.tsv per trait when trait_names is given: one header
+    line, then one line per window: the .msp's window columns (chm, spos, epos, sgpos, egpos, n snps), the joint fields n, status, df1,
+    df2, F, p_joint [, p_adj_F], then per population <pop>.n_hap, .beta, .se, .t, .p [, .p_adj] (the p_adj columns only for a result with
+    permutations; floats with six significant digits, nan where the statistic is), tab-separated -> the paths written"""
+    W, A, T = np.asarray(result.beta).shape
+    if A != len(populations) or W != len(meta_data["spos"]):
+        raise ValueError(f"the result holds {W} windows x {A} populations, the table {len(meta_data['spos'])} x {len(populations)}")
+    if trait_names is None and T != 1:
+        raise ValueError(f"a result of {T} traits needs trait_names")
+    if trait_names is not None and len(trait_names) != T:
+        raise ValueError(f"{len(trait_names)} trait names for {T} traits")
+    perm = result.perm_max_t is not None
+    num = lambda v: format(float(v), ".6g") if np.isfinite(v) else "nan"
+    rows = _meta_strings(meta_data)
+    head = ["#" + META_COLUMNS[0]] + META_COLUMNS[1:] + ["n", "status", "df1", "df2", "F", "p_joint"] + (["p_adj_F"] if perm else [])
+    for p in populations:
+        head += [str(p) + s for s in (".n_hap", ".beta", ".se", ".t", ".p") + ((".p_adj",) if perm else ())]
+    paths = []
+    for t in range(T):
+        path = prefix + (".admixmap.tsv" if trait_names is None else ".admixmap.%s.tsv" % trait_names[t])
+        with open(path, "w") as f:
+            f.write("\t".join(head) + "\n")
+            for k in range(W):
+                cells = rows[k] + [str(int(result.n[k])), str(int(result.status[k])), str(int(result.df1[k])), str(int(result.df2[k])),
+                                   num(result.F[k, t]), num(result.p_joint[k, t])] + ([num(result.p_adj_F[k, t])] if perm else [])
+                for a in range(A):
+                    cells += [str(int(result.n_hap[k, a])), num(result.beta[k, a, t]), num(result.se[k, a, t]), num(result.t[k, a, t]),
+                              num(result.p[k, a, t])] + ([num(result.p_adj_t[k, a, t])] if perm else [])
+                f.write("\t".join(cells) + "\n")
+        paths.append(path)
+    return paths
+
+
 def write_fb(fb_prefix, meta_data, proba, ancestry, query_samples, n_threads=0, ctx=None):
     """<prefix>.fb (postprocess.py:100-126): proba (N, W, A); every value is printed as pandas' to_csv prints a float column
     (numpy's shortest round-trip text of the array's dtype) — by the library, W rows in parallel on the host's cores, or, when a

@@ -987,6 +987,40 @@ int gnx_ancestry_assoc_traits_gt2(gnx_model* m, const uint8_t* G, int64_t n_vari
                                   const uint8_t* use, int32_t min_ac, int64_t c0, int64_t c1, double* snp_y, double* win_y, double* win_yy,
                                   int64_t* n_bad);
 
+/* ---- admixture mapping: the statistics of the regression of T traits on the LOCAL ANCESTRY itself, from the labels alone ------------
+ * (csrc/summary/k_ancestry_assoc_admix.hip; the finish and the max-T permutations: gnomix_amd/admixmap.py)
+ * An addition: nothing that existed changes, so GNX_ABI_VERSION stays 16 (as for gnx_fit_isotonic_f64).
+ * INPUTS.  labels (N, W) int32 with row stride ld_labels >= W, rows 2 i and 2 i + 1 are individual i; Y (N / 2, T) float64 with row stride
+ *   ldy >= T, 1 <= T <= GNX_ASSOC_MAX_T; Z (N / 2, K) float64, contiguous, the CALLER supplies the intercept column, 1 <= K <=
+ *   GNX_ASSOC_MAX_K; use (N / 2,) bytes or NULL (all ones).  There are no genotypes.
+ * PARTICIPATION.  Individual i takes part at window k when use[i] != 0, Z[i, :] is finite, EVERY entry of Y[i, :] is finite and both its
+ *   labels at k lie in [0, A) (gnx_ancestry_assoc_traits' rule with the genotypes taken out).  h_a[i, k] in {0, 1, 2}: how many of i's two
+ *   haplotypes carry label a at window k.
+ * THE STATISTICS, for the windows [w0, w1), nw = w1 - w0, all OVERWRITTEN, one owner per value, plain stores; sums over the participants
+ *   of the window; ldt = T rounded up to a multiple of 16:
+ *     win_i  (nw, 1 + A + A (A + 1) / 2) int32      n, then hs[a] = sum_i h_a, then sum_i h_a h_b for a <= b (row by row)
+ *     win_g  (nw, K (K + 1) / 2 + K A) float64      the upper triangle of Z^T Z row by row, then Z^T H ([k][a])
+ *     win_y  (nw, K + A, ldt) float64               [Z, h_0 .. h_{A-1}]^T Y (ALL A ancestry columns: the host forms any sub-model)
+ *     win_yy (nw, ldt) float64                      diag(Y^T Y)
+ *   Columns t >= T are written as 0.0.  The integers are exact.  No NaN or infinity enters a sum: an entry all of whose terms are zero
+ *   is 0.0.
+ * SUMMATION ORDER.  Every float64 sum starts at +0.0 and runs over the individuals in ascending groups of 4 (i = 4 g .. 4 g + 3), one
+ *   v_mfma_f64_16x16x4_f64 per group; individuals that take no part enter as zeros; the order of the four terms inside one instruction
+ *   is the hardware's.  A value is a function of N and the data alone: not of the grid, the tile sizes, [w0, w1), ld_labels or ldy (a
+ *   sub-range of windows equals the slice of the whole range and the host form equals the _dev form, bit for bit).
+ * GNX_EINVAL before the launch, nothing written: N < 0, W < 1, A < 1, K < 1, T < 1, a stride too small, not 0 <= w0 < w1 <= W, a null
+ *   pointer (use and n_bad may be NULL).  GNX_EUNSUPPORTED, nothing written: A > GNX_ALLELE_MAX_A, K > GNX_ASSOC_MAX_K,
+ *   T > GNX_ASSOC_MAX_T, N > 2^28, N odd.
+ * GNX_EINVAL after the launch: labels outside [0, A) among ALL rows at the windows [w0, w1), *n_bad their count (0 otherwise); labels are
+ *   only compared, such an individual takes no part at that window and every value is written as stated.
+ * Both forms synchronise the context stream once.  In the _dev form every pointer but n_bad is a device pointer. */
+int gnx_ancestry_admixmap_dev(gnx_ctx* ctx, const int32_t* d_labels, int64_t ld_labels, int64_t N, int64_t W, int32_t A, const double* d_Y,
+                              int64_t ldy, int32_t T, const double* d_Z, int32_t K, const uint8_t* d_use, int64_t w0, int64_t w1, int32_t* d_win_i,
+                              double* d_win_g, double* d_win_y, double* d_win_yy, int64_t* n_bad);
+int gnx_ancestry_admixmap(gnx_ctx* ctx, const int32_t* labels, int64_t ld_labels, int64_t N, int64_t W, int32_t A, const double* Y, int64_t ldy,
+                          int32_t T, const double* Z, int32_t K, const uint8_t* use, int64_t w0, int64_t w1, int32_t* win_i, double* win_g,
+                          double* win_y, double* win_yy, int64_t* n_bad);
+
 /* ---- ancestry-specific association for case / control traits: one logistic fit per SNP, on the device ---------------------------------
  * (csrc/summary/k_ancestry_assoc_logit.hip)
  * Everything not stated here is EXACTLY as gnx_ancestry_assoc_stats has it: rows, labels, M, W, A, win(c), h[i, a], d[i, a], y, Z, K, use,
